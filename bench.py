@@ -2,7 +2,7 @@
 """Headline benchmark: Abbe source-points x image-pixels per second on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg1..cfg5] [--shard i/n] [--points K]
-                    [--no-cpu-baseline] [--no-extra]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-extra]]
 
 One "step" = one complete abbeImage call (source-list compaction, Abbe accumulation over every source point --
 and every through-focus plane -- of the configuration, all-reduce when N > 1, post-process) on synthetic inputs
@@ -15,7 +15,11 @@ Launching: under torch.distributed.run the ranks read RANK / LOCAL_RANK / WORLD_
 environment.  Started as a plain process with --gpus N > 1, this file starts the N ranks ITSELF as fresh child
 processes (before anything in the parent touches the GPU), waits for them and relays rank 0's JSON line.
 
-Rank 0 prints one JSON line (contract in the task statement) carrying
+A plain run sets up, warms up, times the K steps, writes the last step's image under --dump-outputs DIR (DIR/image.npy,
+float32; an image above 64 MB as a fixed, seeded sample: DIR/image_sample.npy and its flat indices DIR/image_sample_index.npy)
+and prints the headline line.  Everything else below is measured with --full only.
+
+Rank 0 prints one JSON line (contract in the task statement); with --full it also carries
   roofline        the dominant kernel (name reported by the library, litho_abbe_last_kernels) against the bound the
                   counters and microbenchmarks show: fp32 VALU issue.  achieved = nominal FFT flops (5 N log2 N per
                   transformed line) of one launch / its HIP-event-timed duration, peak = 157.3 TFLOP/s fp32 vector.
@@ -26,10 +30,12 @@ Rank 0 prints one JSON line (contract in the task statement) carrying
                   effective: most of those bytes are never moved), `copy_ceiling_GBs` = this box's own 1 GiB copy rate;
   cpu_baseline    (N = 1) the oracle's torch-CPU op chain, i.e. a port of the reference loop, on a bounded sample, with
                   the GPU-vs-CPU parity of that sample taken on the SAME evaluation path the timed step ran;
-  extra_workloads (default run only) two or more timed steps each of config 1, config 2, one rank's shard of config 4
+  extra_workloads (default workload only) two or more timed steps each of config 1, config 2, one rank's shard of config 4
                   and the config 5 stack (mean by host clock + per-step HIP-event times and their median), so that every
                   BASELINE configuration has a driver-observed number with more than one sample;
-  ranks           (N > 1) per-rank step time, compute time and all-reduce time of one instrumented step.
+  ranks           (N > 1) per-rank step time, compute time and all-reduce time of one instrumented step;
+  prediction      the N-GPU step stated in advance, against the measured one;
+  step_ms         for short steps (config 1), whose events are taken in a pass of K more steps of their own.
 """
 import argparse
 import contextlib
@@ -84,10 +90,45 @@ def parse_args():
                          "without the all-reduce)")
     ap.add_argument("--points", type=int, default=0,
                     help="profiling aid: only the first K consecutive source points (the JSON line is then marked partial)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the image of the last one as DIR/<name>.npy (float32, at most 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline, CPU baseline, extra workloads, per-rank view, prediction")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline leg")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the extra_workloads leg (configs 1, 2, 4-shard, 5) of the default single-GPU run")
-    return ap.parse_args()
+                    help="--full without the extra_workloads leg (configs 1, 2, 4-shard, 5) of the default single-GPU run")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SAMPLE = 1 << 22                 # elements of a sampled output: 16 MB of values + 32 MB of float64 indices
+DUMP_SEED = 20240601
+
+
+def dump_outputs(dirname, outputs):
+    """What the timed path returned, as DIR/<name>.npy in float32.  An output above DUMP_LIMIT_BYTES is written as a fixed, seeded
+    sample of its elements (<name>_sample.npy) with their flat row-major indices (<name>_sample_index.npy, float64): the same
+    shape gives the same indices in every run, so two builds compare element for element.  Returns what was written."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for name, t in outputs.items():
+        t = t.detach().float()
+        if t.numel() * 4 <= DUMP_LIMIT_BYTES:
+            np.save(os.path.join(dirname, f"{name}.npy"), t.cpu().numpy())
+            written[name] = {"file": f"{name}.npy", "shape": list(t.shape), "sampled": False}
+            continue
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(t.numel(), DUMP_SAMPLE, replace=False))
+        vals = t.reshape(-1)[torch.from_numpy(idx).to(t.device)].cpu().numpy()
+        np.save(os.path.join(dirname, f"{name}_sample.npy"), vals)
+        np.save(os.path.join(dirname, f"{name}_sample_index.npy"), idx.astype(np.float64))
+        written[name] = {"file": f"{name}_sample.npy", "index_file": f"{name}_sample_index.npy", "shape": list(t.shape),
+                         "sampled": True, "sample_elements": DUMP_SAMPLE, "seed": DUMP_SEED}
+    return written
 
 
 def spawn_ranks(args):
@@ -510,6 +551,68 @@ def extra_workload(torch, nat, dev, name, shard=None, steps=1, warm_points=0, wa
     return out
 
 
+def roofline_leg(torch, nat, L, step, dev, workload, pn, N):
+    """--full: HIP-event time of each kernel class over one more (untimed) step of this rank's shard, the device's copy and fill
+    rates, and the PMC traffic of profiles/traffic.json against them.  Returns (roofline, plan, executed FFT size)."""
+    nat.set_profiling(True)
+    step()
+    torch.cuda.synchronize()
+    prof = nat.last_profile()
+    plan = nat.last_plan()
+    nat.set_profiling(False)
+    copy_gbs, fill_gbs = measured_ceilings(torch, dev)
+    kern, n_exec = kernel_profile(nat, prof, plan, pn, N, L.embeddedSize(pn, N))
+    # The two pass kernels share the time almost evenly (50.3 % / 49.1 % under rocprofv3) and trade places from run to
+    # run; `roofline` describes the y-pass -- the VALU-bound one, for which a flop fraction means something -- unless the
+    # x-pass leads by more than 5 %.  Both kernels carry their own figures (and their measured bound) under `kernels`.
+    dom = "ypass" if kern["ypass"]["total_ms"] >= 0.95 * kern["xpass"]["total_ms"] else "xpass"
+    traffic_src = attach_traffic(workload, kern, plan)
+    traffic = kern[dom].get("traffic")
+    kern["ypass"]["bound"] = "valu: fp32 issue + per-wave serial latency (load wait, LDS transposes); profiles/r03_ypass_lab.txt"
+    kern["xpass"]["bound"] = ("fabric: the T stores (64-byte granules through the L2 to the Infinity Cache); without them the "
+                              "kernel takes 0.6 of its time (profiles/r02_xpass_diag_variants.txt, r03_ypass_lab.txt)")
+    for k in kern:
+        kern[k]["valu_frac"] = kern[k]["achieved_TFLOPs"] / VALU_PEAK_TFLOPS
+    both_ms = kern["xpass"]["total_ms"] + kern["ypass"]["total_ms"]
+    both_flops = sum(kern[k]["nominal_flops_per_launch"] * kern[k]["launches"] for k in kern)
+    eff40 = 40.0 * pn * pn * prof["ypass_points"] / (both_ms * 1e-3) / 1e9 if both_ms else 0.0
+    dom_s = kern[dom]["avg_launch_ms"] * 1e-3
+    fabric_gbs = traffic / dom_s / 1e9 if traffic and dom_s > 0 else None
+    # "bound" takes the contract's two values ("hbm" | "mfma"): this is the flop side -- priced against the dense fp32 peak,
+    # 157.3 TFLOP/s, which on gfx950 is the same figure for the matrix and the vector pipe; `bound_detail` says which pipe
+    roofline = {"bound": "mfma", "bound_measured": "valu", "bound_detail": "VALU: fp32 vector issue, NOT the matrix pipe -- the path has no MFMA instruction; \"mfma\" is the "
+                                                  "contract's name for the flop side, priced at the dense fp32 peak, which on gfx950 is "
+                                                  "157.3 TFLOP/s for the vector and the matrix pipe alike", "kernel": kern[dom]["kernel"],
+                "achieved": kern[dom]["achieved_TFLOPs"], "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
+                "frac": kern[dom]["achieved_TFLOPs"] / VALU_PEAK_TFLOPS, "traffic": traffic,
+                "avg_launch_ms": kern[dom]["avg_launch_ms"],
+                "nominal_flops_per_launch": kern[dom]["nominal_flops_per_launch"],
+                "kernel_time_frac": kern[dom]["total_ms"] / both_ms if both_ms else None,
+                "fabric_GBs": fabric_gbs, "fabric_frac": fabric_gbs / HBM_PEAK_GBS if fabric_gbs else None,
+                "effective_40B_GBs": eff40, "effective_40B_over_peak": eff40 / HBM_PEAK_GBS,
+                "copy_ceiling_GBs": copy_gbs, "fill_ceiling_GBs": fill_gbs, "hbm_peak_GBs": HBM_PEAK_GBS,
+                "note": "kernel: the y-pass unless the x-pass leads it by more than 5 % (they share the time 50 / 50 and trade "
+                        "places from run to run; both are under `kernels` with their own bound).  "
+                        "bound: fp32 VALU issue (profiles/r03_*: the kernel's instruction stream issues at 1.9 ns per "
+                        "instruction per SIMD against a measured 1.0-1.26 ns floor at two waves per SIMD; packed fp32 "
+                        "gives no extra rate on gfx950).  achieved = nominal 5*N*log2(N) flops per transformed line "
+                        "(pruned transforms execute fewer) / HIP-event launch time.  traffic / fabric_* = PMC bytes the "
+                        "L2 exchanged with the fabric per launch of this workload, Infinity-Cache hits INCLUDED (T is kept "
+                        "inside that cache on purpose): an upper bound on HBM traffic, not HBM traffic.  effective_40B_* "
+                        "divide the SURVEY 8d byte MODEL by x-pass + y-pass kernel time: most of those bytes are never "
+                        "moved, so it exceeds the peak and is not a roofline fraction.  avg_launch_ms comes from HIP events the "
+                        "library records around every launch of ONE extra, untimed step: the marks themselves cost about 4 % "
+                        "(launches x avg_launch_ms of both kernels exceeds ms_per_step by that much), so achieved / frac are "
+                        "slightly conservative; rocprofv3 --kernel-trace of the same command (profiles/) has the unmarked durations",
+                "traffic_source": traffic_src,
+                "hbm_honest": hbm_streaming(kern, plan, L.embeddedSize(pn, N)),
+                "pipeline": {"achieved": both_flops / (both_ms * 1e-3) / 1e12 if both_ms else 0.0,
+                             "frac": both_flops / (both_ms * 1e-3) / 1e12 / VALU_PEAK_TFLOPS if both_ms else 0.0,
+                             "note": "x-pass + y-pass nominal flops over their summed kernel time"},
+                "kernels": kern}
+    return roofline, plan, n_exec
+
+
 def main():
     args = parse_args()
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
@@ -640,15 +743,19 @@ def main():
         marks[args.steps].record()
     fence()
     elapsed_own = time.perf_counter() - t0
-    step_ms = (event_timed_steps(torch, step, args.steps) if short
+    # short steps: their event pass is K more steps of its own (--full only)
+    step_ms = (None if short and not args.full else event_timed_steps(torch, step, args.steps) if short
                else [marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)])
-    elapsed = elapsed_own
+    own_median = statistics.median(step_ms) if step_ms else None
+    elapsed, median_ms = elapsed_own, own_median
     ranks = None
     if world > 1:
         cdev = dev if backend == "nccl" else "cpu"
-        t = torch.tensor([elapsed_own], dtype=torch.float64, device=cdev)
+        t = torch.tensor([elapsed_own, own_median or 0.0], dtype=torch.float64, device=cdev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
+        elapsed = float(t[0].item())
+        median_ms = float(t[1].item()) if own_median is not None else None
+    if world > 1 and args.full:
         # one more, instrumented step: this rank's compute (its shard of the Abbe sum) and the all-reduce, by events
         from lithographysimulator_amd.distributed import shard_bounds
         from lithographysimulator_amd.imageformation import _all_reduce_sum
@@ -667,7 +774,7 @@ def main():
         torch.cuda.synchronize()
         h2 = time.perf_counter()
         mine = torch.tensor([elapsed_own / args.steps * 1e3, e0.elapsed_time(e1), (h2 - h1) * 1e3, float(rhi - rlo),
-                             statistics.median(step_ms)], dtype=torch.float64, device=cdev)
+                             own_median], dtype=torch.float64, device=cdev)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         rows = [[float(v) for v in r.cpu()] for r in allr]
@@ -698,72 +805,21 @@ def main():
                          "collective + waiting for the slowest rank) from one extra instrumented step"}
         del part, sh_all
     ms_per_step = elapsed / args.steps * 1e3
-    # SURVEY 8d asks for the median of >= 5 event-timed calls; `value` stays the contract's mean over the barrier-bracketed region
-    median_ms = max(ranks["median_step_ms"]) if ranks is not None else statistics.median(step_ms)
     units = float(S) * pn * pn * planes                          # source-point*pixels per step, whole job
     value = units * args.steps / elapsed
 
-    # ---- roofline leg: HIP-event time of each kernel class over one more (untimed) step of this rank's shard
-    nat.set_profiling(True)
-    step()
-    torch.cuda.synchronize()
-    prof = nat.last_profile()
+    if rank == 0 and args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, {"image": image})
     plan = nat.last_plan()
-    nat.set_profiling(False)
-    copy_gbs, fill_gbs = measured_ceilings(torch, dev)
-    kern, n_exec = kernel_profile(nat, prof, plan, pn, N, L.embeddedSize(pn, N))
-    # The two pass kernels share the time almost evenly (50.3 % / 49.1 % under rocprofv3) and trade places from run to
-    # run; `roofline` describes the y-pass -- the VALU-bound one, for which a flop fraction means something -- unless the
-    # x-pass leads by more than 5 %.  Both kernels carry their own figures (and their measured bound) under `kernels`.
-    dom = "ypass" if kern["ypass"]["total_ms"] >= 0.95 * kern["xpass"]["total_ms"] else "xpass"
-    traffic_src = attach_traffic(args.workload, kern, plan)
-    traffic = kern[dom].get("traffic")
-    kern["ypass"]["bound"] = "valu: fp32 issue + per-wave serial latency (load wait, LDS transposes); profiles/r03_ypass_lab.txt"
-    kern["xpass"]["bound"] = ("fabric: the T stores (64-byte granules through the L2 to the Infinity Cache); without them the "
-                              "kernel takes 0.6 of its time (profiles/r02_xpass_diag_variants.txt, r03_ypass_lab.txt)")
-    for k in kern:
-        kern[k]["valu_frac"] = kern[k]["achieved_TFLOPs"] / VALU_PEAK_TFLOPS
-    both_ms = kern["xpass"]["total_ms"] + kern["ypass"]["total_ms"]
-    both_flops = sum(kern[k]["nominal_flops_per_launch"] * kern[k]["launches"] for k in kern)
-    eff40 = 40.0 * pn * pn * prof["ypass_points"] / (both_ms * 1e-3) / 1e9 if both_ms else 0.0
-    dom_s = kern[dom]["avg_launch_ms"] * 1e-3
-    fabric_gbs = traffic / dom_s / 1e9 if traffic and dom_s > 0 else None
-    # "bound" takes the contract's two values ("hbm" | "mfma"): this is the flop side -- priced against the dense fp32 peak,
-    # 157.3 TFLOP/s, which on gfx950 is the same figure for the matrix and the vector pipe; `bound_detail` says which pipe
-    roofline = {"bound": "mfma", "bound_measured": "valu", "bound_detail": "VALU: fp32 vector issue, NOT the matrix pipe -- the path has no MFMA instruction; \"mfma\" is the "
-                                                  "contract's name for the flop side, priced at the dense fp32 peak, which on gfx950 is "
-                                                  "157.3 TFLOP/s for the vector and the matrix pipe alike", "kernel": kern[dom]["kernel"],
-                "achieved": kern[dom]["achieved_TFLOPs"], "peak": VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
-                "frac": kern[dom]["achieved_TFLOPs"] / VALU_PEAK_TFLOPS, "traffic": traffic,
-                "avg_launch_ms": kern[dom]["avg_launch_ms"],
-                "nominal_flops_per_launch": kern[dom]["nominal_flops_per_launch"],
-                "kernel_time_frac": kern[dom]["total_ms"] / both_ms if both_ms else None,
-                "fabric_GBs": fabric_gbs, "fabric_frac": fabric_gbs / HBM_PEAK_GBS if fabric_gbs else None,
-                "effective_40B_GBs": eff40, "effective_40B_over_peak": eff40 / HBM_PEAK_GBS,
-                "copy_ceiling_GBs": copy_gbs, "fill_ceiling_GBs": fill_gbs, "hbm_peak_GBs": HBM_PEAK_GBS,
-                "note": "kernel: the y-pass unless the x-pass leads it by more than 5 % (they share the time 50 / 50 and trade "
-                        "places from run to run; both are under `kernels` with their own bound).  "
-                        "bound: fp32 VALU issue (profiles/r03_*: the kernel's instruction stream issues at 1.9 ns per "
-                        "instruction per SIMD against a measured 1.0-1.26 ns floor at two waves per SIMD; packed fp32 "
-                        "gives no extra rate on gfx950).  achieved = nominal 5*N*log2(N) flops per transformed line "
-                        "(pruned transforms execute fewer) / HIP-event launch time.  traffic / fabric_* = PMC bytes the "
-                        "L2 exchanged with the fabric per launch of this workload, Infinity-Cache hits INCLUDED (T is kept "
-                        "inside that cache on purpose): an upper bound on HBM traffic, not HBM traffic.  effective_40B_* "
-                        "divide the SURVEY 8d byte MODEL by x-pass + y-pass kernel time: most of those bytes are never "
-                        "moved, so it exceeds the peak and is not a roofline fraction.  avg_launch_ms comes from HIP events the "
-                        "library records around every launch of ONE extra, untimed step: the marks themselves cost about 4 % "
-                        "(launches x avg_launch_ms of both kernels exceeds ms_per_step by that much), so achieved / frac are "
-                        "slightly conservative; rocprofv3 --kernel-trace of the same command (profiles/) has the unmarked durations",
-                "traffic_source": traffic_src,
-                "hbm_honest": hbm_streaming(kern, plan, L.embeddedSize(pn, N)),
-                "pipeline": {"achieved": both_flops / (both_ms * 1e-3) / 1e12 if both_ms else 0.0,
-                             "frac": both_flops / (both_ms * 1e-3) / 1e12 / VALU_PEAK_TFLOPS if both_ms else 0.0,
-                             "note": "x-pass + y-pass nominal flops over their summed kernel time"},
-                "kernels": kern}
+    n_exec = L.embeddedSize(pn, N) if plan.get("coarse_grid") else N
+    roofline = None
+    if args.full:
+        roofline, plan, n_exec = roofline_leg(torch, nat, L, step, dev, args.workload, pn, N)
 
     out = {"metric": "Abbe source-points x image-pixels per second", "value": value, "unit": "source-pt*px/s",
            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms_per_step,
-           "median_ms_per_step": median_ms, "value_at_median": units / (median_ms * 1e-3) if median_ms > 0 else None,
+           # SURVEY 8d asks for the median of >= 5 event-timed calls (the slowest rank's); `value` stays the mean over the fenced region
+           "median_ms_per_step": median_ms, "value_at_median": units / (median_ms * 1e-3) if median_ms else None,
            "step_ms": step_ms, "step_ms_events_inside_timed_region": not short,
            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32",
            "data": "synthetic",
@@ -771,18 +827,22 @@ def main():
                                   + (f" [{shard_note}]" if shard_note else ""),
                       "pn": pn, "fft_n": N, "executed_fft_n": n_exec, "source_points": S, "source_points_full": S_full, "planes": planes,
                       "points_per_rank": math.ceil(S / world),
-                      # how often this process ran the step's kernels (warm-up + timed + the event pass of short steps + the profiled
-                      # one): scripts/pmc_traffic.py divides whole-process counters by it
-                      "step_executions": args.warmup + args.steps + (args.steps if short else 0) + 1, "pixel_size": PS, "wavelength": WL, "NA": NA,
+                      # how often this process ran the step's kernels (warm-up + timed, with --full + the event pass of short steps + the
+                      # profiled one): scripts/pmc_traffic.py divides whole-process counters by it
+                      "step_executions": args.warmup + args.steps + ((args.steps if short else 0) + 1 if args.full else 0),
+                      "pixel_size": PS, "wavelength": WL, "NA": NA,
                       "parallelism": f"source-point shards x{world}, one all-reduce" if world > 1 else "single GPU",
                       "plan": plan, "image_shape": list(image.shape)},
            "target_abs": {"per_gpu": TARGET_ABS_PER_GPU, "n_gpus": world, "value_over_target": value / (TARGET_ABS_PER_GPU * world),
                           "source": "BASELINE.md: >= 60 % of the 8 TB/s HBM roofline under the SURVEY 8d 40-byte model at 2048^2 = 1.2e11 "
-                                    "source-pt*px/s per GPU (an EFFECTIVE figure: most of those 40 bytes are never moved)"},
-           "roofline": roofline}
+                                    "source-pt*px/s per GPU (an EFFECTIVE figure: most of those 40 bytes are never moved)"}}
+    if roofline is not None:
+        out["roofline"] = roofline
     if ranks is not None:
         out["ranks"] = ranks
-    if not args.shard and args.points == 0:
+    if rank == 0 and args.dump_outputs:
+        out["outputs"] = dumped
+    if args.full and not args.shard and args.points == 0:
         pred = predicted_step(args.workload, world, planes * pn * pn * 4)
         if pred:
             # the record explains itself whichever way it comes out: measured step over predicted step, and (N > 1) where the
@@ -797,11 +857,11 @@ def main():
     # ---- CPU baseline leg: the oracle's op-chain port of the reference loop, rank 0, N = 1 only.  GPU half now (the workload is
     # resident), CPU half after every GPU timing of this run
     cpu_state = None
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         cpu_state = cpu_baseline_prepare(torch, nat, w, plan, full=(args.workload == "cfg1"))
 
-    # ---- every other BASELINE configuration, one or two timed steps each (default single-GPU run only)
-    if world == 1 and not args.no_extra and args.workload == "cfg3" and not args.shard and args.points == 0:
+    # ---- every other BASELINE configuration, one or two timed steps each (single-GPU --full run of the default workload only)
+    if args.full and world == 1 and not args.no_extra and args.workload == "cfg3" and not args.shard and args.points == 0:
         del w, image
         torch.cuda.empty_cache()
         extras = []

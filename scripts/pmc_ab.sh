@@ -9,7 +9,7 @@ i=0
 for grp in "$@"; do
   for v in $A $B; do
     export $K=$v
-    rocprofv3 --pmc $grp --output-format csv -d $O/${K}_${v}_g$i -o pmc -- python3 bench.py --workload $W --points $P --steps 1 --warmup 0 --no-cpu-baseline --no-extra > /dev/null 2> $O/err_${v}_$i.txt
+    rocprofv3 --pmc $grp --output-format csv -d $O/${K}_${v}_g$i -o pmc -- python3 bench.py --full --workload $W --points $P --steps 1 --warmup 0 --no-cpu-baseline --no-extra > /dev/null 2> $O/err_${v}_$i.txt
   done
   i=$((i+1))
 done

@@ -9,7 +9,7 @@ mkdir -p gpurun_out/$R
 while [ $# -ge 2 ]; do
   W=$1; K=$2; shift 2
   D=gpurun_out/$R/pmc_$W
-  B="python3 bench.py --workload $W --steps 1 --warmup 0 --no-cpu-baseline --points $K"
+  B="python3 bench.py --full --workload $W --steps 1 --warmup 0 --no-cpu-baseline --points $K"
   timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $D/fetch -o p -- $B > $D.fetch.json 2> $D.fetch.err
   timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $D/write -o p -- $B > $D.write.json 2> $D.write.err
   timeout 600 rocprofv3 --kernel-trace --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS --output-format csv -d $D/sq1 -o p -- $B > /dev/null 2> $D.sq1.err

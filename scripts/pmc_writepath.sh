@@ -5,7 +5,7 @@ R=$1; W=$2; K=$3
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 D=gpurun_out/$R/wr_$W
 mkdir -p $D
-B="python3 bench.py --workload $W --steps 1 --warmup 0 --no-cpu-baseline --points $K"
+B="python3 bench.py --full --workload $W --steps 1 --warmup 0 --no-cpu-baseline --points $K"
 i=0
 for C in "TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum" "TCC_EA0_WRREQ_STALL_sum TCC_TOO_MANY_EA_WRREQS_STALL_sum" \
          "TCC_EA0_WRREQ_DRAM_CREDIT_STALL_sum TCC_EA0_WRREQ_LEVEL_sum" "TCC_BUSY_sum TCC_TAG_STALL_sum" \

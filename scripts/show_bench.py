@@ -1,4 +1,4 @@
-"""Short summary of a bench.py JSON line: python scripts/show_bench.py file.json"""
+"""Short summary of a `bench.py --full` JSON line: python scripts/show_bench.py file.json"""
 import json
 import sys
 

@@ -120,7 +120,7 @@ def test_check_in_names_the_missing_rank_and_exits_non_zero():
 
 
 def test_default_line_carries_every_baseline_config():
-    """The default run's extra_workloads must name configs 1, 2, 4 (shard) and 5 (+ odd2000) -- read from the source's syntax tree
+    """The --full run's extra_workloads must name configs 1, 2, 4 (shard) and 5 (+ odd2000) -- read from the source's syntax tree
     (the run itself takes minutes): a comment once swallowed an entry of the tuple."""
     import ast
     tree = ast.parse(open(os.path.join(ROOT, "bench.py")).read())
@@ -129,3 +129,46 @@ def test_default_line_carries_every_baseline_config():
         if isinstance(node, ast.For) and isinstance(node.target, ast.Tuple) and [getattr(t, "id", None) for t in node.target.elts] == ["name", "kw"]:
             names = [elt.elts[0].value for elt in node.iter.elts]
     assert names == ["cfg1", "cfg2", "cfg4", "cfg5", "odd2000"], names
+
+
+def test_plain_run_options():
+    """--full and --dump-outputs are off by default, and --steps really is a count of timed steps (at least one)."""
+    import subprocess
+    b = _bench()
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py"]
+        a = b.parse_args()
+        assert a.full is False and a.dump_outputs is None and a.steps >= 1
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out", "--steps", "7", "--warmup", "0"]
+        a = b.parse_args()
+        assert a.full is True and a.dump_outputs == "out" and a.steps == 7 and a.warmup == 0
+    finally:
+        sys.argv = argv
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], capture_output=True, text=True,
+                         timeout=300, cwd=ROOT)
+    assert out.returncode != 0 and "--steps" in out.stderr
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy files; an output above the limit becomes a seeded sample with its flat indices, the same
+    in every run, and never more than 64 MB in all."""
+    import numpy as np
+    import torch
+    b = _bench()
+    assert b.DUMP_SAMPLE * (4 + 8) + 1024 <= b.DUMP_LIMIT_BYTES <= 64_000_000
+    small = torch.arange(12, dtype=torch.float64).reshape(3, 4)
+    w = b.dump_outputs(str(tmp_path / "a"), {"image": small})
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert w["image"]["sampled"] is False and got.dtype == np.float32 and np.array_equal(got, small.numpy())
+    monkeypatch.setattr(b, "DUMP_LIMIT_BYTES", 4000)
+    monkeypatch.setattr(b, "DUMP_SAMPLE", 100)
+    big = torch.rand(2, 40, 50, generator=torch.Generator().manual_seed(1))
+    for d in ("b", "c"):
+        w = b.dump_outputs(str(tmp_path / d), {"image": big})
+        assert w["image"]["sampled"] is True and w["image"]["shape"] == [2, 40, 50]
+        assert not (tmp_path / d / "image.npy").exists()
+    vals, idx = np.load(tmp_path / "b" / "image_sample.npy"), np.load(tmp_path / "b" / "image_sample_index.npy")
+    assert vals.dtype == np.float32 and idx.dtype == np.float64 and vals.shape == idx.shape == (100,)
+    assert np.all(np.diff(idx) > 0) and np.array_equal(vals, big.numpy().reshape(-1)[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "c" / "image_sample_index.npy"))

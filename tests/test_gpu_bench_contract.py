@@ -1,4 +1,5 @@
-"""bench.py end to end on the small config-1 workload: one JSON line with the contract's keys."""
+"""bench.py end to end on the small config-1 workload: one JSON line with the contract's keys (plain run), and with --full
+the roofline, CPU-baseline, per-rank and prediction legs."""
 import json
 import os
 import subprocess
@@ -13,7 +14,7 @@ pytestmark = pytest.mark.gpu
 
 def test_bench_json_contract():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg1", "--steps", "2",
-                          "--warmup", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -55,6 +56,44 @@ def test_bench_json_contract():
     assert "extra_workloads" not in r                           # only the default cfg3 run carries them
 
 
+def test_bench_plain_run_is_lean_and_dumps_what_it_computed(golden, tmp_path):
+    """A plain run (no --full) times exactly --steps steps, carries the headline keys and none of the --full legs, and
+    --dump-outputs writes the image of its last timed step: config 1 in full against the reference's own image of it.  A
+    through-focus stack of 32 planes (536 MB) is written as the seeded sample instead, under 64 MB."""
+    import numpy as np
+    from helpers import TOL_IMAGE_L2, TOL_IMAGE_MAX, rel_l2, rel_max
+    d = tmp_path / "out"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--workload", "cfg1", "--steps", "3",
+                          "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r["metric"] == "Abbe source-points x image-pixels per second" and r["unit"] == "source-pt*px/s"
+    assert r["higher_is_better"] is True and r["dtype"] == "f32" and r["steps"] == 3 and r["warmup"] == 1
+    assert r["ms_per_step"] > 0 and abs(r["value"] - 3233 * 256 * 256 / (r["ms_per_step"] * 1e-3)) < 1e-6 * r["value"]
+    assert r["config"]["step_executions"] == 4
+    for key in ("roofline", "cpu_baseline", "extra_workloads", "prediction", "ranks"):
+        assert key not in r, key
+    img = np.load(d / "image.npy")
+    assert r["outputs"]["image"] == {"file": "image.npy", "shape": r["config"]["image_shape"], "sampled": False}
+    assert img.dtype == np.float32 and list(img.shape) == r["config"]["image_shape"]
+    ref = golden("g5_images.npz")["cfg1_bern_final"]
+    assert rel_max(img, ref) < TOL_IMAGE_MAX and rel_l2(img, ref) < TOL_IMAGE_L2
+
+    d = tmp_path / "stack"
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg5", "--points", "4", "--steps", "1",
+                          "--warmup", "0", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert r["steps"] == 1 and r["outputs"]["image"]["sampled"] is True and r["config"]["image_shape"][0] == 32
+    assert sorted(os.listdir(d)) == ["image_sample.npy", "image_sample_index.npy"]
+    assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64_000_000
+    vals, idx = np.load(d / "image_sample.npy"), np.load(d / "image_sample_index.npy")
+    assert vals.dtype == np.float32 and idx.dtype == np.float64 and vals.shape == idx.shape and np.all(np.isfinite(vals))
+    assert idx[0] >= 0 and idx[-1] < np.prod(r["config"]["image_shape"]) and float(vals.max()) > 0
+
+
 @pytest.mark.parametrize("world", [2, 8])
 def test_bench_launches_its_own_ranks(world):
     """`python bench.py --gpus N` as a PLAIN process (no torch.distributed.run, no WORLD_SIZE) must start the ranks
@@ -66,7 +105,7 @@ def test_bench_launches_its_own_ranks(world):
     env = dict(os.environ, LITHO_BENCH_SHARE_GPU="1", LITHO_BENCH_BACKEND="gloo")
     env.pop("WORLD_SIZE", None); env.pop("RANK", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--workload", "cfg1", "--steps", "2",
-                          "--warmup", "1"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -99,7 +138,8 @@ def test_bench_adopts_the_launchers_world_size_without_gpus_flag():
     for r in range(2):
         env = dict(os.environ, LITHO_BENCH_SHARE_GPU="1", LITHO_BENCH_BACKEND="gloo", RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2",
                    MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), LITHO_BENCH_TIMEOUT_S="240")
-        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg1", "--steps", "5", "--warmup", "1"],
+        procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg1", "--steps", "5", "--warmup", "1",
+                                       "--full"],
                                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT, env=env))
     outs = [p.communicate(timeout=900) for p in procs]
     assert [p.returncode for p in procs] == [0, 0], [o[1][-1500:] for o in outs]
@@ -121,8 +161,8 @@ def test_bench_falls_back_to_a_host_staged_group_when_rccl_cannot_start():
     env = dict(os.environ, LITHO_BENCH_SHARE_GPU="1", LITHO_BENCH_FORCE_RCCL_FAIL="1")
     for k in ("WORLD_SIZE", "RANK", "LITHO_BENCH_BACKEND"):
         env.pop(k, None)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "cfg1", "--steps", "2", "--warmup", "1"],
-                         capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "cfg1", "--steps", "2", "--warmup", "1",
+                          "--full"], capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-2000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert r["n_gpus"] == 2 and r["ranks"]["backend"] == "gloo" and "FORCE_RCCL_FAIL" in r["ranks"]["backend_fallback"]

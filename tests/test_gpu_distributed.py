@@ -209,7 +209,7 @@ def test_bench_multi_gpu_rccl_line():
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LITHO_BENCH_SHARE_GPU", "LITHO_BENCH_BACKEND"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--workload", "cfg2", "--steps", "2",
-                          "--warmup", "1"], capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, timeout=1200, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     r = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][0])
     assert r["n_gpus"] == n and r["config"]["source_points"] == 98832 and len(r["ranks"]["compute_ms"]) == n
