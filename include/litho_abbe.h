@@ -61,6 +61,13 @@ int litho_source_bitmap(int kind, double sigma_in, double sigma_out, int pn,
 int litho_source_compact(const int64_t *bitmap, int pn, int32_t *shifts, int64_t capacity,
                          int32_t *scratch, int64_t *count_host, void *stream);
 
+/* ---- The same compaction for a weighted source: a FLOAT32 map [pn,pn] whose values are intensity weights (lit = w > 0;
+ * no reference counterpart, see litho_abbe_accumulate_weighted) into int32 [S,2] shifts plus fp32 [S] weights, same row-major
+ * order, same scratch and the same asynchronous form (count_host == NULL: S stays in scratch[pn]).  `weights` has room for as
+ * many entries as `shifts` has pairs.  A map of exact 0 / 1 values gives the shift list of litho_source_compact bit for bit. */
+int litho_source_compact_weighted(const float *map, int pn, int32_t *shifts, float *weights, int64_t capacity,
+                                  int32_t *scratch, int64_t *count_host, void *stream);
+
 /* ---- Pupil: Pupil.generateWavefrontError / generatePupilFunction
  * (pupil.py:32-38, 46-111).  coeffs_f16_host: J fp16 bit patterns (uint16) in OSA/ANSI
  * order, as given by the caller, BEFORE the defocus rescale of coefficient 4; the
@@ -183,6 +190,24 @@ int litho_abbe_accumulate_opts(const void *maskFT, const void *pupil, int planes
                                const int32_t *count_dev, int64_t capacity, int pn, int N, float *out,
                                void *workspace, size_t workspace_bytes, void *stream, litho_abbe_plan *plan,
                                const litho_abbe_options *options, int64_t *count_host);
+
+/* ---- Weighted (grey-level) sources: per-point intensity in the Abbe sum.
+ *   out[p][q] += sum_{s<S} w_s | E_{p,s}[q] |^2
+ * The reference treats the source as a bitmap -- `argwhere(lightsource)` keeps "non-zero = lit" (imageformation.py:59) and its
+ * loop adds every |E_s|^2 with weight one (imageformation.py:62-67) -- so a measured pupil fill, a pixelated freeform source or
+ * an apodised annulus cannot be expressed there; this entry goes beyond it.  The argument list of litho_abbe_accumulate_opts
+ * plus `weights`: fp32 [S] (or [capacity] with count_dev), one INTENSITY weight per source point, in the order of `shifts`;
+ * the square root is taken inside the library.  weights == NULL is exactly litho_abbe_accumulate_opts.  Every evaluation path
+ * honours the weights (pruned box, coarse grid, embedded sizes, general mode, stacks, batches, plan reuse); of the launch
+ * planner's options the two opt-in x-pass families (rowpairs, w64x) are ignored.  w_s = 0 is legal and adds nothing; a
+ * negative, NaN or infinite weight is LITHO_E_ARG from the call that PLANS (found in the planning read-back, before anything
+ * is accumulated); a call planned from a record does not look again -- the contract of litho_abbe_accumulate_planned extends
+ * to `weights`.  One limit: a weighted list whose shifts wrap the pupil around the grid for SOME points is not split
+ * (options.split): it runs whole on the general path (litho_abbe_last_plan [0] = 1, [15] != 2), correct and slower. */
+int litho_abbe_accumulate_weighted(const void *maskFT, const void *pupil, int planes, const int32_t *shifts,
+                                   const int32_t *count_dev, int64_t capacity, int pn, int N, float *out,
+                                   void *workspace, size_t workspace_bytes, void *stream, litho_abbe_plan *plan,
+                                   const litho_abbe_options *options, int64_t *count_host, const float *weights);
 
 /* ---- Dry run of the launch planner: what litho_abbe_accumulate* WOULD do for a problem, without touching a device.
  * The reference has no counterpart (its loop has nothing to plan, imageformation.py:62-67); this exists so that the host

@@ -5,11 +5,12 @@ from .imageformation import (PlanCache, abbeImage, abbeIntensity, bossungCurves,
 from ._native import engineOptions                                                      # noqa: F401
 from .layout import (GdsLibrary, flattenLayout, maskFromGDSII, rasterizeLayout, readGDSII,  # noqa: F401
                      writeGDSII)
-from .lightsource import LightSource, sourceShifts, sourceShiftsAsync                                      # noqa: F401
+from .lightsource import (LightSource, sourceShifts, sourceShiftsAsync, sourceWeights,   # noqa: F401
+                          sourceWeightsAsync)
 from .mask import Mask                                                                  # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
 
 __all__ = ["Mask", "LightSource", "Pupil", "abbeImage", "abbeIntensity", "calculateFFTAerial", "postProcess", "resistContour", "bossungCurves", "PlanCache", "engineOptions", "embeddedSize",
-           "sourceShifts", "sourceShiftsAsync", "OSAindexToMN", "generateWavefrontError", "generatePhi", "generateZ",
+           "sourceShifts", "sourceShiftsAsync", "sourceWeights", "sourceWeightsAsync", "OSAindexToMN", "generateWavefrontError", "generatePhi", "generateZ",
            "throughFocusPupils", "readGDSII", "writeGDSII", "flattenLayout", "rasterizeLayout", "maskFromGDSII", "GdsLibrary"]

@@ -24,6 +24,8 @@ _SIGNATURES = {
     "litho_source_bitmap": (c_int, [c_int, c_double, c_double, c_int, c_double, c_double, c_int, c_double,
                                     c_void_p, c_void_p]),
     "litho_source_compact": (c_int, [c_void_p, c_int, c_void_p, c_int64, c_void_p, POINTER(c_int64), c_void_p]),
+    "litho_source_compact_weighted": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_int64),
+                                              c_void_p]),
     "litho_pupil": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p]),
     "litho_pupil_stack": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_void_p]),
     "litho_pupil_phase": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
@@ -36,6 +38,9 @@ _SIGNATURES = {
                                               c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, POINTER(c_int64)]),
     "litho_abbe_accumulate_opts": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_int,
                                            c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, POINTER(c_int64)]),
+    "litho_abbe_accumulate_weighted": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int64, c_int, c_int,
+                                               c_void_p, c_void_p, c_size_t, c_void_p, c_void_p, c_void_p, POINTER(c_int64),
+                                               c_void_p]),
     "litho_abbe_embedded_size": (c_int, [c_int, c_int, POINTER(c_int)]),
     "litho_abbe_plan_dry_run": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_size_t, c_void_p]),
     "litho_abbe_field": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),

@@ -63,12 +63,15 @@ static constexpr int BOX_ROWS_PER_BLOCK = 8;
 // finish block folds them, stores the words on the device AND into the calling thread's pinned, device-mapped host buffer, and
 // raises a sequence flag there, which the host polls (no copy kernel, no interrupt-driven wake-up for a wait of microseconds).
 //   box blocks  [0, nb_box): BOX_ROWS_PER_BLOCK rows of one plane -> slot {rmin, rmax, cmin, cmax, e9, e10, e11, e12, corner}
-//   extent blocks [nb_box, nb_box + nb_ext): grid-stride over the shift list -> slot {dymin, dymax, dxmin, dxmax}
+//   extent blocks [nb_box, nb_box + nb_ext): grid-stride over the shift list -> slot {dymin, dymax, dxmin, dxmax, .., [8] bad weight}
+// Weighted source (weights != nullptr, same length as the list): the extent blocks also look at every weight and flag a negative,
+// NaN or infinite one; the finish block publishes the flag as word [14] (device and host copy), next to the fourteen plan words
+// and in the same read-back -- no second host wait.
 // ----------------------------------------------------------------------------------
 static constexpr int PLAN_PART = 16;
 __global__ __launch_bounds__(256) void k_plan_gather(const float2* __restrict__ P, int pn, int e_lo, int e_hi, int nb_box_x, int nb_box,
-                                                     const int* __restrict__ shifts, long long S, const int* __restrict__ count_dev,
-                                                     int nb_ext, int* __restrict__ part)
+                                                     const int* __restrict__ shifts, const float* __restrict__ weights, long long S,
+                                                     const int* __restrict__ count_dev, int nb_ext, int* __restrict__ part)
 {
     __shared__ int red[4][9];
     const int b = blockIdx.x, wv = threadIdx.x >> 6;
@@ -97,6 +100,10 @@ __global__ __launch_bounds__(256) void k_plan_gather(const float2* __restrict__ 
         for (long long i = (long long)(b - nb_box) * blockDim.x + threadIdx.x; i < S; i += (long long)nb_ext * blockDim.x) {
             const int dy = shifts[2 * i], dx = shifts[2 * i + 1];
             v[0] = min(v[0], dy); v[1] = max(v[1], dy); v[2] = min(v[2], dx); v[3] = max(v[3], dx);
+            if (weights) {
+                const float wt = weights[i];
+                if (!(wt >= 0.f) || wt > 3.402823466e+38f) v[8] = 1;      // negative, NaN, +Inf
+            }
         }
     }
     for (int k = 0; k < 9; ++k)
@@ -119,10 +126,10 @@ __global__ __launch_bounds__(256) void k_plan_finish(const int* __restrict__ par
                                                      const int* __restrict__ count_dev, int* __restrict__ plan,
                                                      volatile int* host_words, int seq)
 {
-    __shared__ int red[4][13];
+    __shared__ int red[4][14];
     const int wv = threadIdx.x >> 6;
-    // [0..3] box, [4..7] shift extents, [8..11] edge words (plan 9..12), [12] corner
-    int v[13] = {INT_MAX, INT_MIN, INT_MAX, INT_MIN, INT_MAX, INT_MIN, INT_MAX, INT_MIN, INT_MAX, INT_MIN, INT_MAX, INT_MIN, 0};
+    // [0..3] box, [4..7] shift extents, [8..11] edge words (plan 9..12), [12] corner, [13] invalid weight seen
+    int v[14] = {INT_MAX, INT_MIN, INT_MAX, INT_MIN, INT_MAX, INT_MIN, INT_MAX, INT_MIN, INT_MAX, INT_MIN, INT_MAX, INT_MIN, 0, 0};
     for (int b = threadIdx.x; b < nb_box; b += blockDim.x) {
         const int* q = part + (size_t)b * PLAN_PART;
         v[0] = min(v[0], q[0]); v[1] = max(v[1], q[1]); v[2] = min(v[2], q[2]); v[3] = max(v[3], q[3]);
@@ -132,14 +139,15 @@ __global__ __launch_bounds__(256) void k_plan_finish(const int* __restrict__ par
     for (int b = threadIdx.x; b < nb_ext; b += blockDim.x) {
         const int* q = part + (size_t)(nb_box + b) * PLAN_PART;
         v[4] = min(v[4], q[0]); v[5] = max(v[5], q[1]); v[6] = min(v[6], q[2]); v[7] = max(v[7], q[3]);
+        v[13] |= q[8];
     }
-    for (int k = 0; k < 13; ++k)
+    for (int k = 0; k < 14; ++k)
         for (int off = 32; off > 0; off >>= 1) {
             const int o = __shfl_xor(v[k], off);
-            v[k] = k == 12 ? (v[k] | o) : (k & 1) ? max(v[k], o) : min(v[k], o);
+            v[k] = k >= 12 ? (v[k] | o) : (k & 1) ? max(v[k], o) : min(v[k], o);
         }
     if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 13; ++k) red[wv][k] = v[k];
+        for (int k = 0; k < 14; ++k) red[wv][k] = v[k];
     __syncthreads();
     // thread k < 14 folds and publishes plan word k (the stores into host memory are PCIe writes: one thread doing all fourteen
     // in a row took 9 us); words: [0..7] as gathered, [8] count, [9..12] = gathered [8..11], [13] = corner flag
@@ -158,6 +166,14 @@ __global__ __launch_bounds__(256) void k_plan_finish(const int* __restrict__ par
             for (int i = 1; i < 4; ++i) a = src == 12 ? (a | red[i][src]) : (src & 1) ? max(a, red[i][src]) : min(a, red[i][src]);
             word = src == 12 ? (a ? 1 : 0) : a;
         }
+        plan[k] = word;
+        if (host_words) {
+            host_words[k] = word;
+            __threadfence_system();
+        }
+    }
+    if (k == PLAN_WORDS) {                                        // word [14]: an invalid weight was seen (weighted calls)
+        const int word = (red[0][13] | red[1][13] | red[2][13] | red[3][13]) ? 1 : 0;
         plan[k] = word;
         if (host_words) {
             host_words[k] = word;
@@ -225,10 +241,17 @@ static hipError_t launch_slab_reduce(const float* slab, float* out, int pn, int 
 //   dI[qy, qx] = Re(2 i^qx Gprof[qy]) for odd qx  +  Re(2 i^qy Hprof[qx]) for odd qy        (centred q)
 // to the band-limited interpolation of the coarse image.  (Derivation and a numpy check: DESIGN.md.)
 // ----------------------------------------------------------------------------------
+// Weighted source (WT): the edge products are quadratic in A_s = sqrt(w_s) P M[. + d_s], so each point's products carry w_s --
+// applied to u (one factor of the product), so that w = 1 is the unweighted arithmetic exactly and w = 4 scales it exactly.
+// (The weights arrive as a trailing parameter pack, empty for the unweighted instantiation -- see k_xpass_abbe.)
+template <typename... Wt>
 __global__ __launch_bounds__(256) void k_nyquist_edges(const float2* __restrict__ P, const float2* __restrict__ M,
                                                        const int* __restrict__ shifts, long long S, EdgeGeom eg,
-                                                       float2* __restrict__ partial)
+                                                       float2* __restrict__ partial, Wt... wts)
 {
+    constexpr bool WT = sizeof...(Wt) != 0;
+    static_assert(sizeof...(Wt) <= 1, "one weight list");
+    [[maybe_unused]] const float* weights = pack_weights(wts...);
     __shared__ float2 su[2][EDGE_MAX], sv[2][EDGE_MAX];
     const int t = threadIdx.x;
     const int edge = t >> 7, lt = t & 127;                     // threads 0..127: edge 0 (kappa and loads), 128..255: edge 1
@@ -256,7 +279,13 @@ __global__ __launch_bounds__(256) void k_nyquist_edges(const float2* __restrict_
                 mu = edge == 0 ? M[(size_t)(i + dy) * eg.pn + eg.c + eg.h + dx] : M[(size_t)(eg.c + eg.h + dy) * eg.pn + i + dx];
             if (pvv.x != 0.f || pvv.y != 0.f)
                 mv = edge == 0 ? M[(size_t)(i + dy) * eg.pn + eg.c - eg.h + dx] : M[(size_t)(eg.c - eg.h + dy) * eg.pn + i + dx];
-            su[edge][lt] = cmul(pu, mu);
+            if constexpr (WT) {
+                const float wt = weights[s];
+                const float2 u = cmul(pu, mu);
+                su[edge][lt] = make_float2(wt * u.x, wt * u.y);
+            } else {
+                su[edge][lt] = cmul(pu, mu);
+            }
             sv[edge][lt] = cmul(pvv, mv);
         }
         __syncthreads();
@@ -525,15 +554,15 @@ static int read_words(const int* dev, int* host, int n, hipStream_t st)
     if (dst != host) memcpy(host, dst, n * sizeof(int));
     return LITHO_OK;
 }
-// Reads the plan words back.
-static int read_plan(const Workspace& w, int host[PLAN_WORDS], hipStream_t st) { return read_words(w.plan, host, PLAN_WORDS, st); }
 
 // The plan words of a call: one gathering launch over the pupil stack and the shift list, one single-block finish that also
 // publishes the words into this thread's pinned buffer, and the host's wait for its sequence flag.  The partial slots live in
 // the head of T (free until the source-point loop starts).
-static int gather_plan(const Workspace& w, const float2* P, int planes, int pn, int pe, const int* shifts, int64_t S,
-                       const int* count_dev, int pl[PLAN_WORDS], hipStream_t st)
+// weights (may be nullptr) / bad_weight: a weighted call's validity check rides along (word [14], see k_plan_gather).
+static int gather_plan(const Workspace& w, const float2* P, int planes, int pn, int pe, const int* shifts, const float* weights,
+                       int64_t S, const int* count_dev, int pl[PLAN_WORDS], int* bad_weight, hipStream_t st)
 {
+    *bad_weight = 0;
     const int nb_box_x = (pn + BOX_ROWS_PER_BLOCK - 1) / BOX_ROWS_PER_BLOCK, nb_box = nb_box_x * planes;
     int nb_ext = (int)((S + 1023) / 1024);
     nb_ext = nb_ext < 1 ? 1 : (nb_ext > 256 ? 256 : nb_ext);
@@ -544,7 +573,7 @@ static int gather_plan(const Workspace& w, const float2* P, int planes, int pn, 
     int* const dp = (pw.dp && hipGetDevice(&cur) == hipSuccess && cur == pw.dev) ? pw.dp : nullptr;
     const int seq = dp ? (pw.seq = pw.seq == INT_MAX ? 1 : pw.seq + 1) : 0;
     hipLaunchKernelGGL(k_plan_gather, dim3(nb_box + nb_ext), dim3(256), 0, st, P, pn, pn / 2 - pe / 4, pn / 2 + pe / 4, nb_box_x, nb_box,
-                       shifts, (long long)S, count_dev, nb_ext, part);
+                       shifts, weights, (long long)S, count_dev, nb_ext, part);
     hipLaunchKernelGGL(k_plan_finish, dim3(1), dim3(256), 0, st, part, nb_box, nb_ext, (long long)S, count_dev, w.plan,
                        (volatile int*)dp, seq);
     HIP_TRY(hipGetLastError());
@@ -560,11 +589,17 @@ static int gather_plan(const Workspace& w, const float2* P, int planes, int pn, 
         }
         if (seen) {
             for (int k = 0; k < PLAN_WORDS; ++k) pl[k] = hw[k];
+            *bad_weight = hw[PLAN_WORDS];
             return LITHO_OK;
         }
         // (a mapping the device could not write: fall through to the copy)
     }
-    return read_plan(w, pl, st);
+    int words[PLAN_WORDS + 1];
+    const int rc = read_words(w.plan, words, PLAN_WORDS + 1, st);
+    if (rc) return rc;
+    for (int k = 0; k < PLAN_WORDS; ++k) pl[k] = words[k];
+    *bad_weight = words[PLAN_WORDS];
+    return LITHO_OK;
 }
 
 // HIP events of one profiled call; destroyed on every exit path.
@@ -630,8 +665,8 @@ static hipError_t zero_slabs(float* slab, int pc, int G, int used, size_t slab_p
 // is a few microseconds of idle device (config 1: 26 us of a 500 us image, profiles/r06_cfg1_timeline.txt); behind it they
 // are issued while the x-pass runs.
 static int accumulate_chunk(const AbbePlan& pp, const SizeOps* ops, const Workspace& w, const float2* twtab,
-                            const float2* M, const float2* Pc, int pc, const int* shifts, int64_t S, int pn, float* dst,
-                            bool zero_dst, hipStream_t st, MarkList& marks, int64_t& nx)
+                            const float2* M, const float2* Pc, int pc, const int* shifts, const float* weights, int64_t S, int pn,
+                            float* dst, bool zero_dst, hipStream_t st, MarkList& marks, int64_t& nx)
 {
     const PassGeom& g = pp.g;
     const int variant = pp.variant, G = pp.G, xchunk = pp.xchunk;
@@ -642,6 +677,7 @@ static int accumulate_chunk(const AbbePlan& pp, const SizeOps* ops, const Worksp
     for (int64_t s0 = 0; s0 < S; s0 += bs) {
         const int nb = (int)((S - s0 < bs) ? (S - s0) : bs);
         const int* sh = shifts + 2 * s0;
+        const float* wt = weights ? weights + s0 : nullptr;    // weighted source: one weight per point, batched with the shifts
         if (fresh) { marks.add(-1, 0); fresh = false; }
         // ---- x-pass: T item (plane q of the chunk, point s) = q * nb + s
         for (int q = 0; q < pc;) {
@@ -649,19 +685,20 @@ static int accumulate_chunk(const AbbePlan& pp, const SizeOps* ops, const Worksp
             float2* Tq = w.T + (size_t)q * nb * g.t_point;
             int np = 1;
             if (pp.rect_x) {
-                HIP_TRY(ops->xpass_rect(Pq, M, sh, Tq, twtab, g, nb, xchunk, st));
+                HIP_TRY(ops->xpass_rect(Pq, M, sh, wt, Tq, twtab, g, nb, xchunk, st));
             } else if (pp.split_x) {
-                HIP_TRY(ops->xpass_split(Pq, M, sh, Tq, twtab, g, nb, xchunk, st));
+                HIP_TRY(ops->xpass_split(Pq, M, sh, wt, Tq, twtab, g, nb, xchunk, st));
             } else if (pp.fused_x) {
                 np = variant == 0 ? 1 : (pc - q >= 4) ? 4 : (pc - q >= 2 ? 2 : 1);
-                HIP_TRY(ops->xpass_abbe(variant, np, Pq, M, sh, Tq, twtab, g, nb, xchunk, st));
+                HIP_TRY(ops->xpass_abbe(variant, np, Pq, M, sh, wt, Tq, twtab, g, nb, xchunk, st));
             } else if (pp.general) {
                 AbbeLoader ld{Pq, M, sh, nullptr, nullptr, 0, 0};
-                HIP_TRY(ops->xpass_general(ld, Tq, twtab, g, nb, st));
+                HIP_TRY(ops->xpass_general(ld, wt, Tq, twtab, g, nb, st));
             } else if (variant >= 0) {
+                if (wt) return LITHO_E_ARG;                    // (cannot happen: a weighted call clears the w64x knob)
                 HIP_TRY(ops->xpass_w64(Pq, M, sh, Tq, twtab, g, nb, st));
             } else {
-                HIP_TRY(ops->xpass_abbe(-1, 1, Pq, M, sh, Tq, twtab, g, nb, xchunk, st));
+                HIP_TRY(ops->xpass_abbe(-1, 1, Pq, M, sh, wt, Tq, twtab, g, nb, xchunk, st));
             }
             q += np;
         }
@@ -700,8 +737,8 @@ static int accumulate_chunk(const AbbePlan& pp, const SizeOps* ops, const Worksp
 //   2. out += Re( sum_kappa Chat[kappa] w_N^(kappa q) ) / pn^2   (N-point zoom transforms: ops / twtab)
 //   3. Gx, Gy from the box edges of P over the whole source list; out += dI (k_nyquist_apply)
 static int reconstruct_plane(const SizeOps* ops, const SizeOps* ops_c, const Workspace& w, const float2* M,
-                             const float2* Pp, const int* shifts, int64_t S, int pn, int N, const EdgeGeom& eg,
-                             const float* ic, float* out, hipStream_t st)
+                             const float2* Pp, const int* shifts, const float* weights, int64_t S, int pn, int N,
+                             const EdgeGeom& eg, const float* ic, float* out, hipStream_t st)
 {
     // 1. forward transform of the real coarse image (the machinery of the mask-spectrum pre-step, window = everything)
     PassGeom gf;
@@ -725,7 +762,8 @@ static int reconstruct_plane(const SizeOps* ops, const SizeOps* ops_c, const Wor
         // three points made k_nyquist_reduce the larger of the two kernels: config 1, 11 us to fold 4 MB of partials)
         int64_t want = (S + 7) / 8;
         const int chunks = (int)(want < 1 ? 1 : (want > GAM_CHUNKS ? GAM_CHUNKS : want));
-        hipLaunchKernelGGL(k_nyquist_edges, dim3(chunks), dim3(256), 0, st, Pp, M, shifts, (long long)S, eg, w.gam);
+        if (weights) hipLaunchKernelGGL((k_nyquist_edges<const float*>), dim3(chunks), dim3(256), 0, st, Pp, M, shifts, (long long)S, eg, w.gam, weights);
+        else hipLaunchKernelGGL((k_nyquist_edges<>), dim3(chunks), dim3(256), 0, st, Pp, M, shifts, (long long)S, eg, w.gam);
         hipLaunchKernelGGL(k_nyquist_reduce, dim3(2 * 2 * EDGE_MAX / NYQ_RED_IDX), dim3(256), 0, st, w.gam, chunks);
         hipLaunchKernelGGL(k_nyquist_profiles, dim3((pn + 255) / 256, 2), dim3(256), 0, st, w.gam, w.twtab, eg, N);
         hipLaunchKernelGGL(k_nyquist_apply, dim3((pn + 255) / 256, pn), dim3(256), 0, st, out, w.gam, pn);
@@ -736,9 +774,9 @@ static int reconstruct_plane(const SizeOps* ops, const SizeOps* ops_c, const Wor
 
 // Everything after the plan words are known: which kernels run and how the work is batched, the source-point loop, the
 // coarse-grid reconstruction.  `pl` = plan words in THIS grid's coordinates.
-static int accumulate_planned(const float2* M, const float2* P, int planes, const int* shifts, int64_t S, const int pl[PLAN_WORDS],
-                              int pn, int N, float* out, const Workspace& w, const Knobs& kn, const SizeOps* ops, hipStream_t st,
-                              bool tw2_ready = false)
+static int accumulate_planned(const float2* M, const float2* P, int planes, const int* shifts, const float* weights, int64_t S,
+                              const int pl[PLAN_WORDS], int pn, int N, float* out, const Workspace& w, const Knobs& kn,
+                              const SizeOps* ops, hipStream_t st, bool tw2_ready = false)
 {
     int rc;
     if (S <= 0) return LITHO_OK;
@@ -761,14 +799,14 @@ static int accumulate_planned(const float2* M, const float2* P, int planes, cons
         const int pc = (planes - p0 < run.PC) ? planes - p0 : run.PC;
         const float2* Pc = P + (size_t)p0 * plane_elems;
         if (!coarse) {
-            rc = accumulate_chunk(pp, ops, w, w.twtab, M, Pc, pc, shifts, S, pn, out + (size_t)p0 * plane_elems, false, st, marks, nx);
+            rc = accumulate_chunk(pp, ops, w, w.twtab, M, Pc, pc, shifts, weights, S, pn, out + (size_t)p0 * plane_elems, false, st, marks, nx);
             if (rc) return rc;
             continue;
         }
-        rc = accumulate_chunk(pc_plan, ops_c, w, w.twtab2, M, Pc, pc, shifts, S, pn, w.ic, true, st, marks, nx);
+        rc = accumulate_chunk(pc_plan, ops_c, w, w.twtab2, M, Pc, pc, shifts, weights, S, pn, w.ic, true, st, marks, nx);
         if (rc) return rc;
         for (int q = 0; q < pc; ++q) {
-            rc = reconstruct_plane(ops, ops_c, w, M, Pc + (size_t)q * plane_elems, shifts, S, pn, N, eg,
+            rc = reconstruct_plane(ops, ops_c, w, M, Pc + (size_t)q * plane_elems, shifts, weights, S, pn, N, eg,
                                    w.ic + (size_t)q * plane_elems, out + (size_t)(p0 + q) * plane_elems, st);
             if (rc) return rc;
         }
@@ -798,9 +836,9 @@ static int accumulate_planned(const float2* M, const float2* P, int planes, cons
     return LITHO_OK;
 }
 
-static int accumulate_embedded(const float2* M, const float2* P, int planes, const int* shifts, int64_t S, const int pl[PLAN_WORDS],
-                               int pn, int pe, int N, float* out, void* ws, size_t ws_bytes, size_t t_cap, const Knobs& kn,
-                               const SizeOps* ops, hipStream_t st);
+static int accumulate_embedded(const float2* M, const float2* P, int planes, const int* shifts, const float* weights, int64_t S,
+                               const int pl[PLAN_WORDS], int pn, int pe, int N, float* out, void* ws, size_t ws_bytes, size_t t_cap,
+                               const Knobs& kn, const SizeOps* ops, hipStream_t st);
 void launch_embed_c64(const float2* src, int planes, int pn, float2* dst, int pe, hipStream_t st);     // optics.hip
 void launch_crop_add_f32(const float* src, int planes, int pe, float* dst, int pn, hipStream_t st);
 
@@ -809,7 +847,7 @@ void launch_crop_add_f32(const float* src, int planes, int pe, float* dst, int p
 static int abbe_accumulate(const float2* M, const float2* P, int planes, const int* shifts, int64_t S,
                            const int* count_dev, int64_t* count_out, int pn, int N, float* out, void* ws,
                            size_t ws_bytes, hipStream_t st, litho_abbe_plan* reuse = nullptr,
-                           const litho_abbe_options* opts = nullptr)
+                           const litho_abbe_options* opts = nullptr, const float* weights = nullptr)
 {
     int rc = check_sizes(pn, N);
     if (rc) return rc;
@@ -821,7 +859,11 @@ static int abbe_accumulate(const float2* M, const float2* P, int planes, const i
     const SizeOps* ops = size_ops(ilog2(N));
     if (!ops) return LITHO_E_ARG;
     if (opts && (opts->size < (int32_t)sizeof(int32_t) || opts->size > 4096)) return LITHO_E_ARG;
-    const Knobs kn = Knobs::read(opts);
+    Knobs kn = Knobs::read(opts);
+    // Weighted source (weights != nullptr: out += sum_s w_s |E_s|^2, one fp32 weight per source point).  The x-pass applies
+    // sqrt(w_s) (weighted sibling kernels of the families a default plan launches), the Nyquist edge products w_s; everything
+    // else is linear in |E|^2 and unchanged.  The two opt-in x-pass families have no weighted variant: their knobs are ignored.
+    if (weights) { kn.rowpairs = 0; kn.w64x = 0; }
     // the grid this problem runs at: its own, or the padded one of an embedded evaluation (embedded_size) when the workspace
     // has room for it (litho_abbe_workspace_bytes says so; an older, smaller workspace simply runs the problem as it is)
     const int pe = run_size(pn, N, kn, ws_bytes);
@@ -850,8 +892,12 @@ static int abbe_accumulate(const float2* M, const float2* P, int planes, const i
     if (from_record) {
         rec_split = record_load(reuse->words, pl, sw);
     } else {
-        rc = gather_plan(w, P, planes, pn, pe, shifts, S, count_dev, pl, st);      // the ONE host wait of the image path
+        int bad_weight = 0;
+        rc = gather_plan(w, P, planes, pn, pe, shifts, weights, S, count_dev, pl, &bad_weight, st);      // the ONE host wait of the image path
         if (rc) return rc;
+        // a negative, NaN or infinite weight: an error of the planning call, before anything is accumulated (a call planned
+        // from a record does not look again -- the same contract as for `pupil` and `shifts`)
+        if (weights && bad_weight) return LITHO_E_ARG;
         if (reuse) {
             record_store(reuse->words, pl, pe, nullptr);     // (a split, below, stores its ten words too)
             reuse->pn = pn; reuse->N = N; reuse->planes = planes; reuse->valid = 1;
@@ -867,7 +913,9 @@ static int abbe_accumulate(const float2* M, const float2* P, int planes, const i
     const bool nowrap = list_nowrap(pl, pn);
     // A planned call splits exactly when its record says the planning call did: it re-runs the three split kernels (same list,
     // same deterministic result, no read-back) and plans the two parts from the recorded counts and extents.
-    if (split_wanted(kn, nowrap, from_record && !rec_split, S)) {
+    // (A WEIGHTED list that wraps for some of its points is not split: carrying the weights through k_split_write would need
+    // two more list regions in the workspace.  It runs whole on the general path, as with options.split = 0: correct, slower.)
+    if (!weights && split_wanted(kn, nowrap, from_record && !rec_split, S)) {
         // Some shift wraps the pupil around the grid -- usually for a minority of the points of a shifted source.  Split the
         // list (stable, on the device; one more 40-byte read-back) and give each part the path it needs: this function
         // again for the non-wrapping points (pruned box, coarse grid, embedding: 2.5 us per point at 1024^2), the
@@ -904,8 +952,8 @@ static int abbe_accumulate(const float2* M, const float2* P, int planes, const i
                 plp[8] = (int)n;
                 const int* lst = part == 0 ? list_a : list_b;
                 // part 0 cannot wrap (it may run embedded); part 1 wraps by construction: general mode at this size
-                if (part == 0 && pe != pn) rc = accumulate_embedded(M, P, planes, lst, n, plp, pn, pe, N, out, ws, ws_bytes, list_start, kn, ops, st);
-                else rc = accumulate_planned(M, P, planes, lst, n, plp, pn, N, out, ws_split, kn, ops, st, tw2_ready);
+                if (part == 0 && pe != pn) rc = accumulate_embedded(M, P, planes, lst, nullptr, n, plp, pn, pe, N, out, ws, ws_bytes, list_start, kn, ops, st);
+                else rc = accumulate_planned(M, P, planes, lst, nullptr, n, plp, pn, N, out, ws_split, kn, ops, st, tw2_ready);
                 if (rc) return rc;
                 launches += g_last_plan[6];
             }
@@ -914,16 +962,16 @@ static int abbe_accumulate(const float2* M, const float2* P, int planes, const i
             return LITHO_OK;
         }
     }
-    if (pe == pn || !nowrap || kn.force_general) return accumulate_planned(M, P, planes, shifts, S, pl, pn, N, out, w, kn, ops, st, tw2_ready);
-    return accumulate_embedded(M, P, planes, shifts, S, pl, pn, pe, N, out, ws, ws_bytes, 0, kn, ops, st);
+    if (pe == pn || !nowrap || kn.force_general) return accumulate_planned(M, P, planes, shifts, weights, S, pl, pn, N, out, w, kn, ops, st, tw2_ready);
+    return accumulate_embedded(M, P, planes, shifts, weights, S, pl, pn, pe, N, out, ws, ws_bytes, 0, kn, ops, st);
 }
 
 // The embedded evaluation of a non-wrapping source list: pad into the scratch behind the padded size's workspace regions, run at
 // pe, add the centre back.  t_cap > 0: byte offset in the workspace at which the T region must end (the lists of a split
 // source list follow it).
-static int accumulate_embedded(const float2* M, const float2* P, int planes, const int* shifts, int64_t S, const int pl[PLAN_WORDS],
-                               int pn, int pe, int N, float* out, void* ws, size_t ws_bytes, size_t t_cap, const Knobs& kn,
-                               const SizeOps* ops, hipStream_t st)
+static int accumulate_embedded(const float2* M, const float2* P, int planes, const int* shifts, const float* weights, int64_t S,
+                               const int pl[PLAN_WORDS], int pn, int pe, int N, float* out, void* ws, size_t ws_bytes, size_t t_cap,
+                               const Knobs& kn, const SizeOps* ops, hipStream_t st)
 {
     int rc;
 
@@ -945,7 +993,7 @@ static int accumulate_embedded(const float2* M, const float2* P, int planes, con
         const int pc = planes - p0 < COARSE_PLANES ? planes - p0 : COARSE_PLANES;
         launch_embed_c64(P + (size_t)p0 * pn * pn, pc, pn, P2, pe, st);
         HIP_TRY(zero_async(O2, (size_t)pc * e2 * sizeof(float), st));
-        rc = accumulate_planned(M2, P2, pc, shifts, S, pl2, pe, N, O2, w2, kn, ops, st);
+        rc = accumulate_planned(M2, P2, pc, shifts, weights, S, pl2, pe, N, O2, w2, kn, ops, st);
         if (rc) return rc;
         launch_crop_add_f32(O2, pc, pe, out + (size_t)p0 * pn * pn, pn, st);
         HIP_TRY(hipGetLastError());
@@ -963,7 +1011,8 @@ static int abbe_field(const float2* pf, const float2* M, int pn, int N, float2* 
     if (!carve(ws, ws_bytes, pn, N, w)) return LITHO_E_WORKSPACE;
     hipLaunchKernelGGL(k_twiddle_table, dim3((N + 255) / 256), dim3(256), 0, st, w.twtab, N);
     int pl[PLAN_WORDS];
-    rc = gather_plan(w, pf, 1, pn, pn, nullptr, 0, nullptr, pl, st);      // the pupil's support box (no shift list)
+    int unused = 0;
+    rc = gather_plan(w, pf, 1, pn, pn, nullptr, nullptr, 0, nullptr, pl, &unused, st);      // the pupil's support box (no shift list)
     if (rc) return rc;
     if (pl[1] < pl[0]) {                                      // zero pupil -> zero field
         HIP_TRY(zero_async(field, (size_t)pn * pn * sizeof(float2), st));
@@ -975,7 +1024,7 @@ static int abbe_field(const float2* pf, const float2* M, int pn, int N, float2* 
     AbbeLoader ld{pf, M, w.plan + 16, nullptr, nullptr, 0, 0};
     const SizeOps* ops = size_ops(ilog2(N));
     if (!ops) return LITHO_E_ARG;
-    HIP_TRY(ops->xpass_general(ld, w.T, w.twtab, g, 1, st));
+    HIP_TRY(ops->xpass_general(ld, nullptr, w.T, w.twtab, g, 1, st));
     HIP_TRY(ops->ypass_field(+1, w.T, field, w.twtab, g, st));
     return LITHO_OK;
 }
@@ -1079,6 +1128,15 @@ int litho_abbe_accumulate_opts(const void* maskFT, const void* pupil, int planes
 {
     return litho::abbe_accumulate((const float2*)maskFT, (const float2*)pupil, planes, shifts, capacity, count_dev,
                                   count_host, pn, N, out, workspace, workspace_bytes, (hipStream_t)stream, plan, options);
+}
+
+int litho_abbe_accumulate_weighted(const void* maskFT, const void* pupil, int planes, const int32_t* shifts,
+                                   const int32_t* count_dev, int64_t capacity, int pn, int N, float* out, void* workspace,
+                                   size_t workspace_bytes, void* stream, litho_abbe_plan* plan,
+                                   const litho_abbe_options* options, int64_t* count_host, const float* weights)
+{
+    return litho::abbe_accumulate((const float2*)maskFT, (const float2*)pupil, planes, shifts, capacity, count_dev,
+                                  count_host, pn, N, out, workspace, workspace_bytes, (hipStream_t)stream, plan, options, weights);
 }
 
 int litho_abbe_field(const void* pf, const void* maskFT, int pn, int N, void* field, void* workspace,

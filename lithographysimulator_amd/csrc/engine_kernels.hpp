@@ -107,11 +107,24 @@ __device__ __forceinline__ void diag_keep(float2 v, unsigned o) { asm volatile("
 // a held output row in registers: two workgroups per CU instead of three.
 // (Those figures are with plain stores; since the T stores carry sc1 -- no write-allocate fetch -- one row per workgroup on
 // 8-column tiles takes 19.6 us per item itself and the pairs 19.8: the knob stays as a parity-tested variant, nothing more.)
-template <int LOG2N, int RL, bool PRUNED, int NP, int RP = 1>
+// Weighted source (I = sum_s w_s |E_s|^2): the weights reach the x-pass kernels as a trailing parameter PACK Wt -- empty for the
+// unweighted instantiation, whose signature, name as tools print it ("k_xpass_abbe<11, 1, true, 1, 1>") and machine code are
+// thereby exactly what they were before weights existed; `const float*` for the weighted one ("k_xpass_abbe<11, 1, true, 1, 1,
+// float const*>").  The gathered mask-spectrum window of point s is scaled by the amplitude a_s = sqrt(weights[s]) BEFORE the
+// P * M product (one scalar per source point, read next to its shift and prefetched with the next window), so a_s = 1
+// reproduces the unweighted arithmetic operation for operation and everything downstream -- T, the y-pass, the slabs, the
+// coarse-grid reconstruction -- is unchanged.
+__device__ __forceinline__ const float* pack_weights() { return nullptr; }
+__device__ __forceinline__ const float* pack_weights(const float* w) { return w; }
+
+template <int LOG2N, int RL, bool PRUNED, int NP, int RP = 1, typename... Wt>
 __global__ __launch_bounds__(Launch<LOG2N>::THREADS, (RP == 2 ? Launch<LOG2N>::WAVES / Launch<LOG2N>::WG_PER_CU * 2 : Launch<LOG2N>::WAVES)) void k_xpass_abbe(
     const float2* __restrict__ P, const float2* __restrict__ M, const int* __restrict__ shifts,
-    float2* __restrict__ Tbuf, const float2* __restrict__ twtab, PassGeom g, int nb, int chunk)
+    float2* __restrict__ Tbuf, const float2* __restrict__ twtab, PassGeom g, int nb, int chunk, Wt... wts)
 {
+    constexpr bool WT = sizeof...(Wt) != 0;
+    static_assert(sizeof...(Wt) <= 1 && !(WT && RP == 2), "weighted x-pass: one weight list, one row per workgroup (a weighted call ignores the row-pair knob)");
+    [[maybe_unused]] const float* weights = pack_weights(wts...);
     // NP = planes of a through-focus stack handled by this workgroup (P points at the first of them,
     // planes are pn*pn apart).  The mask-spectrum window of a source point is gathered ONCE and multiplied by
     // the NP pupil rows held in registers; T item (plane p, point s) = p * nb + s.
@@ -194,7 +207,9 @@ __global__ __launch_bounds__(Launch<LOG2N>::THREADS, (RP == 2 ? Launch<LOG2N>::W
 
     int flip = 0;
     float2 mnext[16];
+    [[maybe_unused]] float wnext = 1.f;           // WT: weight of the point whose window sits in mnext
     if (s_begin < s_end) load_window(s_begin, 0, mnext);
+    if constexpr (WT) { if (s_begin < s_end) wnext = weights[s_begin]; }
     // Consume the first window HERE, so that the compiler waits for it in the preheader.  Otherwise the loop header
     // inherits "loads may be pending" from the entry edge and opens every iteration with s_waitcnt vmcnt(0) -- which,
     // with vmcnt shared between loads and stores on gfx950, also waits for the previous iteration's eight T stores
@@ -226,6 +241,8 @@ __global__ __launch_bounds__(Launch<LOG2N>::THREADS, (RP == 2 ? Launch<LOG2N>::W
                 constexpr int e = decltype(e_)::value;
                 if constexpr ((IN >> e) & 1u) mv[e] = mnext[e];
             });
+            [[maybe_unused]] float amp = 1.f;
+            if constexpr (WT) amp = sqrtf(wnext);
 #ifndef LITHO_XPASS_NO_PREFETCH
             // the next window is in flight while this one's NP transforms run (the LDS-only
             // barriers of the FFT do not drain vmcnt); the last iteration re-reads its own window
@@ -235,6 +252,13 @@ __global__ __launch_bounds__(Launch<LOG2N>::THREADS, (RP == 2 ? Launch<LOG2N>::W
             if constexpr (rr + 1 < RP) load_window(s, rr + 1, mnext);
             else if (s + 1 < s_end) load_window(s + 1, 0, mnext);
 #endif
+            if constexpr (WT) {
+                wnext = weights[s + 1 < s_end ? s + 1 : s];
+                static_for<0, 16>([&](auto e_) {
+                    constexpr int e = decltype(e_)::value;
+                    if constexpr ((IN >> e) & 1u) mv[e] = make_float2(amp * mv[e].x, amp * mv[e].y);
+                });
+            }
             static_for<0, NP>([&](auto p_) {
                 constexpr int p = decltype(p_)::value;
                 float2 x[16];
@@ -288,11 +312,15 @@ __global__ __launch_bounds__(Launch<LOG2N>::THREADS, (RP == 2 ? Launch<LOG2N>::W
 // the adjacent columns 2v and 2v + 1, T is written with 16-byte stores in its usual layout: the y-pass does not
 // know the difference.
 // ----------------------------------------------------------------------------------
-template <int LOG2N>
+// (Wt: weighted source, the window is scaled by sqrt(weights[s]) before both products -- see k_xpass_abbe.)
+template <int LOG2N, typename... Wt>
 __global__ __launch_bounds__(Launch<LOG2N - 1>::THREADS, Launch<LOG2N - 1>::WAVES) void k_xpass_split(
     const float2* __restrict__ P, const float2* __restrict__ M, const int* __restrict__ shifts,
-    float2* __restrict__ Tbuf, const float2* __restrict__ twtab, PassGeom g, int nb, int chunk)
+    float2* __restrict__ Tbuf, const float2* __restrict__ twtab, PassGeom g, int nb, int chunk, Wt... wts)
 {
+    constexpr bool WT = sizeof...(Wt) != 0;
+    static_assert(sizeof...(Wt) <= 1, "one weight list");
+    [[maybe_unused]] const float* weights = pack_weights(wts...);
     using F = LineFFT<LOG2N - 1, +1>;
     using LC = Launch<LOG2N - 1>;
     static_assert(LC::L == 1, "split x-pass: one row per workgroup");
@@ -346,6 +374,13 @@ __global__ __launch_bounds__(Launch<LOG2N - 1>::THREADS, Launch<LOG2N - 1>::WAVE
             constexpr int e = decltype(e_)::value;
             if constexpr ((IN >> e) & 1u) mv[e] = buf_load_c64(rM, koff[e] != BUF_OOB ? (mrow + koff[e]) * 8u : BUF_OOB);
         });
+        if constexpr (WT) {
+            const float amp = sqrtf(weights[s]);
+            static_for<0, 16>([&](auto e_) {
+                constexpr int e = decltype(e_)::value;
+                if constexpr ((IN >> e) & 1u) mv[e] = make_float2(amp * mv[e].x, amp * mv[e].y);
+            });
+        }
         float2 x[16], even[16];
         static_for<0, 16>([&](auto e_) {
             constexpr int e = decltype(e_)::value;
@@ -443,6 +478,27 @@ struct AbbeLoader {
         int pc = (col - dx) % g.pn;
         if (pc < 0) pc += g.pn;
         return cmul(prow[pc], mrow[col]);
+    }
+};
+
+// Loader: the same product for a weighted source: the mask-spectrum sample is scaled by a_s = sqrt(weights[s]) before the
+// product (a_s = 1: AbbeLoader's arithmetic exactly).  A loader type of its own, so k_xpass<.., AbbeLoader> is untouched.
+struct AbbeLoaderW {
+    AbbeLoader base;
+    const float* weights;    // [nb] of this batch
+    float amp, pad_;
+    __device__ __forceinline__ void begin_line(int s, int a, const PassGeom& g) {
+        base.begin_line(s, a, g);
+        amp = sqrtf(weights[s]);
+    }
+    __device__ __forceinline__ float2 load(int k, const PassGeom& g) const {
+        const int col = k + g.c;
+        const float2 m = base.mrow[col];
+        const float2 ms = make_float2(amp * m.x, amp * m.y);
+        if (!g.general) return cmul(base.prow[col], ms);
+        int pc = (col - base.dx) % g.pn;
+        if (pc < 0) pc += g.pn;
+        return cmul(base.prow[pc], ms);
     }
 };
 
@@ -719,15 +775,17 @@ struct SizeOps {
     // variant: -1 = generic (any even pn, runtime predication); 0/1/2 = pruned, RL = log2(N/pn).
     // np = planes fused into the launch (1, 2 or 4; the generic variant takes 1 only): P points at the first
     // plane, T item (p, s) = p * nb + s.
-    hipError_t (*xpass_abbe)(int variant, int np, const float2* P, const float2* M, const int* shifts, float2* T,
+    // wts (here and below): nullptr, or the weights [nb] of the batch -- then the weighted instantiation runs
+    // (k_xpass_*<.., float const*>, k_xpass<.., AbbeLoaderW>); the unweighted launches are what they were.
+    hipError_t (*xpass_abbe)(int variant, int np, const float2* P, const float2* M, const int* shifts, const float* wts, float2* T,
                              const float2* tw, const PassGeom& g, int nb, int chunk, hipStream_t st);
-    hipError_t (*xpass_general)(const AbbeLoader& ld, float2* T, const float2* tw, const PassGeom& g, int nb,
+    hipError_t (*xpass_general)(const AbbeLoader& ld, const float* wts, float2* T, const float2* tw, const PassGeom& g, int nb,
                                 hipStream_t st);
     // N = 2 pn as two N/2-point transforms per row (k_xpass_split; N = 8192 only): hipErrorNotSupported otherwise
-    hipError_t (*xpass_split)(const float2* P, const float2* M, const int* shifts, float2* T, const float2* tw,
+    hipError_t (*xpass_split)(const float2* P, const float2* M, const int* shifts, const float* wts, float2* T, const float2* tw,
                               const PassGeom& g, int nb, int chunk, hipStream_t st);
     // several adjacent box rows per wave, whole-line T stores (k_xpass_rect; N = 512..2048, 8-column tiles)
-    hipError_t (*xpass_rect)(const float2* P, const float2* M, const int* shifts, float2* T, const float2* tw,
+    hipError_t (*xpass_rect)(const float2* P, const float2* M, const int* shifts, const float* wts, float2* T, const float2* tw,
                              const PassGeom& g, int nb, int chunk, hipStream_t st);
     hipError_t (*xpass_real_fwd)(const RealImageLoader& ld, float2* T, const float2* tw, const PassGeom& g,
                                  hipStream_t st);
@@ -773,7 +831,7 @@ hipError_t launch_ypass_wave(const float2* T, float* slab, const float2* tw, con
                              int G, int gstride, hipStream_t st);
 
 template <int LOG2N>
-hipError_t launch_xpass_rect(const float2* P, const float2* M, const int* shifts, float2* T, const float2* tw,
+hipError_t launch_xpass_rect(const float2* P, const float2* M, const int* shifts, const float* wts, float2* T, const float2* tw,
                              const PassGeom& g, int nb, int chunk, hipStream_t st);
 
 template <int LOG2N>
@@ -781,9 +839,23 @@ struct SizeImpl {
     using LC = Launch<LOG2N>;
 
     template <int RL, bool PRUNED, int NP, int RP = 1>
-    static hipError_t xa(const float2* P, const float2* M, const int* shifts, float2* T, const float2* tw,
+    static hipError_t xa(const float2* P, const float2* M, const int* shifts, const float* wts, float2* T, const float2* tw,
                          const PassGeom& g, int nb, int chunk, hipStream_t st)
     {
+        if (wts) {
+            if constexpr (RP == 1) {
+                static LdsOnce once_wt;
+                auto kern = k_xpass_abbe<LOG2N, RL, PRUNED, NP, 1, const float*>;
+                hipError_t e = set_lds(once_wt, kern, LC::LDS_BYTES);
+                if (e != hipSuccess) return e;
+                dim3 grid(LC::L == 1 ? (g.rows + 31) / 32 * 32 : (g.rows + LC::L - 1) / LC::L, (nb + chunk - 1) / chunk);
+                hipLaunchKernelGGL(kern, grid, dim3(LC::THREADS), LC::LDS_BYTES, st, P, M, shifts, T, tw, g, nb, chunk, wts);
+                note_kernel(0, PRUNED ? "k_xpass_abbe<%d, %d, true, %d, 1, float const*>" : "k_xpass_abbe<%d, %d, false, %d, 1, float const*>", LOG2N, RL, NP);
+                return hipGetLastError();
+            } else {
+                return hipErrorInvalidValue;                   // (a weighted call never plans row pairs)
+            }
+        }
         static LdsOnce once;
         auto kern = k_xpass_abbe<LOG2N, RL, PRUNED, NP, RP>;
         hipError_t e = set_lds(once, kern, LC::LDS_BYTES);
@@ -796,34 +868,45 @@ struct SizeImpl {
         return hipGetLastError();
     }
     template <int RL>
-    static hipError_t xa_np(int np, const float2* P, const float2* M, const int* shifts, float2* T, const float2* tw,
+    static hipError_t xa_np(int np, const float2* P, const float2* M, const int* shifts, const float* wts, float2* T, const float2* tw,
                             const PassGeom& g, int nb, int chunk, hipStream_t st)
     {
         if constexpr (LOG2N == 12 && RL == 0) {
-            if (np == 1 && g.row_pairs) return xa<RL, true, 1, 2>(P, M, shifts, T, tw, g, nb, chunk, st);
+            if (np == 1 && g.row_pairs) return xa<RL, true, 1, 2>(P, M, shifts, wts, T, tw, g, nb, chunk, st);
         }
-        if (np == 1) return xa<RL, true, 1>(P, M, shifts, T, tw, g, nb, chunk, st);
+        if (np == 1) return xa<RL, true, 1>(P, M, shifts, wts, T, tw, g, nb, chunk, st);
         if constexpr (RL >= 1) {       // RL = 0 (N = pn) has 9 live input slots: 2 or 4 pupil rows would spill
-            if (np == 2) return xa<RL, true, 2>(P, M, shifts, T, tw, g, nb, chunk, st);
-            if (np == 4) return xa<RL, true, 4>(P, M, shifts, T, tw, g, nb, chunk, st);
+            if (np == 2) return xa<RL, true, 2>(P, M, shifts, wts, T, tw, g, nb, chunk, st);
+            if (np == 4) return xa<RL, true, 4>(P, M, shifts, wts, T, tw, g, nb, chunk, st);
         }
         return hipErrorInvalidValue;
     }
-    static hipError_t xpass_abbe(int variant, int np, const float2* P, const float2* M, const int* shifts, float2* T,
+    static hipError_t xpass_abbe(int variant, int np, const float2* P, const float2* M, const int* shifts, const float* wts, float2* T,
                                  const float2* tw, const PassGeom& g, int nb, int chunk, hipStream_t st)
     {
         switch (variant) {
-            case 0: return xa_np<0>(np, P, M, shifts, T, tw, g, nb, chunk, st);
-            case 1: return xa_np<1>(np, P, M, shifts, T, tw, g, nb, chunk, st);
-            case 2: return xa_np<2>(np, P, M, shifts, T, tw, g, nb, chunk, st);
+            case 0: return xa_np<0>(np, P, M, shifts, wts, T, tw, g, nb, chunk, st);
+            case 1: return xa_np<1>(np, P, M, shifts, wts, T, tw, g, nb, chunk, st);
+            case 2: return xa_np<2>(np, P, M, shifts, wts, T, tw, g, nb, chunk, st);
             default:
                 if (np != 1) return hipErrorInvalidValue;
-                return xa<-1, false, 1>(P, M, shifts, T, tw, g, nb, chunk, st);
+                return xa<-1, false, 1>(P, M, shifts, wts, T, tw, g, nb, chunk, st);
         }
     }
-    static hipError_t xpass_general(const AbbeLoader& ld, float2* T, const float2* tw, const PassGeom& g, int nb,
+    static hipError_t xpass_general(const AbbeLoader& ld, const float* wts, float2* T, const float2* tw, const PassGeom& g, int nb,
                                     hipStream_t st)
     {
+        if (wts) {
+            static LdsOnce once_wt;
+            auto kern = k_xpass<LOG2N, +1, AbbeLoaderW>;
+            hipError_t e = set_lds(once_wt, kern, LC::LDS_BYTES);
+            if (e != hipSuccess) return e;
+            AbbeLoaderW lw{ld, wts, 1.f, 0.f};
+            hipLaunchKernelGGL(kern, dim3((g.rows + LC::L - 1) / LC::L, nb), dim3(LC::THREADS), LC::LDS_BYTES, st, lw, T,
+                               tw, g);
+            note_kernel(0, "k_xpass<%d, 1, litho::AbbeLoaderW>", LOG2N);
+            return hipGetLastError();
+        }
         static LdsOnce once;
         auto kern = k_xpass<LOG2N, +1, AbbeLoader>;
         hipError_t e = set_lds(once, kern, LC::LDS_BYTES);
@@ -833,11 +916,21 @@ struct SizeImpl {
         note_kernel(0, "k_xpass<%d, 1, litho::AbbeLoader>", LOG2N);
         return hipGetLastError();
     }
-    static hipError_t xpass_split(const float2* P, const float2* M, const int* shifts, float2* T, const float2* tw,
+    static hipError_t xpass_split(const float2* P, const float2* M, const int* shifts, const float* wts, float2* T, const float2* tw,
                                   const PassGeom& g, int nb, int chunk, hipStream_t st)
     {
         if constexpr (LOG2N == 13) {
             using LH = Launch<LOG2N - 1>;
+            if (wts) {
+                static LdsOnce once_wt;
+                auto kern = k_xpass_split<LOG2N, const float*>;
+                hipError_t e = set_lds(once_wt, kern, LH::LDS_BYTES);
+                if (e != hipSuccess) return e;
+                dim3 grid((g.rows + 31) / 32 * 32, (nb + chunk - 1) / chunk);
+                hipLaunchKernelGGL(kern, grid, dim3(LH::THREADS), LH::LDS_BYTES, st, P, M, shifts, T, tw, g, nb, chunk, wts);
+                note_kernel(0, "k_xpass_split<%d, float const*>", LOG2N);
+                return hipGetLastError();
+            }
             static LdsOnce once;
             auto kern = k_xpass_split<LOG2N>;
             hipError_t e = set_lds(once, kern, LH::LDS_BYTES);
@@ -850,10 +943,10 @@ struct SizeImpl {
             return hipErrorNotSupported;
         }
     }
-    static hipError_t xpass_rect(const float2* P, const float2* M, const int* shifts, float2* T, const float2* tw,
+    static hipError_t xpass_rect(const float2* P, const float2* M, const int* shifts, const float* wts, float2* T, const float2* tw,
                                  const PassGeom& g, int nb, int chunk, hipStream_t st)
     {
-        if constexpr (LOG2N >= 9 && LOG2N <= 13) return launch_xpass_rect<LOG2N>(P, M, shifts, T, tw, g, nb, chunk, st);
+        if constexpr (LOG2N >= 9 && LOG2N <= 13) return launch_xpass_rect<LOG2N>(P, M, shifts, wts, T, tw, g, nb, chunk, st);
         else return hipErrorNotSupported;
     }
     static hipError_t xpass_real_fwd(const RealImageLoader& ld, float2* T, const float2* tw, const PassGeom& g,

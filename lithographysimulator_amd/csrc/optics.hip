@@ -73,11 +73,19 @@ __global__ void k_source_bitmap(SourceParams sp, int64_t* __restrict__ bitmap)
 }
 
 // ---- row-major ordered compaction of a bitmap into (dy,dx) pairs (imageformation.py:59)
-__global__ void k_row_counts(const int64_t* __restrict__ bitmap, int pn, int* __restrict__ counts)
+// One set of kernels for both source kinds: an int64 bitmap (lit = non-zero, the reference's argwhere) and a float32 weight map
+// (lit = w > 0; the weight travels with the pair into `weights`).
+__device__ __forceinline__ bool source_lit(int64_t v) { return v != 0; }
+__device__ __forceinline__ bool source_lit(float v) { return v > 0.f; }
+__device__ __forceinline__ void source_keep(float*, long long, int64_t) {}
+__device__ __forceinline__ void source_keep(float* weights, long long pos, float v) { weights[pos] = v; }
+
+template <typename Px>
+__global__ void k_row_counts(const Px* __restrict__ bitmap, int pn, int* __restrict__ counts)
 {
     const int row = blockIdx.x;
     int cnt = 0;
-    for (int c = threadIdx.x; c < pn; c += blockDim.x) cnt += bitmap[(size_t)row * pn + c] != 0;
+    for (int c = threadIdx.x; c < pn; c += blockDim.x) cnt += source_lit(bitmap[(size_t)row * pn + c]);
     for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
     __shared__ int part[4];
     if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = cnt;
@@ -107,8 +115,9 @@ __global__ void k_row_scan(int* __restrict__ counts, int pn)
     if (threadIdx.x == 1023) counts[pn] = sums[1023];
 }
 
-__global__ void k_row_write(const int64_t* __restrict__ bitmap, int pn, const int* __restrict__ offsets,
-                            int32_t* __restrict__ shifts, long long capacity)
+template <typename Px>
+__global__ void k_row_write(const Px* __restrict__ bitmap, int pn, const int* __restrict__ offsets,
+                            int32_t* __restrict__ shifts, float* __restrict__ weights, long long capacity)
 {
     const int row = blockIdx.x;          // one wave per row keeps the order trivially
     const int lane = threadIdx.x;
@@ -116,11 +125,12 @@ __global__ void k_row_write(const int64_t* __restrict__ bitmap, int pn, const in
     const int c = pn / 2;
     for (int c0 = 0; c0 < pn; c0 += 64) {
         const int col = c0 + lane;
-        const bool lit = col < pn && bitmap[(size_t)row * pn + col] != 0;
+        const Px px = col < pn ? bitmap[(size_t)row * pn + col] : Px(0);
+        const bool lit = source_lit(px);
         const unsigned long long m = __ballot(lit);
         if (lit) {
             const long long pos = base + __popcll(m & ((1ull << lane) - 1ull));
-            if (pos < capacity) { shifts[2 * pos] = row - c; shifts[2 * pos + 1] = col - c; }
+            if (pos < capacity) { shifts[2 * pos] = row - c; shifts[2 * pos + 1] = col - c; source_keep(weights, pos, px); }
         }
         base += __popcll(m);
     }
@@ -130,8 +140,9 @@ __global__ void k_row_write(const int64_t* __restrict__ bitmap, int pn, const in
 // itself (at most 64 strided loads per lane) -- two launches per compaction instead of three; `counts` stays raw, the last row
 // leaves the total in counts[pn] (litho_abbe_accumulate_counted's count_dev).
 static constexpr int ROW_SUM_MAX = 4096;
-__global__ void k_row_write_sum(const int64_t* __restrict__ bitmap, int pn, int* __restrict__ counts,
-                                int32_t* __restrict__ shifts, long long capacity)
+template <typename Px>
+__global__ void k_row_write_sum(const Px* __restrict__ bitmap, int pn, int* __restrict__ counts,
+                                int32_t* __restrict__ shifts, float* __restrict__ weights, long long capacity)
 {
     const int row = blockIdx.x;
     const int lane = threadIdx.x;
@@ -142,11 +153,12 @@ __global__ void k_row_write_sum(const int64_t* __restrict__ bitmap, int pn, int*
     const int c = pn / 2;
     for (int c0 = 0; c0 < pn; c0 += 64) {
         const int col = c0 + lane;
-        const bool lit = col < pn && bitmap[(size_t)row * pn + col] != 0;
+        const Px px = col < pn ? bitmap[(size_t)row * pn + col] : Px(0);
+        const bool lit = source_lit(px);
         const unsigned long long m = __ballot(lit);
         if (lit) {
             const long long pos = base + __popcll(m & ((1ull << lane) - 1ull));
-            if (pos < capacity) { shifts[2 * pos] = row - c; shifts[2 * pos + 1] = col - c; }
+            if (pos < capacity) { shifts[2 * pos] = row - c; shifts[2 * pos + 1] = col - c; source_keep(weights, pos, px); }
         }
         base += __popcll(m);
     }
@@ -437,18 +449,18 @@ int litho_source_bitmap(int kind, double sigma_in, double sigma_out, int pn, dou
     return LITHO_OK;
 }
 
-int litho_source_compact(const int64_t* bitmap, int pn, int32_t* shifts, int64_t capacity, int32_t* scratch,
-                         int64_t* count_host, void* stream)
+extern "C++" {
+template <typename Px>
+static int source_compact(const Px* bitmap, int pn, int32_t* shifts, float* weights, int64_t capacity, int32_t* scratch,
+                          int64_t* count_host, hipStream_t st)
 {
     using namespace litho;
-    if (!bitmap || !shifts || !scratch || pn < 1 || capacity < 0) return LITHO_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_row_counts, dim3(pn), dim3(256), 0, st, bitmap, pn, scratch);
+    hipLaunchKernelGGL(k_row_counts<Px>, dim3(pn), dim3(256), 0, st, bitmap, pn, scratch);
     if (pn <= ROW_SUM_MAX) {
-        hipLaunchKernelGGL(k_row_write_sum, dim3(pn), dim3(64), 0, st, bitmap, pn, scratch, shifts, (long long)capacity);
+        hipLaunchKernelGGL(k_row_write_sum<Px>, dim3(pn), dim3(64), 0, st, bitmap, pn, scratch, shifts, weights, (long long)capacity);
     } else {
         hipLaunchKernelGGL(k_row_scan, dim3(1), dim3(1024), 0, st, scratch, pn);
-        hipLaunchKernelGGL(k_row_write, dim3(pn), dim3(64), 0, st, bitmap, pn, scratch, shifts, (long long)capacity);
+        hipLaunchKernelGGL(k_row_write<Px>, dim3(pn), dim3(64), 0, st, bitmap, pn, scratch, shifts, weights, (long long)capacity);
     }
     HIP_TRY(hipGetLastError());
     if (!count_host) return LITHO_OK;                // asynchronous form: S stays on the device in scratch[pn]
@@ -457,6 +469,21 @@ int litho_source_compact(const int64_t* bitmap, int pn, int32_t* shifts, int64_t
     HIP_TRY(hipStreamSynchronize(st));
     *count_host = total;
     return total > capacity ? LITHO_E_ARG : LITHO_OK;
+}
+}  // extern "C++"
+
+int litho_source_compact(const int64_t* bitmap, int pn, int32_t* shifts, int64_t capacity, int32_t* scratch,
+                         int64_t* count_host, void* stream)
+{
+    if (!bitmap || !shifts || !scratch || pn < 1 || capacity < 0) return LITHO_E_ARG;
+    return source_compact(bitmap, pn, shifts, nullptr, capacity, scratch, count_host, (hipStream_t)stream);
+}
+
+int litho_source_compact_weighted(const float* map, int pn, int32_t* shifts, float* weights, int64_t capacity,
+                                  int32_t* scratch, int64_t* count_host, void* stream)
+{
+    if (!map || !shifts || !weights || !scratch || pn < 2 || (pn & 1) || capacity < 0) return LITHO_E_ARG;
+    return source_compact(map, pn, shifts, weights, capacity, scratch, count_host, (hipStream_t)stream);
 }
 
 // c[j] (fp32 values of the fp16 coefficients, coefficient 4 already rescaled) -> the per-term constants of pupil.py:46-77

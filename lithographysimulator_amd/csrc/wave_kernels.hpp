@@ -726,11 +726,16 @@ __global__ __launch_bounds__(256 * GW, 2) void k_ypass_rect(
 // instruction writes WHOLE 128-byte lines (measured 4.2-4.3 TB/s against 3.4 for the 64-byte granules of the
 // one-row-per-workgroup x-pass, scripts/ubench/write_bw.hip L0/L1).  No workgroup barriers.
 // ----------------------------------------------------------------------------------
-template <int LOG2N, bool FULL = false>
+// (Wt: weighted source, the mask-spectrum sample is scaled by sqrt(weights[s]) before the product; the weights arrive as a
+// trailing parameter pack, empty for the unweighted instantiation -- see k_xpass_abbe.)
+template <int LOG2N, bool FULL = false, typename... Wt>
 __global__ __launch_bounds__(256, 2) void k_xpass_rect(
     const float2* __restrict__ P, const float2* __restrict__ M, const int* __restrict__ shifts,
-    float2* __restrict__ Tbuf, const float2* __restrict__ twtab, PassGeom g, int nb, int chunk)
+    float2* __restrict__ Tbuf, const float2* __restrict__ twtab, PassGeom g, int nb, int chunk, Wt... wts)
 {
+    constexpr bool WT = sizeof...(Wt) != 0;
+    static_assert(sizeof...(Wt) <= 1, "one weight list");
+    [[maybe_unused]] const float* weights = pack_weights(wts...);
     static_assert(LOG2N >= 9 && LOG2N <= 11, "multi-row-per-wave x-pass: N = 512, 1024, 2048");
     using W = WaveSq<6>;
     // FULL: N = pn (coarse-grid transforms): half of the samples live, every bin kept
@@ -767,6 +772,8 @@ __global__ __launch_bounds__(256, 2) void k_xpass_rect(
 
     for (int s = s_begin; s < s_end; ++s) {
         const int dy = shifts[2 * s], dx = shifts[2 * s + 1];
+        [[maybe_unused]] float amp = 1.f;
+        if constexpr (WT) amp = sqrtf(weights[s]);
         float2 x[S];
         static_for<0, NL>([&](auto q_) {
             constexpr int line = decltype(q_)::value;
@@ -777,7 +784,14 @@ __global__ __launch_bounds__(256, 2) void k_xpass_rect(
                 make_rsrc(M + (size_t)(r0 + (rvalid ? line : 0) + dy) * g.pn + dx + g.c + g.kx0, rvalid ? win_bytes : 0u);
             static_for<0, H>([&](auto j_) {
                 constexpr int j = decltype(j_)::value;
-                if constexpr (j <= JL || j >= H - JL) x[line * H + j] = cmul(buf_load_c64(rP, slot_off(j)), buf_load_c64(rM, slot_off(j)));
+                if constexpr (j <= JL || j >= H - JL) {
+                    if constexpr (WT) {
+                        const float2 m = buf_load_c64(rM, slot_off(j));
+                        x[line * H + j] = cmul(buf_load_c64(rP, slot_off(j)), make_float2(amp * m.x, amp * m.y));
+                    } else {
+                        x[line * H + j] = cmul(buf_load_c64(rP, slot_off(j)), buf_load_c64(rM, slot_off(j)));
+                    }
+                }
                 else x[line * H + j] = make_float2(0.f, 0.f);
             });
         });
@@ -795,7 +809,7 @@ __global__ __launch_bounds__(256, 2) void k_xpass_rect(
 }
 
 template <int LOG2N>
-hipError_t launch_xpass_rect(const float2* P, const float2* M, const int* shifts, float2* T, const float2* tw,
+hipError_t launch_xpass_rect(const float2* P, const float2* M, const int* shifts, const float* wts, float2* T, const float2* tw,
                              const PassGeom& g, int nb, int chunk, hipStream_t st)
 {
     if constexpr (LOG2N >= 9 && LOG2N <= 11) {
@@ -805,6 +819,24 @@ hipError_t launch_xpass_rect(const float2* P, const float2* M, const int* shifts
         constexpr int NL = 4096 >> LOG2N;
         const int groups = (g.rows + NL - 1) / NL;
         const dim3 grid((groups + 3) / 4, (nb + chunk - 1) / chunk);
+        if (wts) {
+            if (g.N == g.pn) {
+                static LdsOnce once_full_wt;
+                auto kern = k_xpass_rect<LOG2N, true, const float*>;
+                hipError_t e = set_lds(once_full_wt, kern, lds);
+                if (e != hipSuccess) return e;
+                hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, P, M, shifts, T, tw, g, nb, chunk, wts);
+                note_kernel(0, "k_xpass_rect<%d, true, float const*>", LOG2N);
+                return hipGetLastError();
+            }
+            static LdsOnce once_wt;
+            auto kern = k_xpass_rect<LOG2N, false, const float*>;
+            hipError_t e = set_lds(once_wt, kern, lds);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, P, M, shifts, T, tw, g, nb, chunk, wts);
+            note_kernel(0, "k_xpass_rect<%d, false, float const*>", LOG2N);
+            return hipGetLastError();
+        }
         if (g.N == g.pn) {
             static LdsOnce once_full;
             auto kern = k_xpass_rect<LOG2N, true>;
@@ -969,7 +1001,7 @@ hipError_t launch_ypass_wave(const float2* T, float* slab, const float2* tw, con
 #define LITHO_DEFINE_WAVE_OPS(L2)                                                                            \
     template hipError_t launch_ypass_wave<L2>(const float2*, float*, const float2*, const PassGeom&, int, int, int, \
                                               int, hipStream_t);                                             \
-    template hipError_t launch_xpass_rect<L2>(const float2*, const float2*, const int*, float2*, const float2*,  \
+    template hipError_t launch_xpass_rect<L2>(const float2*, const float2*, const int*, const float*, float2*, const float2*,  \
                                               const PassGeom&, int, int, hipStream_t);
 
 }  // namespace litho

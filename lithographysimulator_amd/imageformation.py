@@ -5,7 +5,7 @@ import ctypes
 import torch
 
 from . import _native as nat
-from .lightsource import sourceShifts, sourceShiftsAsync
+from .lightsource import sourceShifts, sourceShiftsAsync, sourceWeights, sourceWeightsAsync
 from .mask import Mask          # the reference forgets this import at module level
 
 
@@ -67,6 +67,8 @@ class PlanCache:
     def __init__(self):
         self.record = nat.PlanRecord()
         self.shifts = None          # compacted (dy,dx) list of the source bitmap (abbeImage)
+        self.weights = None         # ... and, for a weighted source map, its weights (same order, same capacity)
+        self.weight_sum = None      # their sum, a 0-dim device tensor (normalize=True divides by it on the device)
         self.count = None           # its device-side count, until the first call has brought it to the host
         self.S = None
         self.workspace = None       # engine scratch of the planned calls (kept alive for captured graphs)
@@ -76,6 +78,7 @@ class PlanCache:
     def invalidate(self):
         self.record.valid = 0
         self.shifts = self.count = self.S = self.identity = self.image_identity = None
+        self.weights = self.weight_sum = None
 
     @property
     def valid(self):
@@ -98,7 +101,7 @@ def embeddedSize(pn: int, N: int) -> int:
     return size.value
 
 
-def _plan_workspace(plan, dev, pn, N, pupilF, shifts):
+def _plan_workspace(plan, dev, pn, N, pupilF, shifts, weights=None):
     """Engine scratch for a call at grid size pn; with a PlanCache, ITS workspace (graphs captured from planned calls hold raw
     pointers into it) and the identity check of the tensors the plan was made for."""
     if plan is None:
@@ -107,13 +110,15 @@ def _plan_workspace(plan, dev, pn, N, pupilF, shifts):
         plan.workspace, plan._ws_key = nat.workspace(dev, pn, N), (pn, N)
     ident = _identity(pupilF) + ((shifts.data_ptr(), shifts._version, str(shifts.device)),)   # not the list's length: a
     # caller may pass the compacted list at its capacity first (with `count`) and as a [:S] view afterwards
+    if weights is not None:
+        ident += ((weights.data_ptr(), weights._version, str(weights.device)),)
     if plan.valid and plan.identity is not None and plan.identity != ident:
         plan.record.valid = 0                          # another pupil / source list, or an in-place write: plan afresh
     plan.identity = ident
     return plan.workspace
 
 
-def abbeIntensity(maskFT, pupilF, shifts, N, out=None, count=None, plan=None, options=None):
+def abbeIntensity(maskFT, pupilF, shifts, N, out=None, count=None, plan=None, options=None, weights=None):
     """The loop of abbeImage (imageformation.py:54-67) for an explicit (dy,dx) list:
     returns / accumulates into the raw fp32 intensity [planes?,pn,pn] BEFORE post-processing.
     pupilF may be [pn,pn] or a through-focus stack [planes,pn,pn].
@@ -122,7 +127,11 @@ def abbeIntensity(maskFT, pupilF, shifts, N, out=None, count=None, plan=None, op
     stream once.  `plan`: optional PlanCache (see there); the call then returns (intensity, S) as well.
     `options`: optional mapping of launch-planner options for THIS call (litho_abbe_options: coarse, batch, groups,
     xchunk, tile, plane_chunk, ...; see _native.engineOptions), merged over the enclosing engineOptions blocks.
-    Mask sizes other than N and N / 2 run embedded in the next such grid, inside the library (embeddedSize)."""
+    Mask sizes other than N and N / 2 run embedded in the next such grid, inside the library (embeddedSize).
+    `weights`: optional float32 [S] tensor on the mask's device, one INTENSITY weight per row of `shifts` (a weighted,
+    grey-level source: sum_s w_s |E_s|^2; sourceWeights).  Combines with count, plan and options.  w = 0 adds nothing;
+    a negative, NaN or infinite weight raises ValueError from the call that plans (a call planned from a PlanCache record
+    does not look again).  Without weights the call goes to the same C entries as ever."""
     pn = _square(maskFT, "maskFT")
     if pupilF.dim() not in (2, 3) or tuple(pupilF.shape[-2:]) != (pn, pn) or (pupilF.dim() == 3 and pupilF.shape[0] < 1):
         # e.g. a default Pupil() (pixelNumber 64) with a 256^2 mask: the reference fails at pf * maskFFFT
@@ -147,9 +156,27 @@ def abbeIntensity(maskFT, pupilF, shifts, N, out=None, count=None, plan=None, op
     nat.check(rc, "abbeImage")
     if count is not None and (count.dtype != torch.int32 or count.numel() != 1 or count.device != m.device):
         raise ShapeError("count must be a 1-element int32 tensor on the mask's device")
-    ws = _plan_workspace(plan, dev, pn, int(N), pupilF, shifts)
+    if weights is not None:
+        if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.dim() != 1
+                or weights.shape[0] != shifts.shape[0] or weights.device != m.device):
+            raise ShapeError(f"weights must be a float32 tensor of shape ({shifts.shape[0]},) on {m.device}, one per row of "
+                             f"shifts; got {getattr(weights, 'dtype', type(weights))} {tuple(getattr(weights, 'shape', ()))} "
+                             f"on {getattr(weights, 'device', None)}")
+        wt = weights.contiguous()
+    ws = _plan_workspace(plan, dev, pn, int(N), pupilF, shifts, weights)
     opts = nat.current_options(options)
     with torch.cuda.device(dev):
+        if weights is not None:
+            S = ctypes.c_int64(0)
+            nat.check(nat.lib().litho_abbe_accumulate_weighted(nat.ptr(m), nat.ptr(p), planes, nat.ptr(sh),
+                                                               nat.ptr(count) if count is not None else None, sh.shape[0],
+                                                               pn, int(N), nat.ptr(out), nat.ptr(ws), ws.numel(),
+                                                               nat.stream_ptr(dev),
+                                                               ctypes.byref(plan.record) if plan is not None else None,
+                                                               ctypes.byref(opts) if opts is not None else None,
+                                                               ctypes.byref(S), nat.ptr(wt)),
+                      "litho_abbe_accumulate_weighted (sizes, or a negative / NaN / infinite weight)")
+            return (out, S.value) if (plan is not None or count is not None) else out
         if opts is not None:
             S = ctypes.c_int64(0)
             nat.check(nat.lib().litho_abbe_accumulate_opts(nat.ptr(m), nat.ptr(p), planes, nat.ptr(sh),
@@ -263,7 +290,7 @@ def _all_reduce_sum(image, group):
 
 def abbeImage(mask, maskFT: torch.Tensor, pupilF: torch.Tensor, lightsource: torch.Tensor, pixelSize: int,
               deltaK: float, wavelength, fft: bool, device: torch.device, group=None, normalize: bool = False,
-              plan_cache: PlanCache = None, options=None):
+              plan_cache: PlanCache = None, options=None, weighted: bool = False):
     """Drop-in for imageformation.py:47-77.  `pupilF` may also be a through-focus stack [planes,pn,pn] (BASELINE
     config 5; the reference's counterpart is a Python loop over Pupil(...) + abbeImage(...)), in which case the
     result is [planes,pn',pn'].
@@ -278,7 +305,15 @@ def abbeImage(mask, maskFT: torch.Tensor, pupilF: torch.Tensor, lightsource: tor
     `plan_cache`: optional PlanCache for sequences of images with the same pupil and source (single GPU): from the second
     call on, no source compaction, no planning launches and no host wait.  Not combinable with `group`.
 
-    `options`: optional mapping of launch-planner options for this call (see abbeIntensity)."""
+    `options`: optional mapping of launch-planner options for this call (see abbeIntensity).
+
+    `weighted`: False (default) -- `lightsource` is the reference's bitmap, non-zero = lit (imageformation.py:59), exactly as
+    before.  True -- `lightsource` is a real map [pn,pn] whose values are per-point intensity weights (a measured pupil fill,
+    a freeform or apodised source): the image is sum_s w_s |E_s|^2 over the pixels with w > 0, and `normalize` divides by
+    sum_s w_s (the global sum when sharded) instead of S, on the device.  The reference cannot express this."""
+    if weighted:
+        return _abbe_image_weighted(mask, maskFT, pupilF, lightsource, pixelSize, deltaK, wavelength, fft, device, group,
+                                    normalize, plan_cache, options)
     if not fft:
         raise NotImplementedError("only the FFT formulation (fft=True) is built; the direct integral "
                                   "(imageformation.py:3-30) is outside the hot path")
@@ -327,3 +362,60 @@ def abbeImage(mask, maskFT: torch.Tensor, pupilF: torch.Tensor, lightsource: tor
     if normalize and total > 0:
         image /= float(total)
     return postProcess(image, epsilon)                                      # imageformation.py:69-77
+
+
+def _abbe_image_weighted(mask, maskFT, pupilF, lightsource, pixelSize, deltaK, wavelength, fft, device, group, normalize,
+                         plan_cache, options):
+    """abbeImage(..., weighted=True): the same three branches (plan cache / single GPU / sharded) with the weights travelling
+    next to the shifts.  Kept apart so that an unweighted call reaches sourceShifts, abbeIntensity and postProcess with exactly
+    the arguments it always did."""
+    if not fft:
+        raise NotImplementedError("only the FFT formulation (fft=True) is built; the direct integral "
+                                  "(imageformation.py:3-30) is outside the hot path")
+    epsilon, N = Mask.calculateEpsilonN(self=mask, deltaK=deltaK, pixelSize=pixelSize, wavelength=wavelength)
+    pixelNumber = _square(maskFT, "maskFT")
+    if pupilF.dim() not in (2, 3) or tuple(pupilF.shape[-2:]) != (pixelNumber, pixelNumber):
+        raise ShapeError(f"pupilF must be [{pixelNumber},{pixelNumber}] or [planes,{pixelNumber},{pixelNumber}] to "
+                         f"match maskFT; got {tuple(pupilF.shape)} (build the Pupil with mask.pixelNumber)")
+    if tuple(lightsource.shape) != (pixelNumber, pixelNumber) or lightsource.is_complex():
+        raise ShapeError(f"a weighted source must be a real map [{pixelNumber},{pixelNumber}] (the mask's pixelNumber); got "
+                         f"{lightsource.dtype} {tuple(lightsource.shape)}")
+    dev = nat.require_gpu(device)
+    maskFT = maskFT.to(dev)
+    from .distributed import resolve_group, shard_bounds
+    group = resolve_group(group)
+    if group is not None and plan_cache is not None:
+        raise ValueError("plan_cache is for single-GPU image sequences; a sharded call (group=...) plans per rank and per "
+                         "call -- pass one or the other")
+    if plan_cache is not None:
+        planes = pupilF.shape[0] if pupilF.dim() == 3 else 1
+        r = plan_cache.record
+        ident = _identity(pupilF, lightsource) + ("weighted",)
+        if (plan_cache.shifts is None or plan_cache.weights is None or not plan_cache.valid
+                or (r.pn, r.N, r.planes) != (pixelNumber, int(N), planes) or plan_cache.image_identity != ident):
+            plan_cache.invalidate()
+            plan_cache.image_identity = ident
+            plan_cache.shifts, plan_cache.weights, plan_cache.count = sourceWeightsAsync(lightsource.to(dev), pixelNumber)
+            image, total = abbeIntensity(maskFT, pupilF.to(dev), plan_cache.shifts, N, count=plan_cache.count, plan=plan_cache,
+                                         options=options, weights=plan_cache.weights)
+            plan_cache.S, plan_cache.count = total, None
+            plan_cache.weight_sum = plan_cache.weights[:total].sum()          # device side, no host wait
+        else:
+            image, total = abbeIntensity(maskFT, pupilF.to(dev), plan_cache.shifts[:plan_cache.S], N, plan=plan_cache,
+                                         options=options, weights=plan_cache.weights[:plan_cache.S])
+        wsum = plan_cache.weight_sum
+    elif group is None:
+        shifts, weights, count = sourceWeightsAsync(lightsource.to(dev), pixelNumber)
+        image, total = abbeIntensity(maskFT, pupilF.to(dev), shifts, N, count=count, options=options, weights=weights)
+        wsum = weights[:total].sum()
+    else:
+        import torch.distributed as dist
+        shifts, weights = sourceWeights(lightsource.to(dev), pixelNumber)
+        total = shifts.shape[0]
+        lo, hi = shard_bounds(total, dist.get_rank(group), dist.get_world_size(group))
+        image = abbeIntensity(maskFT, pupilF.to(dev), shifts[lo:hi], N, options=options, weights=weights[lo:hi])
+        _all_reduce_sum(image, group)
+        wsum = weights.sum()                                    # every rank compacts the whole map: the GLOBAL sum
+    if normalize and total > 0:
+        image /= wsum.to(image.dtype)
+    return postProcess(image, epsilon)

@@ -72,3 +72,44 @@ def sourceShifts(lightsource: torch.Tensor, pixelNumber: int) -> torch.Tensor:
         nat.check(nat.lib().litho_source_compact(nat.ptr(bm), pn, nat.ptr(shifts), pn * pn, nat.ptr(scratch),
                                                  ctypes.byref(count), nat.stream_ptr(dev)), "litho_source_compact")
     return shifts[:count.value]
+
+
+def _weight_map(lightsource, pixelNumber):
+    dev = nat.require_gpu(lightsource.device)
+    pn = int(pixelNumber)
+    if lightsource.dim() != 2 or lightsource.shape[0] != pn or lightsource.shape[1] != pn:
+        raise ValueError(f"the source map must be [{pn},{pn}] (the mask's pixelNumber); got {tuple(lightsource.shape)}")
+    if lightsource.is_complex():
+        raise ValueError("a weighted source map holds real intensity weights; got a complex tensor")
+    return dev, pn, lightsource.to(torch.float32).contiguous()
+
+
+def sourceWeightsAsync(lightsource: torch.Tensor, pixelNumber: int):
+    """Compaction of a WEIGHTED source -- a real map [pn,pn] whose values are per-point intensity weights (lit = w > 0) --
+    without a host read-back: (shifts [pn*pn,2] int32, weights [pn*pn] float32, count), only the first S rows written,
+    count = 1-element int32 device tensor holding S.  For abbeIntensity(..., weights=..., count=...).  The reference has no
+    counterpart: its source is a bitmap (imageformation.py:59)."""
+    dev, pn, wm = _weight_map(lightsource, pixelNumber)
+    shifts = torch.empty((pn * pn, 2), dtype=torch.int32, device=dev)
+    weights = torch.empty(pn * pn, dtype=torch.float32, device=dev)
+    scratch = torch.empty(pn + 1, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_source_compact_weighted(nat.ptr(wm), pn, nat.ptr(shifts), nat.ptr(weights), pn * pn,
+                                                          nat.ptr(scratch), None, nat.stream_ptr(dev)),
+                  "litho_source_compact_weighted")
+    return shifts, weights, scratch[pn:pn + 1]
+
+
+def sourceWeights(lightsource: torch.Tensor, pixelNumber: int):
+    """(shifts int32 [S,2], weights float32 [S]) of a weighted source map, row-major like sourceShifts; a map of exact
+    0 / 1 values gives sourceShifts' list and weights of one."""
+    dev, pn, wm = _weight_map(lightsource, pixelNumber)
+    shifts = torch.empty((pn * pn, 2), dtype=torch.int32, device=dev)
+    weights = torch.empty(pn * pn, dtype=torch.float32, device=dev)
+    scratch = torch.empty(pn + 1, dtype=torch.int32, device=dev)
+    count = ctypes.c_int64(0)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_source_compact_weighted(nat.ptr(wm), pn, nat.ptr(shifts), nat.ptr(weights), pn * pn,
+                                                          nat.ptr(scratch), ctypes.byref(count), nat.stream_ptr(dev)),
+                  "litho_source_compact_weighted")
+    return shifts[:count.value], weights[:count.value]
