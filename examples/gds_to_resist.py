@@ -1,6 +1,7 @@
-"""GDSII layout -> mask -> partially coherent aerial image -> constant-threshold resist contour, on one MI355X.
+"""GDSII layout -> mask -> partially coherent aerial image -> resist contour (constant threshold, optionally on the
+diffused aerial image) -> sub-pixel critical dimension, on one MI355X.
 
-    python examples/gds_to_resist.py [layout.gds] [--top NAME] [--layer 7 --datatype 0] [--pn 512] [--pixel 25]
+    python examples/gds_to_resist.py [layout.gds] [--top NAME] [--layer 7 --datatype 0] [--pn 512] [--pixel 25] [--diffusion 30]
 
 Without a file it writes a small line/space layout (a 12-bar grating placed by an AREF plus a wire drawn as a PATH) to
 /tmp and uses that.  Prints the image statistics and the printed line width on the centre row; saves nothing."""
@@ -40,6 +41,7 @@ def main():
     ap.add_argument("--pn", type=int, default=512)
     ap.add_argument("--pixel", type=float, default=25.0)
     ap.add_argument("--threshold", type=float, default=0.3, help="resist threshold as a fraction of the clear-field intensity")
+    ap.add_argument("--diffusion", type=float, default=0.0, metavar="NM", help="acid diffusion length (Gaussian sigma, nm) of the diffused aerial image; 0 = none")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     wl, na = 193.0, 0.7
@@ -55,7 +57,7 @@ def main():
     # clear-field level: the same optics over an all-open mask
     clear = L.abbeIntensity(L.Mask(torch.ones((a.pn, a.pn), dtype=torch.int16), a.pixel, dev).fraunhofer(wl, True), pupil, shifts, N)
     level = float(clear[a.pn // 2, a.pn // 2])
-    image, contour = L.resistContour(raw, eps, a.threshold * level, return_image=True)
+    image, contour = L.resistContour(raw, eps, a.threshold * level, return_image=True, diffusionLength=a.diffusion, pixelSize=a.pixel)
     image = image / level
     print(f"{shifts.shape[0]} source points, FFT size {N}, image {tuple(image.shape)}: min {float(image.min()):.3f} max {float(image.max()):.3f} (clear field = 1)")
     row = contour[contour.shape[0] // 2].cpu().numpy().astype(np.int8)
@@ -63,6 +65,15 @@ def main():
     if len(edges) >= 2:
         widths = (edges[1::2] - edges[0::2][:len(edges[1::2])]) * a.pixel
         print(f"centre row: {len(widths)} exposed runs above threshold, widths (nm): {widths[:12].tolist()}")
+    # sub-pixel CD of the exposed feature nearest the centre of the centre row (the pixel widths above move in steps of --pixel)
+    n = contour.shape[0]
+    lit = np.flatnonzero(row)
+    if len(lit):
+        col = int(lit[np.argmin(np.abs(lit - n // 2))])
+        cd, x_lo, x_hi, ils_lo, ils_hi = L.measureCD(image, a.threshold, [(n // 2, col, 0)], a.pixel, exposed=True)[0, 0, 0].tolist()
+        print(f"centre feature through column {col}: sub-pixel CD {cd:.2f} nm (edges at {x_lo:.3f} and {x_hi:.3f} px, "
+              f"image log-slope {ils_lo:.4f} / {ils_hi:.4f} per nm"
+              + (f", diffusion length {a.diffusion:g} nm)" if a.diffusion > 0 else ")"))
     print(f"resist contour: {int(contour.sum())} of {contour.numel()} pixels above {a.threshold:.2f} x clear field")
 
 

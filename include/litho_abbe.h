@@ -262,6 +262,32 @@ int litho_postprocess(const float *raw, int planes, int pn, double epsilon, floa
 int litho_postprocess_resist(const float *raw, int planes, int pn, double epsilon, double gain, double threshold,
                              float *out, uint8_t *resist, void *stream);
 
+/* ---- Diffused aerial image (the simplest resist model in practical use: Gaussian acid diffusion of the image, then the
+ * threshold), fused into the same pass.  The reference has NO counterpart (its README.md:21 lists resist modelling as an
+ * open goal), so the definition is this one; checked against the CPU restatement tests/resist_oracle.py.  I = the image
+ * litho_postprocess writes (zero border included), zero outside the grid; taps g[k] = exp(-k^2 / (2 sigma_px^2)),
+ * k = -R..R, R = ceil(4 sigma_px), normalised to sum 1 in double and rounded to fp32; D = I convolved with g along the
+ * rows and along the columns, fp32 accumulation; resist = 1 where fp32(D * gain) >= fp32(threshold).  sigma_px =
+ * diffusion length / pixel pitch of the post-processed grid (the mask's pixelSize).  sigma_px = 0 is the identity, bit for
+ * bit litho_postprocess_resist; R > 32 (sigma_px > 8), a negative or non-finite sigma_px: LITHO_E_ARG.  out (fp32 D) and
+ * resist (uint8) may each be NULL, not both.  Asynchronous: one kernel, no allocation, no host wait. */
+int litho_postprocess_resist_diffused(const float *raw, int planes, int pn, double epsilon, double gain, double threshold,
+                                      double sigma_px, float *out, uint8_t *resist, void *stream);
+
+/* ---- Sub-pixel critical-dimension metrology on cut lines (no reference counterpart; checked against
+ * tests/resist_oracle.py).  image fp32 [planes,n,n] on the post-processed grid (aerial or diffused); gauges int32
+ * [n_gauges][3] = (row, col, axis) on the device, axis 0: measure along the row through (row, col), 1: along the column;
+ * gains_host: n_gains <= 64 host floats (doses, or dose / S).  out fp32 [n_gains][planes][n_gauges][5] =
+ * (cd_nm, x_lo, x_hi, ils_lo, ils_hi).  Along the gauge's line v[0..n-1] with c the gauge's coordinate on it:
+ * u[i] = fp32(v[i] * gain), inside(i) = (u[i] >= fp32(threshold)) == (exposed != 0) -- pixel for pixel the contour mask.
+ * !inside(c): cd_nm = 0, the rest NaN.  Else [lo, hi] = the maximal run of inside samples through c,
+ * x_lo = lo - 1 + (T - u[lo-1]) / (u[lo] - u[lo-1]) (lo = 0: -0.5), x_hi = hi + (T - u[hi]) / (u[hi+1] - u[hi])
+ * (hi = n - 1: n - 0.5), in pixels; cd_nm = (x_hi - x_lo) * pixel_size; ils_* = |u[b] - u[a]| / (T * pixel_size) of the
+ * crossing segment (image log-slope per nm), NaN at a border edge.  A gauge outside the grid (or axis not 0 / 1) writes
+ * five NaN and reads nothing.  Asynchronous, no allocation, no host wait. */
+int litho_measure_cd(const float *image, int planes, int n, const int32_t *gauges, int n_gauges, const float *gains_host,
+                     int n_gains, double threshold, int exposed, double pixel_size, float *out, void *stream);
+
 /* ---- Layout rasteriser: the device side of the GDSII import (lithographysimulator_amd/layout.py).  SURVEY.md section
  * 8(f) row 4: the reference has NO counterpart (README.md:20-22 lists GDSII import among its unbuilt goals), it is the
  * caller side of Mask(geometry, pixelSize) (mask.py:5-30), so there is no parity target; checked bit for bit against

@@ -47,6 +47,10 @@ _SIGNATURES = {
     "litho_postprocess_size": (c_int, [c_int, c_double, POINTER(c_int)]),
     "litho_postprocess": (c_int, [c_void_p, c_int, c_int, c_double, c_void_p, c_void_p]),
     "litho_postprocess_resist": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    "litho_postprocess_resist_diffused": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_double, c_double, c_void_p,
+                                                  c_void_p, c_void_p]),
+    "litho_measure_cd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_double, c_int, c_double,
+                                 c_void_p, c_void_p]),
     "litho_mask_spectrum": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "litho_rasterize_work_bytes": (c_size_t, [c_int]),
     "litho_rasterize_edges": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_double, c_void_p, c_size_t, c_void_p, c_void_p]),

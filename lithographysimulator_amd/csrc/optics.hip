@@ -356,6 +356,154 @@ __global__ void k_postprocess(const float* __restrict__ raw, int pn, int ns, int
     if constexpr (RESIST) resist[o] = (v * gain >= threshold) ? 1 : 0;
 }
 
+// ---- diffused aerial image (no reference counterpart; definition in include/litho_abbe.h)
+// The post-processed image convolved with a separable Gaussian (acid diffusion), then the same threshold as above -- in ONE
+// pass over HBM: a workgroup owns a DIFF_TX x DIFF_TY output tile, fills tile + halo R in LDS by evaluating bilinear_at on
+// `raw` (zero in the padded border and outside the grid), so the post-processed image itself is never written and re-read;
+// then the row pass and the column pass run out of LDS.  Lanes map to consecutive x in all three phases: the global loads
+// and stores are coalesced, and every LDS access of a wave is 64 consecutive dwords (the column pass walks rows of the
+// row-major array with the lane as the column) -- conflict-free.  The symmetric taps are paired, (t[-k] + t[k]) * g[k].
+// LDS: ((DIFF_TX + 2R) + DIFF_TX) * (DIFF_TY + 2R) floats: 23 KiB at R = 5 (six workgroups per CU), 72 KiB at R = 32.
+static constexpr int DIFF_RMAX = 32, DIFF_TX = 64, DIFF_TY = 32;
+struct DiffTaps {
+    float g[DIFF_RMAX + 1];                          // g[|k|], normalised over k = -R .. R; rides in the kernel arguments
+};
+static size_t diff_lds_bytes(int R) { return sizeof(float) * (size_t)(2 * DIFF_TX + 2 * R) * (DIFF_TY + 2 * R); }
+
+// Fill of tile + halo: four rows per step, every global load issued before the first LDS store (one element per step left the
+// phase waiting on HBM latency row after row).  Branch-free: coordinates are clamped into the image and the value is selected
+// afterwards; SAME (equal sizes, a plain copy) is a template parameter so that the loads of a step stay in one basic block.
+template <bool SAME>
+__device__ __forceinline__ void diff_fill(const float* __restrict__ rawp, int pn, int ns, int pW, float rs, int gx0, int gy0,
+                                          int W, int H, int lane, int wave, float* __restrict__ tile)
+{
+    for (int i = lane; i < W; i += 64) {
+        const int ix = gx0 + i - pW;                 // column of the resampled image; the border and everything outside are zero
+        const bool col_in = ix >= 0 && ix < ns;
+        const int ixc = max(0, min(ix, ns - 1));
+        for (int j0 = wave; j0 < H; j0 += 16) {
+            float v[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                v[u] = bilinear_at(rawp, pn, max(0, min(gy0 + j0 + 4 * u - pW, ns - 1)), ixc, rs, SAME, true);
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int j = j0 + 4 * u, iy = gy0 + j - pW;
+                if (j < H) tile[j * W + i] = (col_in && iy >= 0 && iy < ns) ? v[u] : 0.f;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_postprocess_diffused(const float* __restrict__ raw, int pn, int ns, int pW, int n_out,
+                                                              float rs, const DiffTaps taps, int R, float* __restrict__ out,
+                                                              float gain, float threshold, unsigned char* __restrict__ resist)
+{
+    extern __shared__ __attribute__((aligned(16))) float diff_lds[];
+    const int W = DIFF_TX + 2 * R, H = DIFF_TY + 2 * R;
+    float* tile = diff_lds;                          // [H][W]      post-processed image, tile + halo
+    float* rows = diff_lds + H * W;                  // [H][DIFF_TX] after the row pass
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int x0 = blockIdx.x * DIFF_TX, y0 = blockIdx.y * DIFF_TY;
+    const float* rawp = raw + (size_t)blockIdx.z * pn * pn;
+    if (ns == pn) diff_fill<true>(rawp, pn, ns, pW, rs, x0 - R, y0 - R, W, H, lane, wave, tile);
+    else diff_fill<false>(rawp, pn, ns, pW, rs, x0 - R, y0 - R, W, H, lane, wave, tile);
+    // lane k keeps tap k; a pass reads it with v_readlane (k is wave-uniform): no memory access for the taps in the loops
+    const int gv = __float_as_int(lane <= DIFF_RMAX ? taps.g[lane] : 0.f);
+    auto tap = [&](int k) { return __int_as_float(__builtin_amdgcn_readlane(gv, k)); };
+    auto conv = [&](const float* c, const int stride) {      // four tap pairs per step: their eight LDS reads go out together
+        float acc = tap(0) * c[0];
+        int k = 1;
+        for (; k + 3 <= R; k += 4) {
+            const float s0 = c[-k * stride] + c[k * stride], s1 = c[-(k + 1) * stride] + c[(k + 1) * stride];
+            const float s2 = c[-(k + 2) * stride] + c[(k + 2) * stride], s3 = c[-(k + 3) * stride] + c[(k + 3) * stride];
+            acc = acc + tap(k) * s0;
+            acc = acc + tap(k + 1) * s1;
+            acc = acc + tap(k + 2) * s2;
+            acc = acc + tap(k + 3) * s3;
+        }
+        for (; k <= R; ++k) acc = acc + tap(k) * (c[-k * stride] + c[k * stride]);
+        return acc;
+    };
+    __syncthreads();
+    for (int j = wave; j < H; j += 4) {
+        rows[j * DIFF_TX + lane] = conv(tile + j * W + R + lane, 1);
+    }
+    __syncthreads();
+    const int ox = x0 + lane;
+    for (int y = wave; y < DIFF_TY; y += 4) {
+        const int oy = y0 + y;
+        if (oy >= n_out) break;
+        const float acc = conv(rows + (y + R) * DIFF_TX + lane, DIFF_TX);
+        if (ox < n_out) {
+            const size_t o = ((size_t)blockIdx.z * n_out + oy) * n_out + ox;
+            if (out) out[o] = acc;
+            if (resist) resist[o] = (acc * gain >= threshold) ? 1 : 0;
+        }
+    }
+}
+
+// ---- sub-pixel edge finder on cut lines (no reference counterpart; definition in include/litho_abbe.h)
+// One 64-lane wave per (plane, gauge), the gains in a loop inside.  From the gauge's sample the wave scans outward in
+// 64-sample chunks; __ballot + a bit scan give the first sample of the other kind (or the border) -- no LDS, no barrier,
+// and the scan stops at the feature's edge.  A row gauge reads 64 consecutive floats per chunk; a column gauge reads with
+// stride n, one sample per 128-byte line: accepted, a gauge list is small against the image passes next to it.
+static constexpr int CD_GAINS = 64;
+struct CdGains {
+    float g[CD_GAINS];
+};
+
+__global__ __launch_bounds__(64) void k_measure_cd(const float* __restrict__ image, int planes, int n,
+                                                   const int32_t* __restrict__ gauges, int G, const CdGains gains, int n_gains,
+                                                   float T, int exposed, float ps, float* __restrict__ out)
+{
+    const int g = blockIdx.x, p = blockIdx.y, lane = threadIdx.x;
+    const int row = gauges[3 * g], col = gauges[3 * g + 1], axis = gauges[3 * g + 2];
+    const bool ok = row >= 0 && row < n && col >= 0 && col < n && (axis == 0 || axis == 1);   // else: never touch the image
+    const size_t stride = axis == 0 ? 1 : (size_t)n;
+    const float* line = image + (size_t)p * n * n + (axis == 0 ? (size_t)row * n : (size_t)col);
+    const int c = axis == 0 ? col : row;
+    const bool ex = exposed != 0;
+    const float nan = __builtin_nanf("");
+    for (int gi = 0; gi < n_gains; ++gi) {
+        const float gain = gains.g[gi];
+        auto u = [&](int i) { return line[(size_t)i * stride] * gain; };
+        float cd = nan, x_lo = nan, x_hi = nan, ils_lo = nan, ils_hi = nan;
+        if (ok && ((u(c) >= T) == ex)) {
+            int lo = 0, hi = n - 1;
+            for (int s = c + 1;; s += 64) {                                       // first sample to the right that is not inside
+                const int i = s + lane;
+                const unsigned long long m = __ballot(i >= n || ((u(i) >= T) != ex));
+                if (m) { hi = s + __ffsll((long long)m) - 2; break; }
+            }
+            for (int s = c - 1;; s -= 64) {                                       // ... and to the left
+                const int i = s - lane;
+                const unsigned long long m = __ballot(i < 0 || ((u(i) >= T) != ex));
+                if (m) { lo = s - __ffsll((long long)m) + 2; break; }
+            }
+            x_lo = -0.5f;
+            if (lo > 0) {
+                const float a = u(lo - 1), b = u(lo);
+                x_lo = (float)(lo - 1) + (T - a) / (b - a);
+                ils_lo = fabsf(b - a) / (T * ps);
+            }
+            x_hi = (float)n - 0.5f;
+            if (hi < n - 1) {
+                const float a = u(hi), b = u(hi + 1);
+                x_hi = (float)hi + (T - a) / (b - a);
+                ils_hi = fabsf(b - a) / (T * ps);
+            }
+            cd = (x_hi - x_lo) * ps;
+        } else if (ok) {
+            cd = 0.f;
+        }
+        if (lane == 0) {
+            float* o = out + (((size_t)gi * planes + p) * G + g) * 5;
+            o[0] = cd; o[1] = x_lo; o[2] = x_hi; o[3] = ils_lo; o[4] = ils_hi;
+        }
+    }
+}
+
 // bilinear up-scaling of the int16 mask geometry (mask.py:76-77) into a dense fp32 image
 __global__ void k_scale_mask(const int16_t* __restrict__ geo, int pn, int ns, float rs, float* __restrict__ out)
 {
@@ -651,6 +799,79 @@ int litho_postprocess_resist(const float* raw, int planes, int pn, double epsilo
     const float rs = (float)(1.0 / scale);
     hipLaunchKernelGGL(k_postprocess<true>, dim3((n_out + 255) / 256, n_out, planes), dim3(256), 0, (hipStream_t)stream,
                        raw, pn, ns, pW, n_out, rs, out, (float)gain, (float)threshold, (unsigned char*)resist);
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+int litho_postprocess_resist_diffused(const float* raw, int planes, int pn, double epsilon, double gain, double threshold,
+                                      double sigma_px, float* out, uint8_t* resist, void* stream)
+{
+    using namespace litho;
+    int n_out = 0;
+    int rc = litho_postprocess_size(pn, epsilon, &n_out);
+    if (rc) return rc;
+    if (!raw || (!out && !resist) || planes < 1 || planes > 65535 || !(gain == gain) || !(threshold == threshold)) return LITHO_E_ARG;
+    if (!(sigma_px >= 0.0) || !(sigma_px <= (double)DIFF_RMAX / 4.0)) return LITHO_E_ARG;   // NaN, negative, R = ceil(4 sigma) > 32
+    const double scale = 1.0 / epsilon;
+    const int ns = (int)std::floor((double)pn * scale);
+    const int pW = (int)std::floor((pn - std::nearbyint(pn / epsilon)) / 2.0);
+    const float rs = (float)(1.0 / scale);
+    hipStream_t st = (hipStream_t)stream;
+    if (sigma_px == 0.0) {                           // the identity: the very kernels of litho_postprocess(_resist)
+        const dim3 grid((n_out + 255) / 256, n_out, planes);
+        if (resist)
+            hipLaunchKernelGGL(k_postprocess<true>, grid, dim3(256), 0, st, raw, pn, ns, pW, n_out, rs, out, (float)gain,
+                               (float)threshold, (unsigned char*)resist);
+        else
+            hipLaunchKernelGGL(k_postprocess<false>, grid, dim3(256), 0, st, raw, pn, ns, pW, n_out, rs, out, 1.0f, 0.0f,
+                               (unsigned char*)nullptr);
+        HIP_TRY(hipGetLastError());
+        return LITHO_OK;
+    }
+    const int R = (int)std::ceil(4.0 * sigma_px);
+    if (R < 1 || R > DIFF_RMAX) return LITHO_E_ARG;
+    double g[DIFF_RMAX + 1], sum = 0.0;
+    for (int k = 0; k <= R; ++k) {
+        g[k] = std::exp(-(double)k * k / (2.0 * sigma_px * sigma_px));
+        sum += k ? 2.0 * g[k] : g[k];
+    }
+    DiffTaps taps;
+    memset(&taps, 0, sizeof(taps));
+    for (int k = 0; k <= R; ++k) taps.g[k] = (float)(g[k] / sum);
+    const size_t lds = diff_lds_bytes(R);
+    if (lds > 64 * 1024) {                           // once per device: the worst case, R = DIFF_RMAX
+        static unsigned lds_done = 0;
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        const unsigned bit = 1u << (dev & 31);
+        if (!(__atomic_load_n(&lds_done, __ATOMIC_ACQUIRE) & bit)) {
+            HIP_TRY(hipFuncSetAttribute((const void*)k_postprocess_diffused, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)diff_lds_bytes(DIFF_RMAX)));
+            __atomic_fetch_or(&lds_done, bit, __ATOMIC_RELEASE);
+        }
+    }
+    hipLaunchKernelGGL(k_postprocess_diffused, dim3((n_out + DIFF_TX - 1) / DIFF_TX, (n_out + DIFF_TY - 1) / DIFF_TY, planes),
+                       dim3(256), lds, st, raw, pn, ns, pW, n_out, rs, taps, R, out, (float)gain, (float)threshold,
+                       (unsigned char*)resist);
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+int litho_measure_cd(const float* image, int planes, int n, const int32_t* gauges, int n_gauges, const float* gains_host,
+                     int n_gains, double threshold, int exposed, double pixel_size, float* out, void* stream)
+{
+    using namespace litho;
+    if (!image || !gauges || !gains_host || !out || planes < 1 || planes > 65535 || n < 1 || n_gauges < 1) return LITHO_E_ARG;
+    if (n_gains < 1 || n_gains > CD_GAINS || !(threshold == threshold) || !(pixel_size > 0.0) || std::isinf(pixel_size))
+        return LITHO_E_ARG;
+    CdGains gains;
+    memset(&gains, 0, sizeof(gains));
+    for (int i = 0; i < n_gains; ++i) {
+        if (!(gains_host[i] == gains_host[i])) return LITHO_E_ARG;
+        gains.g[i] = gains_host[i];
+    }
+    hipLaunchKernelGGL(k_measure_cd, dim3(n_gauges, planes), dim3(64), 0, (hipStream_t)stream, image, planes, n, gauges, n_gauges,
+                       gains, n_gains, (float)threshold, exposed, (float)pixel_size, out);
     HIP_TRY(hipGetLastError());
     return LITHO_OK;
 }

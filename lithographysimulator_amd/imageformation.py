@@ -225,11 +225,33 @@ def postProcess(raw, epsilon):
     return out
 
 
-def resistContour(raw, epsilon, threshold, dose=1.0, return_image=False):
+def _sigma_px(diffusionLength, pixelSize, what):
+    """diffusionLength / pixelSize, both in nanometres; 0.0 (the identity) when there is no diffusion."""
+    d = float(diffusionLength)
+    if d == 0.0:
+        return 0.0
+    if pixelSize is None:
+        raise ValueError(f"{what}: diffusionLength needs pixelSize (the pitch of the post-processed grid, nm)")
+    ps = float(pixelSize)
+    if not (d > 0.0 and d != float("inf")) or not (ps > 0.0 and ps != float("inf")):
+        raise ValueError(f"{what}: diffusionLength must be finite and >= 0 and pixelSize finite and > 0; got {d} and {ps}")
+    if d / ps > 8.0:
+        raise ValueError(f"{what}: diffusionLength / pixelSize = {d / ps:g} pixels; the Gaussian's support 4 sigma may "
+                         "span at most 32 pixels (sigma <= 8 pixels)")
+    return d / ps
+
+
+def resistContour(raw, epsilon, threshold, dose=1.0, return_image=False, diffusionLength=0.0, pixelSize=None):
     """Constant-threshold resist model on the post-processed grid, fused into the post-process pass (the reference
     lists photoresist response as an open goal, README.md:21; nothing to be compatible with): uint8 mask, 1 where
     dose * image >= threshold.  `raw` is the accumulated intensity [pn,pn] or [planes,pn,pn] (abbeIntensity);
-    with return_image=True the fp32 aerial image of the same pass comes back too: (image, resist)."""
+    with return_image=True the fp32 aerial image of the same pass comes back too: (image, resist).
+
+    `diffusionLength` > 0 (nm; needs `pixelSize`, the mask's, = the pitch of the post-processed grid): the diffused
+    aerial image -- the post-processed image convolved with a Gaussian of that sigma (acid diffusion; zero outside the
+    grid), in the same single pass, and thresholded the same way; the returned image is then the diffused one.  At the
+    default 0 the call is exactly what it was."""
+    sigma = _sigma_px(diffusionLength, pixelSize, "resistContour")
     dev = nat.require_gpu(raw.device)
     stacked = raw.dim() == 3
     planes = raw.shape[0] if stacked else 1
@@ -241,25 +263,93 @@ def resistContour(raw, epsilon, threshold, dose=1.0, return_image=False):
     resist = torch.empty(shape, dtype=torch.uint8, device=dev)
     image = torch.empty(shape, dtype=torch.float32, device=dev) if return_image else None
     with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_postprocess_resist(nat.ptr(r), planes, pn, float(epsilon), float(dose), float(threshold),
-                                                     nat.ptr(image) if return_image else None, nat.ptr(resist),
-                                                     nat.stream_ptr(dev)), "litho_postprocess_resist")
+        if sigma > 0.0:
+            nat.check(nat.lib().litho_postprocess_resist_diffused(nat.ptr(r), planes, pn, float(epsilon), float(dose),
+                                                                  float(threshold), sigma,
+                                                                  nat.ptr(image) if return_image else None, nat.ptr(resist),
+                                                                  nat.stream_ptr(dev)), "litho_postprocess_resist_diffused")
+        else:
+            nat.check(nat.lib().litho_postprocess_resist(nat.ptr(r), planes, pn, float(epsilon), float(dose), float(threshold),
+                                                         nat.ptr(image) if return_image else None, nat.ptr(resist),
+                                                         nat.stream_ptr(dev)), "litho_postprocess_resist")
     return (image, resist) if return_image else resist
 
 
-def bossungCurves(raw, epsilon, threshold, doses, pixelSize, row=None, column=None, exposed=False):
+def measureCD(image, threshold, gauges, pixelSize, doses=(1.0,), exposed=False):
+    """Sub-pixel critical dimensions on cut lines of an image on the post-processed grid -- the aerial image (postProcess)
+    or the diffused one (resistContour(..., return_image=True, diffusionLength=...)); no reference counterpart.
+    `image` fp32 [n,n] (one plane) or [planes,n,n]; `gauges` = (row, col, axis) triples (a sequence or an integer tensor
+    [G,3]): the feature through pixel (row, col), measured along the row (axis 0) or the column (axis 1); `doses` at most
+    64 gains.  Returns fp32 [len(doses), planes, G, 5] = (cd_nm, x_lo, x_hi, ils_lo, ils_hi): the run of samples with
+    (dose * image >= threshold) == exposed through the gauge -- the very pixels of resistContour -- with each end moved
+    to where the linear interpolant between the last inside and the first outside sample crosses the threshold (pixel
+    units; -0.5 / n - 0.5 at a border), cd_nm = (x_hi - x_lo) * pixelSize, and the image log-slope
+    |du/dx| / threshold per nm at either edge (NaN at a border).  cd_nm = 0 and NaN elsewhere where the gauge's pixel is
+    of the other kind; five NaN for a gauge outside the grid."""
+    if not isinstance(image, torch.Tensor) or image.dim() not in (2, 3) or image.shape[-1] != image.shape[-2] \
+            or image.dtype != torch.float32:
+        raise ShapeError(f"measureCD: image must be a float32 tensor [n,n] or [planes,n,n]; got "
+                         f"{getattr(image, 'dtype', type(image))} {tuple(getattr(image, 'shape', ()))}")
+    g = gauges if isinstance(gauges, torch.Tensor) else torch.tensor(gauges, dtype=torch.int32)
+    if g.dim() != 2 or g.shape[1] != 3 or g.shape[0] < 1 or g.is_floating_point() or g.is_complex() or g.dtype == torch.bool:
+        raise ShapeError(f"measureCD: gauges must be integer (row, col, axis) triples [G,3], G >= 1; got {g.dtype} "
+                         f"{tuple(g.shape)}")
+    gains = [float(d) for d in doses]
+    if not 1 <= len(gains) <= 64:
+        raise ShapeError(f"measureCD: between 1 and 64 doses per call; got {len(gains)}")
+    if not float(pixelSize) > 0.0:
+        raise ValueError(f"measureCD: pixelSize must be > 0; got {pixelSize}")
+    dev = nat.require_gpu(image.device)
+    if isinstance(gauges, torch.Tensor) and gauges.device != image.device:
+        raise ShapeError(f"measureCD: gauges live on {gauges.device}, the image on {image.device}")
+    img = image.contiguous()
+    planes = img.shape[0] if img.dim() == 3 else 1
+    n = img.shape[-1]
+    g = g.to(device=dev, dtype=torch.int32).contiguous()
+    G = g.shape[0]
+    out = torch.empty((len(gains), planes, G, 5), dtype=torch.float32, device=dev)
+    arr = (ctypes.c_float * len(gains))(*gains)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_measure_cd(nat.ptr(img), planes, n, nat.ptr(g), G, arr, len(gains), float(threshold),
+                                             1 if exposed else 0, float(pixelSize), nat.ptr(out), nat.stream_ptr(dev)),
+                  "litho_measure_cd")
+    return out
+
+
+def bossungCurves(raw, epsilon, threshold, doses, pixelSize, row=None, column=None, exposed=False, subpixel=False,
+                  diffusionLength=0.0):
     """Process-window table of a through-focus stack (the caller-side driver config 5 implies; the
     reference has no such function -- its counterpart would be a loop over Pupil + abbeImage + a hand measurement):
     critical dimension in nanometres [len(doses), planes] of the feature that crosses (row, column) of the
     post-processed grid (default: its centre), measured along that row on the resist contour dose * image >= threshold
     (one fused post-process + threshold pass per dose, every focal plane at once).  The feature is the run of UNEXPOSED
     pixels through the point (a line of a dark-field line/space pattern; exposed=True: the run of exposed pixels, a space
-    or contact); 0 where the point is of the other kind.  `raw` = abbeIntensity of the stack, [planes, pn, pn]."""
+    or contact); 0 where the point is of the other kind.  `raw` = abbeIntensity of the stack, [planes, pn, pn].
+
+    `subpixel=True`: the same run with its two ends interpolated to the threshold crossing (measureCD's cd_nm) instead of
+    a pixel count -- within one pixelSize of the count, and resolving the few nanometres a Bossung curve is about; one
+    image pass for the whole stack and one measureCD call for all doses.  `diffusionLength` (nm): measure the diffused
+    aerial image (resistContour) instead of the plain one; pixelSize is the grid pitch.  Defaults: as before."""
     if raw.dim() != 3:
         raise ShapeError(f"bossungCurves takes the accumulated intensity of a stack [planes,pn,pn]; got {tuple(raw.shape)}")
+    sigma = _sigma_px(diffusionLength, pixelSize, "bossungCurves")
+    if subpixel:
+        if sigma > 0.0:
+            image, _ = resistContour(raw, epsilon, threshold, return_image=True, diffusionLength=diffusionLength,
+                                     pixelSize=pixelSize)
+        else:
+            image = postProcess(raw, epsilon)
+        n = image.shape[-1]
+        r = n // 2 if row is None else int(row)
+        c = n // 2 if column is None else int(column)
+        return measureCD(image, threshold, [(r, c, 0)], pixelSize, doses=doses, exposed=exposed)[:, :, 0, 0]
     table = []
     for dose in doses:
-        contour = resistContour(raw, epsilon, threshold, dose=float(dose))          # uint8 [planes, n, n]
+        if sigma > 0.0:
+            contour = resistContour(raw, epsilon, threshold, dose=float(dose), diffusionLength=diffusionLength,
+                                    pixelSize=pixelSize)
+        else:
+            contour = resistContour(raw, epsilon, threshold, dose=float(dose))      # uint8 [planes, n, n]
         n = contour.shape[-1]
         r = n // 2 if row is None else int(row)
         c = n // 2 if column is None else int(column)
