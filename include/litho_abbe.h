@@ -304,6 +304,18 @@ int litho_rasterize_edges(const double *edges, int64_t n_edges, int pn, double x
 int litho_mask_spectrum(const int16_t *geometry, int pn, double epsilon, int N, void *spectrum,
                         void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- The same pre-step for a complex field transmission (phase-shift and grey masks).  The reference has no counterpart;
+ * this is the definition: transmission complex64 [pn,pn] (a binary mask is the special case of values 0 and 1); the
+ * spectrum is the chain of mask.py:74-90 applied to a complex image -- bilinear resize by epsilon of the real and of the
+ * imaginary part, each in fp32 with torch's coordinate rule, pad or crop to N, centred forward DFT, centre pn x pn.  Every
+ * step is linear: spectrum = S(Re t) + i S(Im t) with S = litho_mask_spectrum's chain; a transmission of zeros and ones
+ * gives litho_mask_spectrum's result bit for bit.  One x-pass and one y-pass.  Same workspace, error codes and argument
+ * checks as litho_mask_spectrum, made before anything touches a device: a null pointer, an odd pn or epsilon <= 0 ->
+ * LITHO_E_ARG, N < pn -> LITHO_E_NSMALL.  Values are not inspected: a NaN in the transmission propagates into the
+ * spectrum.  Asynchronous, no allocation, no host wait; safe inside a captured graph. */
+int litho_mask_spectrum_complex(const void *transmission /* complex64 [pn,pn] */, int pn, double epsilon, int N,
+                                void *spectrum, void *workspace, size_t workspace_bytes, void *stream);
+
 /* ---- Introspection for bench.py / tests: what the last litho_abbe_accumulate on this
  * thread planned.  fields: [0]=mode (0 pruned box, 1 general/wrapping), [1]=box row0,
  * [2]=box col0, [3]=box rows, [4]=box cols, [5]=points per batch, [6]=x-pass launches,

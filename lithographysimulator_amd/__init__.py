@@ -7,10 +7,10 @@ from .layout import (GdsLibrary, flattenLayout, maskFromGDSII, rasterizeLayout, 
                      writeGDSII)
 from .lightsource import (LightSource, sourceShifts, sourceShiftsAsync, sourceWeights,   # noqa: F401
                           sourceWeightsAsync)
-from .mask import Mask                                                                  # noqa: F401
+from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
 
-__all__ = ["Mask", "LightSource", "Pupil", "abbeImage", "abbeIntensity", "calculateFFTAerial", "postProcess", "resistContour", "measureCD", "bossungCurves", "PlanCache", "engineOptions", "embeddedSize",
+__all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "abbeImage", "abbeIntensity", "calculateFFTAerial", "postProcess", "resistContour", "measureCD", "bossungCurves", "PlanCache", "engineOptions", "embeddedSize",
            "sourceShifts", "sourceShiftsAsync", "sourceWeights", "sourceWeightsAsync", "OSAindexToMN", "generateWavefrontError", "generatePhi", "generateZ",
            "throughFocusPupils", "readGDSII", "writeGDSII", "flattenLayout", "rasterizeLayout", "maskFromGDSII", "GdsLibrary"]

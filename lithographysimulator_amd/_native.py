@@ -52,6 +52,7 @@ _SIGNATURES = {
     "litho_measure_cd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_double, c_int, c_double,
                                  c_void_p, c_void_p]),
     "litho_mask_spectrum": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "litho_mask_spectrum_complex": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "litho_rasterize_work_bytes": (c_size_t, [c_int]),
     "litho_rasterize_edges": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_double, c_void_p, c_size_t, c_void_p, c_void_p]),
     "litho_abbe_last_plan": (c_int, [POINTER(c_int64)]),

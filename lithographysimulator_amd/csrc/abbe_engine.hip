@@ -1030,17 +1030,25 @@ static int abbe_field(const float2* pf, const float2* M, int pn, int N, float2* 
 }
 
 void launch_scale_mask(const int16_t* geo, int pn, int ns, double scale, float* out, hipStream_t st);   // optics.hip
+void launch_scale_mask_c64(const float2* t, int pn, int ns, double scale, float2* out, hipStream_t st);  // optics.hip
 
-// Mask._ffFraunhofer (mask.py:74-90): bilinear scale by epsilon, pad/crop to N, centred
-// forward DFT, keep the centre pn x pn:  spec[q] = sum_j padded[j] w^(-(j-N/2)(q-c)).
-static int mask_spectrum(const int16_t* geo, int pn, double eps, int N, float2* spec, void* ws, size_t ws_bytes,
-                         hipStream_t st)
+// What the int16 and the complex mask-spectrum entries share: argument checks, the workspace, the size ns of the scaled image,
+// its window [j0, j1) in the padded N x N frame (padding pW; negative: the scaled image is cropped) and the pass geometry.
+struct MaskSetup {
+    Workspace w;
+    PassGeom g;
+    const SizeOps* ops;
+    int ns, off;                                                 // image sample of frame sample j: j - pW = (j - j0) + off
+};
+
+// px_bytes: bytes per sample of the scaled image, which lives in the slab region (free during this call)
+static int mask_setup(const void* in, size_t px_bytes, int pn, double eps, int N, const void* spec, void* ws, size_t ws_bytes,
+                      MaskSetup& m)
 {
     int rc = check_sizes(pn, N);
     if (rc) return rc;
-    if (!geo || !spec || !(eps > 0)) return LITHO_E_ARG;
-    Workspace w;
-    if (!carve(ws, ws_bytes, pn, N, w)) return LITHO_E_WORKSPACE;
+    if (!in || !spec || !(eps > 0)) return LITHO_E_ARG;
+    if (!carve(ws, ws_bytes, pn, N, m.w)) return LITHO_E_WORKSPACE;
     const int ns = (int)floor((double)pn * eps);                 // F.interpolate output size (mask.py:77)
     if (ns < 1) return LITHO_E_ARG;
     const int diff = (N - pn) - (ns - pn);                       // mask.py:79, Python floor division
@@ -1048,13 +1056,12 @@ static int mask_spectrum(const int16_t* geo, int pn, double eps, int N, float2* 
     const int j0 = pW > 0 ? pW : 0;
     const int j1 = (pW + ns < N) ? pW + ns : N;
     const size_t nt = (pn + 3) / 4;
-    if ((size_t)ns * ns * sizeof(float) > (size_t)g_cap(pn) * nt * 4 * pn * sizeof(float)) return LITHO_E_WORKSPACE;
-    if (((size_t)(pn + 15) / 16 * 16) * (size_t)(j1 - j0) * sizeof(float2) > w.t_bytes) return LITHO_E_WORKSPACE;
-    float* scaled = w.slab;                                      // the slab region is free here
-    hipLaunchKernelGGL(k_twiddle_table, dim3((N + 255) / 256), dim3(256), 0, st, w.twtab, N);
-    launch_scale_mask(geo, pn, ns, eps, scaled, st);
-    HIP_TRY(hipGetLastError());
-    PassGeom g;
+    if ((size_t)ns * ns * px_bytes > (size_t)g_cap(pn) * nt * 4 * pn * sizeof(float)) return LITHO_E_WORKSPACE;
+    if (((size_t)(pn + 15) / 16 * 16) * (size_t)(j1 - j0) * sizeof(float2) > m.w.t_bytes) return LITHO_E_WORKSPACE;
+    m.ops = size_ops(ilog2(N));
+    if (!m.ops) return LITHO_E_ARG;
+    m.ns = ns; m.off = j0 - pW;
+    PassGeom& g = m.g;
     g.pn = pn; g.c = pn / 2; g.N = N; g.nt = (int)nt;
     g.kx0 = j0 - N / 2; g.kx1 = j1 - N / 2;
     g.ky0 = g.kx0; g.ky1 = g.kx1;
@@ -1062,11 +1069,42 @@ static int mask_spectrum(const int16_t* geo, int pn, double eps, int N, float2* 
     g.xmask = slot_mask(N, g.kx0, g.kx1);
     g.ymask = slot_mask(N, g.ky0, g.ky1);
     set_tile(g, g.rows);
-    RealImageLoader ld{scaled, ns, j0 - pW, nullptr};
-    const SizeOps* ops = size_ops(ilog2(N));
-    if (!ops) return LITHO_E_ARG;
-    HIP_TRY(ops->xpass_real_fwd(ld, w.T, w.twtab, g, st));
-    HIP_TRY(ops->ypass_field(-1, w.T, spec, w.twtab, g, st));
+    return LITHO_OK;
+}
+
+// Mask._ffFraunhofer (mask.py:74-90): bilinear scale by epsilon, pad/crop to N, centred
+// forward DFT, keep the centre pn x pn:  spec[q] = sum_j padded[j] w^(-(j-N/2)(q-c)).
+static int mask_spectrum(const int16_t* geo, int pn, double eps, int N, float2* spec, void* ws, size_t ws_bytes,
+                         hipStream_t st)
+{
+    MaskSetup m;
+    int rc = mask_setup(geo, sizeof(float), pn, eps, N, spec, ws, ws_bytes, m);
+    if (rc) return rc;
+    float* scaled = m.w.slab;                                    // the slab region is free here
+    hipLaunchKernelGGL(k_twiddle_table, dim3((N + 255) / 256), dim3(256), 0, st, m.w.twtab, N);
+    launch_scale_mask(geo, pn, m.ns, eps, scaled, st);
+    HIP_TRY(hipGetLastError());
+    RealImageLoader ld{scaled, m.ns, m.off, nullptr};
+    HIP_TRY(m.ops->xpass_real_fwd(ld, m.w.T, m.w.twtab, m.g, st));
+    HIP_TRY(m.ops->ypass_field(-1, m.w.T, spec, m.w.twtab, m.g, st));
+    return LITHO_OK;
+}
+
+// The same chain on a complex64 transmission: the scaled image is float2 (8 ns^2 bytes of the slab region), ONE x-pass and
+// ONE y-pass -- the transform is complex anyway, so a complex mask costs the extra input bytes and nothing else.
+static int mask_spectrum_complex(const float2* t, int pn, double eps, int N, float2* spec, void* ws, size_t ws_bytes,
+                                 hipStream_t st)
+{
+    MaskSetup m;
+    int rc = mask_setup(t, sizeof(float2), pn, eps, N, spec, ws, ws_bytes, m);
+    if (rc) return rc;
+    float2* scaled = (float2*)m.w.slab;
+    hipLaunchKernelGGL(k_twiddle_table, dim3((N + 255) / 256), dim3(256), 0, st, m.w.twtab, N);
+    launch_scale_mask_c64(t, pn, m.ns, eps, scaled, st);
+    HIP_TRY(hipGetLastError());
+    ComplexImageLoader ld{scaled, m.ns, m.off, nullptr};
+    HIP_TRY(m.ops->xpass_cplx_fwd(ld, m.w.T, m.w.twtab, m.g, st));
+    HIP_TRY(m.ops->ypass_field(-1, m.w.T, spec, m.w.twtab, m.g, st));
     return LITHO_OK;
 }
 
@@ -1151,6 +1189,13 @@ int litho_mask_spectrum(const int16_t* geometry, int pn, double epsilon, int N, 
 {
     return litho::mask_spectrum(geometry, pn, epsilon, N, (float2*)spectrum, workspace, workspace_bytes,
                                 (hipStream_t)stream);
+}
+
+int litho_mask_spectrum_complex(const void* transmission, int pn, double epsilon, int N, void* spectrum, void* workspace,
+                                size_t workspace_bytes, void* stream)
+{
+    return litho::mask_spectrum_complex((const float2*)transmission, pn, epsilon, N, (float2*)spectrum, workspace,
+                                        workspace_bytes, (hipStream_t)stream);
 }
 
 int litho_abbe_set_profiling(int on)

@@ -523,6 +523,16 @@ struct RealImageLoader {
     }
 };
 
+// Loader: a complex image (the bilinearly scaled complex mask transmission): RealImageLoader's window, `off` and padding
+// semantics; load() returns the stored float2 -- 8 bytes per lane, consecutive lanes on consecutive samples.
+struct ComplexImageLoader {
+    const float2* img;       // [n,n]
+    int n, off;
+    const float2* row;
+    __device__ __forceinline__ void begin_line(int, int a, const PassGeom&) { row = img + (size_t)(a + off) * n + off; }
+    __device__ __forceinline__ float2 load(int k, const PassGeom& g) const { return row[k - g.kx0]; }
+};
+
 // ----------------------------------------------------------------------------------
 // y-pass with |E|^2 accumulation in registers over the batch
 // ----------------------------------------------------------------------------------
@@ -804,6 +814,9 @@ struct SizeOps {
                             const PassGeom& g, int nb, hipStream_t st);
     hipError_t (*ypass_w64)(const float2* T, float* slab, const float2* tw, const PassGeom& g, int nb, int planes,
                             int G, int gstride, hipStream_t st);
+    // forward x-pass of a complex image (the scaled complex mask transmission)
+    hipError_t (*xpass_cplx_fwd)(const ComplexImageLoader& ld, float2* T, const float2* tw, const PassGeom& g,
+                                 hipStream_t st);
 };
 const SizeOps* size_ops(int log2n);      // nullptr outside 4..14
 
@@ -960,6 +973,17 @@ struct SizeImpl {
                            g);
         return hipGetLastError();
     }
+    static hipError_t xpass_cplx_fwd(const ComplexImageLoader& ld, float2* T, const float2* tw, const PassGeom& g,
+                                     hipStream_t st)
+    {
+        static LdsOnce once;
+        auto kern = k_xpass<LOG2N, -1, ComplexImageLoader>;
+        hipError_t e = set_lds(once, kern, LC::LDS_BYTES);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3((g.rows + LC::L - 1) / LC::L, 1), dim3(LC::THREADS), LC::LDS_BYTES, st, ld, T, tw,
+                           g);
+        return hipGetLastError();
+    }
     template <int RL, bool PRUNED>
     static hipError_t ya(const float2* T, float* slab, const float2* tw, const PassGeom& g, int nb, int planes, int G,
                          int gstride, hipStream_t st)
@@ -1060,7 +1084,7 @@ struct SizeImpl {
                                  &SizeImpl<L2>::xpass_real_fwd, &SizeImpl<L2>::ypass_acc,            \
                                  &SizeImpl<L2>::ypass_field, &SizeImpl<L2>::xpass_field_inv,         \
                                  &SizeImpl<L2>::ypass_addreal, &SizeImpl<L2>::xpass_w64,             \
-                                 &SizeImpl<L2>::ypass_w64};                                          \
+                                 &SizeImpl<L2>::ypass_w64, &SizeImpl<L2>::xpass_cplx_fwd};           \
         return &ops;                                                                                 \
     }
 

@@ -519,6 +519,37 @@ void launch_scale_mask(const int16_t* geo, int pn, int ns, double scale, float* 
     hipLaunchKernelGGL(k_scale_mask, dim3((ns + 255) / 256, ns), dim3(256), 0, st, geo, pn, ns, rs, out);
 }
 
+// The same resize of a complex64 transmission (no reference counterpart; definition in include/litho_abbe.h): the real and
+// the imaginary part each go through bilinear_at's arithmetic -- the same coordinates, weights and order of operations --
+// so a transmission of zeros and ones gives the int16 kernel's real part bit for bit and an imaginary part of exactly zero.
+// Consecutive lanes read consecutive (up-scaling: nearly consecutive) 8-byte samples and write consecutive float2.
+__global__ void k_scale_mask_c64(const float2* __restrict__ t, int pn, int ns, float rs, float2* __restrict__ out)
+{
+    const int ox = blockIdx.x * blockDim.x + threadIdx.x;
+    const int oy = blockIdx.y;
+    if (ox >= ns) return;
+    float2 v;
+    if (ns == pn) {                                      // equal sizes: torch copies
+        v = t[(size_t)oy * pn + ox];
+    } else {
+        int y0, y1, x0, x1;
+        float ly0, ly1, lx0, lx1;
+        lin_coord(oy, rs, pn, y0, y1, ly0, ly1);
+        lin_coord(ox, rs, pn, x0, x1, lx0, lx1);
+        const float2 a00 = t[(size_t)y0 * pn + x0], a01 = t[(size_t)y0 * pn + x1];
+        const float2 a10 = t[(size_t)y1 * pn + x0], a11 = t[(size_t)y1 * pn + x1];
+        v.x = ly0 * (lx0 * a00.x + lx1 * a01.x) + ly1 * (lx0 * a10.x + lx1 * a11.x);
+        v.y = ly0 * (lx0 * a00.y + lx1 * a01.y) + ly1 * (lx0 * a10.y + lx1 * a11.y);
+    }
+    out[(size_t)oy * ns + ox] = v;
+}
+
+void launch_scale_mask_c64(const float2* t, int pn, int ns, double scale, float2* out, hipStream_t st)
+{
+    const float rs = (float)(1.0 / scale);
+    hipLaunchKernelGGL(k_scale_mask_c64, dim3((ns + 255) / 256, ns), dim3(256), 0, st, t, pn, ns, rs, out);
+}
+
 static int osa_n(int j) { return (int)std::ceil(0.5 * (-3.0 + std::sqrt(9.0 + 8.0 * j))); }
 
 static double factorial(int v) { double f = 1.0; for (int i = 2; i <= v; ++i) f *= i; return f; }

@@ -412,9 +412,32 @@ def rasterizeLayout(polygons: Sequence[np.ndarray], pixelNumber: int, pixelSize:
 
 
 def maskFromGDSII(source, pixelNumber: int, pixelSize: float, top: Optional[str] = None,
-                  layers: Optional[Sequence[Tuple[int, int]]] = None, origin=None, device=None):
-    """GDSII file -> `Mask` (the object abbeImage takes): read, flatten `top`, rasterise the chosen layers."""
+                  layers: Optional[Sequence[Tuple[int, int]]] = None, origin=None, device=None,
+                  transmissions: Optional[Dict[Tuple[int, int], complex]] = None, background: complex = 0):
+    """GDSII file -> `Mask` (the object abbeImage takes): read, flatten `top`, rasterise the chosen layers.
+
+    transmissions = {(layer, datatype): complex} makes a phase-shift / grey mask instead: every listed layer is rasterised
+    on its own and the rasters are composed in the mapping's order -- a later layer overrides an earlier one where both
+    cover a pixel, `background` fills what no layer covers; `layers` is not used.  With origin=None the window is centred
+    on the bounding box of all listed layers together, so that the rasters share one grid."""
     from .mask import Mask
     lib = source if isinstance(source, GdsLibrary) else readGDSII(source)
+    if transmissions is not None:
+        import torch
+        polys = {key: flattenLayout(lib, top, [key]) for key in transmissions}
+        if origin is None:
+            pts = [q for ps in polys.values() for q in ps]
+            ctr = (np.min([q.min(axis=0) for q in pts], axis=0) + np.max([q.max(axis=0) for q in pts], axis=0)) / 2.0 \
+                if pts else np.zeros(2)
+            origin = (float(ctr[0]) - int(pixelNumber) * pixelSize / 2.0, float(ctr[1]) - int(pixelNumber) * pixelSize / 2.0)
+        t = None
+        for key, value in transmissions.items():
+            geo = rasterizeLayout(polys[key], pixelNumber, pixelSize, origin, device)
+            if t is None:
+                t = torch.full(geo.shape, complex(background), dtype=torch.complex64, device=geo.device)
+            t[geo != 0] = complex(value)
+        if t is None:
+            raise ValueError("maskFromGDSII: transmissions is empty")
+        return Mask(pixelSize=pixelSize, device=t.device, transmission=t)
     geo = rasterizeLayout(flattenLayout(lib, top, layers), pixelNumber, pixelSize, origin, device)
     return Mask(geo, pixelSize, geo.device)

@@ -1,15 +1,74 @@
 """Mask: same object API as the reference's mask.py, spectrum computed by HIP kernels."""
+import cmath
+import math
+
 import torch
 
 from . import _native as nat
 
 
-class Mask:
-    """Mirror of reference mask.py:3-90 (class Mask)."""
+def _phasor(phase, what):
+    """exp(i phase) with multiples of pi/2 exact: pi -> (-1, 0), not (-1, 1.2e-16)."""
+    phase = float(phase)
+    if not math.isfinite(phase):
+        raise ValueError(f"{what}: the phase must be finite; got {phase}")
+    q = phase / (math.pi / 2)
+    if abs(q - round(q)) < 1e-12:                                           # 3 * math.pi / 2 is one ulp off 3 quarter turns
+        return (1 + 0j, 1j, -1 + 0j, -1j)[int(round(q)) % 4]
+    return cmath.exp(1j * phase)
 
-    def __init__(self, geometry: torch.Tensor = None, pixelSize: int = 25, device: torch.device = None):
+
+def attenuatedPSM(geometry: torch.Tensor, transmittance: float = 0.06, phase: float = math.pi) -> torch.Tensor:
+    """Complex transmission (complex64, geometry's shape and device) of an attenuated phase-shift mask: 1 where
+    geometry != 0 (clear), sqrt(transmittance) exp(i phase) elsewhere (the absorber; 6 % and pi: MoSi at 193 nm)."""
+    transmittance = float(transmittance)
+    if not 0.0 <= transmittance <= 1.0:                                     # NaN fails both comparisons
+        raise ValueError(f"attenuatedPSM: the transmittance is an intensity ratio in [0, 1]; got {transmittance}")
+    absorber = math.sqrt(transmittance) * _phasor(phase, "attenuatedPSM")
+    geometry = torch.as_tensor(geometry)
+    t = torch.full(geometry.shape, absorber, dtype=torch.complex64, device=geometry.device)
+    t[geometry != 0] = 1
+    return t
+
+
+def alternatingPSM(geometry: torch.Tensor, shifter: torch.Tensor, phase: float = math.pi) -> torch.Tensor:
+    """Complex transmission (complex64) of an alternating-aperture mask: clear pixels (geometry != 0) transmit 1, those
+    under the shifter (shifter != 0) exp(i phase); everything else is opaque."""
+    shifted = _phasor(phase, "alternatingPSM")
+    geometry = torch.as_tensor(geometry)
+    shifter = torch.as_tensor(shifter).to(geometry.device)
+    if shifter.shape != geometry.shape:
+        raise ValueError(f"alternatingPSM: geometry {tuple(geometry.shape)} and shifter {tuple(shifter.shape)} differ in shape")
+    clear = geometry != 0
+    t = torch.zeros(geometry.shape, dtype=torch.complex64, device=geometry.device)
+    t[clear] = 1
+    t[clear & (shifter != 0)] = shifted
+    return t
+
+
+class Mask:
+    """Mirror of reference mask.py:3-90 (class Mask).  `transmission` (no reference counterpart) makes it a phase-shift
+    or grey mask: a complex field transmission per pixel instead of the 0 / 1 geometry."""
+
+    def __init__(self, geometry: torch.Tensor = None, pixelSize: int = 25, device: torch.device = None,
+                 transmission: torch.Tensor = None):
         self.device = nat.pick_device(device, "mask")                      # mask.py:7-18
-        if (geometry is None or type(geometry) is not torch.Tensor) or (
+        self.transmission = None
+        if transmission is not None:
+            # a new argument: the reference's "never raises" demo fallback below does not apply to it
+            from .imageformation import ShapeError
+            if geometry is not None:
+                raise ShapeError("Mask takes a geometry or a transmission, not both")
+            if (type(transmission) is not torch.Tensor or transmission.dim() != 2
+                    or transmission.shape[0] != transmission.shape[1] or transmission.numel() == 0
+                    or not (transmission.is_floating_point() or transmission.is_complex())):
+                what = (f"{tuple(transmission.shape)} {transmission.dtype}" if type(transmission) is torch.Tensor
+                        else type(transmission).__name__)
+                raise ShapeError(f"transmission must be a square 2-D floating or complex tensor; got {what}")
+            self.transmission = transmission.to(dtype=torch.complex64, device=self.device).contiguous()
+            self.geometry = (self.transmission != 0).to(torch.int16)       # the footprint, for plotting
+            self.pixelNumber = self.geometry.size()[0]
+        elif (geometry is None or type(geometry) is not torch.Tensor) or (
                 len(geometry.size()) != 2 or geometry.size()[0] != geometry.size()[1]):
             # mask.py:20-27: never raises, falls back to the 64x64 four-bar demo
             print("Mask not defined or invalid. Check that it is a torch tensor and is square. Using demo instead.")
@@ -46,9 +105,16 @@ class Mask:
         """mask.py:74-90 as one C-ABI call (bilinear scale, centred forward DFT, crop)."""
         dev = nat.require_gpu(self.device)
         pn = self.pixelNumber
-        geo = self.geometry.contiguous()
         spec = torch.empty((pn, pn), dtype=torch.complex64, device=dev)
         ws = nat.workspace(dev, pn, N)
+        if self.transmission is not None:
+            t = self.transmission.contiguous()
+            with torch.cuda.device(dev):
+                nat.check(nat.lib().litho_mask_spectrum_complex(nat.ptr(t), pn, float(epsilon), int(N), nat.ptr(spec),
+                                                                nat.ptr(ws), ws.numel(), nat.stream_ptr(dev)),
+                          "litho_mask_spectrum_complex")
+            return spec
+        geo = self.geometry.contiguous()
         with torch.cuda.device(dev):
             nat.check(nat.lib().litho_mask_spectrum(nat.ptr(geo), pn, float(epsilon), int(N), nat.ptr(spec),
                                                     nat.ptr(ws), ws.numel(), nat.stream_ptr(dev)),

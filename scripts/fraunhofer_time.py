@@ -1,14 +1,23 @@
-"""Mask.fraunhofer (litho_mask_spectrum) time per mask next to the image time of the same size."""
+"""Mask.fraunhofer time per mask: the int16 entry (litho_mask_spectrum) next to the complex-transmission entry
+(litho_mask_spectrum_complex) of the same footprint -- twice the input bytes through the same two FFT launches."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import lithographysimulator_amd as L
 from lithographysimulator_amd.synthetic import bernoulli_mask
 dev = torch.device("cuda", 0)
-for pn in (256, 512, 1000, 1024, 2048, 4096):
-    mask = L.Mask(bernoulli_mask(pn), 25, dev)
+
+
+def per_mask_us(mask):
     mask.fraunhofer(193., True); torch.cuda.synchronize()
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     a.record()
     for _ in range(20): mask.fraunhofer(193., True)
     b.record(); torch.cuda.synchronize()
-    print(f"pn {pn:5d}: fraunhofer {a.elapsed_time(b) / 20 * 1e3:9.1f} us per mask", flush=True)
+    return a.elapsed_time(b) / 20 * 1e3
+
+
+for pn in (256, 512, 1000, 1024, 2048, 4096):
+    geo = bernoulli_mask(pn)
+    t_i = per_mask_us(L.Mask(geo, 25, dev))
+    t_c = per_mask_us(L.Mask(pixelSize=25, device=dev, transmission=L.attenuatedPSM(geo)))
+    print(f"pn {pn:5d}: fraunhofer int16 {t_i:9.1f} us per mask, complex64 {t_c:9.1f} us per mask, ratio {t_c / t_i:5.2f}", flush=True)
