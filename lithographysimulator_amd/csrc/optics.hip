@@ -25,17 +25,20 @@ __device__ __forceinline__ float h16(float v) { return __half2float(__float2half
 static float h16_host(float v) { return __half2float(__float2half_rn(v)); }
 
 // torch.arange(start, end, step, dtype=float16)[i] on CPU (lightsource.py:39-40,
-// pupil.py:53): filled 16 lanes at a time, chunk base rounded to fp16 first; a tail
-// shorter than 16 is h(start + step*i).
+// pupil.py:53), AVX512 build (rule and evidence: SURVEY.md a4-recipe, golden g18): the first
+// (n / 32) * 32 elements are filled 32 per trip as two 16-lane vectors, each from a base fma(step, i0, start) that is
+// rounded to fp16 first, lane l = h(fma(l, step, base)); the last n % 32 elements are h(fma(step, i, start)).  Every
+// multiply-add rounds ONCE in the reference, so each is an explicit __fmaf_rn: this file is built with
+// -ffp-contract=off, and the contraction setting must not decide the result either way.
 __device__ __forceinline__ float sigma_axis(int i, int n, float fs, float fst)
 {
-    const int full = (n / 16) * 16;
+    const int full = (n / 32) * 32;
     if (i < full) {
         const int i0 = (i / 16) * 16;
-        const float base = h16(fs + fst * (float)i0);
-        return h16(base + (float)(i - i0) * fst);
+        const float base = h16(__fmaf_rn(fst, (float)i0, fs));
+        return h16(__fmaf_rn((float)(i - i0), fst, base));
     }
-    return h16(fs + fst * (float)i);
+    return h16(__fmaf_rn(fst, (float)i, fs));
 }
 
 __device__ __forceinline__ float radius16(float x, float y)

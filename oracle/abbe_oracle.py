@@ -69,21 +69,39 @@ def calculate_epsilon_n(deltaK: float, pixelSize: float, wavelength: float) -> T
 # --------------------------------------------------------------------------
 # a5  source sampling  (lightsource.py:34-73)
 # --------------------------------------------------------------------------
+def _fma32(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
+    """fp32 a*b + c with ONE rounding.  The product of two fp32 values is exact in double, and for the axis operands
+    (|values| <= 4, steps >= 2^-20) so is the sum, so the only rounding is the conversion back to fp32."""
+    return (a.double() * b.double() + c.double()).to(F32)
+
+
 def _sigma_axis(pn: int, shift: float) -> torch.Tensor:
-    """torch.arange(-2-shift, 2-shift, 4/pn, dtype=fp16) (lightsource.py:39-40, pupil.py:53).
-    torch-CPU fills fp16 aranges 16 lanes at a time: the chunk base start+step*i0 is
-    evaluated in fp32 and ROUNDED TO fp16, then lane l is h(base + l*step); a tail shorter
-    than 16 is h(start + step*i).  Identical to h(start+i*step) whenever the shift is
-    fp16-exact (every BASELINE config), differs for shifts such as 0.2.  The element count
-    is ceil((end-start)/step) in double."""
+    """torch.arange(-2-shift, 2-shift, 4/pn, dtype=fp16) (lightsource.py:39-40, pupil.py:53) as torch-CPU fills it under
+    its AVX512 capability (the goldens' build; worked out from golden g18 and torch 2.10 on such a CPU):
+
+    * start and step are kept in fp32; the element count n is ceil((end-start)/step) in double;
+    * the first (n // 32) * 32 elements are written by the vector loop, 32 per trip as two 16-lane vectors.  A vector
+      whose first index is i0 (a multiple of 16) takes its base fma(step, i0, start) -- ONE rounding to fp32 -- and
+      ROUNDS IT TO fp16; lane l is then h(fma(l, step, base)), again one fp32 rounding before the fp16 one;
+    * the remaining n % 32 elements come from the scalar loop: h(fma(step, i, start)), no fp16-rounded base.
+
+    Every multiply-add is fused.  With separately rounded products the centre sample of pn = 30 is 0 instead of 2^-23 and
+    52 of g18's 105 axes differ; with a vector region of (n // 16) * 16 every size that is no multiple of 32 differs in
+    its last partial 32-block.  Identical to h(start + i*step) whenever start and step are exact in fp16 and the products
+    in fp32 (every power-of-two size at an fp16-exact shift).  The reference is ISA-dependent here: torch 2.10 gives these
+    values under its AVX512 and AVX2 capabilities (552 (pn, shift) pairs compared, 0 differ), but with
+    ATEN_CPU_CAPABILITY=default there is no vector loop and no fp16-rounded base, and 21 of the 552 axes change.  The
+    goldens are AVX512 ones and this function follows them.  Sizes of 32768 and more (torch splits the fill across
+    threads) are not covered."""
     start, end, step = -2.0 - shift, 2.0 - shift, 4.0 / pn
     n = int(math.ceil((end - start) / step))
     i = torch.arange(n)
     fs, fst = _fs(start), _fs(step)
     i0 = (i // 16) * 16
-    vec = h(h(fs + fst * i0.to(F32)) + (i - i0).to(F32) * fst)
-    tail = h(fs + fst * i.to(F32))
-    return torch.where(i < (n // 16) * 16, vec, tail)
+    base = h(_fma32(fst, i0.to(F32), fs))
+    vec = h(_fma32((i - i0).to(F32), fst, base))
+    tail = h(_fma32(fst, i.to(F32), fs))
+    return torch.where(i < (n // 32) * 32, vec, tail)
 
 
 def _source_radius(pn: int, shiftX: float, shiftY: float):

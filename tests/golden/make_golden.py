@@ -8,6 +8,7 @@ reference's source never enters this repository and never travels to the GPU box
 
 Environment the committed fixtures were made with: torch 2.10.0+rocm7.0 (CPU), 8 threads.
 Fixture groups follow SURVEY.md section 8c (G1..G7).
+g18 (`make_golden.py g18`) is written with fixed zip timestamps and regenerates byte for byte on the same machine.
 """
 import hashlib
 import math
@@ -642,6 +643,145 @@ def g16_odd_sizes():
     save("g16_odd_sizes.npz", **out)
 
 
+def save_reproducible(name, **arrays):
+    """np.savez_compressed with the clock that zipfile stamps every member with held at 1980-01-01, so that a second run
+    on the same machine writes the same bytes (the arrays go in in insertion order)."""
+    import types
+    import zipfile
+    from unittest import mock
+    frozen = types.SimpleNamespace(time=lambda: 0.0, localtime=lambda *_: (1980, 1, 1, 0, 0, 0, 1, 1, 0))
+    with mock.patch.object(zipfile, "time", frozen):
+        save(name, **arrays)
+
+
+def pack_bits(a):
+    """0/1 array of any shape -> zlib-packed bits, as g1 stores its bitmaps."""
+    packed = np.packbits(np.ascontiguousarray(a).astype(np.uint8).reshape(-1))
+    return np.frombuffer(zlib.compress(packed.tobytes(), 9), dtype=np.uint8)
+
+
+G18_AXIS_PN = (14, 16, 30, 46, 62, 64, 96, 100, 118, 120, 200, 502, 1000, 1500, 3000)
+G18_AXIS_SHIFT = (0.0, 0.2, -0.1, 0.0625, 0.3, -0.37, 0.41)
+G18_SRC_PN = (14, 30, 46, 62, 100, 118)
+G18_SRC_SIGMA = ((0.0, 0.3), (0.2, 0.95), (0.55, 0.6), (0.0, 1.0), (0.7, 1.2), (0.333, 0.777))
+G18_SRC_SHIFT = ((0.0, 0.0), (0.2, -0.1), (0.0625, 0.3), (-0.37, 0.41))
+G18_SRC_QUASAR = ((1, 0.0), (2, 0.5), (3, 0.3), (4, -math.pi / 8), (6, math.pi / 12), (8, -1.0), (5, 7.0), (16, 0.1),
+                  (64, 0.01), (4, -7.5))
+G18_LARGE_PN = (200, 502, 1000, 3000)
+G18_LARGE_SHIFT = ((0.0, 0.0), (-0.37, 0.41))
+G18_NALAM = ((0.7, 193.0), (0.33, 13.5), (1.35, 193.0), (0.6, 248.0))
+G18_PUPIL_PN = (14, 30, 46, 64)
+G18_PUPIL_PN_FEW = (100, 118, 256)               # J36, tiny and big at (0.7, 193) only
+G18_FEW = ("J36", "tiny", "big")
+G18_TF_DEFOCUS = (-500.0, -33.0, 0.5, 250.0)
+G18_TF_PN = (30, 64)
+G18_TF_NALAM = (1, 2)                            # indices into G18_NALAM: (0.33, 13.5) and (1.35, 193)
+G18_TF_VECTORS = ("J28", "J36")
+
+
+def g18_vectors():
+    """The aberration vectors of the pupil sweep, fp16.  The random ones come from one seeded generator, in this order."""
+    gen = torch.Generator().manual_seed(18)
+    vec = {}
+    for J in (21, 28, 36, 45, 66):
+        v = (torch.rand(J, generator=gen, dtype=torch.float64) * 2 - 1) * (0.03 if J >= 45 else 0.05)
+        v[:2] = 0
+        vec[f"J{J}"] = v.to(torch.float16)
+    vec["tiny"] = f16([0, 0, 1e-4, -2e-4, 1.0, 3e-5, -1e-4, 6e-5])          # products are fp16-subnormal
+    vec["big"] = f16([0.5, -0.3, 0.4, -0.6, 900, 0.7, -0.2, 0.3, 0.25, -0.4])
+    vec["short3"] = f16([0.25, 0.1, -0.1])                                  # J < 4: no defocus rescale
+    v = (torch.rand(13, generator=gen, dtype=torch.float64) * 2 - 1) * 0.05
+    v[:2] = 0
+    v[4] = -500
+    vec["J13_defocus_m500"] = v.to(torch.float16)
+    return vec
+
+
+def g18_optics_sweep():
+    """Source and pupil kernels away from the demo grids (sizes that are no multiple of 32 or 64, shifts that fp16 cannot
+    hold, every wedge count, four (NA, wavelength) pairs, 3 to 66 Zernike terms), by the reference itself: its fp16
+    torch.arange axes, its source bitmaps, its fp16 wavefront errors and its r <= 1 support.  phi is not stored: it is a
+    function of W and the support.  Made under torch's default CPU capability, which is recorded in the file."""
+    print("G18 optics sweep")
+    out = {"torch_version": np.array(torch.__version__), "cpu_capability": np.array(torch.backends.cpu.get_cpu_capability())}
+    # axes: what lightsource.py:39-40 and pupil.py:53 build, as raw fp16 bits, [shift, pn]
+    out["axis_pn"] = np.array(G18_AXIS_PN, dtype=np.int64)
+    out["axis_shift"] = np.array(G18_AXIS_SHIFT, dtype=np.float64)
+    for pn in G18_AXIS_PN:
+        rows = [torch.arange(-2 - s, 2 - s, 2 * 2 / pn, dtype=torch.float16, device=CPU) for s in G18_AXIS_SHIFT]
+        assert all(r.numel() == pn for r in rows), pn
+        out[f"axis_{pn}"] = torch.stack(rows).view(torch.int16).numpy().view(np.uint16)
+    # sources, small sizes: [sigma, shift, kind, pn, pn]; kind 0 = annular, kind 1 + q = quasar q
+    out["src_pn"] = np.array(G18_SRC_PN, dtype=np.int64)
+    out["src_sigma"] = np.array(G18_SRC_SIGMA, dtype=np.float64)
+    out["src_shift"] = np.array(G18_SRC_SHIFT, dtype=np.float64)
+    out["src_quasar"] = np.array(G18_SRC_QUASAR, dtype=np.float64)
+    for pn in G18_SRC_PN:
+        bms = np.zeros((len(G18_SRC_SIGMA), len(G18_SRC_SHIFT), 1 + len(G18_SRC_QUASAR), pn, pn), dtype=np.uint8)
+        for a, (sin, sout) in enumerate(G18_SRC_SIGMA):
+            for b, (sx, sy) in enumerate(G18_SRC_SHIFT):
+                ls = quiet(ref_ls.LightSource, sin, sout, pn, NA, sx, sy, CPU)
+                bms[a, b, 0] = ls.generateAnnular().numpy()
+                for q, (count, rot) in enumerate(G18_SRC_QUASAR):
+                    bms[a, b, 1 + q] = ls.generateQuasar(int(count), rot).numpy()
+        assert bms.max() <= 1
+        out[f"src_packed_{pn}"] = pack_bits(bms)
+        print(f"   sources {pn}: {bms.shape[0] * bms.shape[1] * bms.shape[2]} bitmaps, {int(bms.sum())} lit")
+    # sources, large sizes: count, per-row counts, hash
+    out["srcL_pn"] = np.array(G18_LARGE_PN, dtype=np.int64)
+    out["srcL_shift"] = np.array(G18_LARGE_SHIFT, dtype=np.float64)
+    for pn in G18_LARGE_PN:
+        for b, (sx, sy) in enumerate(G18_LARGE_SHIFT):
+            for kind in ("annular", "quasar"):
+                bm = source(kind, pn, 0.4, 0.8, sx, sy, *QUASAR).numpy().astype(np.uint8)
+                key = f"srcL_{kind}_{b}_{pn}"
+                out[f"{key}_count"] = np.int64(bm.sum())
+                out[f"{key}_rows"] = bm.sum(1).astype(np.int32)
+                out[f"{key}_sha256"] = np.frombuffer(hashlib.sha256(np.packbits(bm).tobytes()).digest(), dtype=np.uint8)
+    # pupils: fp16 W as raw bits [nalam, vector, pn, pn]; the support once per pn
+    vec = g18_vectors()
+    names = list(vec)
+    out["pupil_nalam"] = np.array(G18_NALAM, dtype=np.float64)
+    out["pupil_pn"] = np.array(G18_PUPIL_PN, dtype=np.int64)
+    out["pupil_pn_few"] = np.array(G18_PUPIL_PN_FEW, dtype=np.int64)
+    out["pupil_names"] = np.array(names)
+    out["pupil_names_few"] = np.array(G18_FEW)
+    for name, v in vec.items():
+        out[f"vec_{name}"] = v.view(torch.int16).numpy().view(np.uint16)
+
+    def w_bits(v, pn, na, lam):
+        W = ref_pupil.generateWavefrontError(v.clone(), pn, na, lam, CPU)          # fresh vector: the call rescales it (Q2)
+        return W.real.to(torch.float16).view(torch.int16).numpy().view(np.uint16)
+
+    for pn in G18_PUPIL_PN + G18_PUPIL_PN_FEW:
+        few = pn in G18_PUPIL_PN_FEW
+        out[f"pupil_W_{pn}"] = np.stack([np.stack([w_bits(vec[n], pn, na, lam) for n in (G18_FEW if few else names)])
+                                         for na, lam in (G18_NALAM[:1] if few else G18_NALAM)])
+        support = ref_pupil.generatePhi(torch.zeros((pn, pn), dtype=torch.complex64), pn, CPU) != 0
+        out[f"pupil_support_{pn}"] = pack_bits(support.numpy())
+        print(f"   pupils {pn}: W {out[f'pupil_W_{pn}'].shape}, support {int(support.sum())}")
+    # through-focus planes: the reference's loop `ab = v.clone(); ab[4] = d`, [nalam, vector, plane, pn, pn]
+    out["tf_defocus"] = np.array(G18_TF_DEFOCUS, dtype=np.float64)
+    out["tf_nalam_index"] = np.array(G18_TF_NALAM, dtype=np.int64)
+    out["tf_names"] = np.array(G18_TF_VECTORS)
+    out["tf_pn"] = np.array(G18_TF_PN, dtype=np.int64)
+    for pn in G18_TF_PN:
+        planes = []
+        for k in G18_TF_NALAM:
+            na, lam = G18_NALAM[k]
+            per_vec = []
+            for n in G18_TF_VECTORS:
+                per_plane = []
+                for d in G18_TF_DEFOCUS:
+                    ab = vec[n].clone()
+                    ab[4] = d
+                    per_plane.append(w_bits(ab, pn, na, lam))
+                per_vec.append(np.stack(per_plane))
+            planes.append(np.stack(per_vec))
+        out[f"tf_W_{pn}"] = np.stack(planes)
+    save_reproducible("g18_optics_sweep.npz", **out)
+
+
 if __name__ == "__main__":
     torch.manual_seed(0)
     if os.environ.get("LITHO_GOLDEN_THREADS"):
@@ -650,4 +790,5 @@ if __name__ == "__main__":
     for g in which:
         {"g1": g1_sources, "g2": g2_pupils, "g3": g3_mask_spectra, "g4": g4_fields,
          "g5": g5_images, "g6": g6_through_focus, "g8": g8_large_pupils, "g9": g9_config5_stack, "g10": g10_contiguous_shards,
-         "g11": g11_config2_full, "g12": g12_shard4096, "g13": g13_config3_long_run, "g14": g14_config3_rank_shard, "g15": g15_config5_stack_run, "g16": g16_odd_sizes, "g17": g17_config4_fold_run}[g]()
+         "g11": g11_config2_full, "g12": g12_shard4096, "g13": g13_config3_long_run, "g14": g14_config3_rank_shard, "g15": g15_config5_stack_run, "g16": g16_odd_sizes, "g17": g17_config4_fold_run,
+         "g18": g18_optics_sweep}[g]()

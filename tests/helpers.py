@@ -61,6 +61,65 @@ def unpack_bitmap(blob: np.ndarray, pn: int) -> np.ndarray:
     return bits[:pn * pn].reshape(pn, pn)
 
 
+def unpack_bits(blob: np.ndarray, shape) -> np.ndarray:
+    """zlib-packed bits (make_golden.pack_bits) -> uint8 0/1 array of `shape`."""
+    bits = np.unpackbits(np.frombuffer(zlib.decompress(blob.tobytes()), dtype=np.uint8))
+    return bits[:int(np.prod(shape))].reshape(shape)
+
+
+def f16_from_bits(bits: np.ndarray) -> torch.Tensor:
+    """raw uint16 -> fp16 tensor of the same shape."""
+    return torch.from_numpy(np.ascontiguousarray(bits).view(np.int16)).view(torch.float16)
+
+
+def g18_source_cases(g, pn):
+    """Every small-size source case of golden g18 at `pn`: (label, sin, sout, sx, sy, count, rot, bitmap), count None for
+    the annular source.  The order is the fixture's: sigma pair, shift, kind."""
+    sig, sh, qs = g["src_sigma"], g["src_shift"], g["src_quasar"]
+    bms = unpack_bits(g[f"src_packed_{pn}"], (len(sig), len(sh), 1 + len(qs), pn, pn))
+    for a, (sin, sout) in enumerate(sig):
+        for b, (sx, sy) in enumerate(sh):
+            yield f"annular {sin}-{sout} shift ({sx},{sy})", float(sin), float(sout), float(sx), float(sy), None, 0.0, bms[a, b, 0]
+            for q, (count, rot) in enumerate(qs):
+                yield (f"quasar({int(count)},{rot:.4g}) {sin}-{sout} shift ({sx},{sy})", float(sin), float(sout), float(sx),
+                       float(sy), int(count), float(rot), bms[a, b, 1 + q])
+
+
+def g18_large_source_cases(g):
+    """The large-size source cases of golden g18: (key, pn, kind, sx, sy); annular and quasar(4, -pi/8), 0.4-0.8."""
+    for pn in g["srcL_pn"]:
+        for b, (sx, sy) in enumerate(g["srcL_shift"]):
+            for kind in ("annular", "quasar"):
+                yield f"srcL_{kind}_{b}_{int(pn)}", int(pn), kind, float(sx), float(sy)
+
+
+def g18_pupil_cases(g):
+    """Every single-pupil case of golden g18: (label, pn, NA, wavelength, fp16 vector, fp16 W)."""
+    nalam = g["pupil_nalam"]
+    for pn in list(g["pupil_pn"]) + list(g["pupil_pn_few"]):
+        few = pn in g["pupil_pn_few"]
+        W = g[f"pupil_W_{int(pn)}"]
+        for a, (na, lam) in enumerate(nalam[:1] if few else nalam):
+            for v, name in enumerate(g["pupil_names_few"] if few else g["pupil_names"]):
+                yield (f"pn {int(pn)} NA {na} lambda {lam} {name}", int(pn), float(na), float(lam),
+                       f16_from_bits(g[f"vec_{name}"]), f16_from_bits(W[a, v]))
+
+
+def g18_focus_cases(g):
+    """The through-focus cases of golden g18: (label, pn, NA, wavelength, fp16 vector, fp16 W [planes, pn, pn])."""
+    for pn in g["tf_pn"]:
+        W = g[f"tf_W_{int(pn)}"]
+        for a, k in enumerate(g["tf_nalam_index"]):
+            na, lam = g["pupil_nalam"][int(k)]
+            for v, name in enumerate(g["tf_names"]):
+                yield (f"pn {int(pn)} NA {na} lambda {lam} {name}", int(pn), float(na), float(lam),
+                       f16_from_bits(g[f"vec_{name}"]), f16_from_bits(W[a, v]))
+
+
+def g18_support(g, pn):
+    return unpack_bits(g[f"pupil_support_{pn}"], (pn, pn)).astype(bool)
+
+
 def subsample_bitmap(bitmap: torch.Tensor, K: int) -> torch.Tensor:
     pts = torch.argwhere(bitmap)
     S = pts.shape[0]

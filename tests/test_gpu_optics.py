@@ -6,7 +6,8 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import (NA, PS, PUPIL_CASES, SOURCE_CASES, TOL_IMAGE_MAX, TOL_PHI, WL, f16, rel_max, sha256_packed, unpack_bitmap)
+from helpers import (NA, PS, PUPIL_CASES, SOURCE_CASES, TOL_IMAGE_MAX, TOL_PHI, WL, f16, g18_focus_cases, g18_large_source_cases,
+                     g18_pupil_cases, g18_source_cases, g18_support, rel_max, sha256_packed, unpack_bitmap)
 
 pytestmark = pytest.mark.gpu
 
@@ -343,3 +344,148 @@ def test_bossung_curves_of_a_through_focus_stack(L, dev):
     assert bool((dark[0] >= dark[1]).all()) and bool((dark[1] >= dark[2]).all())        # more dose: unexposed lines shrink
     assert bool((bright[0] <= bright[1]).all()) and bool((bright[1] <= bright[2]).all())  # ... exposed spaces widen
     assert torch.equal(dark[:, 0], dark[:, 4]) and torch.equal(dark[:, 1], dark[:, 3])  # symmetric through focus
+
+
+# ---------------------------------------------------------------- golden g18: off the demo grids, fixture only
+def _report(bad, total, what):
+    assert not bad, f"{len(bad)} of {total} {what} differ from the reference:\n  " + "\n  ".join(bad[:40])
+
+
+def _ordered(bits16):
+    """fp16 bit patterns -> integers in value order (adjacent values differ by one)."""
+    b = bits16.to(torch.int32) & 0xFFFF
+    return torch.where(b < 0x8000, b, 0x8000 - b)
+
+
+def _w_mismatches(W, Wref):
+    """(values that differ bit for bit, those of them that are NOT exactly one fp16 ulp away)."""
+    a, b = W.cpu().view(torch.int16), Wref.view(torch.int16)
+    diff = a != b
+    far = diff & ((_ordered(a) - _ordered(b)).abs() != 1)
+    return int(diff.sum()), int(far.sum())
+
+
+def _phi_f64(W16):
+    """exp(i 2 pi W) with the exponential in float64.  Its ARGUMENT is the reference's: pupil.py:103 multiplies the
+    complex64 W by the Python scalar 1j*2*pi, i.e. by fp32(2 pi) with one fp32 rounding of the product, and that rounding
+    belongs to the operation, not to the kernel's error (for |W| = 5 it alone moves phi by 3e-6)."""
+    ang = (torch.tensor(2 * math.pi, dtype=torch.float32) * W16.to(torch.float32)).double()
+    return torch.complex(torch.cos(ang), torch.sin(ang))
+
+
+@pytest.mark.parametrize("pn", [14, 30, 46, 62, 100, 118])
+def test_g18_source_bitmaps_and_lists(golden, L, dev, pn):
+    """k_source_bitmap and the compaction at sizes that are no multiple of 32 (the axis' scalar tail, lit at 30 and 62), four
+    shifts of which three are not fp16 numbers, wedge counts 1 .. 64, rotations beyond +-2 pi: 264 bitmaps per size, every
+    pixel, and sourceShifts = argwhere - pn // 2 of the golden bitmap."""
+    g = golden("g18_optics_sweep.npz")
+    bad, total = [], 0
+    for label, sin, sout, sx, sy, count, rot, ref in g18_source_cases(g, pn):
+        ls = L.LightSource(sin, sout, pn, NA, sx, sy, dev)
+        bm = ls.generateAnnular() if count is None else ls.generateQuasar(count, rot)
+        total += 1
+        flips = int((bm.cpu().numpy() != ref).sum())
+        want = np.argwhere(ref).astype(np.int32) - pn // 2
+        lists_equal = np.array_equal(L.sourceShifts(bm, pn).cpu().numpy(), want)
+        if flips or not lists_equal:
+            bad.append(f"{label}: {flips} pixels{'' if lists_equal else ', source list differs'}")
+    print(f"g18 sources pn {pn}: {len(bad)} of {total} differ")
+    _report(bad, total, f"source cases at pn {pn}")
+
+
+def test_g18_source_bitmaps_large(golden, L, dev):
+    """200, 502, 1000 and 3000, centred and shifted by (-0.37, 0.41): lit count, every row count, sha256 of the packed bits;
+    the source list against argwhere of the bitmap the hash has just identified with the reference's."""
+    g = golden("g18_optics_sweep.npz")
+    bad, total = [], 0
+    for key, pn, kind, sx, sy in g18_large_source_cases(g):
+        bm_dev = _source(L, dev, pn, kind, 0.4, 0.8, sx, sy)
+        bm = bm_dev.cpu().numpy()
+        total += 1
+        rows = int((bm.sum(1).astype(np.int32) != g[f"{key}_rows"]).sum())
+        same = np.array_equal(sha256_packed(bm), g[f"{key}_sha256"])
+        lists_equal = np.array_equal(L.sourceShifts(bm_dev, pn).cpu().numpy(), np.argwhere(bm).astype(np.int32) - pn // 2)
+        if int(bm.sum()) != int(g[f"{key}_count"]) or rows or not same or not lists_equal:
+            bad.append(f"{key}: count {int(bm.sum())} vs {int(g[f'{key}_count'])}, {rows} row counts differ, "
+                       f"sha256 {'equal' if same else 'differs'}, list {'equal' if lists_equal else 'differs'}")
+    print(f"g18 large sources: {len(bad)} of {total} differ")
+    _report(bad, total, "large source cases")
+
+
+def test_g18_pupils(golden, L, dev):
+    """k_pupil_packed (J <= 32) and k_pupil with its staged table (J = 36, 45, 66 -- that path's first comparison with the
+    reference) at pn 14 .. 256, four (NA, wavelength) pairs, fp16-subnormal products, a 900 nm defocus and a vector too
+    short for the defocus rescale: fp16 W, the r <= 1 support, and phi against exp(i 2 pi W_golden) in float64.
+
+    W: the reference and the oracle agree on all of these on the CPU, so a difference is the kernel's.  The only legitimate
+    one is a flipped fp16 rounding after atan2 / cos / sin / pow (correctly rounded here, SLEEF within 1 ulp there), budgeted
+    in SURVEY 8c at 1e-5 of the pixels compared, each exactly one fp16 ulp away.  OBSERVED on MI355X: 0 of 531,468 values in
+    153 cases -- so 0 is asserted."""
+    g = golden("g18_optics_sweep.npz")
+    bad, total, pixels, mism_total, worst = [], 0, 0, 0, 0.0
+    for label, pn, na, lam, vec, Wref in g18_pupil_cases(g):
+        W = L.Pupil(pn, lam, na, vec.clone(), dev).generateWavefrontError().real.to(torch.float16)
+        phi = L.Pupil(pn, lam, na, vec.clone(), dev).generatePupilFunction().cpu()
+        total += 1
+        pixels += pn * pn
+        mism, far = _w_mismatches(W, Wref)
+        mism_total += mism
+        support = torch.from_numpy(g18_support(g, pn))
+        flips = int(((phi != 0) != support).sum())
+        want = torch.where(support, _phi_f64(Wref), torch.zeros((), dtype=torch.complex128))
+        err = float((phi.to(torch.complex128) - want).abs().max())
+        worst = max(worst, err)
+        if mism or flips or not err < TOL_PHI:
+            bad.append(f"{label}: {mism} W values ({far} by more than one ulp), {flips} support pixels, phi error {err:.2e}")
+    print(f"g18 pupils: {len(bad)} of {total} cases differ; {mism_total} of {pixels} fp16 W values; worst phi error {worst:.2e}")
+    _report(bad, total, "pupil cases")
+    assert mism_total == 0
+
+
+def test_g18_through_focus(golden, L, dev):
+    """throughFocusPupils at defocus -500, -33, 0.5 and 250 nm on a 28-term vector (k_pupil_stack) and a 36-term one (plane by
+    plane through the staged table), at (NA, wavelength) = (0.33, 13.5) and (1.35, 193), pn 30 and 64: every plane bit-identical
+    in W and phi to the single Pupil call with that defocus, whose W is the reference's (one golden W per plane)."""
+    g = golden("g18_optics_sweep.npz")
+    defocus = [float(d) for d in g["tf_defocus"]]
+    bad, total = [], 0
+    for label, pn, na, lam, vec, Wref in g18_focus_cases(g):
+        before = vec.clone()
+        W, phi = L.throughFocusPupils(pn, lam, na, vec, defocus, dev, wavefront=True)
+        assert torch.equal(vec, before) and tuple(W.shape) == tuple(phi.shape) == (len(defocus), pn, pn)
+        for p, d in enumerate(defocus):
+            ab = vec.clone()
+            ab[4] = d
+            W1 = L.Pupil(pn, lam, na, ab.clone(), dev).generateWavefrontError().real.to(torch.float16)
+            phi1 = L.Pupil(pn, lam, na, ab.clone(), dev).generatePupilFunction()
+            total += 1
+            mism, _ = _w_mismatches(W1, Wref[p])
+            same_w = torch.equal(W[p].view(torch.int16), W1.view(torch.int16))
+            same_phi = torch.equal(torch.view_as_real(phi[p]), torch.view_as_real(phi1))
+            if mism or not same_w or not same_phi:
+                bad.append(f"{label} defocus {d}: single call {mism} W values off the reference, stack W "
+                           f"{'equal' if same_w else 'differs'}, stack phi {'equal' if same_phi else 'differs'}")
+    print(f"g18 through focus: {len(bad)} of {total} planes differ")
+    _report(bad, total, "through-focus planes")
+
+
+@pytest.mark.parametrize("pn", [30, 100])
+def test_g18_generate_phi_complex_wavefront(golden, L, dev, pn):
+    """k_pupil_phase on a wavefront with a non-zero imaginary part (an absorbing pupil): exp(-2 pi Im) (cos, sin)(2 pi Re),
+    evaluated in float64 on the golden support, zero outside.  The arguments are the reference's fp32 products with
+    fp32(2 pi) (see _phi_f64); what remains is three fp32 roundings (magnitude, cos / sin, product) of 6e-8 relative each,
+    inside TOL_PHI scaled by the magnitude."""
+    g = golden("g18_optics_sweep.npz")
+    gen = torch.Generator().manual_seed(pn)
+    re = (torch.rand(pn, pn, generator=gen) - 0.5).to(torch.float32)
+    im = ((torch.rand(pn, pn, generator=gen) - 0.5) * 0.6).to(torch.float32)
+    phi = L.generatePhi(torch.complex(re, im).to(dev), pn, dev).cpu().to(torch.complex128)
+    support = torch.from_numpy(g18_support(g, pn))
+    twopi = torch.tensor(2 * math.pi, dtype=torch.float32)
+    mag = torch.exp(-(twopi * im).double())
+    ang = (twopi * re).double()
+    want = torch.where(support, mag * torch.complex(torch.cos(ang), torch.sin(ang)), torch.zeros((), dtype=torch.complex128))
+    assert torch.equal(phi != 0, support)
+    rel = float(((phi - want).abs() / torch.where(support, mag, torch.ones_like(mag))).max())
+    print(f"g18 generatePhi pn {pn}: worst error / magnitude {rel:.2e}, magnitudes {float(mag.min()):.2f} .. {float(mag.max()):.2f}")
+    assert rel < TOL_PHI

@@ -9,7 +9,8 @@ import torch
 from oracle import abbe_oracle as O
 from lithographysimulator_amd.synthetic import bernoulli_mask, lines_mask
 from helpers import (DEMO_AB, NA, PS, PUPIL_CASES, SOURCE_CASES, TOL_FIELD, TOL_IMAGE_L2, TOL_IMAGE_MAX, WL,
-                     c_oracle_field, crop_center, f16, load_c_oracle, rel_l2, rel_max, sha256_packed,
+                     c_oracle_field, crop_center, f16, f16_from_bits, g18_focus_cases, g18_large_source_cases,
+                     g18_pupil_cases, g18_source_cases, g18_support, load_c_oracle, rel_l2, rel_max, sha256_packed,
                      subsample_bitmap, unpack_bitmap)
 
 
@@ -284,3 +285,97 @@ def test_pupil_support_at_large_sizes(golden, pn):
     assert int(nz.sum()) == int(g[f"nz_defocus_p100_{pn}"])
     assert np.array_equal(nz.sum(1).to(torch.int32).numpy(), g[f"rowcount_defocus_p100_{pn}"])
     assert np.array_equal(phi[::64, ::64].numpy(), g[f"phisub_defocus_p100_{pn}"])
+
+
+# ---------------------------------------------------------------- G18 (sizes, shifts, wedge counts and term counts off the demo grids)
+def _report(bad, total, what):
+    assert not bad, f"{len(bad)} of {total} {what} differ from the reference:\n  " + "\n  ".join(bad[:40])
+
+
+def test_g18_made_under_the_default_cpu_capability(golden):
+    """The reference's own fp16 arange depends on the vector ISA torch dispatches to; the goldens are the AVX512
+    ones."""
+    g = golden("g18_optics_sweep.npz")
+    assert str(g["cpu_capability"]) == "AVX512" and str(g["torch_version"]).startswith("2.")
+
+
+def test_g18_sigma_axes_exact(golden):
+    """torch.arange(-2 - shift, 2 - shift, 4 / pn, dtype=float16) of the reference, 15 sizes x 7 shifts, bit for bit."""
+    g = golden("g18_optics_sweep.npz")
+    bad = []
+    for pn in g["axis_pn"]:
+        ref = f16_from_bits(g[f"axis_{int(pn)}"])
+        for k, shift in enumerate(g["axis_shift"]):
+            got = O._sigma_axis(int(pn), float(shift)).to(torch.float16)
+            wrong = torch.nonzero(got.view(torch.int16) != ref[k].view(torch.int16)).flatten().tolist() \
+                if got.shape == ref[k].shape else ["length"]
+            if wrong:
+                bad.append(f"pn {int(pn)} shift {shift}: indices {wrong[:8]}{' ...' if len(wrong) > 8 else ''}")
+    print(f"g18 axes: {len(bad)} of {len(g['axis_pn']) * len(g['axis_shift'])} differ")
+    _report(bad, len(g["axis_pn"]) * len(g["axis_shift"]), "sigma axes")
+
+
+def test_g18_source_bitmaps_small_exact(golden):
+    """Annular and quasar (wedge counts 1 .. 64, rotations beyond +-2 pi) bitmaps at sizes that are no multiple of 32, four
+    shifts, six sigma pairs: 1584 bitmaps, every pixel."""
+    g = golden("g18_optics_sweep.npz")
+    bad, total = [], 0
+    for pn in g["src_pn"]:
+        for label, sin, sout, sx, sy, count, rot, ref in g18_source_cases(g, int(pn)):
+            bm = O.source_annular(sin, sout, int(pn), sx, sy) if count is None else \
+                O.source_quasar(sin, sout, int(pn), count, rot, sx, sy)
+            total += 1
+            flips = int((bm.numpy() != ref).sum())
+            if flips:
+                bad.append(f"pn {int(pn)} {label}: {flips} pixels")
+    print(f"g18 small sources: {len(bad)} of {total} differ")
+    _report(bad, total, "source bitmaps")
+
+
+def test_g18_source_bitmaps_large_exact(golden):
+    """200, 502, 1000, 3000: centred and shifted by (-0.37, 0.41), where the scalar tail of the axis is lit."""
+    g = golden("g18_optics_sweep.npz")
+    bad, total = [], 0
+    for key, pn, kind, sx, sy in g18_large_source_cases(g):
+        bm = make_source(pn, kind, 0.4, 0.8, sx, sy).numpy()
+        total += 1
+        rows = int((bm.sum(1).astype(np.int32) != g[f"{key}_rows"]).sum())
+        if int(bm.sum()) != int(g[f"{key}_count"]) or rows or not np.array_equal(sha256_packed(bm), g[f"{key}_sha256"]):
+            bad.append(f"{key}: count {int(bm.sum())} vs {int(g[f'{key}_count'])}, {rows} row counts differ")
+    print(f"g18 large sources: {len(bad)} of {total} differ")
+    _report(bad, total, "large source bitmaps")
+
+
+def test_g18_pupil_support_exact(golden):
+    g = golden("g18_optics_sweep.npz")
+    bad = []
+    sizes = [int(p) for p in list(g["pupil_pn"]) + list(g["pupil_pn_few"])]
+    for pn in sizes:
+        r, _ = O._pupil_grid(pn)
+        flips = int(((r <= 1).numpy() != g18_support(g, pn)).sum())
+        if flips:
+            bad.append(f"pn {pn}: {flips} pixels")
+    _report(bad, len(sizes), "pupil supports")
+
+
+def test_g18_wavefronts_exact(golden):
+    """fp16 W for 3 to 66 terms, four (NA, wavelength) pairs, fp16-subnormal products and a 900 nm defocus, plus the
+    through-focus planes: bit for bit."""
+    g = golden("g18_optics_sweep.npz")
+    bad, total = [], 0
+    for label, pn, na, lam, vec, Wref in g18_pupil_cases(g):
+        W = O.wavefront_error(vec.clone(), pn, na, lam)
+        total += 1
+        mism = int((W.view(torch.int16) != Wref.view(torch.int16)).sum())
+        if mism:
+            bad.append(f"{label}: {mism} values")
+    for label, pn, na, lam, vec, Wref in g18_focus_cases(g):
+        for p, d in enumerate(g["tf_defocus"]):
+            ab = vec.clone()
+            ab[4] = float(d)
+            total += 1
+            mism = int((O.wavefront_error(ab, pn, na, lam).view(torch.int16) != Wref[p].view(torch.int16)).sum())
+            if mism:
+                bad.append(f"{label} defocus {d}: {mism} values")
+    print(f"g18 wavefronts: {len(bad)} of {total} differ")
+    _report(bad, total, "fp16 wavefronts")
