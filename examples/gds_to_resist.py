@@ -1,7 +1,7 @@
 """GDSII layout -> mask -> partially coherent aerial image -> resist contour (constant threshold, optionally on the
 diffused aerial image) -> sub-pixel critical dimension, on one MI355X.
 
-    python examples/gds_to_resist.py [layout.gds] [--top NAME] [--layer 7 --datatype 0] [--pn 512] [--pixel 25] [--diffusion 30]
+    python examples/gds_to_resist.py [layout.gds] [--top NAME] [--layer 7 --datatype 0] [--pn 512] [--pixel 25] [--diffusion 30] [--antialias 8]
 
 Without a file it writes a small line/space layout (a 12-bar grating placed by an AREF plus a wire drawn as a PATH) to
 /tmp and uses that.  Prints the image statistics and the printed line width on the centre row; saves nothing."""
@@ -42,12 +42,18 @@ def main():
     ap.add_argument("--pixel", type=float, default=25.0)
     ap.add_argument("--threshold", type=float, default=0.3, help="resist threshold as a fraction of the clear-field intensity")
     ap.add_argument("--diffusion", type=float, default=0.0, metavar="NM", help="acid diffusion length (Gaussian sigma, nm) of the diffused aerial image; 0 = none")
+    ap.add_argument("--antialias", type=int, default=1, choices=(1, 2, 4, 8, 16),
+                    help="s > 1: area-coverage raster on s x s sub-centres per pixel (a grey mask; edges keep their position to pixel / s)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     wl, na = 193.0, 0.7
     path = a.gds or demo_layout("/tmp/litho_demo.gds")
-    mask = L.maskFromGDSII(path, a.pn, a.pixel, top=a.top, layers=[(a.layer, a.datatype)], device=dev)
-    print(f"{path}: {int(mask.geometry.sum())} of {a.pn * a.pn} mask pixels set")
+    mask = L.maskFromGDSII(path, a.pn, a.pixel, top=a.top, layers=[(a.layer, a.datatype)], device=dev, antialias=a.antialias)
+    if mask.transmission is None:
+        print(f"{path}: {int(mask.geometry.sum())} of {a.pn * a.pn} mask pixels set")
+    else:
+        print(f"{path}: covered area {float(mask.transmission.real.sum()):.3f} of {a.pn * a.pn} mask pixels "
+              f"({a.antialias} x {a.antialias} sub-centres per pixel)")
     source = L.LightSource(0.4, 0.8, a.pn, na, device=dev).generateAnnular()
     pupil = L.Pupil(a.pn, wl, na, torch.tensor([0, 0, 0, 0, 30], dtype=torch.float16), dev).generatePupilFunction()
     mft = mask.fraunhofer(wl, True)

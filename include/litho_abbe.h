@@ -299,6 +299,21 @@ size_t litho_rasterize_work_bytes(int pn);
 int litho_rasterize_edges(const double *edges, int64_t n_edges, int pn, double x0, double y0, double pixel, void *work,
                           size_t work_bytes, int16_t *geometry, void *stream);
 
+/* ---- Area coverage (anti-aliased raster): the same inside rule on s x s sub-centres per pixel, s in {1, 2, 4, 8, 16}.  Sub-grid
+ * pitch q = pixel / (double)s (one fp64 division on the host); sub-centre (R, C) lies at (x0 + (C + 0.5) q, y0 + (R + 0.5) q),
+ * R, C in [0, pn s), and is inside exactly when litho_rasterize_edges at (pn s, q) with the same x0, y0 sets pixel (R, C).
+ * coverage fp32 [pn][pn] = (inside sub-centres of the pixel) / s^2, exact.  So coverage * s^2 equals the s x s block sums of that
+ * binary raster bit for bit: overlapping polygons union, the order in which the integer atomics land cannot show.
+ * The [pn s][pn s + 1] sub-grid work array (1 GiB at 2048^2, s = 8) is not required: the call works through BANDS of whole pixel
+ * rows, as many as work_bytes holds (at most pn; litho_rasterize_coverage_work_bytes(pn, s, band_rows) = band_rows * s *
+ * (pn s + 1) * 4 bytes, 0 for a bad argument), and the result does not depend on the band height.  Less than one pixel row of
+ * workspace: LITHO_E_WORKSPACE.  s outside the set, pn < 1, pn * s > 32768, a null pointer, pixel <= 0 or a NaN origin:
+ * LITHO_E_ARG, before any launch.  Non-finite and horizontal edges are skipped.  Asynchronous: three kernels per band, no
+ * allocation, no host wait. */
+size_t litho_rasterize_coverage_work_bytes(int pn, int s, int band_rows);
+int litho_rasterize_coverage(const double *edges, int64_t n_edges, int pn, double x0, double y0, double pixel, int s, void *work,
+                             size_t work_bytes, float *coverage, void *stream);
+
 /* ---- Mask spectrum pre-step: Mask._ffFraunhofer (mask.py:74-90).  geometry int16
  * [pn,pn]; spectrum complex64 [pn,pn].  Uses the same workspace as the Abbe calls. */
 int litho_mask_spectrum(const int16_t *geometry, int pn, double epsilon, int N, void *spectrum,

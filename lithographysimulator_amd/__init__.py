@@ -3,8 +3,8 @@ quarterwave0/LithographySimulator (Mask / LightSource / Pupil / abbeImage)."""
 from .imageformation import (PlanCache, abbeImage, abbeIntensity, bossungCurves, calculateFFTAerial,   # noqa: F401
                              embeddedSize, measureCD, postProcess, resistContour)
 from ._native import engineOptions                                                      # noqa: F401
-from .layout import (GdsLibrary, flattenLayout, maskFromGDSII, rasterizeLayout, readGDSII,  # noqa: F401
-                     writeGDSII)
+from .layout import (GdsLibrary, composeTransmission, flattenLayout, maskFromGDSII,       # noqa: F401
+                     rasterizeLayout, readGDSII, writeGDSII)
 from .lightsource import (LightSource, sourceShifts, sourceShiftsAsync, sourceWeights,   # noqa: F401
                           sourceWeightsAsync)
 from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
@@ -13,4 +13,4 @@ from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,   
 
 __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "abbeImage", "abbeIntensity", "calculateFFTAerial", "postProcess", "resistContour", "measureCD", "bossungCurves", "PlanCache", "engineOptions", "embeddedSize",
            "sourceShifts", "sourceShiftsAsync", "sourceWeights", "sourceWeightsAsync", "OSAindexToMN", "generateWavefrontError", "generatePhi", "generateZ",
-           "throughFocusPupils", "readGDSII", "writeGDSII", "flattenLayout", "rasterizeLayout", "maskFromGDSII", "GdsLibrary"]
+           "throughFocusPupils", "readGDSII", "writeGDSII", "flattenLayout", "rasterizeLayout", "composeTransmission", "maskFromGDSII", "GdsLibrary"]

@@ -55,6 +55,9 @@ _SIGNATURES = {
     "litho_mask_spectrum_complex": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "litho_rasterize_work_bytes": (c_size_t, [c_int]),
     "litho_rasterize_edges": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_double, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "litho_rasterize_coverage_work_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "litho_rasterize_coverage": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_double, c_int, c_void_p, c_size_t, c_void_p,
+                                         c_void_p]),
     "litho_abbe_last_plan": (c_int, [POINTER(c_int64)]),
     "litho_abbe_last_kernels": (c_int, [c_void_p, c_void_p, c_size_t]),
     "litho_abbe_set_profiling": (c_int, [c_int]),
@@ -288,6 +291,11 @@ def last_plan():
 
 def rasterize_work_bytes(pn: int) -> int:
     return int(lib().litho_rasterize_work_bytes(int(pn)))
+
+
+def rasterize_coverage_work_bytes(pn: int, s: int, band_rows: int) -> int:
+    """Bytes of litho_rasterize_coverage's workspace for bands of `band_rows` pixel rows; 0 for a bad argument."""
+    return int(lib().litho_rasterize_coverage_work_bytes(int(pn), int(s), int(band_rows)))
 
 
 def last_kernels():

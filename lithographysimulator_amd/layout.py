@@ -9,7 +9,9 @@ against hand-computed placements, and the device rasteriser bit for bit against 
 Host side (this file, numpy): stream-format reader and writer, hierarchy flattening (SREF / AREF with reflection,
 magnification, rotation), PATH -> outline polygon, BOX -> rectangle.  Device side (csrc/layout.hip through the C ABI):
 `rasterizeLayout` -- a pixel is 1 when its CENTRE lies inside the union of the polygons (non-zero winding, half-open
-on edges: a centre exactly on a left or bottom edge is inside, on a right or top edge outside).
+on edges: a centre exactly on a left or bottom edge is inside, on a right or top edge outside); with antialias = s the
+same rule on s x s sub-centres per pixel gives the pixel's area coverage, and `composeTransmission` turns coverages
+into the grey / phase-shift transmission `Mask(transmission=...)` takes.
 
 Coordinates: GDSII database units are integers; `GdsLibrary.user_unit_m` is metres per database unit.  The raster
 calls take nanometres: x = columns, y = rows, row 0 at the BOTTOM of the window (y grows with the row index), pixel
@@ -385,12 +387,27 @@ def polygonEdges(polygons: Sequence[np.ndarray]) -> np.ndarray:
     return np.ascontiguousarray(np.concatenate(rows, axis=0)) if rows else np.zeros((0, 4))
 
 
-def rasterizeLayout(polygons: Sequence[np.ndarray], pixelNumber: int, pixelSize: float, origin=None, device=None):
+ANTIALIAS_LEVELS = (1, 2, 4, 8, 16)
+COVERAGE_WORK_BYTES = 256 << 20            # default ceiling of the coverage rasteriser's workspace
+
+
+def rasterizeLayout(polygons: Sequence[np.ndarray], pixelNumber: int, pixelSize: float, origin=None, device=None,
+                    antialias: int = 1, workBytes: Optional[int] = None):
     """Binary mask raster (torch int16 [pn, pn] on `device`, what `Mask` takes) of polygons given in nanometres.
-    origin = (x0, y0) of the window's lower-left corner; None centres the window on the polygons' bounding box."""
+    origin = (x0, y0) of the window's lower-left corner; None centres the window on the polygons' bounding box.
+
+    antialias = s in (2, 4, 8, 16): the AREA COVERAGE of every pixel instead, float32 [pn, pn] in [0, 1] -- the fraction of
+    the pixel's s x s sub-centres (pitch pixelSize / s) that lie inside under the same rule, exact multiples of 1 / s^2; it
+    equals the s x s block mean of the binary raster at (pn * s, pixelSize / s) on the same origin, so an edge moves the
+    raster in steps of pixelSize / s instead of pixelSize.  What `Mask(transmission=...)` and `composeTransmission` take.
+    workBytes: ceiling of the device workspace (None: the whole sub-grid if it fits in 256 MiB, else 256 MiB); the rasteriser
+    works through bands of as many pixel rows as fit, and the result does not depend on it."""
     import torch
 
     from . import _native as nat
+    s = int(antialias)
+    if s != antialias or s not in ANTIALIAS_LEVELS:
+        raise ValueError(f"rasterizeLayout: antialias must be one of {ANTIALIAS_LEVELS}; got {antialias!r}")
     dev = nat.require_gpu(nat.pick_device(device, "layout"))
     pn = int(pixelNumber)
     edges = polygonEdges(polygons)
@@ -401,9 +418,21 @@ def rasterizeLayout(polygons: Sequence[np.ndarray], pixelNumber: int, pixelSize:
         else:
             ctr = np.zeros(2)
         origin = (float(ctr[0]) - pn * pixelSize / 2.0, float(ctr[1]) - pn * pixelSize / 2.0)
+    ed = torch.from_numpy(edges.reshape(-1)).to(dev) if len(edges) else torch.zeros(4, dtype=torch.float64, device=dev)
+    if s > 1:
+        full = nat.rasterize_coverage_work_bytes(pn, s, pn)
+        if full == 0:
+            raise ValueError(f"rasterizeLayout: pixelNumber * antialias must lie in 1..32768; got {pn} * {s}")
+        nbytes = min(full, COVERAGE_WORK_BYTES) if workBytes is None else int(workBytes)
+        cov = torch.empty((pn, pn), dtype=torch.float32, device=dev)
+        work = torch.empty((max(nbytes, 1),), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            nat.check(nat.lib().litho_rasterize_coverage(nat.ptr(ed), int(len(edges)), pn, float(origin[0]), float(origin[1]),
+                                                         float(pixelSize), s, nat.ptr(work), nbytes, nat.ptr(cov),
+                                                         nat.stream_ptr(dev)), "litho_rasterize_coverage")
+        return cov
     geo = torch.empty((pn, pn), dtype=torch.int16, device=dev)
     work = torch.empty((nat.rasterize_work_bytes(pn),), dtype=torch.uint8, device=dev)
-    ed = torch.from_numpy(edges.reshape(-1)).to(dev) if len(edges) else torch.zeros(4, dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
         nat.check(nat.lib().litho_rasterize_edges(nat.ptr(ed), int(len(edges)), pn, float(origin[0]), float(origin[1]),
                                                   float(pixelSize), nat.ptr(work), work.numel(), nat.ptr(geo),
@@ -411,16 +440,51 @@ def rasterizeLayout(polygons: Sequence[np.ndarray], pixelNumber: int, pixelSize:
     return geo
 
 
+def composeTransmission(coverages, values, background: complex = 0):
+    """Complex field transmission (complex64) of stacked mask layers from their area coverages: t = background, then for
+    every layer in order  t = t * (1 - cov) + value * cov  -- the area-averaged thin-mask transmission of a pixel far below
+    the optical resolution: the part of the pixel the layer covers transmits `value`, the rest what lay there before.  With
+    coverages of 0 and 1 this is "a later layer overrides an earlier one" exactly; a half-covered pi shifter (value -1) over
+    clear glass (background 1) transmits 0.  `coverages`: real tensors of one shape (rasterizeLayout(..., antialias=s), or
+    0 / 1 rasters), on any device; `values`: one complex number per layer.  Pure torch."""
+    import torch
+    coverages, values = list(coverages), list(values)
+    if len(coverages) != len(values):
+        raise ValueError(f"composeTransmission: {len(coverages)} coverages for {len(values)} values")
+    if not coverages:
+        raise ValueError("composeTransmission: no layers")
+    t = None
+    for cov, value in zip(coverages, values):
+        cov = torch.as_tensor(cov)
+        if cov.is_complex():
+            raise ValueError("composeTransmission: a coverage is a real area fraction")
+        cov = cov.to(torch.float32)
+        if t is None:
+            t = torch.full(cov.shape, complex(background), dtype=torch.complex64, device=cov.device)
+        elif cov.shape != t.shape:
+            raise ValueError(f"composeTransmission: coverages of shapes {tuple(t.shape)} and {tuple(cov.shape)}")
+        t = t * (1 - cov) + complex(value) * cov
+    return t
+
+
 def maskFromGDSII(source, pixelNumber: int, pixelSize: float, top: Optional[str] = None,
                   layers: Optional[Sequence[Tuple[int, int]]] = None, origin=None, device=None,
-                  transmissions: Optional[Dict[Tuple[int, int], complex]] = None, background: complex = 0):
+                  transmissions: Optional[Dict[Tuple[int, int], complex]] = None, background: complex = 0,
+                  antialias: int = 1):
     """GDSII file -> `Mask` (the object abbeImage takes): read, flatten `top`, rasterise the chosen layers.
 
     transmissions = {(layer, datatype): complex} makes a phase-shift / grey mask instead: every listed layer is rasterised
     on its own and the rasters are composed in the mapping's order -- a later layer overrides an earlier one where both
     cover a pixel, `background` fills what no layer covers; `layers` is not used.  With origin=None the window is centred
-    on the bounding box of all listed layers together, so that the rasters share one grid."""
+    on the bounding box of all listed layers together, so that the rasters share one grid.
+
+    antialias = s > 1 (2, 4, 8, 16): the layers are rasterised to area coverage (rasterizeLayout) and the mask is a grey
+    one, `Mask(transmission=coverage)`, or with `transmissions` the composition `composeTransmission` defines: edges that
+    do not lie on pixel lines keep their position to pixelSize / s.  At the default 1 nothing changes."""
     from .mask import Mask
+    if int(antialias) != antialias or int(antialias) not in ANTIALIAS_LEVELS:
+        raise ValueError(f"maskFromGDSII: antialias must be one of {ANTIALIAS_LEVELS}; got {antialias!r}")
+    antialias = int(antialias)
     lib = source if isinstance(source, GdsLibrary) else readGDSII(source)
     if transmissions is not None:
         import torch
@@ -430,6 +494,12 @@ def maskFromGDSII(source, pixelNumber: int, pixelSize: float, top: Optional[str]
             ctr = (np.min([q.min(axis=0) for q in pts], axis=0) + np.max([q.max(axis=0) for q in pts], axis=0)) / 2.0 \
                 if pts else np.zeros(2)
             origin = (float(ctr[0]) - int(pixelNumber) * pixelSize / 2.0, float(ctr[1]) - int(pixelNumber) * pixelSize / 2.0)
+        if antialias > 1:
+            if not transmissions:
+                raise ValueError("maskFromGDSII: transmissions is empty")
+            covs = [rasterizeLayout(polys[key], pixelNumber, pixelSize, origin, device, antialias=antialias) for key in transmissions]
+            t = composeTransmission(covs, list(transmissions.values()), background)
+            return Mask(pixelSize=pixelSize, device=t.device, transmission=t)
         t = None
         for key, value in transmissions.items():
             geo = rasterizeLayout(polys[key], pixelNumber, pixelSize, origin, device)
@@ -439,5 +509,8 @@ def maskFromGDSII(source, pixelNumber: int, pixelSize: float, top: Optional[str]
         if t is None:
             raise ValueError("maskFromGDSII: transmissions is empty")
         return Mask(pixelSize=pixelSize, device=t.device, transmission=t)
+    if antialias > 1:
+        cov = rasterizeLayout(flattenLayout(lib, top, layers), pixelNumber, pixelSize, origin, device, antialias=antialias)
+        return Mask(pixelSize=pixelSize, device=cov.device, transmission=cov)
     geo = rasterizeLayout(flattenLayout(lib, top, layers), pixelNumber, pixelSize, origin, device)
     return Mask(geo, pixelSize, geo.device)
