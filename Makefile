@@ -40,6 +40,9 @@ build/optics.o: $(CSRC)/optics.hip $(CSRC)/engine_common.hpp include/litho_abbe.
 build/layout.o: $(CSRC)/layout.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
+build/metrology.o: $(CSRC)/metrology.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 build/common.o: $(CSRC)/common.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -47,7 +50,7 @@ build/common.o: $(CSRC)/common.hip $(CSRC)/engine_common.hpp include/litho_abbe.
 build/plan_dry_run.o: $(CSRC)/plan_dry_run.cpp $(CSRC)/abbe_plan.hpp include/litho_abbe.h
 	@mkdir -p build
 	g++ -O2 -std=c++17 -fPIC -Wall -Wextra -c $< -o $@
-$(OUT): build/abbe_engine.o build/optics.o build/layout.o build/common.o build/plan_dry_run.o $(INST) $(INSTW)
+$(OUT): build/abbe_engine.o build/optics.o build/layout.o build/metrology.o build/common.o build/plan_dry_run.o $(INST) $(INSTW)
 	@mkdir -p lithographysimulator_amd/lib
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 

@@ -288,6 +288,27 @@ int litho_postprocess_resist_diffused(const float *raw, int planes, int pn, doub
 int litho_measure_cd(const float *image, int planes, int n, const int32_t *gauges, int n_gauges, const float *gains_host,
                      int n_gains, double threshold, int exposed, double pixel_size, float *out, void *stream);
 
+/* ---- Edge placement error on layout edges (no reference counterpart; checked against tests/epe_oracle.py).  image fp32
+ * [planes,n,n] on the post-processed grid (aerial or diffused), on the device; sites fp32 [n_sites][4] = (x, y, nx, ny) on
+ * the device; gains_host: n_gains <= 64 host floats (doses, or dose / S), as litho_measure_cd.  out fp32
+ * [n_gains][planes][n_sites][3] = (epe_nm, ils_per_nm, t_k).  All arithmetic is fp32 in exactly this order:
+ * Coordinates: image-grid pixel units, sample (row r, column c) sits at (x = c, y = r) -- the convention of
+ * litho_measure_cd's x_lo.  (nx, ny) points OUT of the feature and is not normalised; t runs in pixels along it.
+ * Samples: h = 0.5, K = ceil(range_px / h) <= 64; for k = -K .. K: t_k = (float)k * 0.5f, px = x + t_k * nx,
+ * py = y + t_k * ny (one multiply and one add each).  A sample is VALID iff px and py are finite, 0 <= px <= n - 1 and
+ * 0 <= py <= n - 1; an invalid sample carries no information and is never read.  i0 = min((int)floorf(px), n - 2),
+ * fx = px - i0 (the same for y), v = (1 - fy) * ((1 - fx) * a + fx * b) + fy * ((1 - fx) * c + fx * d) with a, b the row
+ * j0 samples at i0, i0 + 1 and c, d those of row j0 + 1; u_k = v * gain.  in(u) = ((u >= T) == (exposed != 0)), as in
+ * litho_measure_cd.  Interval k (-K <= k < K) is a CROSSING when both ends are valid, in(u_k) holds and in(u_{k+1}) does not
+ * (leaving the feature going outward); among the crossings the one with the smallest |2k + 1| is taken, on a tie the one
+ * with k >= 0.  t* = t_k + h * ((T - u_k) / (u_{k+1} - u_k)); epe_nm = t* * pixel_size (positive: the printed feature
+ * reaches beyond the target edge); ils_per_nm = |u_{k+1} - u_k| / ((h * pixel_size) * T); t_k pins the chosen interval.
+ * Three NaN when no crossing lies in range, when the site is not finite, or when n < 2.  LITHO_E_ARG, nothing written: a
+ * null pointer, n_sites < 1, planes < 1 (or > 65535), n < 1, n_gains outside 1..64, a NaN gain, range_px outside (0, 32] or
+ * not finite, pixel_size <= 0 or not finite.  Asynchronous: one kernel, no allocation, no host wait. */
+int litho_measure_epe(const float *image, int planes, int n, const float *sites, int64_t n_sites, const float *gains_host,
+                      int n_gains, float threshold, int exposed, float range_px, float pixel_size, float *out, void *stream);
+
 /* ---- Layout rasteriser: the device side of the GDSII import (lithographysimulator_amd/layout.py).  SURVEY.md section
  * 8(f) row 4: the reference has NO counterpart (README.md:20-22 lists GDSII import among its unbuilt goals), it is the
  * caller side of Mask(geometry, pixelSize) (mask.py:5-30), so there is no parity target; checked bit for bit against

@@ -7,10 +7,13 @@ from .layout import (GdsLibrary, composeTransmission, flattenLayout, maskFromGDS
                      rasterizeLayout, readGDSII, writeGDSII)
 from .lightsource import (LightSource, sourceShifts, sourceShiftsAsync, sourceWeights,   # noqa: F401
                           sourceWeightsAsync)
+from .metrology import (LayoutSites, OPCResult, biasLayout, correctLayout,             # noqa: F401
+                        imageRegistration, layoutSites, measureEPE)
 from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
 
 __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "abbeImage", "abbeIntensity", "calculateFFTAerial", "postProcess", "resistContour", "measureCD", "bossungCurves", "PlanCache", "engineOptions", "embeddedSize",
            "sourceShifts", "sourceShiftsAsync", "sourceWeights", "sourceWeightsAsync", "OSAindexToMN", "generateWavefrontError", "generatePhi", "generateZ",
-           "throughFocusPupils", "readGDSII", "writeGDSII", "flattenLayout", "rasterizeLayout", "composeTransmission", "maskFromGDSII", "GdsLibrary"]
+           "throughFocusPupils", "readGDSII", "writeGDSII", "flattenLayout", "rasterizeLayout", "composeTransmission", "maskFromGDSII", "GdsLibrary",
+           "imageRegistration", "layoutSites", "measureEPE", "biasLayout", "correctLayout", "LayoutSites", "OPCResult"]

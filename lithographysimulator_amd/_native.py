@@ -6,7 +6,7 @@ import contextlib
 import ctypes
 import os
 import threading
-from ctypes import POINTER, c_char_p, c_double, c_int, c_int64, c_size_t, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_size_t, c_void_p
 
 import torch
 
@@ -51,6 +51,8 @@ _SIGNATURES = {
                                                   c_void_p, c_void_p]),
     "litho_measure_cd": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_double, c_int, c_double,
                                  c_void_p, c_void_p]),
+    "litho_measure_epe": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_float, c_int, c_float, c_float,
+                                  c_void_p, c_void_p]),
     "litho_mask_spectrum": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "litho_mask_spectrum_complex": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "litho_rasterize_work_bytes": (c_size_t, [c_int]),
