@@ -43,6 +43,9 @@ build/layout.o: $(CSRC)/layout.hip $(CSRC)/engine_common.hpp include/litho_abbe.
 build/metrology.o: $(CSRC)/metrology.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
+build/contour.o: $(CSRC)/contour.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 build/common.o: $(CSRC)/common.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -50,7 +53,11 @@ build/common.o: $(CSRC)/common.hip $(CSRC)/engine_common.hpp include/litho_abbe.
 build/plan_dry_run.o: $(CSRC)/plan_dry_run.cpp $(CSRC)/abbe_plan.hpp include/litho_abbe.h
 	@mkdir -p build
 	g++ -O2 -std=c++17 -fPIC -Wall -Wextra -c $< -o $@
-$(OUT): build/abbe_engine.o build/optics.o build/layout.o build/metrology.o build/common.o build/plan_dry_run.o $(INST) $(INSTW)
+# the contour linker (cycles of the `next` permutation): plain C++ as well -- tests/test_contour_cpu.py builds it alone too
+build/contour_link.o: $(CSRC)/contour_link.cpp include/litho_abbe.h
+	@mkdir -p build
+	g++ -O2 -std=c++17 -fPIC -Wall -Wextra -c $< -o $@
+$(OUT): build/abbe_engine.o build/optics.o build/layout.o build/metrology.o build/contour.o build/common.o build/plan_dry_run.o build/contour_link.o $(INST) $(INSTW)
 	@mkdir -p lithographysimulator_amd/lib
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 

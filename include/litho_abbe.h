@@ -309,6 +309,57 @@ int litho_measure_cd(const float *image, int planes, int n, const int32_t *gauge
 int litho_measure_epe(const float *image, int planes, int n, const float *sites, int64_t n_sites, const float *gains_host,
                       int n_gains, float threshold, int exposed, float range_px, float pixel_size, float *out, void *stream);
 
+/* ---- Printed contours as polygons: a marching-squares tracer (no reference counterpart; checked against
+ * tests/contour_oracle.py).  image fp32 [planes,n,n] on the device, sample (row r, column c) at (x = c, y = r) as in
+ * litho_measure_epe; gains_host: n_gains <= 64 host floats.  One IMAGE is a (gain, plane) pair, numbered gain * planes + plane;
+ * a = fl32(u * gain), one fp32 multiply; a sample is INSIDE iff (a >= T) == (exposed != 0), litho_measure_epe's predicate (NaN
+ * compares false).  The grid is extended by one ring of virtual samples, rows and columns -1 and n, that are never inside: every
+ * contour is a closed loop, and a feature that touches the border is closed along the border samples.
+ * Vertices: exactly one on every CROSSED grid edge (one end inside, the other not).  H(r, c) joins (r, c) and (r, c + 1),
+ * r in [0, n - 1], c in [-1, n - 1]; V(r, c) joins (r, c) and (r + 1, c), r in [-1, n - 1], c in [0, n - 1].  From the
+ * lower-index sample a to the higher-index one b: t = (T - a) / (b - a) in fp32; if !(t >= 0 && t <= 1) then t = 0.5 (non-finite
+ * data only); the vertex is (c + t, r) on H and (c, r + t) on V, one fp32 add of the exact integer and t; on an edge with a
+ * virtual end it is the real sample's own position.
+ * Numbering (the order of the outputs): for r = -1 .. n - 1 the crossed H edges of row r by ascending c (they exist for r >= 0),
+ * then the crossed V edges between rows r and r + 1 by ascending c.
+ * Linking: next[] is a permutation of one image's crossed edges, image-local int32.  Walking v -> next[v] the feature lies on
+ * the LEFT in (x = column, y = row) axes: an outer boundary has positive shoelace area, a hole negative.  Every cell (between
+ * extended rows i - 1, i and columns j - 1, j; i, j in [0, n]) has zero, one or two entry edges and as many exits.  A saddle
+ * (two diagonal corners inside; all four are then real) is resolved by m = ((a_tl + a_tr) + (a_bl + a_br)) * 0.25f in that
+ * fp32 order: (m >= T) == exposed joins the two inside corners, otherwise each is cut off on its own.
+ * Polygons = the cycles of next, each from its lowest-numbered vertex, ordered by that number (litho_contour_link, host).
+ * Vertex count per image <= 2 n (n + 1): int32 up to n = 16384.
+ * Two calls and one read-back between them, the caller's: litho_contour_count classifies (one wave per extended row and plane,
+ * the gains in a loop inside) and scans, leaving int64 counts_dev[image]; the caller reads them, forms offsets_host[images + 1]
+ * (offsets[0] = 0, exclusive sums of the counts), sizes xy_out fp32 [total][2] and next_out int32 [total], and litho_contour_emit
+ * with the SAME image, gains, T, exposed and work writes image i's vertices at offsets[i] .. offsets[i + 1].  An image whose
+ * offsets do not match the count found is left unwritten.  work: litho_contour_work_bytes(n, planes, n_gains) device bytes, 8-byte
+ * aligned, untouched between the two calls (0 for a bad argument).  LITHO_E_ARG before any launch: a null pointer, n < 1 (or
+ * > 16384), planes outside 1..65535, n_gains outside 1..64, a NaN gain, offsets that decrease; LITHO_E_WORKSPACE: work_bytes
+ * too small.  Image values are never turned into addresses.  Asynchronous, no allocation, no host wait: emit copies the offsets
+ * to the device with an asynchronous copy on `stream`, so offsets_host must stay allocated and unchanged until `stream` has
+ * passed that copy (until the stream is synchronised, or an event recorded after the call has completed); gains_host is read
+ * before either call returns. */
+size_t litho_contour_work_bytes(int n, int planes, int n_gains);
+int litho_contour_count(const float *image, int planes, int n, const float *gains_host, int n_gains, float threshold,
+                        int exposed, void *work, size_t work_bytes, int64_t *counts_dev /* int64 per image */, void *stream);
+int litho_contour_emit(const float *image, int planes, int n, const float *gains_host, int n_gains, float threshold, int exposed,
+                       void *work, size_t work_bytes, const int64_t *offsets_host /* images + 1 */, float *xy_out,
+                       int32_t *next_out, void *stream);
+
+/* ---- HOST: the cycles of a permutation next[0 .. V) in O(V).  order[V] receives the indices cycle by cycle, every cycle from its
+ * lowest index, the cycles by ascending lowest index; starts[n_cycles + 1] (room for V + 1) the cycles' bounds in `order`.  An
+ * index outside [0, V), or one reached twice (not a permutation): LITHO_E_ARG, nothing is read out of bounds.  No device. */
+int litho_contour_link(const int32_t *next_host, int64_t V, int64_t *order_host, int64_t *starts_host, int64_t *n_cycles_host);
+
+/* ---- Dose-focus envelope for process-variation bands: lo[r][c] = min, hi[r][c] = max over all (gain, plane) pairs of
+ * fl32(image[plane][r][c] * gain), folded with fminf / fmaxf in the order plane-major, gain-minor (a NaN product is skipped
+ * unless all are NaN).  image fp32 [planes,n,n], lo_out / hi_out fp32 [n,n], all on the device.  The contour of hi at T is the
+ * union, that of lo the intersection, of the exposed features over all conditions.  Argument checks as litho_contour_count.
+ * Asynchronous: one kernel, no allocation, no host wait. */
+int litho_dose_focus_envelope(const float *image, int planes, int n, const float *gains_host, int n_gains, float *lo_out,
+                              float *hi_out, void *stream);
+
 /* ---- Layout rasteriser: the device side of the GDSII import (lithographysimulator_amd/layout.py).  SURVEY.md section
  * 8(f) row 4: the reference has NO counterpart (README.md:20-22 lists GDSII import among its unbuilt goals), it is the
  * caller side of Mask(geometry, pixelSize) (mask.py:5-30), so there is no parity target; checked bit for bit against

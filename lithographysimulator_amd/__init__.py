@@ -9,6 +9,8 @@ from .lightsource import (LightSource, sourceShifts, sourceShiftsAsync, sourceWe
                           sourceWeightsAsync)
 from .metrology import (LayoutSites, OPCResult, biasLayout, correctLayout,             # noqa: F401
                         imageRegistration, layoutSites, measureEPE)
+from .contours import (Contours, contourVertices, contoursToGDSII, contoursToLayout,   # noqa: F401
+                       doseFocusEnvelope, processVariationBand, simplifyContour, traceContours)
 from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
@@ -16,4 +18,6 @@ from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,   
 __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "abbeImage", "abbeIntensity", "calculateFFTAerial", "postProcess", "resistContour", "measureCD", "bossungCurves", "PlanCache", "engineOptions", "embeddedSize",
            "sourceShifts", "sourceShiftsAsync", "sourceWeights", "sourceWeightsAsync", "OSAindexToMN", "generateWavefrontError", "generatePhi", "generateZ",
            "throughFocusPupils", "readGDSII", "writeGDSII", "flattenLayout", "rasterizeLayout", "composeTransmission", "maskFromGDSII", "GdsLibrary",
-           "imageRegistration", "layoutSites", "measureEPE", "biasLayout", "correctLayout", "LayoutSites", "OPCResult"]
+           "imageRegistration", "layoutSites", "measureEPE", "biasLayout", "correctLayout", "LayoutSites", "OPCResult",
+           "Contours", "contourVertices", "traceContours", "contoursToLayout", "simplifyContour", "contoursToGDSII", "doseFocusEnvelope",
+           "processVariationBand"]

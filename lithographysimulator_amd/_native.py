@@ -53,6 +53,12 @@ _SIGNATURES = {
                                  c_void_p, c_void_p]),
     "litho_measure_epe": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_float, c_int, c_float, c_float,
                                   c_void_p, c_void_p]),
+    "litho_contour_work_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "litho_contour_count": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "litho_contour_emit": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
+                                   c_void_p, c_void_p]),
+    "litho_contour_link": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
+    "litho_dose_focus_envelope": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "litho_mask_spectrum": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "litho_mask_spectrum_complex": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "litho_rasterize_work_bytes": (c_size_t, [c_int]),

@@ -362,9 +362,10 @@ def flattenLayout(lib: GdsLibrary, top: Optional[str] = None, layers: Optional[S
     return [q for batch in _oriented_batches(out, nm) for q in batch]
 
 
-def _oriented_batches(polygons, scale=1.0):
+def _oriented_batches(polygons, scale=1.0, orient=True):
     """The polygons made counter-clockwise (a reflection turns them clockwise) and scaled, as [n, k, 2] arrays grouped
-    by vertex count k (in order of first appearance): layouts are millions of rectangles, not a Python loop over them."""
+    by vertex count k (in order of first appearance): layouts are millions of rectangles, not a Python loop over them.
+    orient=False leaves every polygon's sense as it came."""
     groups: Dict[int, List[np.ndarray]] = {}
     for q in polygons:
         q = np.asarray(q, dtype=np.float64).reshape(-1, 2)
@@ -374,16 +375,18 @@ def _oriented_batches(polygons, scale=1.0):
     for k, items in groups.items():
         a = np.stack(items) * scale
         area2 = np.sum(a[:, :, 0] * np.roll(a[:, :, 1], -1, axis=1) - np.roll(a[:, :, 0], -1, axis=1) * a[:, :, 1], axis=1)
-        cw = area2 < 0
-        a[cw] = a[cw, ::-1]
+        if orient:
+            cw = area2 < 0
+            a[cw] = a[cw, ::-1]
         batches.append(a)
     return batches
 
 
-def polygonEdges(polygons: Sequence[np.ndarray]) -> np.ndarray:
+def polygonEdges(polygons: Sequence[np.ndarray], orient: bool = True) -> np.ndarray:
     """[n_edges, 4] float64 (x0, y0, x1, y1) of the closed polygons, every polygon made counter-clockwise first (so that
-    overlapping polygons add winding numbers of the same sign: the raster is their UNION)."""
-    rows = [np.concatenate([a, np.roll(a, -1, axis=1)], axis=2).reshape(-1, 4) for a in _oriented_batches(polygons)]
+    overlapping polygons add winding numbers of the same sign: the raster is their UNION).  orient=False keeps every
+    polygon's sense: a clockwise polygon SUBTRACTS winding, which is how the holes of traced contours rasterise as holes."""
+    rows = [np.concatenate([a, np.roll(a, -1, axis=1)], axis=2).reshape(-1, 4) for a in _oriented_batches(polygons, orient=orient)]
     return np.ascontiguousarray(np.concatenate(rows, axis=0)) if rows else np.zeros((0, 4))
 
 
@@ -392,7 +395,7 @@ COVERAGE_WORK_BYTES = 256 << 20            # default ceiling of the coverage ras
 
 
 def rasterizeLayout(polygons: Sequence[np.ndarray], pixelNumber: int, pixelSize: float, origin=None, device=None,
-                    antialias: int = 1, workBytes: Optional[int] = None):
+                    antialias: int = 1, workBytes: Optional[int] = None, orient: bool = True):
     """Binary mask raster (torch int16 [pn, pn] on `device`, what `Mask` takes) of polygons given in nanometres.
     origin = (x0, y0) of the window's lower-left corner; None centres the window on the polygons' bounding box.
 
@@ -401,7 +404,9 @@ def rasterizeLayout(polygons: Sequence[np.ndarray], pixelNumber: int, pixelSize:
     equals the s x s block mean of the binary raster at (pn * s, pixelSize / s) on the same origin, so an edge moves the
     raster in steps of pixelSize / s instead of pixelSize.  What `Mask(transmission=...)` and `composeTransmission` take.
     workBytes: ceiling of the device workspace (None: the whole sub-grid if it fits in 256 MiB, else 256 MiB); the rasteriser
-    works through bands of as many pixel rows as fit, and the result does not depend on it."""
+    works through bands of as many pixel rows as fit, and the result does not depend on it.
+    orient=False: the polygons keep their sense instead of being made counter-clockwise (polygonEdges), so that clockwise
+    polygons -- the holes of traceContours -- cut out of the counter-clockwise ones around them."""
     import torch
 
     from . import _native as nat
@@ -410,7 +415,7 @@ def rasterizeLayout(polygons: Sequence[np.ndarray], pixelNumber: int, pixelSize:
         raise ValueError(f"rasterizeLayout: antialias must be one of {ANTIALIAS_LEVELS}; got {antialias!r}")
     dev = nat.require_gpu(nat.pick_device(device, "layout"))
     pn = int(pixelNumber)
-    edges = polygonEdges(polygons)
+    edges = polygonEdges(polygons, orient=orient)
     if origin is None:
         if len(edges):
             lo, hi = edges[:, :2].min(axis=0), edges[:, :2].max(axis=0)
