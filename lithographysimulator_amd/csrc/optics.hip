@@ -362,7 +362,7 @@ __global__ void k_postprocess(const float* __restrict__ raw, int pn, int ns, int
 // ---- diffused aerial image (no reference counterpart; definition in include/litho_abbe.h)
 // The post-processed image convolved with a separable Gaussian (acid diffusion), then the same threshold as above -- in ONE
 // pass over HBM: a workgroup owns a DIFF_TX x DIFF_TY output tile, fills tile + halo R in LDS by evaluating bilinear_at on
-// `raw` (zero in the padded border and outside the grid), so the post-processed image itself is never written and re-read;
+// `raw` (zero in the padded border and outside the OUTPUT grid), so the post-processed image itself is never written and re-read;
 // then the row pass and the column pass run out of LDS.  Lanes map to consecutive x in all three phases: the global loads
 // and stores are coalesced, and every LDS access of a wave is 64 consecutive dwords (the column pass walks rows of the
 // row-major array with the lane as the column) -- conflict-free.  The symmetric taps are paired, (t[-k] + t[k]) * g[k].
@@ -377,12 +377,12 @@ static size_t diff_lds_bytes(int R) { return sizeof(float) * (size_t)(2 * DIFF_T
 // phase waiting on HBM latency row after row).  Branch-free: coordinates are clamped into the image and the value is selected
 // afterwards; SAME (equal sizes, a plain copy) is a template parameter so that the loads of a step stay in one basic block.
 template <bool SAME>
-__device__ __forceinline__ void diff_fill(const float* __restrict__ rawp, int pn, int ns, int pW, float rs, int gx0, int gy0,
-                                          int W, int H, int lane, int wave, float* __restrict__ tile)
+__device__ __forceinline__ void diff_fill(const float* __restrict__ rawp, int pn, int ns, int pW, int n_out, float rs, int gx0,
+                                          int gy0, int W, int H, int lane, int wave, float* __restrict__ tile)
 {
     for (int i = lane; i < W; i += 64) {
-        const int ix = gx0 + i - pW;                 // column of the resampled image; the border and everything outside are zero
-        const bool col_in = ix >= 0 && ix < ns;
+        const int gx = gx0 + i, ix = gx - pW;        // column of the output grid, and of the resampled image
+        const bool col_in = gx >= 0 && gx < n_out && ix >= 0 && ix < ns;   // zero outside the grid (what pW < 0 crops away too) and in the border
         const int ixc = max(0, min(ix, ns - 1));
         for (int j0 = wave; j0 < H; j0 += 16) {
             float v[4];
@@ -391,8 +391,8 @@ __device__ __forceinline__ void diff_fill(const float* __restrict__ rawp, int pn
                 v[u] = bilinear_at(rawp, pn, max(0, min(gy0 + j0 + 4 * u - pW, ns - 1)), ixc, rs, SAME, true);
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const int j = j0 + 4 * u, iy = gy0 + j - pW;
-                if (j < H) tile[j * W + i] = (col_in && iy >= 0 && iy < ns) ? v[u] : 0.f;
+                const int j = j0 + 4 * u, gy = gy0 + j, iy = gy - pW;
+                if (j < H) tile[j * W + i] = (col_in && gy >= 0 && gy < n_out && iy >= 0 && iy < ns) ? v[u] : 0.f;
             }
         }
     }
@@ -409,8 +409,8 @@ __global__ __launch_bounds__(256) void k_postprocess_diffused(const float* __res
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int x0 = blockIdx.x * DIFF_TX, y0 = blockIdx.y * DIFF_TY;
     const float* rawp = raw + (size_t)blockIdx.z * pn * pn;
-    if (ns == pn) diff_fill<true>(rawp, pn, ns, pW, rs, x0 - R, y0 - R, W, H, lane, wave, tile);
-    else diff_fill<false>(rawp, pn, ns, pW, rs, x0 - R, y0 - R, W, H, lane, wave, tile);
+    if (ns == pn) diff_fill<true>(rawp, pn, ns, pW, n_out, rs, x0 - R, y0 - R, W, H, lane, wave, tile);
+    else diff_fill<false>(rawp, pn, ns, pW, n_out, rs, x0 - R, y0 - R, W, H, lane, wave, tile);
     // lane k keeps tap k; a pass reads it with v_readlane (k is wave-uniform): no memory access for the taps in the loops
     const int gv = __float_as_int(lane <= DIFF_RMAX ? taps.g[lane] : 0.f);
     auto tap = [&](int k) { return __int_as_float(__builtin_amdgcn_readlane(gv, k)); };
