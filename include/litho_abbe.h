@@ -360,6 +360,27 @@ int litho_contour_link(const int32_t *next_host, int64_t V, int64_t *order_host,
 int litho_dose_focus_envelope(const float *image, int planes, int n, const float *gains_host, int n_gains, float *lo_out,
                               float *hi_out, void *stream);
 
+/* ---- Hopkins imaging: SOCS kernels from the transmission cross coefficient (no reference counterpart -- the reference images by
+ * the Abbe sum alone, imageformation.py:54-67; checked against tests/socs_oracle.py).  For a pupil P [n,n] and a source weight map
+ * W [n,n] (d = (row - n/2, col - n/2), as `shifts`), T = sum_s w_s roll(P, d_s) roll(P, d_s)^H is Hermitian positive semidefinite,
+ * and the weighted Abbe image is sum_k |field(phi_k)|^2 at shift (0,0) for any phi with sum_k phi_k phi_k^H = T.  T x needs no
+ * source list: T x = ifft2(ph . fft2(Wsh . ifft2(conj(ph) . fft2(x)))), ph = fft2(P), Wsh = ifftshift(W), all transforms the plain
+ * DFT below.  The factorisation itself (subspace iteration) is lithographysimulator_amd/socs.py; DESIGN.md section 10.
+ *
+ * litho_fft2_c2c: data complex64 [batch,n,n], in place: the standard 2-D DFT, out[u][v] = sum_jk in[j][k] exp(-/+ 2 pi i (j u + k v) / n)
+ * (inverse != 0: the + sign), neither centred nor scaled -- forward then inverse returns n^2 x.  n a power of two, 16..4096;
+ * anything else, batch < 1 or a null pointer: LITHO_E_ARG.  Asynchronous, no allocation, no host wait. */
+int litho_fft2_c2c(void *data, int batch, int n, int inverse, void *stream);
+/* litho_tcc_apply: Y[b] = T X[b], b < batch, by the formula above including the n^-4 of its two inverse transforms.  pupil_hat
+ * complex64 [n,n] = litho_fft2_c2c of the pupil; weight_shifted fp32 [n,n]; X, Y complex64 [batch,n,n]; Y may BE X, and must not
+ * overlap it otherwise (LITHO_E_ARG).  Sizes and errors as litho_fft2_c2c.  Asynchronous, no allocation, no host wait. */
+int litho_tcc_apply(const void *pupil_hat, const float *weight_shifted, const void *X, void *Y, int batch, int n, void *stream);
+/* litho_socs_fold: out[g][i] (+)= sum_{k<K} stack[g K + k][i], i < elems, g < groups: the K coherent images of every plane summed
+ * in ascending k with one running fp32 sum per element (accumulate != 0: starting from out's value, otherwise overwriting it).
+ * stack fp32 [groups K, elems], out fp32 [groups, elems], not overlapping.  groups 1..65535, K >= 1, elems >= 1, else LITHO_E_ARG.
+ * Asynchronous: one kernel. */
+int litho_socs_fold(const float *stack, int groups, int K, int64_t elems, float *out, int accumulate, void *stream);
+
 /* ---- Layout rasteriser: the device side of the GDSII import (lithographysimulator_amd/layout.py).  SURVEY.md section
  * 8(f) row 4: the reference has NO counterpart (README.md:20-22 lists GDSII import among its unbuilt goals), it is the
  * caller side of Mask(geometry, pixelSize) (mask.py:5-30), so there is no parity target; checked bit for bit against

@@ -11,6 +11,7 @@ from .metrology import (LayoutSites, OPCResult, biasLayout, correctLayout,      
                         imageRegistration, layoutSites, measureEPE)
 from .contours import (Contours, contourVertices, contoursToGDSII, contoursToLayout,   # noqa: F401
                        doseFocusEnvelope, processVariationBand, simplifyContour, traceContours)
+from .socs import SOCSKernels, hopkinsImage, hopkinsIntensity, socsKernels          # noqa: F401
 from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
@@ -20,4 +21,4 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "throughFocusPupils", "readGDSII", "writeGDSII", "flattenLayout", "rasterizeLayout", "composeTransmission", "maskFromGDSII", "GdsLibrary",
            "imageRegistration", "layoutSites", "measureEPE", "biasLayout", "correctLayout", "LayoutSites", "OPCResult",
            "Contours", "contourVertices", "traceContours", "contoursToLayout", "simplifyContour", "contoursToGDSII", "doseFocusEnvelope",
-           "processVariationBand"]
+           "processVariationBand", "SOCSKernels", "socsKernels", "hopkinsIntensity", "hopkinsImage"]

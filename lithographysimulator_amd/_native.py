@@ -59,6 +59,9 @@ _SIGNATURES = {
                                    c_void_p, c_void_p]),
     "litho_contour_link": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
     "litho_dose_focus_envelope": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "litho_fft2_c2c": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
+    "litho_tcc_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "litho_socs_fold": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_void_p]),
     "litho_mask_spectrum": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "litho_mask_spectrum_complex": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "litho_rasterize_work_bytes": (c_size_t, [c_int]),

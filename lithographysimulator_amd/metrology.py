@@ -256,7 +256,8 @@ class OPCResult:
 
 def correctLayout(polygons, pixelNumber, pixelSize, origin, wavelength, pupil, source, threshold, *, spacing, iterations=6,
                   gain=0.6, maxBias, antialias=16, exposed=True, diffusionLength=0.0, searchRange=8.0,
-                  imager: Optional[Callable] = None, epe: Optional[Callable] = None, device=None) -> OPCResult:
+                  imager: Optional[Callable] = None, epe: Optional[Callable] = None, device=None, model="abbe",
+                  kernels=64) -> OPCResult:
     """Model-based optical proximity correction of a Manhattan layout (nanometres; the polygons are the mask's openings):
     edge fragments of at most `spacing` are moved along their normals until the printed contour lies on the target's edges.
     Every iteration: biasLayout -> rasterizeLayout(antialias=) -> Mask(transmission=) -> fraunhofer -> abbeIntensity through
@@ -267,10 +268,16 @@ def correctLayout(polygons, pixelNumber, pixelSize, origin, wavelength, pupil, s
     mask tone nor that step is defined for it yet).  `threshold` is absolute, on the returned image's scale (raw
     sums over the source points); `pupil` the pupil function [pn,pn], `source` the source bitmap [pn,pn] or a (dy,dx) list.
 
+    `model="socs"`: the optical setting is factored once into `kernels` SOCS kernels (socsKernels: Hopkins imaging, an
+    approximation unless `kernels` reaches the number of lit source points) and every iteration's image is those K fields
+    (hopkinsIntensity) instead of one field per source point.  The default "abbe" is the path described above, call for call.
+
     `imager(polygons) -> image` replaces the raster-to-image steps and `epe(image) -> EPE in nm per site` (NaN where nothing
     is found) the measurement, so the loop itself runs without a GPU on any model; give both or neither."""
     if (imager is None) != (epe is None):
         raise ValueError("correctLayout: imager and epe replace the image and its measurement together; give both or neither")
+    if model not in ("abbe", "socs"):
+        raise ValueError(f"correctLayout: model must be 'abbe' or 'socs'; got {model!r}")
     if not exposed:
         raise ValueError("correctLayout: the loop is defined for exposed features (the polygons are the mask's openings and print "
                          "bright); for exposed=False neither the mask tone nor the step of a site that finds no edge is defined yet")
@@ -287,7 +294,7 @@ def correctLayout(polygons, pixelNumber, pixelSize, origin, wavelength, pupil, s
     biasLayout(target, sites, np.zeros(len(sites)))            # raises for a non-Manhattan layout before any image is made
     if imager is None:
         imager, epe = _gpu_model(pn, ps, origin, wavelength, pupil, source, threshold, antialias, exposed, diffusionLength,
-                                 searchRange, sites, device)
+                                 searchRange, sites, device, model, kernels)
     bias = np.zeros(len(sites))
     history, measured, best = [], [], None
     for it in range(iterations):
@@ -308,7 +315,7 @@ def correctLayout(polygons, pixelNumber, pixelSize, origin, wavelength, pupil, s
 
 
 def _gpu_model(pn, ps, origin, wavelength, pupil, source, threshold, antialias, exposed, diffusionLength, searchRange, sites,
-               device):
+               device, model="abbe", kernels=64):
     """(imager, epe) of correctLayout on the HIP path."""
     import torch
 
@@ -327,12 +334,25 @@ def _gpu_model(pn, ps, origin, wavelength, pupil, source, threshold, antialias, 
     cache = PlanCache()
     state = {}
     site_rows = torch.from_numpy(sites.sites_px).to(dev)
+    if model == "socs":
+        from .socs import hopkinsIntensity, socsKernels
+        if tuple(source.shape) == (pn, pn):
+            bitmap = source.to(dev)
+        else:                                                   # a (dy,dx) list: its bitmap, a repeated point counted as often
+            rc = source.to(device=dev, dtype=torch.int64) + pn // 2
+            if rc.numel() and (int(rc.min()) < 0 or int(rc.max()) > pn - 1):
+                raise ShapeError(f"correctLayout: a source shift lies outside the {pn} x {pn} source grid")
+            bitmap = torch.zeros((pn, pn), dtype=torch.float32, device=dev)
+            bitmap.index_put_((rc[:, 0], rc[:, 1]), torch.ones(rc.shape[0], dtype=torch.float32, device=dev), accumulate=True)
+        state["socs"] = socsKernels(pupil, bitmap, kernels=kernels)
 
     def imager(polys):
         raster = rasterizeLayout(polys, pn, ps, origin, dev, antialias=antialias)
         mask = Mask(pixelSize=ps, device=dev, transmission=raster) if raster.is_floating_point() else Mask(raster, ps, dev)
         mft = mask.fraunhofer(wavelength, True)
-        if "shifts" not in state:
+        if model == "socs":
+            raw = hopkinsIntensity(mft, state["socs"], N)
+        elif "shifts" not in state:
             if tuple(source.shape) == (pn, pn):
                 shifts, count = sourceShiftsAsync(source.to(dev), pn)
             else:
