@@ -31,11 +31,12 @@ def tcc(A):
 
 
 def dense_apply(P, W, X):
-    """T X without a source list: ifft2(ph . fft2(Wsh . ifft2(conj(ph) . fft2(X)))), ph = fft2(P), Wsh = ifftshift(W); X [..., pn, pn]."""
-    ph = np.fft.fft2(np.asarray(P, dtype=np.complex128))
-    wsh = np.fft.ifftshift(np.asarray(W, dtype=np.float64))
-    X = np.asarray(X, dtype=np.complex128)
-    return np.fft.ifft2(ph * np.fft.fft2(wsh * np.fft.ifft2(ph.conj() * np.fft.fft2(X))))
+    """T X without a source list: ifft2(ph . fft2(Wsh . ifft2(conj(ph) . fft2(X)))), ph = fft2(P), Wsh = ifftshift(W); X [..., pn, pn].
+    complex128 throughout; the transforms are torch's on the CPU (numpy's take a second per 2048^2 vector), numpy in and out."""
+    ph = torch.fft.fft2(torch.from_numpy(np.asarray(P, dtype=np.complex128)))
+    wsh = torch.fft.ifftshift(torch.from_numpy(np.asarray(W, dtype=np.float64)))
+    X = torch.from_numpy(np.asarray(X, dtype=np.complex128))
+    return torch.fft.ifft2(ph * torch.fft.fft2(wsh * torch.fft.ifft2(ph.conj() * torch.fft.fft2(X)))).numpy()
 
 
 def gram(P, W):
@@ -50,14 +51,37 @@ def gram(P, W):
     return a[:, None] * a[None, :] * R[diff[..., 0], diff[..., 1]]
 
 
-def exact_kernels(P, W):
+def exact_spectrum(P, W):
+    """The non-zero eigenvalues of T, descending, float64 [S]: those of the S x S Gram matrix (exact_kernels without the kernels)."""
+    return np.linalg.eigvalsh(gram(P, W))[::-1].copy()
+
+
+def exact_kernels(P, W, K=None):
     """(kernels complex128 [S,pn,pn] scaled by sqrt(lambda), lambda descending) from eigh of the S x S Gram matrix:
-    G u = lambda u  =>  phi = A^T conj(u) is an eigenvector of T with |phi|^2 = lambda."""
+    G u = lambda u  =>  phi = A^T conj(u) is an eigenvector of T with |phi|^2 = lambda.  With K, only the top K kernels are
+    formed ([K,pn,pn]); lambda stays the whole spectrum [S]."""
     pn = np.asarray(P).shape[0]
     lam, U = np.linalg.eigh(gram(P, W))
     lam, U = lam[::-1], U[:, ::-1]
+    if K is not None:
+        U = U[:, :K]
     phi = (explicit_A(P, W).T @ U.conj()).T.reshape(-1, pn, pn)
     return phi, lam
+
+
+def residual_norm(A, Phi):
+    """Spectral norm of T - sum_k phi_k phi_k^H without the F x F matrix; A [S,F] = explicit_A, Phi [K,...] the kernels (flattened
+    here).  With B = [A; Phi] and D = diag(+1 (S times), -1 (K times)) the residual is B^T D conj(B), and its non-zero eigenvalues
+    are those of D (B B^H), an (S+K) x (S+K) matrix.  That matrix is not normal -- where the kernels reproduce T its zero
+    eigenvalue is defective and moves by the square root of the rounding -- so the same eigenvalues are taken from a Hermitian
+    one: B^T = Q R (Householder, backward stable in B) gives B^T D conj(B) = Q (R D R^H) Q^H.  Eckart-Young: no K kernels
+    leave less than lambda_{K+1}, and the exact top K leave exactly that."""
+    A = np.asarray(A, dtype=np.complex128)
+    Phi = np.asarray(Phi, dtype=np.complex128).reshape(np.asarray(Phi).shape[0], -1)
+    R = np.linalg.qr(np.concatenate([A, Phi]).T, mode="r")
+    D = np.concatenate([np.ones(A.shape[0]), -np.ones(Phi.shape[0])])
+    H = (R * D[None, :]) @ R.conj().T
+    return float(np.abs(np.linalg.eigvalsh((H + H.conj().T) / 2.0)).max())
 
 
 def apply_as_applier(P, W):
@@ -132,3 +156,96 @@ def truth(name):
         P, W, M, N = problem(name)
         _truths[name] = abbe_truth(P, M, W, N)
     return _truths[name]
+
+
+# ---- truncated kernels: the settings and the assertions the CPU and the GPU tests share ---------------------------------------
+TRUNC_PN, TRUNC_N = 64, 128
+TRUNC_RUNS = [(s, K, 16) for s in "abcd" for K in (16, 64)] + [("a", 24, 8)]      # (setting, kernels, oversample); iterations 2
+TOL_EIG = 1e-5                 # x lambda_1: the project's eigenvalue tolerance for the fp32 operator
+TOL_CAPTURED_LOW = 1e-3        # captured may fall this far below the exact top-K fraction (test_truncated_kernels_on_the_device)
+TRUNCATION_RULE = 1.5          # x lambda_{K+1}: the project's truncation rule, here in operator norm
+_settings, _exact = {}, {}
+
+
+def truncated_setting(name):
+    """(P complex64, W float32 map) at pn 64, from oracle.abbe_oracle and helpers:
+    "a" ideal pupil, annular 0.4-0.8 with weight 1 (S = 380);  "b" demo aberrations, disc 0-0.6, weight 1 (S = 293);
+    "c" demo aberrations, helpers.SOURCE_CASES["annular_shift"] (it wraps), grey_weights (S = 380);
+    "d" as "c" with weights 10^(-4 u), u uniform from a seeded CPU generator: four decades;
+    "a_demo", "a_f120": source "a" under the demo aberrations and under 120 nm defocus (the planes of the stack)."""
+    if name not in _settings:
+        from helpers import DEMO_AB, NA, SOURCE_CASES, WL, f16
+        pn = TRUNC_PN
+        ab = {"a": None, "a_f120": f16([0, 0, 0, 0, 120])}.get(name, f16(DEMO_AB))
+        P = O.pupil_function(ab, pn, NA, WL).to(torch.complex64)
+        if name in ("c", "d"):
+            src = SOURCE_CASES["annular_shift"]
+            bitmap = O.source_annular(src["sin"], src["sout"], pn, src["sx"], src["sy"])
+            if name == "c":
+                W = grey_weights(bitmap)
+            else:
+                u = torch.rand((pn, pn), generator=torch.Generator().manual_seed(11), dtype=torch.float64)
+                W = (10.0 ** (-4.0 * u) * (bitmap != 0)).to(torch.float32)
+        else:
+            W = (O.source_annular(0.0, 0.6, pn) if name == "b" else O.source_annular(0.4, 0.8, pn)).to(torch.float32)
+        _settings[name] = (P, W)
+    return _settings[name]
+
+
+def truncated_mask():
+    """The Bernoulli mask's spectrum at pn 64 (N = 128)."""
+    if "mask" not in _settings:
+        from helpers import PS, WL
+        from lithographysimulator_amd.synthetic import bernoulli_mask
+        _settings["mask"] = O.mask_spectrum(bernoulli_mask(TRUNC_PN), PS, WL)
+    return _settings["mask"]
+
+
+def truncated_exact(name):
+    """(lambda float64 [S] descending, A [S,F], trace = sum W * sum |P|^2) of a setting, computed once."""
+    if name not in _exact:
+        P, W = truncated_setting(name)
+        p, w = P.numpy().astype(np.complex128), W.numpy().astype(np.float64)
+        _exact[name] = (exact_spectrum(p, w), explicit_A(p, w), float(w.sum()) * float((np.abs(p) ** 2).sum()))
+    return _exact[name]
+
+
+def check_truncated(tag, name, K, kernels, eigenvalues, captured, box):
+    """Every assertion on one plane's truncated kernel set except the image (the issue's list, in its order); prints what it
+    observed and returns it as a dict.  `kernels` complex [K,pn,pn], `eigenvalues` [K], `captured` a float, `box` the plane's
+    masking box or None."""
+    lam, A, tr = truncated_exact(name)
+    P, W = truncated_setting(name)
+    pn = TRUNC_PN
+    theta = np.asarray(torch.as_tensor(eigenvalues).cpu().numpy(), dtype=np.float64)
+    phi = torch.as_tensor(kernels).cpu().numpy().astype(np.complex128)
+    assert theta.shape == (K,) and phi.shape == (K, pn, pn) and K < lam.shape[0]
+    # ordering and interlacing: Rayleigh-Ritz values never exceed the exact ones
+    excess = float((theta - lam[:K]).max() / lam[0])
+    assert (np.diff(theta) <= 0).all() and (theta >= 0).all(), (tag, theta)
+    assert excess <= TOL_EIG, (tag, excess)
+    # captured
+    exact = float(lam[:K].sum() / tr)
+    energy = (np.abs(phi) ** 2).sum(axis=(1, 2))
+    e_energy = float(np.abs(energy - theta).max() / theta[0])
+    assert abs(float(captured) - theta.sum() / tr) <= 1e-12, (tag, float(captured), theta.sum() / tr)
+    assert e_energy <= TOL_EIG, (tag, e_energy)
+    deficit = exact - float(captured)
+    assert -TOL_EIG <= deficit <= TOL_CAPTURED_LOW, (tag, float(captured), exact)
+    # quality of the subspace, in operator norm
+    res = residual_norm(A, phi)
+    ratio = res / lam[K]
+    assert (1 - 1e-3) * lam[K] <= res <= TRUNCATION_RULE * lam[K], (tag, res, lam[K], ratio)
+    # masking box
+    wraps = box is None
+    if not wraps:
+        r_lo, r_hi, c_lo, c_hi = box
+        outside = np.ones((pn, pn), dtype=bool)
+        outside[r_lo:r_hi + 1, c_lo:c_hi + 1] = False
+        assert r_hi - r_lo + 1 < pn and c_hi - c_lo + 1 < pn and outside.any(), (tag, box)
+        assert int((phi[:, outside] != 0).sum()) == 0 and int((phi[:, ~outside] != 0).sum()) > 0, (tag, box)
+    print(f"{tag}: S {lam.shape[0]}, K {K}: theta - lambda max {excess:+.2e} lambda_1 (bound {TOL_EIG:.0e}); energy identity "
+          f"{e_energy:.2e} theta_1 (bound {TOL_EIG:.0e}); captured {float(captured):.6f}, exact {exact:.6f}, deficit {deficit:.2e} "
+          f"(bounds -{TOL_EIG:.0e} ... {TOL_CAPTURED_LOW:.0e}); residual / lambda_K+1 {ratio:.4f} (bounds 0.999 ... "
+          f"{TRUNCATION_RULE}); box {box}")
+    return dict(excess=excess, energy=e_energy, deficit=deficit, ratio=ratio, wraps=wraps)

@@ -7,7 +7,11 @@ Error = max |got - truth| / max |truth|.  Bound = 4 x the error of torch's CPU c
 the project's "4 x the fp32 floor" rule of test_gpu_spectrum.py, with the floor taken from the reference arithmetic and never from
 the code under test.  Forward then inverse returns n^2 x under the same bound (4 x the forward floor of that input).
 
-Measured on an MI355X: error / floor 0.76 ... 1.29 over the 36 one-way cases, 1.18 ... 1.96 over the 18 round trips."""
+n = 16 with a batch of 65,537 runs the transposes' second launch (grid.z holds 65,535 matrices), and the matrices of that launch
+are held to the bound on their own as well.
+
+Measured on an MI355X: error / floor 0.76 ... 1.29 over the 36 one-way cases, 1.18 ... 1.96 over the 18 round trips; batch 65,537:
+1.07 both ways, matrices 65,535 and 65,536 at 6.4e-8 and 5.2e-8 of the batch's maximum, 0.97 of their own complex64 floor."""
 import numpy as np
 import pytest
 import torch
@@ -33,17 +37,21 @@ def nat():
 _inputs = {}
 
 
+def _make_input(n, batch):
+    g = torch.Generator().manual_seed(1000 * n + batch)
+    x = torch.view_as_complex(torch.randn((batch, n, n, 2), generator=g, dtype=torch.float32))
+    x128 = x.numpy().astype(np.complex128)
+    fwd = np.fft.fft2(x128)
+    inv = np.fft.ifft2(x128) * float(n * n)
+    floor_f = np.abs(torch.fft.fft2(x).numpy() - fwd).max() / np.abs(fwd).max()
+    floor_i = np.abs(torch.fft.ifft2(x, norm="forward").numpy() - inv).max() / np.abs(inv).max()
+    return x, fwd, inv, floor_f, floor_i
+
+
 def _input(n, batch):
     """(x complex64, forward truth, inverse truth, forward floor, inverse floor), computed once per shape."""
     if (n, batch) not in _inputs:
-        g = torch.Generator().manual_seed(1000 * n + batch)
-        x = torch.view_as_complex(torch.randn((batch, n, n, 2), generator=g, dtype=torch.float32))
-        x128 = x.numpy().astype(np.complex128)
-        fwd = np.fft.fft2(x128)
-        inv = np.fft.ifft2(x128) * float(n * n)
-        floor_f = np.abs(torch.fft.fft2(x).numpy() - fwd).max() / np.abs(fwd).max()
-        floor_i = np.abs(torch.fft.ifft2(x, norm="forward").numpy() - inv).max() / np.abs(inv).max()
-        _inputs[(n, batch)] = (x, fwd, inv, floor_f, floor_i)
+        _inputs[(n, batch)] = _make_input(n, batch)
     return _inputs[(n, batch)]
 
 
@@ -75,6 +83,36 @@ def test_forward_then_inverse_returns_n2_x(nat, dev, n, batch):
     err = np.abs(got - want).max() / np.abs(want).max()
     print(f"n {n} batch {batch} round trip: error {err:.3e}, forward floor {floor_f:.3e}, quotient {err / floor_f:.2f} (bound 4)")
     assert err <= 4 * floor_f
+
+
+@pytest.fixture(scope="module")
+def many():
+    """n 16, batch 65,537: transpose() launches grid.z = 65,535 matrices and then the other two.  (x, forward truth, inverse
+    truth, floors) as _input gives them, kept for this module's two directions only."""
+    return _make_input(16, 65537)
+
+
+@pytest.mark.parametrize("inverse", [False, True])
+def test_fft2_batch_beyond_one_transpose_launch(nat, dev, many, inverse):
+    x, fwd, inv, floor_f, floor_i = many
+    want, floor = (inv, floor_i) if inverse else (fwd, floor_f)
+    got = _fft2(nat, dev, x.to(dev), inverse).cpu().numpy()
+    scale = np.abs(want).max()
+    err = np.abs(got - want).max() / scale
+    # the matrices of the second transpose launch, on their own: against the whole batch's scale under the whole batch's bound,
+    # and each against its own maximum under 4 x the complex64 floor of these matrices
+    tail = slice(65535, None)
+    ref = (torch.fft.ifft2(x[tail], norm="forward") if inverse else torch.fft.fft2(x[tail])).numpy()
+    own = np.abs(want[tail]).max(axis=(1, 2))
+    tail_err = np.abs(got[tail] - want[tail]).max(axis=(1, 2))
+    tail_floor = (np.abs(ref - want[tail]).max(axis=(1, 2)) / own).max()
+    print(f"n 16 batch 65537 {'inverse' if inverse else 'forward'}: error {err:.3e}, floor {floor:.3e}, quotient {err / floor:.2f} "
+          f"(bound 4); matrices 65535, 65536: {tail_err / scale} of the batch's maximum, {tail_err / own} of their own (floor "
+          f"{tail_floor:.3e}, quotient {(tail_err / own).max() / tail_floor:.2f}, bound 4)")
+    assert err <= 4 * floor
+    assert (tail_err / scale <= 4 * floor).all()
+    assert (tail_err / own <= 4 * tail_floor).all()
+    assert np.abs(want[tail]).min() > 0 and not np.array_equal(got[65535], got[65536])
 
 
 def test_refusals(nat, dev):

@@ -9,7 +9,11 @@ points), where Hopkins and Abbe are the same sum.  The fold is checked bit for b
 Measured on an MI355X: litho_tcc_apply 1.22 (pn 32) and 1.18 (pn 64) of the complex64 formula's own error (bound 4), in place equal
 to out of place bit for bit; full-rank images max 5.1e-7 ... 8.7e-7 and l2 2.5e-7 ... 4.0e-7 of the float64 Abbe sum in the five
 cases (bounds 2e-5 and 5e-6); chunked folds identical bit for bit; K = 24 of 92: 1.06 x the exact truncation's error (bound 1.5);
-correctLayout at K = 797: first iterate 4.8e-6 max, 2.3e-6 l2 from the Abbe model's."""
+correctLayout at K = 797: first iterate 4.8e-6 max, 2.3e-6 l2 from the Abbe model's.  Fold edges (a 4,199,495-element row through
+the grid-stride loop, 1 ... 3 elements, 65,535 groups, K 300, views 1 ... 3 floats into their allocations): no element differs.
+N = 4 pn: (64, 256) ran at its own size on the generic kernels, one launch per kernel (embedded size 64, variant -1, 40 launches),
+max 6.8e-7, l2 3.2e-7; (128, 512) ran embedded in 256 (variant 1, 4 launches), max 6.8e-7, l2 2.6e-7; the wrapping source at pn 64
+(no box, generic kernels, chunks of 7): max 4.1e-7, l2 2.0e-7 (against abbeIntensity(weights=): 4.8e-7 ... 6.1e-7 max)."""
 import numpy as np
 import pytest
 import torch
@@ -112,6 +116,80 @@ def test_fold_is_the_sequential_fp32_sum_bit_for_bit(nat, dev, K, elems):
     assert f(None, 1, K, elems, nat.ptr(out), 0, nat.stream_ptr(dev)) == nat.E_ARG
 
 
+def _fold_want(stack, start, groups, K, accumulate):
+    """The sequential fp32 sum, k ascending, one running sum per element (numpy float32 adds)."""
+    want = start.numpy().copy() if accumulate else np.zeros(tuple(start.shape), dtype=np.float32)
+    for gi in range(groups):
+        for k in range(K):
+            want[gi] = want[gi] + stack[gi * K + k].numpy()
+    assert want.dtype == np.float32
+    return want
+
+
+# beyond 4096 workgroups of 256 threads x 4 elements the kernel strides: a whole stride, a partial second one and a 3-element tail
+FOLD_STRIDE = 4096 * 256 * 4
+FOLD_EDGES = [(FOLD_STRIDE + 4 * (256 * 5 + 17) + 3, 3, 2),                     # (elems, K, groups)
+              (1, 3, 2), (2, 3, 2), (3, 3, 2),                                 # the tail alone
+              (6, 2, 65535),                                                    # the largest grid.y
+              (1000, 300, 2)]
+
+
+@pytest.mark.parametrize("elems,K,groups", FOLD_EDGES)
+def test_fold_edges_bit_for_bit(nat, dev, elems, K, groups):
+    g = torch.Generator().manual_seed(elems % 100003 + K)
+    stack = torch.randn((groups * K, elems), generator=g, dtype=torch.float32)
+    start = torch.randn((groups, elems), generator=g, dtype=torch.float32)
+    sd = stack.to(dev)
+    for accumulate in (0, 1):
+        want = _fold_want(stack, start, groups, K, accumulate)
+        out = start.to(dev).clone()
+        nat.check(nat.lib().litho_socs_fold(nat.ptr(sd), groups, K, elems, nat.ptr(out), accumulate, nat.stream_ptr(dev)),
+                  "litho_socs_fold")
+        torch.cuda.synchronize()
+        got = out.cpu().numpy()
+        wrong = int((got != want).sum())
+        print(f"fold elems {elems} K {K} groups {groups} accumulate {accumulate}: {wrong} of {want.size} elements differ")
+        assert wrong == 0
+        assert torch.equal(sd.cpu(), stack)                                     # the stack is read only
+
+
+@pytest.mark.parametrize("offset", [1, 2, 3])
+def test_fold_from_views_that_are_only_4_byte_aligned(nat, dev, offset):
+    """`stack` and `out` start `offset` floats into their allocations; elems is odd, so every row has another alignment.  The
+    floats around the views stay what they were."""
+    elems, K, groups = 1031, 5, 3
+    g = torch.Generator().manual_seed(offset)
+    stack = torch.randn((groups * K, elems), generator=g, dtype=torch.float32)
+    start = torch.randn((groups, elems), generator=g, dtype=torch.float32)
+    for accumulate in (0, 1):
+        want = _fold_want(stack, start, groups, K, accumulate)
+        sbuf = torch.full((offset + stack.numel() + 4,), 7.0, dtype=torch.float32, device=dev)
+        obuf = torch.full((offset + start.numel() + 4,), 9.0, dtype=torch.float32, device=dev)
+        sv, ov = sbuf[offset:offset + stack.numel()], obuf[offset:offset + start.numel()]
+        sv.copy_(stack.reshape(-1).to(dev))
+        ov.copy_(start.reshape(-1).to(dev))
+        assert sv.data_ptr() % 16 == 4 * offset and ov.data_ptr() % 16 == 4 * offset
+        nat.check(nat.lib().litho_socs_fold(nat.ptr(sv), groups, K, elems, nat.ptr(ov), accumulate, nat.stream_ptr(dev)),
+                  "litho_socs_fold")
+        torch.cuda.synchronize()
+        assert np.array_equal(ov.cpu().numpy().reshape(groups, elems), want), (offset, accumulate)
+        assert bool((obuf[:offset] == 9.0).all()) and bool((obuf[offset + start.numel():] == 9.0).all())
+        assert bool((sbuf[:offset] == 7.0).all()) and bool((sbuf[offset + stack.numel():] == 7.0).all())
+
+
+def test_fold_refuses_what_its_grid_cannot_hold(nat, dev):
+    """groups = 65536 (grid.y ends at 65535) and elems = 2^40 + 1; both return before anything is launched, so the buffers may
+    be small and stay as they were."""
+    sd = torch.ones((4, 8), dtype=torch.float32, device=dev)
+    out = torch.full((2, 8), 3.0, dtype=torch.float32, device=dev)
+    f, st = nat.lib().litho_socs_fold, nat.stream_ptr(dev)
+    assert f(nat.ptr(sd), 65536, 2, 6, nat.ptr(out), 0, st) == nat.E_ARG
+    assert f(nat.ptr(sd), 1, 2, (1 << 40) + 1, nat.ptr(out), 0, st) == nat.E_ARG
+    assert f(nat.ptr(sd), 1, 2, 8, None, 0, st) == nat.E_ARG
+    torch.cuda.synchronize()
+    assert bool((out == 3.0).all()) and bool((sd == 1.0).all())
+
+
 # ---- full-rank parity --------------------------------------------------------------------------------------------------------
 _strided = {}
 
@@ -164,6 +242,40 @@ def test_full_rank_parity_strided(L, dev, nat, pn, N):
     assert int((k.kernels[:, outside] != 0).sum()) == 0 and r_hi - r_lo + 1 < pn and c_hi - c_lo + 1 < pn
     _check(f"pn {pn} N {N} hopkins vs float64 Abbe", got, truth)
     _check(f"pn {pn} N {N} hopkins vs abbeIntensity(weights=)", got, L.abbeIntensity(mft, pf, sel, N, weights=w).cpu().double())
+
+
+@pytest.mark.parametrize("pn,N", [(64, 256), (128, 512)])
+def test_full_rank_parity_at_n_equal_4_pn(L, dev, nat, pn, N):
+    """N = 4 pn: neither of the engine's specialised geometries (pn = N, pn = N / 2).  Which grid and which kernels the engine
+    takes for the kernel stack is printed, not predicted."""
+    from lithographysimulator_amd.imageformation import embeddedSize
+    mft, pf, sel, w, W, truth = _strided_problem(L, dev, pn, N)
+    k = L.socsKernels(pf, W, kernels=40, oversample=0)
+    assert k.K == 40 and k.boxes[0] is not None
+    got = L.hopkinsIntensity(mft, k, N)
+    print(f"pn {pn} N {N}: captured {k.captured:.8f}, box {k.boxes[0]}, litho_abbe_embedded_size {embeddedSize(pn, N)}, "
+          f"plan {nat.last_plan()}")
+    _check(f"pn {pn} N {N} hopkins vs float64 Abbe", got, truth)
+    _check(f"pn {pn} N {N} hopkins vs abbeIntensity(weights=)", got, L.abbeIntensity(mft, pf, sel, N, weights=w).cpu().double())
+    assert abs(k.captured - 1.0) < 1e-5
+
+
+def test_full_rank_parity_with_a_wrapping_source_at_64(L, dev, nat):
+    """The shifted annular source of the truncated tests' setting (c), thinned to 40 strided points: no masking box, so the
+    engine sees full-grid kernels; folded in chunks of 7."""
+    pn, N = SO.TRUNC_PN, SO.TRUNC_N
+    P, Wc = SO.truncated_setting("c")
+    W = Wc * SO.strided_points(Wc > 0, 40)
+    M = SO.truncated_mask()
+    Pd, Wd, Md = P.to(dev), W.to(dev), M.to(dev)
+    k = L.socsKernels(Pd, Wd, kernels=40, oversample=0)
+    assert k.K == 40 and k.lit_points == 40 and k.boxes == [None]
+    got = L.hopkinsIntensity(Md, k, N, kernelChunk=7)
+    print(f"wrapping source at pn 64: captured {k.captured:.8f}, plan {nat.last_plan()}")
+    _check("wrap64 hopkins vs float64 Abbe", got, SO.abbe_truth(P, M, W.numpy(), N))
+    sh, w = L.sourceWeights(Wd, pn)
+    _check("wrap64 hopkins vs abbeIntensity(weights=)", got, L.abbeIntensity(Md, Pd, sh, N, weights=w).cpu().double())
+    assert abs(k.captured - 1.0) < 1e-5
 
 
 def test_kernel_chunks_give_the_same_image(L, dev):

@@ -167,3 +167,69 @@ def test_an_integer_bitmap_means_weight_one():
     want = SO.abbe_truth(P, M, ones, N)
     img = SO.kernel_image(k.kernels, M, N)
     assert rel_max(img, want) < TOL_IMAGE_MAX and rel_l2(img, want) < TOL_IMAGE_L2
+
+
+# ---- the oracle's spectrum and residual norm, and the host algebra on truncated sets (pn 64) ----------------------------------
+def test_exact_spectrum_and_top_k_kernels():
+    P, W, M, N = case("wrap32")
+    phi, lam = SO.exact_kernels(P.numpy(), W.numpy())
+    spec = SO.exact_spectrum(P.numpy(), W.numpy())
+    top, lam_top = SO.exact_kernels(P.numpy(), W.numpy(), K=24)
+    assert spec.shape == (92,) and spec.dtype == np.float64 and (np.diff(spec) <= 0).all()
+    assert np.abs(spec - lam).max() <= 1e-12 * lam[0] and np.array_equal(lam_top, lam)
+    assert top.shape == (24, 32, 32) and np.array_equal(top, phi[:24])
+
+
+@pytest.mark.parametrize("name", ["wrap32", "focus64"])
+def test_residual_norm_against_eckart_young(name):
+    """The exact top-K kernels leave exactly lambda_{K+1}; no kernels at all leave lambda_1; all S leave nothing."""
+    P, W, M, N = case(name)
+    A = SO.explicit_A(P.numpy(), W.numpy())
+    phi, lam = SO.exact_kernels(P.numpy(), W.numpy())
+    S, F = A.shape
+    for K in (1, 8, 24, S - 1):
+        r = SO.residual_norm(A, phi[:K])
+        print(f"{name} K {K}: residual {r:.12e}, lambda_K+1 {lam[K]:.12e}, relative difference {abs(r - lam[K]) / lam[K]:.1e}")
+        assert abs(r - lam[K]) <= 1e-10 * lam[K]
+    r0 = SO.residual_norm(A, np.zeros((5, F)))
+    rS = SO.residual_norm(A, phi)
+    print(f"{name}: zero rows {r0:.12e} (lambda_1 {lam[0]:.12e}), all {S} kernels {rS / lam[0]:.1e} lambda_1")
+    assert abs(r0 - lam[0]) <= 1e-10 * lam[0]
+    assert rS <= 1e-12 * lam[0]
+    if name == "wrap32":                                                        # and it is the norm of the explicit residual
+        K = 24
+        E = SO.tcc(A) - np.einsum("kf,kg->fg", phi[:K].reshape(K, -1), phi[:K].reshape(K, -1).conj())
+        assert abs(np.linalg.norm(E, 2) - SO.residual_norm(A, phi[:K])) <= 1e-10 * lam[K]
+
+
+def test_the_pn64_settings_are_what_the_tests_say():
+    sizes = {n: int((SO.truncated_setting(n)[1] > 0).sum()) for n in "abcd"}
+    assert sizes == {"a": 380, "b": 293, "c": 380, "d": 380}
+    w = SO.truncated_setting("d")[1]
+    assert float(w[w > 0].min()) < 2e-4 and float(w.max()) > 0.5                # four decades
+    for n in "cd":                                                              # the shifted source is not symmetric
+        W = SO.truncated_setting(n)[1]
+        assert not torch.equal(W, W.T)
+
+
+@pytest.mark.parametrize("name,K,oversample", SO.TRUNC_RUNS)
+def test_truncated_host_algebra_at_64(name, K, oversample):
+    """socsKernels with the float64 dense operator as `applier`: what tests/test_gpu_socs_truncated.py asserts on the device,
+    minus the image."""
+    import lithographysimulator_amd as L
+    P, W = SO.truncated_setting(name)
+    k = L.socsKernels(P, W, kernels=K, oversample=oversample, applier=SO.apply_as_applier(P.numpy(), W.numpy()))
+    seen = SO.check_truncated(f"cpu {name}", name, K, k.kernels, k.eigenvalues, k.captured, k.boxes[0])
+    assert seen["wraps"] == (name in "cd") and k.K == K and abs(k.trace - SO.truncated_exact(name)[2]) <= 1e-12 * k.trace
+
+
+def test_truncated_host_algebra_on_a_stack():
+    import lithographysimulator_amd as L
+    names = ("a_demo", "a_f120")
+    Ps = [SO.truncated_setting(n)[0] for n in names]
+    W = SO.truncated_setting("a")[1]
+    k = L.socsKernels(torch.stack(Ps), W, applier=[SO.apply_as_applier(p.numpy(), W.numpy()) for p in Ps])
+    assert tuple(k.kernels.shape) == (2, 64, 64, 64)
+    for p, n in enumerate(names):
+        SO.check_truncated(f"cpu stack plane {p} ({n})", n, 64, k.kernels[p], k.eigenvalues[p], float(k.captured[p]), k.boxes[p])
+    assert rel_max(k.kernels[1].abs(), k.kernels[0].abs()) > 1e-2               # the planes' kernels differ
