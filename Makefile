@@ -50,6 +50,10 @@ build/contour.o: $(CSRC)/contour.hip $(CSRC)/engine_common.hpp include/litho_abb
 build/socs.o: $(CSRC)/socs.hip $(CSRC)/fft_core.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(FFTFLAGS) -c $< -o $@
+# mask gradients: the centred pruned line transforms of the fields and of their adjoint, the same line FFT and flags
+build/socs_grad.o: $(CSRC)/socs_grad.hip $(CSRC)/fft_core.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) $(FFTFLAGS) -c $< -o $@
 build/common.o: $(CSRC)/common.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -61,7 +65,7 @@ build/plan_dry_run.o: $(CSRC)/plan_dry_run.cpp $(CSRC)/abbe_plan.hpp include/lit
 build/contour_link.o: $(CSRC)/contour_link.cpp include/litho_abbe.h
 	@mkdir -p build
 	g++ -O2 -std=c++17 -fPIC -Wall -Wextra -c $< -o $@
-$(OUT): build/abbe_engine.o build/optics.o build/layout.o build/metrology.o build/contour.o build/socs.o build/common.o build/plan_dry_run.o build/contour_link.o $(INST) $(INSTW)
+$(OUT): build/abbe_engine.o build/optics.o build/layout.o build/metrology.o build/contour.o build/socs.o build/socs_grad.o build/common.o build/plan_dry_run.o build/contour_link.o $(INST) $(INSTW)
 	@mkdir -p lithographysimulator_amd/lib
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 

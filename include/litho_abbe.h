@@ -381,6 +381,26 @@ int litho_tcc_apply(const void *pupil_hat, const float *weight_shifted, const vo
  * Asynchronous: one kernel. */
 int litho_socs_fold(const float *stack, int groups, int K, int64_t elems, float *out, int accumulate, void *stream);
 
+/* ---- Mask gradients of Hopkins imaging (csrc/socs_grad.hip; no reference counterpart, checked against tests/socs_grad_oracle.py).
+ * With F[q][i] = exp(+2 pi i (i - c)(q - c) / N), c = pn / 2, q, i in [0, pn), the engine's chain at shift (0,0) is L(X) = F X F^T,
+ * the coherent fields are E_k = L(phi_k . M) and I = sum_k |E_k|^2.  For a real loss l with G = dl/dI,
+ *   g = dl/dRe M + i dl/dIm M = 2 sum_p sum_k conj(phi_pk) . L^H(G_p . E_pk),   L^H(Y) = conj(F) Y conj(F)^T,
+ * torch's convention for the gradient of a complex leaf (dl = Re <g, dM>).  pn and N powers of two, 16..4096 (anything else, a
+ * batch < 1 or a null pointer: LITHO_E_ARG), N >= pn (LITHO_E_NSMALL); every check is made before any launch.  All calls are
+ * asynchronous, allocate nothing and wait for nothing.
+ *
+ * litho_socs_fields: fields[b] = L(kernels[b] . maskFT), b < batch; kernels, fields complex64 [batch,pn,pn], maskFT complex64 [pn,pn];
+ * fields must not overlap kernels. */
+int litho_socs_fields(const void *kernels, const void *maskFT, int batch, int pn, int N, void *fields, void *stream);
+/* litho_socs_vjp: grad (+)= 2 sum_b conj(kernels[b]) . L^H(gradI[b / K] . L(kernels[b] . maskFT)), b < groups K ascending, one running
+ * fp32 sum per component and no atomics: the result is deterministic, and calls on consecutive chunks of the kernels with
+ * accumulate != 0 give the chunk-ordered sum (accumulate == 0 starts from zero).  kernels complex64 [groups K,pn,pn] with item
+ * g K + k = kernel k of plane g, gradI fp32 [groups,pn,pn], grad complex64 [pn,pn].  work: litho_socs_vjp_work_bytes(groups, K, pn)
+ * device bytes (the field stack; 0 for a bad argument), less is LITHO_E_WORKSPACE. */
+size_t litho_socs_vjp_work_bytes(int groups, int K, int pn);
+int litho_socs_vjp(const void *kernels, const void *maskFT, const float *gradI, int groups, int K, int pn, int N, void *grad,
+                   int accumulate, void *work, size_t work_bytes, void *stream);
+
 /* ---- Layout rasteriser: the device side of the GDSII import (lithographysimulator_amd/layout.py).  SURVEY.md section
  * 8(f) row 4: the reference has NO counterpart (README.md:20-22 lists GDSII import among its unbuilt goals), it is the
  * caller side of Mask(geometry, pixelSize) (mask.py:5-30), so there is no parity target; checked bit for bit against

@@ -12,6 +12,8 @@ from .metrology import (LayoutSites, OPCResult, biasLayout, correctLayout,      
 from .contours import (Contours, contourVertices, contoursToGDSII, contoursToLayout,   # noqa: F401
                        doseFocusEnvelope, processVariationBand, simplifyContour, traceContours)
 from .socs import SOCSKernels, hopkinsImage, hopkinsIntensity, socsKernels          # noqa: F401
+from .ilt import (ILTResult, hopkinsFields, hopkinsGradient, hopkinsIntensityAD,       # noqa: F401
+                  maskSpectrumAdjoint, optimizeMask, postProcessAdjoint)
 from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
@@ -21,4 +23,5 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "throughFocusPupils", "readGDSII", "writeGDSII", "flattenLayout", "rasterizeLayout", "composeTransmission", "maskFromGDSII", "GdsLibrary",
            "imageRegistration", "layoutSites", "measureEPE", "biasLayout", "correctLayout", "LayoutSites", "OPCResult",
            "Contours", "contourVertices", "traceContours", "contoursToLayout", "simplifyContour", "contoursToGDSII", "doseFocusEnvelope",
-           "processVariationBand", "SOCSKernels", "socsKernels", "hopkinsIntensity", "hopkinsImage"]
+           "processVariationBand", "SOCSKernels", "socsKernels", "hopkinsIntensity", "hopkinsImage",
+           "hopkinsFields", "hopkinsGradient", "hopkinsIntensityAD", "maskSpectrumAdjoint", "postProcessAdjoint", "optimizeMask", "ILTResult"]

@@ -1,0 +1,324 @@
+"""Mask gradients on the GPU: litho_socs_fields / litho_socs_vjp (csrc/socs_grad.hip), hopkinsFields, hopkinsGradient,
+hopkinsIntensityAD, the two bookend adjoints and optimizeMask, against the float64 definitions of tests/socs_grad_oracle.py.
+
+Size regimes of the new line kernel k_centred_rows<log2 pn, sign, load> (LABNOTES "Mask gradients"), and the case that reaches
+each (fields everywhere; the gradient wherever the dense float64 formula is cheap, pn <= 1024):
+  * lines per workgroup: pn <= 512, a line takes T = pn / 16 < 64 threads and a workgroup carries 64 / T lines -- (16, 16) ...
+    (256, 512); pn >= 1024, one line per workgroup -- (1024, 1024), (1024, 2048), (2048, 4096), (4096, 4096);
+  * transforms per line: m = N / pn = 1 -- (16, 16), (64, 64), (1024, 1024), (4096, 4096); 1 < m <= pn, m pre-modulated
+    transforms of the line held in registers -- (16, 32), (32, 64), (32, 128), (64, 128), (128, 256), (256, 512), (1024, 2048),
+    (2048, 4096); m > pn, where only the pn values of r that own an output run and the store guard q in [0, pn) decides
+    -- (16, 512) with m = 32 and (16, 4096) with m = 256;
+  * the line FFT inside it: one radix-16 pass after the leading radix, pn 16 ... 128; two passes with the second pass's
+    twiddles in LDS, pn 256 ... 1024 -- (256, 512), (1024, .); two passes with those twiddles in registers, pn 2048 --
+    (2048, 4096); three passes, pn 4096 -- (4096, 4096).
+The cases beyond the sizes 16 ... 128 use K = 2 at the smallest pn of their regime.  From pn 1024 on the float64 truth of the
+fields is evaluated on a 40 x 40 sub-grid of the outputs that holds the corners, the centre and the rows next to them
+(E[rows, cols] = F[rows] (phi . M) F[cols]^T); the gradient at pn 1024 is held against the dense formula.
+
+Bounds: fields helpers.TOL_FIELD; images and gradients helpers.TOL_IMAGE_MAX / TOL_IMAGE_L2 (the complex64 floor of the gradient
+formula is 7.9e-7 / 7.5e-7, under a quarter of them: socs_grad_oracle.py); adjoints 1e-5 ||A x|| ||y||.  Every test prints what
+it observed (-s)."""
+import math
+
+import numpy as np
+import pytest
+import torch
+
+import socs_grad_oracle as GO
+import socs_oracle as SO
+from helpers import NA, PS, TOL_FIELD, TOL_IMAGE_L2, TOL_IMAGE_MAX, WL, rel_l2, rel_max
+from oracle import abbe_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+SIZES = GO.GRAD_SIZES + GO.EXTRA_SIZES
+LARGE = GO.LARGE_GRAD_SIZES + [(2048, 4096), (4096, 4096)]
+
+
+@pytest.fixture(scope="module")
+def dev():
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    return torch.device("cuda", 0)
+
+
+@pytest.fixture(scope="module")
+def L():
+    import lithographysimulator_amd as L
+    from lithographysimulator_amd import _native as nat
+    assert nat.lib().litho_target_arch() == b"gfx950"
+    return L
+
+
+@pytest.fixture(scope="module")
+def nat():
+    from lithographysimulator_amd import _native
+    return _native
+
+
+def _socs(L, kernels, dev):
+    """A SOCSKernels around given kernels ([K,pn,pn] or [planes,K,pn,pn]): only the kernels matter to the calls under test."""
+    k = kernels.to(torch.complex64).to(dev).contiguous()
+    planes = k.shape[0] if k.dim() == 4 else 1
+    K = k.shape[-3]
+    lam = torch.ones((planes, K) if k.dim() == 4 else (K,), dtype=torch.float64)
+    return L.SOCSKernels(k, lam, 1.0, 1.0, 1.0, K, [None] * planes)
+
+
+_named = {}
+
+
+def _named_case(name, K):
+    """(kernels complex64 [K,pn,pn], M, N) of socs_oracle.problem(name): exact kernels, box-limited ("plain32") or wrapping."""
+    if (name, K) not in _named:
+        P, W, M, N = SO.problem(name)
+        _named[(name, K)] = (torch.from_numpy(SO.exact_kernels(P.numpy(), W.numpy(), K)[0]).to(torch.complex64), M, N)
+    return _named[(name, K)]
+
+
+def _check_grad(tag, got, want):
+    e_max = float((got.cpu().to(torch.complex128) - want).abs().max() / want.abs().max())
+    e_l2 = float(torch.linalg.norm(got.cpu().to(torch.complex128) - want) / torch.linalg.norm(want))
+    print(f"{tag}: max {e_max:.2e} (bound {GO.TOL_GRAD_MAX:.0e}), l2 {e_l2:.2e} (bound {GO.TOL_GRAD_L2:.0e})")
+    assert e_max < GO.TOL_GRAD_MAX and e_l2 < GO.TOL_GRAD_L2, (tag, e_max, e_l2)
+
+
+# ---- fields ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pn,N", SIZES)
+def test_fields_against_the_oracle(L, dev, pn, N):
+    """Random band-limited kernels, the complex spectrum of an attenuated phase-shift mask; one plane and a stack of two."""
+    for planes in (1, 2):
+        k, M, _ = GO.sized_case(pn, N, 2, planes)
+        got = L.hopkinsFields(M.to(dev), _socs(L, k, dev), N)
+        want = GO.fields(k, M, N)
+        assert got.dtype == torch.complex64 and tuple(got.shape) == tuple(k.shape)
+        e = rel_max(got.cpu(), want)
+        print(f"fields pn {pn} N {N} planes {planes}: {e:.2e} (bound {TOL_FIELD:.0e})")
+        assert e < TOL_FIELD
+
+
+@pytest.mark.parametrize("pn,N", LARGE)
+def test_fields_with_one_line_per_workgroup(L, dev, pn, N):
+    """pn 1024, 2048 (register twiddles) and 4096 (three passes), K = 2: the truth on a 40 x 40 sub-grid of the outputs,
+    E[rows, cols] = F[rows] (phi . M) F[cols]^T."""
+    k, M, _ = GO.sized_case(pn, N, 2, 1)
+    got = L.hopkinsFields(M.to(dev), _socs(L, k, dev), N).cpu()
+    c = pn // 2
+    idx = torch.tensor(sorted(set([0, 1, 2, c - 2, c - 1, c, c + 1, pn - 2, pn - 1] + list(range(5, pn, pn // 31)))))[:40]
+    F = O.centred_dft_matrix(pn, N)[idx]
+    want = F @ (k.to(torch.complex128) * M.to(torch.complex128)) @ F.T
+    e = rel_max(got[:, idx][:, :, idx], want)
+    print(f"fields pn {pn} N {N} on {len(idx)} x {len(idx)} outputs: {e:.2e} (bound {TOL_FIELD:.0e})")
+    assert e < TOL_FIELD
+
+
+@pytest.mark.parametrize("name", ["plain32", "wrap32"])
+def test_fields_of_exact_kernels_and_a_binary_mask(L, dev, name):
+    """Box-limited and wrapping kernels (K = 5 of 92), the Bernoulli mask's spectrum and an attenuated phase-shift mask's."""
+    k, M, N = _named_case(name, 5)
+    psm = GO.sized_case(32, N, 5, 1)[1]
+    for tag, m in (("binary", M), ("attenuated PSM", psm)):
+        e = rel_max(L.hopkinsFields(m.to(dev), _socs(L, k, dev), N).cpu(), GO.fields(k, m, N))
+        print(f"fields {name} {tag}: {e:.2e} (bound {TOL_FIELD:.0e})")
+        assert e < TOL_FIELD
+
+
+@pytest.mark.parametrize("name", ["plain32", "wrap32"])
+def test_fields_agree_with_the_engine(L, dev, name):
+    """sum_k |hopkinsFields|^2, folded on the host in float64, against the unchanged hopkinsIntensity (full rank, K = 92)."""
+    k, M, N = _named_case(name, None)
+    socs = _socs(L, k, dev)
+    E = L.hopkinsFields(M.to(dev), socs, N).cpu().to(torch.complex128)
+    mine = (E.real ** 2 + E.imag ** 2).sum(dim=0)
+    engine = L.hopkinsIntensity(M.to(dev), socs, N).cpu().double()
+    e_max, e_l2 = rel_max(mine, engine), rel_l2(mine, engine)
+    print(f"{name}: sum |fields|^2 vs hopkinsIntensity max {e_max:.2e} (bound {TOL_IMAGE_MAX:.0e}), l2 {e_l2:.2e} (bound {TOL_IMAGE_L2:.0e})")
+    assert e_max < TOL_IMAGE_MAX and e_l2 < TOL_IMAGE_L2
+
+
+@pytest.mark.parametrize("pn,N", [(32, 128), (64, 128), (128, 128)])
+def test_fields_agree_with_the_engine_on_a_stack(L, dev, pn, N):
+    k, M, _ = GO.sized_case(pn, N, 5, 2)
+    socs = _socs(L, k, dev)
+    E = L.hopkinsFields(M.to(dev), socs, N).cpu().to(torch.complex128)
+    mine = (E.real ** 2 + E.imag ** 2).sum(dim=1)
+    engine = L.hopkinsIntensity(M.to(dev), socs, N).cpu().double()
+    for p in range(2):
+        e_max, e_l2 = rel_max(mine[p], engine[p]), rel_l2(mine[p], engine[p])
+        print(f"pn {pn} N {N} plane {p}: max {e_max:.2e}, l2 {e_l2:.2e}")
+        assert e_max < TOL_IMAGE_MAX and e_l2 < TOL_IMAGE_L2
+
+
+# ---- gradient ----------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("pn,N", SIZES)
+def test_gradient_against_the_oracle(L, dev, pn, N):
+    """K in {1, 2, 5}, one plane and two, G with both signs and a block of zeros; an all-zero G gives exact zeros; `out=` is
+    accumulated into."""
+    for K in (1, 2, 5):
+        for planes in (1, 2):
+            k, M, G = GO.sized_case(pn, N, K, planes)
+            socs, Md, Gd = _socs(L, k, dev), M.to(dev), G.to(dev)
+            assert bool((G < 0).any()) and bool((G > 0).any()) and bool((G == 0).any())
+            want = GO.gradient(k, M, N, G)
+            got = L.hopkinsGradient(Md, socs, N, Gd)
+            assert got.dtype == torch.complex64 and tuple(got.shape) == (pn, pn)
+            _check_grad(f"gradient pn {pn} N {N} K {K} planes {planes}", got, want)
+            zero = L.hopkinsGradient(Md, socs, N, torch.zeros_like(Gd))
+            assert int(torch.count_nonzero(torch.view_as_real(zero))) == 0
+            if K == 5:
+                start = torch.view_as_complex(torch.randn((pn, pn, 2), generator=torch.Generator().manual_seed(3))).to(dev)
+                acc = start.clone()
+                assert L.hopkinsGradient(Md, socs, N, Gd, out=acc) is acc
+                _check_grad(f"  accumulated into out, planes {planes}", acc - start, want)
+
+
+@pytest.mark.parametrize("pn,N", GO.LARGE_GRAD_SIZES)
+def test_gradient_with_one_line_per_workgroup(L, dev, pn, N):
+    """pn 1024, K = 2, one plane, against the dense float64 formula, element by element under the gradient's bounds."""
+    k, M, G = GO.sized_case(pn, N, 2, 1)
+    got = L.hopkinsGradient(M.to(dev), _socs(L, k, dev), N, G.to(dev))
+    _check_grad(f"gradient pn {pn} N {N} K 2", got, GO.gradient(k, M, N, G))
+
+
+@pytest.mark.parametrize("name", ["plain32", "wrap32"])
+def test_gradient_at_full_rank(L, dev, name):
+    k, M, N = _named_case(name, None)
+    G = GO.random_G((32, 32), 9)
+    _check_grad(f"gradient {name} K 92", L.hopkinsGradient(M.to(dev), _socs(L, k, dev), N, G.to(dev)), GO.gradient(k, M, N, G))
+
+
+def test_chunks_are_the_chunk_ordered_sum(L, dev):
+    """K = 5: every chunking within the bound; the whole set as one chunk is the default bit for bit; chunks of two equal the
+    sum built from single-chunk calls with `out=`, bit for bit."""
+    pn, N = 64, 128
+    for planes in (1, 2):
+        k, M, G = GO.sized_case(pn, N, 5, planes)
+        socs, Md, Gd = _socs(L, k, dev), M.to(dev), G.to(dev)
+        want = GO.gradient(k, M, N, G)
+        default = L.hopkinsGradient(Md, socs, N, Gd)
+        got = {c: L.hopkinsGradient(Md, socs, N, Gd, kernelChunk=c) for c in (1, 2, 5)}
+        for c, g in got.items():
+            _check_grad(f"planes {planes} kernelChunk {c}", g, want)
+        assert torch.equal(torch.view_as_real(got[5]), torch.view_as_real(default))
+        k4 = k if planes == 2 else k[None]
+        built = None
+        for c0 in (0, 2, 4):
+            part = _socs(L, k4[:, c0:c0 + 2] if planes == 2 else k4[0, c0:c0 + 2], dev)
+            built = L.hopkinsGradient(Md, part, N, Gd, out=built)
+        assert torch.equal(torch.view_as_real(got[2]), torch.view_as_real(built))
+    with pytest.raises(ValueError):
+        L.hopkinsGradient(Md, socs, N, Gd, kernelChunk=0)
+
+
+def test_two_calls_give_the_same_bits(L, dev):
+    k, M, G = GO.sized_case(128, 256, 5, 2)
+    socs, Md, Gd = _socs(L, k, dev), M.to(dev), G.to(dev)
+    a, b = L.hopkinsGradient(Md, socs, 256, Gd), L.hopkinsGradient(Md, socs, 256, Gd)
+    assert torch.equal(torch.view_as_real(a), torch.view_as_real(b))
+    fa, fb = L.hopkinsFields(Md, socs, 256), L.hopkinsFields(Md, socs, 256)
+    assert torch.equal(torch.view_as_real(fa), torch.view_as_real(fb))
+
+
+def test_autograd_reaches_the_mask_spectrum(L, dev):
+    k, M, G = GO.sized_case(64, 128, 5, 2)
+    socs, Gd = _socs(L, k, dev), G.to(dev)
+    leaf = M.to(dev).clone().requires_grad_(True)
+    image = L.hopkinsIntensityAD(leaf, socs, 128)
+    assert torch.equal(image.detach(), L.hopkinsIntensity(M.to(dev), socs, 128))
+    (Gd * image).sum().backward()
+    direct = L.hopkinsGradient(M.to(dev), socs, 128, Gd)
+    assert leaf.grad is not None and leaf.grad.dtype == torch.complex64
+    assert torch.equal(torch.view_as_real(leaf.grad), torch.view_as_real(direct))
+
+
+# ---- the bookends' adjoints against the device forwards --------------------------------------------------------------------------
+@pytest.mark.parametrize("pn", [32, 64])
+@pytest.mark.parametrize("name", ["shrink", "crop", "copy"])
+def test_device_adjoints_by_the_dot_product_test(L, dev, pn, name):
+    ps, eps, N = GO.epsilon_regimes(pn)[name]
+    gen = torch.Generator().manual_seed(pn + len(name))
+    t = torch.view_as_complex(torch.randn((pn, pn, 2), generator=gen, dtype=torch.float32))
+    y = torch.view_as_complex(torch.randn((pn, pn, 2), generator=gen, dtype=torch.float32))
+    St = L.Mask(transmission=t, pixelSize=ps, device=dev)._ffFraunhofer(eps, N).cpu().to(torch.complex128)
+    Shy = L.maskSpectrumAdjoint(y.to(dev), pn, eps, N)
+    assert Shy.dtype == torch.complex64 and tuple(Shy.shape) == (pn, pn) and Shy.is_contiguous()
+    lhs = complex((St.conj() * y.to(torch.complex128)).sum())
+    rhs = complex((t.to(torch.complex128).conj() * Shy.cpu().to(torch.complex128)).sum())
+    rel_s = abs(lhs - rhs) / float(torch.linalg.norm(St) * torch.linalg.norm(y.to(torch.complex128)))
+    raw = torch.rand((2, pn, pn), generator=gen, dtype=torch.float32)
+    img = L.postProcess(raw.to(dev), eps).cpu().double()
+    gy = torch.randn(tuple(img.shape), generator=gen, dtype=torch.float32)
+    back = L.postProcessAdjoint(gy.to(dev), pn, eps)
+    assert back.dtype == torch.float32 and tuple(back.shape) == (2, pn, pn)
+    rel_p = abs(float((img * gy.double()).sum()) - float((raw.double() * back.cpu().double()).sum())) / float(
+        torch.linalg.norm(img) * torch.linalg.norm(gy.double()))
+    print(f"pn {pn} {name} (epsilon {eps:.4f}, N {N}): mask spectrum {rel_s:.2e}, post-process {rel_p:.2e} (bound {GO.TOL_ADJOINT:.0e})")
+    assert rel_s <= GO.TOL_ADJOINT and rel_p <= GO.TOL_ADJOINT
+
+
+# ---- the loop --------------------------------------------------------------------------------------------------------------------
+def test_optimize_mask_on_the_device(L, dev):
+    """pn 64, full rank of a 40-point source, two isolated contacts, 12 iterations at the defaults (chosen on the CPU oracle
+    chain: test_socs_grad_cpu.py::test_optimize_mask_the_setting_of_the_device_test)."""
+    pn = 64
+    pupil = L.Pupil(pn, WL, NA, None, dev).generatePupilFunction()
+    W = SO.strided_points(O.source_annular(0.4, 0.8, pn), 40).to(torch.float32).to(dev)
+    socs = L.socsKernels(pupil, W, kernels=40, oversample=0)
+    assert socs.K == 40
+    open_mask = L.Mask(torch.ones((pn, pn), dtype=torch.int16), PS, dev)
+    clear = L.hopkinsImage(open_mask, open_mask.fraunhofer(WL, True), socs, PS, open_mask.deltaK, WL, normalize=True)
+    n_out = clear.shape[-1]
+    threshold = 0.3 * float(clear[n_out // 2, n_out // 2])
+    target = torch.zeros((n_out, n_out), dtype=torch.float32, device=dev)
+    for r, c, s in [(20, 20, 6), (38, 40, 6)]:
+        target[r:r + s, c:c + s] = 1.0
+    res = L.optimizeMask(target, socs, PS, open_mask.deltaK, WL, threshold, iterations=12)
+    print(f"optimizeMask pn 64: losses {['%.6f' % v for v in res.losses]}, best {res.best}")
+    assert len(res.losses) == 13 and all(math.isfinite(v) for v in res.losses)
+    assert res.best == int(np.argmin(res.losses)) and res.losses[res.best] < res.losses[0]
+    assert res.mask.dtype == torch.bool and tuple(res.mask.shape) == (pn, pn) and res.mask.device == dev
+    assert res.transmission.dtype == torch.complex64 and not bool(torch.isnan(torch.view_as_real(res.transmission)).any())
+    assert not bool(torch.isnan(res.theta).any())
+    with pytest.raises(ValueError):
+        L.optimizeMask(target[:-1, :-1], socs, PS, open_mask.deltaK, WL, threshold)
+
+
+# ---- argument errors -------------------------------------------------------------------------------------------------------------
+def test_argument_errors_come_back_without_a_launch(L, dev, nat):
+    from lithographysimulator_amd.imageformation import ShapeError
+    lib = nat.lib()
+    k, M, G = GO.sized_case(32, 64, 2, 1)
+    kd, Md, Gd = k.to(dev), M.to(dev), G.to(dev)
+    canary = torch.full((32, 32), 7 + 7j, dtype=torch.complex64, device=dev)
+    fields = torch.full((2, 32, 32), 7 + 7j, dtype=torch.complex64, device=dev)
+    work = torch.empty(2 * 32 * 32 * 8, dtype=torch.uint8, device=dev)
+    st = nat.stream_ptr(dev)
+    p = nat.ptr
+    for pn, N, rc in ((33, 64, nat.E_ARG), (8, 64, nat.E_ARG), (8192, 8192, nat.E_ARG), (32, 48, nat.E_ARG), (32, 8192, nat.E_ARG),
+                      (32, 16, nat.E_NSMALL)):
+        assert lib.litho_socs_fields(p(kd), p(Md), 2, pn, N, p(fields), st) == rc
+        assert lib.litho_socs_vjp(p(kd), p(Md), p(Gd), 1, 2, pn, N, p(canary), 0, p(work), work.numel(), st) == rc
+    assert lib.litho_socs_fields(None, p(Md), 2, 32, 64, p(fields), st) == nat.E_ARG
+    assert lib.litho_socs_fields(p(kd), p(Md), 0, 32, 64, p(fields), st) == nat.E_ARG
+    assert lib.litho_socs_vjp(p(kd), p(Md), None, 1, 2, 32, 64, p(canary), 0, p(work), work.numel(), st) == nat.E_ARG
+    assert lib.litho_socs_vjp(p(kd), p(Md), p(Gd), 1, 2, 32, 64, p(canary), 0, None, work.numel(), st) == nat.E_ARG
+    assert lib.litho_socs_vjp(p(kd), p(Md), p(Gd), 1, 2, 32, 64, p(canary), 0, p(work), work.numel() - 1, st) == nat.E_WORKSPACE
+    assert lib.litho_socs_vjp_work_bytes(1, 2, 32) == work.numel() and lib.litho_socs_vjp_work_bytes(1, 2, 33) == 0
+    torch.cuda.synchronize()
+    assert bool((canary == 7 + 7j).all()) and bool((fields == 7 + 7j).all())          # nothing was launched
+    socs = _socs(L, k, dev)
+    with pytest.raises(ValueError):
+        L.hopkinsFields(Md, socs, 48)
+    with pytest.raises(RuntimeError, match="smaller than the mask"):
+        L.hopkinsGradient(Md, socs, 16, Gd)
+    for bad_G in (Gd[:16], Gd.cpu(), Gd.to(torch.complex64), Gd[None]):
+        with pytest.raises(ShapeError):
+            L.hopkinsGradient(Md, socs, 64, bad_G)
+    for bad_out in (torch.empty((32, 32), dtype=torch.float32, device=dev), torch.empty((32, 64), dtype=torch.complex64, device=dev)[:, ::2],
+                    torch.empty((16, 16), dtype=torch.complex64, device=dev), torch.empty((32, 32), dtype=torch.complex64)):
+        with pytest.raises(ShapeError):
+            L.hopkinsGradient(Md, socs, 64, Gd, out=bad_out)
+    with pytest.raises(ShapeError):
+        L.hopkinsGradient(Md, _socs(L, k, torch.device("cpu")), 64, Gd)
+    with pytest.raises(ValueError):
+        L.maskSpectrumAdjoint(Md, 32, 1.0, 8192)
