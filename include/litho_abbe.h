@@ -381,6 +381,44 @@ int litho_tcc_apply(const void *pupil_hat, const float *weight_shifted, const vo
  * Asynchronous: one kernel. */
 int litho_socs_fold(const float *stack, int groups, int K, int64_t elems, float *out, int accumulate, void *stream);
 
+/* ---- Vector (polarised, high-NA) Hopkins imaging (csrc/socs.hip; no reference counterpart, checked against tests/vector_oracle.py;
+ * DESIGN.md section 10).  Pupil grid point (row i, column j) is sigma = ((j - pn/2) 4/pn, (i - pn/2) 4/pn), the reference's grid
+ * (pupil.py:105-111).  Direction cosines in the image medium of refractive index `index`: alpha = NA sigma_x / index,
+ * beta = NA sigma_y / index, gamma = sqrt(1 - alpha^2 - beta^2); NA < index; where alpha^2 + beta^2 >= 1 every factor is 0.
+ * M_cj maps polarisation component j in {x, y} at the mask side (paraxial object side, thin mask) onto field component
+ * c in {x, y, z} at the wafer:
+ *   M_xx = 1 - alpha^2 / (1 + gamma)   M_xy = M_yx = -alpha beta / (1 + gamma)   M_yy = 1 - beta^2 / (1 + gamma)
+ *   M_zx = -alpha                      M_zy = -beta
+ * (columns orthonormal).  radiometric != 0: every factor times gamma^(-1/2), the aplanatic energy factor.  Defocus z in nm:
+ * every factor times exp(+2 pi i index z (1 - gamma) / wavelength), the exact high-NA defocus phase (the sign of the rho^2 term
+ * of the reference's coefficient 4; not its Zernike-normalised scale).  The six planes of a pupil P are Q_cj = P . M_cj, stored
+ * as plane t = 2 c + j.
+ *
+ * Polarisation: a real symmetric 2 x 2 coherency per source point as three maps on the source grid, W_xx, W_yy, W_xy (the
+ * intensity weight map times the coherency entry).  For source point s (weight w_s, shift d_s) and every pure state m of its
+ * coherency (weight mu_m, unit vector e_m), a_smc = sqrt(w_s mu_m) roll(e_mx Q_cx + e_my Q_cy, d_s); the image is
+ * I = sum_smc |L_N(a_smc . M)|^2 with the engine's chain L_N, and the vector transmission cross coefficient T = sum_smc a a^H,
+ *   T x = sum_c sum_j Q_cj (*) ( sum_j' W_jj' . (Q_cj' (star) x) )              (circular on the n grid), in transforms
+ *   u_cj' = ifft2(conj(q_cj') . fft2(x)),  v_cj = sum_j' ifftshift(W_jj') . u_cj',  T x = ifft2(sum_cj q_cj . fft2(v_cj)),
+ * q = fft2(Q): 14 transforms per vector.  Hermitian positive semidefinite, rank <= 3 S for a rank-one coherency at every lit
+ * point and <= 5 S otherwise (M_xy = M_yx); it factors into SOCS kernels as the scalar one does.
+ *
+ * litho_vector_pupils: out complex64 [planes,6,pn,pn] from pupil complex64 [planes,pn,pn], one kernel launch per plane; factors
+ * and phase in double per cell, multiplied into the fp32 pupil value, each component rounded once.  defocus_nm_host: `planes`
+ * values on the host (read before the call returns), or NULL for none; wavelength is read only with it.  pn even, 16..16384.
+ * NA >= index, planes < 1, a null pupil or out, a non-finite defocus: LITHO_E_ARG.  Asynchronous, no allocation. */
+int litho_vector_pupils(const void *pupil, int planes, int pn, double NA, double index, int radiometric, const double *defocus_nm_host,
+                        double wavelength, void *out, void *stream);
+/* litho_tcc_apply_vector: Y[b] = T X[b], b < batch, by the three steps above including the n^-4 of the inverse transforms.  q_hat
+ * complex64 [6,n,n] = litho_fft2_c2c of the six planes (natural orientation; transposed once into the head of `work`);
+ * w_shifted fp32 [3,n,n] = ifftshift of W_xx, W_yy, W_xy; X, Y complex64 [batch,n,n]; Y may BE X, and must not overlap it
+ * otherwise (LITHO_E_ARG).  work: litho_tcc_apply_vector_work_bytes(batch, n) = 48 (batch + 1) n^2 device bytes, 8-byte aligned
+ * (0 for a bad argument); less is LITHO_E_WORKSPACE.  n a power of two, 16..4096, batch 1..2^20.  No atomics, fixed summation
+ * order: two calls give the same bits, and so does any split of the batch.  Asynchronous, no allocation, no host wait. */
+size_t litho_tcc_apply_vector_work_bytes(int batch, int n);
+int litho_tcc_apply_vector(const void *q_hat, const float *w_shifted, const void *X, void *Y, int batch, int n, void *work,
+                           size_t work_bytes, void *stream);
+
 /* ---- Mask gradients of Hopkins imaging (csrc/socs_grad.hip; no reference counterpart, checked against tests/socs_grad_oracle.py).
  * With F[q][i] = exp(+2 pi i (i - c)(q - c) / N), c = pn / 2, q, i in [0, pn), the engine's chain at shift (0,0) is L(X) = F X F^T,
  * the coherent fields are E_k = L(phi_k . M) and I = sum_k |E_k|^2.  For a real loss l with G = dl/dI,

@@ -14,6 +14,8 @@ from .contours import (Contours, contourVertices, contoursToGDSII, contoursToLay
 from .socs import SOCSKernels, hopkinsImage, hopkinsIntensity, socsKernels          # noqa: F401
 from .ilt import (ILTResult, hopkinsFields, hopkinsGradient, hopkinsIntensityAD,       # noqa: F401
                   maskSpectrumAdjoint, optimizeMask, postProcessAdjoint)
+from .vector import (sourcePolarization, vectorAbbeIntensity, vectorPupils,            # noqa: F401
+                     vectorSocsKernels)
 from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
@@ -24,4 +26,5 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "imageRegistration", "layoutSites", "measureEPE", "biasLayout", "correctLayout", "LayoutSites", "OPCResult",
            "Contours", "contourVertices", "traceContours", "contoursToLayout", "simplifyContour", "contoursToGDSII", "doseFocusEnvelope",
            "processVariationBand", "SOCSKernels", "socsKernels", "hopkinsIntensity", "hopkinsImage",
-           "hopkinsFields", "hopkinsGradient", "hopkinsIntensityAD", "maskSpectrumAdjoint", "postProcessAdjoint", "optimizeMask", "ILTResult"]
+           "hopkinsFields", "hopkinsGradient", "hopkinsIntensityAD", "maskSpectrumAdjoint", "postProcessAdjoint", "optimizeMask", "ILTResult",
+           "vectorPupils", "sourcePolarization", "vectorSocsKernels", "vectorAbbeIntensity"]

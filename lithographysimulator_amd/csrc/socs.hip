@@ -7,7 +7,8 @@
 // three device entries it needs:
 //   litho_fft2_c2c   the plain (uncentred, unscaled) 2-D DFT, in place, from the line transforms of fft_core.hpp;
 //   litho_tcc_apply  Y = T X for a batch of vectors;
-//   litho_socs_fold  out[g] (+)= sum_k stack[g K + k], the only new kernel on the per-image path.
+//   litho_socs_fold  out[g] (+)= sum_k stack[g K + k], the only new kernel on the per-image path;
+// and, for vector (polarised, high-NA) imaging, litho_vector_pupils and litho_tcc_apply_vector further down.
 // No reference counterpart (the reference images by the Abbe sum alone, imageformation.py:54-67); checked against
 // tests/socs_oracle.py.
 //
@@ -206,6 +207,128 @@ static hipError_t fft2_transposed(float2* data, int batch, int n, int sign, hipS
     return fft_rows(data, (long long)batch * n, n, sign, st);
 }
 
+// ---- vector (polarised, high-NA) imaging: the six planes of a pupil and the vector TCC (include/litho_abbe.h) ----
+// Plane t = 2 c + j of a pupil is Q_cj = P . M_cj: polarisation component j in {x, y} at the mask onto field component
+// c in {x, y, z} at the wafer.  The vector TCC is
+//   T x = sum_c sum_j Q_cj (*) ( sum_j' W_jj' . (Q_cj' (star) x) ),
+// one forward transform of x, six inverse transforms, the 2 x 2 weight mix, six forward transforms, one inverse: 14 per vector.
+static constexpr int VEC_T = 6;
+
+// One thread per grid cell of one pupil plane: factors and defocus phase in double, each component rounded once.
+__global__ __launch_bounds__(256) void k_vector_pupils(const float2* __restrict__ pupil, int pn, double NA, double index,
+                                                       int radiometric, double waves /* index z / wavelength */,
+                                                       float2* __restrict__ out)
+{
+    const size_t cells = (size_t)pn * pn;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= cells) return;
+    const int r = (int)(i / pn), c = (int)(i - (size_t)r * pn);
+    const double a = NA * ((double)(c - pn / 2) * 4.0 / (double)pn) / index;
+    const double b = NA * ((double)(r - pn / 2) * 4.0 / (double)pn) / index;
+    const double s = a * a + b * b;
+    if (!(s < 1.0)) {                                              // evanescent in the image medium: every factor is 0
+#pragma unroll
+        for (int t = 0; t < VEC_T; ++t) out[(size_t)t * cells + i] = make_float2(0.f, 0.f);
+        return;
+    }
+    const double g = sqrt(1.0 - s), d = 1.0 / (1.0 + g);
+    const double m[VEC_T] = {1.0 - a * a * d, -a * b * d, -a * b * d, 1.0 - b * b * d, -a, -b};
+    const double f = radiometric ? 1.0 / sqrt(g) : 1.0;
+    double sn, cs;
+    sincospi(2.0 * waves * (s * d), &sn, &cs);                     // 1 - g = s / (1 + g), without the cancellation
+    const float2 p = pupil[i];
+    const double pr = f * ((double)p.x * cs - (double)p.y * sn), pi = f * ((double)p.x * sn + (double)p.y * cs);
+#pragma unroll
+    for (int t = 0; t < VEC_T; ++t) out[(size_t)t * cells + i] = make_float2((float)(pr * m[t]), (float)(pi * m[t]));
+}
+
+// The three pointwise kernels of litho_tcc_apply_vector.  A thread owns two consecutive complex samples (one 16-byte access
+// per array; buffers are promised 8-byte aligned only) and walks the vectors b = blockIdx.y, blockIdx.y + gridDim.y, ...; what
+// does not depend on b -- the six spectra, the three weights -- is read once and kept in registers.  Every spectrum here is in
+// the TRANSPOSED orientation the transform pairs leave (head of the file), the pupil spectra included, so every access is
+// contiguous.
+typedef float float4c __attribute__((ext_vector_type(4), aligned(8)));
+typedef float float2w __attribute__((ext_vector_type(2), aligned(4)));
+
+__device__ __forceinline__ float4c cmul2(float4c a, float4c b)
+{
+    float4c o;
+    o.x = fmaf(a.x, b.x, -a.y * b.y);
+    o.y = fmaf(a.x, b.y, a.y * b.x);
+    o.z = fmaf(a.z, b.z, -a.w * b.w);
+    o.w = fmaf(a.z, b.w, a.w * b.z);
+    return o;
+}
+
+// U[b][t] = conj(qt[t]) . xt[b], t < 6
+__global__ __launch_bounds__(256) void k_vec_fan_out(const float2* __restrict__ xt, const float2* __restrict__ qt,
+                                                     float2* __restrict__ U, size_t cells, int batch)
+{
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (2 * p >= cells) return;
+    float4c q[VEC_T];
+#pragma unroll
+    for (int t = 0; t < VEC_T; ++t) {
+        q[t] = *reinterpret_cast<const float4c*>(qt + (size_t)t * cells + 2 * p);
+        q[t].y = -q[t].y;
+        q[t].w = -q[t].w;
+    }
+    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+        const float4c x = *reinterpret_cast<const float4c*>(xt + (size_t)b * cells + 2 * p);
+#pragma unroll
+        for (int t = 0; t < VEC_T; ++t)
+            *reinterpret_cast<float4c*>(U + ((size_t)b * VEC_T + t) * cells + 2 * p) = cmul2(x, q[t]);
+    }
+}
+
+// In place on U[b][2 c + j]: (u_c0, u_c1) <- scale (Wxx u_c0 + Wxy u_c1, Wxy u_c0 + Wyy u_c1), c < 3; w = [Wxx, Wyy, Wxy]
+// (natural orientation, as U is here); scale = n^-4, a power of two, goes onto the weights first.
+__global__ __launch_bounds__(256) void k_vec_mix(float2* __restrict__ U, const float* __restrict__ w, size_t cells, int batch,
+                                                 float scale)
+{
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (2 * p >= cells) return;
+    const float2w wxx = *reinterpret_cast<const float2w*>(w + 2 * p) * scale;
+    const float2w wyy = *reinterpret_cast<const float2w*>(w + cells + 2 * p) * scale;
+    const float2w wxy = *reinterpret_cast<const float2w*>(w + 2 * cells + 2 * p) * scale;
+    const float4c fxx = {wxx.x, wxx.x, wxx.y, wxx.y}, fyy = {wyy.x, wyy.x, wyy.y, wyy.y}, fxy = {wxy.x, wxy.x, wxy.y, wxy.y};
+    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+#pragma unroll
+        for (int c = 0; c < VEC_T / 2; ++c) {
+            float4c* u0 = reinterpret_cast<float4c*>(U + ((size_t)b * VEC_T + 2 * c) * cells + 2 * p);
+            float4c* u1 = reinterpret_cast<float4c*>(U + ((size_t)b * VEC_T + 2 * c + 1) * cells + 2 * p);
+            const float4c a = *u0, d = *u1;
+            *u0 = fxx * a + fxy * d;
+            *u1 = fxy * a + fyy * d;
+        }
+    }
+}
+
+// yt[b] = sum_t qt[t] . U[b][t], t ascending, one running sum per sample
+__global__ __launch_bounds__(256) void k_vec_fan_in(const float2* __restrict__ U, const float2* __restrict__ qt,
+                                                    float2* __restrict__ yt, size_t cells, int batch)
+{
+    const size_t p = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (2 * p >= cells) return;
+    float4c q[VEC_T];
+#pragma unroll
+    for (int t = 0; t < VEC_T; ++t) q[t] = *reinterpret_cast<const float4c*>(qt + (size_t)t * cells + 2 * p);
+    for (int b = blockIdx.y; b < batch; b += gridDim.y) {
+        float4c acc = cmul2(*reinterpret_cast<const float4c*>(U + (size_t)b * VEC_T * cells + 2 * p), q[0]);
+#pragma unroll
+        for (int t = 1; t < VEC_T; ++t)
+            acc += cmul2(*reinterpret_cast<const float4c*>(U + ((size_t)b * VEC_T + t) * cells + 2 * p), q[t]);
+        *reinterpret_cast<float4c*>(yt + (size_t)b * cells + 2 * p) = acc;
+    }
+}
+
+static constexpr int VEC_MAX_BATCH = 1 << 20;
+
+static size_t vector_work_bytes(int batch, int n)
+{
+    return (size_t)VEC_T * ((size_t)batch + 1) * (size_t)n * n * sizeof(float2);      // the six spectra, then six planes per vector
+}
+
 }  // namespace litho
 
 extern "C" {
@@ -263,6 +386,75 @@ int litho_socs_fold(const float* stack, int groups, int K, int64_t elems, float*
     hipLaunchKernelGGL(k_socs_fold, dim3((unsigned)blocks, (unsigned)groups), dim3(256), 0, (hipStream_t)stream, stack, K,
                        (long long)elems, out, accumulate ? 1 : 0);
     HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+int litho_vector_pupils(const void* pupil, int planes, int pn, double NA, double index, int radiometric, const double* defocus_nm_host,
+                        double wavelength, void* out, void* stream)
+{
+    using namespace litho;
+    if (!pupil || !out || planes < 1 || planes > 65535 || pn < 16 || pn > 16384 || (pn & 1)) return LITHO_E_ARG;
+    if (!(NA > 0.0) || !(index > 0.0) || !(NA < index) || !(index < 1e6)) return LITHO_E_ARG;
+    if (defocus_nm_host) {
+        if (!(wavelength > 0.0) || !(wavelength < 1e300)) return LITHO_E_ARG;
+        for (int p = 0; p < planes; ++p)
+            if (!(defocus_nm_host[p] > -1e300 && defocus_nm_host[p] < 1e300)) return LITHO_E_ARG;
+    }
+    const size_t cells = (size_t)pn * pn;
+    const dim3 grid((unsigned)((cells + 255) / 256));
+    for (int p = 0; p < planes; ++p) {                              // one launch per plane: its defocus travels as an argument
+        const double waves = defocus_nm_host ? index * defocus_nm_host[p] / wavelength : 0.0;
+        hipLaunchKernelGGL(k_vector_pupils, grid, dim3(256), 0, (hipStream_t)stream, (const float2*)pupil + (size_t)p * cells, pn, NA,
+                           index, radiometric ? 1 : 0, waves, (float2*)out + (size_t)p * VEC_T * cells);
+    }
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+size_t litho_tcc_apply_vector_work_bytes(int batch, int n)
+{
+    using namespace litho;
+    if (batch < 1 || batch > VEC_MAX_BATCH || !fft_size_ok(n)) return 0;
+    return vector_work_bytes(batch, n);
+}
+
+int litho_tcc_apply_vector(const void* q_hat, const float* w_shifted, const void* X, void* Y, int batch, int n, void* work,
+                           size_t work_bytes, void* stream)
+{
+    using namespace litho;
+    if (!q_hat || !w_shifted || !X || !Y || !work || batch < 1 || batch > VEC_MAX_BATCH || !fft_size_ok(n)) return LITHO_E_ARG;
+    const size_t cells = (size_t)n * n, bytes = cells * (size_t)batch * sizeof(float2);
+    const uintptr_t x0 = (uintptr_t)X, y0 = (uintptr_t)Y;
+    if (x0 != y0 && x0 < y0 + bytes && y0 < x0 + bytes) return LITHO_E_ARG;      // Y is X, or does not overlap it
+    if (work_bytes < vector_work_bytes(batch, n)) return LITHO_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    float2* y = (float2*)Y;
+    float2* qt = (float2*)work;                                     // the six pupil spectra, transposed
+    float2* U = qt + (size_t)VEC_T * cells;                         // [batch][6][n][n]
+    HIP_TRY(hipMemcpyAsync(qt, q_hat, (size_t)VEC_T * cells * sizeof(float2), hipMemcpyDeviceToDevice, st));
+    if (x0 != y0) HIP_TRY(hipMemcpyAsync(Y, X, bytes, hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(k_socs_twiddles, dim3(SOCS_MAX_N / 256), dim3(256), 0, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(transpose(qt, VEC_T, n, st));
+    // enough workgroups to fill the device at small n; the vectors beyond gridDim.y are walked inside the thread
+    const unsigned bx = (unsigned)((cells / 2 + 255) / 256);
+    unsigned by = 2048 / bx;
+    if (by < 1) by = 1;
+    if (by > (unsigned)batch) by = (unsigned)batch;
+    const dim3 grid(bx, by);
+    const float scale = 1.0f / ((float)n * (float)n * (float)n * (float)n);
+    // correlation with the six planes: the values at the source points' shifts, per field component and polarisation
+    HIP_TRY(fft2_transposed(y, batch, n, -1, st));
+    hipLaunchKernelGGL(k_vec_fan_out, grid, dim3(256), 0, st, (const float2*)y, (const float2*)qt, U, cells, batch);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(fft2_transposed(U, VEC_T * batch, n, +1, st));
+    hipLaunchKernelGGL(k_vec_mix, grid, dim3(256), 0, st, U, w_shifted, cells, batch, scale);
+    HIP_TRY(hipGetLastError());
+    // convolution with the six planes, summed
+    HIP_TRY(fft2_transposed(U, VEC_T * batch, n, -1, st));
+    hipLaunchKernelGGL(k_vec_fan_in, grid, dim3(256), 0, st, (const float2*)U, (const float2*)qt, y, cells, batch);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(fft2_transposed(y, batch, n, +1, st));
     return LITHO_OK;
 }
 

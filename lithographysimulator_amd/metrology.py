@@ -257,7 +257,7 @@ class OPCResult:
 def correctLayout(polygons, pixelNumber, pixelSize, origin, wavelength, pupil, source, threshold, *, spacing, iterations=6,
                   gain=0.6, maxBias, antialias=16, exposed=True, diffusionLength=0.0, searchRange=8.0,
                   imager: Optional[Callable] = None, epe: Optional[Callable] = None, device=None, model="abbe",
-                  kernels=64) -> OPCResult:
+                  kernels=64, socs=None) -> OPCResult:
     """Model-based optical proximity correction of a Manhattan layout (nanometres; the polygons are the mask's openings):
     edge fragments of at most `spacing` are moved along their normals until the printed contour lies on the target's edges.
     Every iteration: biasLayout -> rasterizeLayout(antialias=) -> Mask(transmission=) -> fraunhofer -> abbeIntensity through
@@ -271,6 +271,8 @@ def correctLayout(polygons, pixelNumber, pixelSize, origin, wavelength, pupil, s
     `model="socs"`: the optical setting is factored once into `kernels` SOCS kernels (socsKernels: Hopkins imaging, an
     approximation unless `kernels` reaches the number of lit source points) and every iteration's image is those K fields
     (hopkinsIntensity) instead of one field per source point.  The default "abbe" is the path described above, call for call.
+    `socs`: a SOCSKernels (socsKernels, or vectorSocsKernels for polarised high-NA imaging) used instead of factoring `pupil`
+    and `source`; with model="socs" only, one plane, and its pn must be the window's (ValueError otherwise).
 
     `imager(polygons) -> image` replaces the raster-to-image steps and `epe(image) -> EPE in nm per site` (NaN where nothing
     is found) the measurement, so the loop itself runs without a GPU on any model; give both or neither."""
@@ -278,6 +280,15 @@ def correctLayout(polygons, pixelNumber, pixelSize, origin, wavelength, pupil, s
         raise ValueError("correctLayout: imager and epe replace the image and its measurement together; give both or neither")
     if model not in ("abbe", "socs"):
         raise ValueError(f"correctLayout: model must be 'abbe' or 'socs'; got {model!r}")
+    if socs is not None:
+        from .socs import SOCSKernels
+        if not isinstance(socs, SOCSKernels):
+            raise TypeError("correctLayout: socs must be a SOCSKernels (socsKernels / vectorSocsKernels)")
+        if model != "socs":
+            raise ValueError("correctLayout: socs= goes with model='socs'")
+        if socs.pn != int(pixelNumber) or socs.stacked:
+            raise ValueError(f"correctLayout: the kernels are {'a stack of ' if socs.stacked else ''}{socs.pn} x {socs.pn}, the "
+                             f"window {int(pixelNumber)} x {int(pixelNumber)}: one plane on the window's grid is needed")
     if not exposed:
         raise ValueError("correctLayout: the loop is defined for exposed features (the polygons are the mask's openings and print "
                          "bright); for exposed=False neither the mask tone nor the step of a site that finds no edge is defined yet")
@@ -294,7 +305,7 @@ def correctLayout(polygons, pixelNumber, pixelSize, origin, wavelength, pupil, s
     biasLayout(target, sites, np.zeros(len(sites)))            # raises for a non-Manhattan layout before any image is made
     if imager is None:
         imager, epe = _gpu_model(pn, ps, origin, wavelength, pupil, source, threshold, antialias, exposed, diffusionLength,
-                                 searchRange, sites, device, model, kernels)
+                                 searchRange, sites, device, model, kernels, socs)
     bias = np.zeros(len(sites))
     history, measured, best = [], [], None
     for it in range(iterations):
@@ -315,7 +326,7 @@ def correctLayout(polygons, pixelNumber, pixelSize, origin, wavelength, pupil, s
 
 
 def _gpu_model(pn, ps, origin, wavelength, pupil, source, threshold, antialias, exposed, diffusionLength, searchRange, sites,
-               device, model="abbe", kernels=64):
+               device, model="abbe", kernels=64, socs=None):
     """(imager, epe) of correctLayout on the HIP path."""
     import torch
 
@@ -334,7 +345,10 @@ def _gpu_model(pn, ps, origin, wavelength, pupil, source, threshold, antialias, 
     cache = PlanCache()
     state = {}
     site_rows = torch.from_numpy(sites.sites_px).to(dev)
-    if model == "socs":
+    if model == "socs" and socs is not None:
+        from .socs import hopkinsIntensity
+        state["socs"] = socs
+    elif model == "socs":
         from .socs import hopkinsIntensity, socsKernels
         if tuple(source.shape) == (pn, pn):
             bitmap = source.to(dev)

@@ -1,0 +1,167 @@
+"""CPU restatement of the vector (polarised, high-NA) imaging definitions (include/litho_abbe.h) in numpy
+float64, written from the definitions and not from the kernels or from lithographysimulator_amd/vector.py.  Nothing in the
+reference images with polarisation, so this file is the parity target of litho_vector_pupils, litho_tcc_apply_vector,
+vectorSocsKernels and vectorAbbeIntensity; it is itself pinned to physics by the two-beam closed form and to the scalar Abbe sum
+by the low-NA limit (tests/test_vector_cpu.py).  TEST INFRASTRUCTURE ONLY.
+
+Pupil grid point (row i, column j): sigma = ((j - pn/2) 4/pn, (i - pn/2) 4/pn).  alpha = NA sigma_x / n, beta = NA sigma_y / n,
+gamma = sqrt(1 - alpha^2 - beta^2); plane t = 2 c + j of a pupil P is Q_cj = P . M_cj, c in (x, y, z), j in (x, y).
+Source point s sits at pixel (r, c) of the weight map with W > 0, row-major, d_s = (r - pn/2, c - pn/2); its coherency is
+degree . e e^T + (1 - degree)/2 . I, with pure states (mu_m, e_m); the rows of the explicit operator are
+a_smc = sqrt(w_s mu_m) roll(e_mx Q_cx + e_my Q_cy, d_s) and T = A^T conj(A), as in socs_oracle."""
+import numpy as np
+import torch
+
+import socs_oracle as SO
+from oracle import abbe_oracle as O
+
+OPTICS = [(0.7, 1.0), (1.35, 1.44)]            # (NA, index of the image medium): dry, and ArF immersion in water
+
+
+def sigma_grid(pn):
+    k = (np.arange(pn, dtype=np.float64) - pn // 2) * 4.0 / pn
+    return np.broadcast_to(k[None, :], (pn, pn)), np.broadcast_to(k[:, None], (pn, pn))          # sigma_x (columns), sigma_y (rows)
+
+
+def cosines(pn, NA, n):
+    """(alpha, beta, gamma, inside): gamma is 1 where alpha^2 + beta^2 >= 1 (those cells are outside)."""
+    sx, sy = sigma_grid(pn)
+    a, b = NA * sx / n, NA * sy / n
+    inside = a * a + b * b < 1.0
+    return a, b, np.sqrt(np.where(inside, 1.0 - a * a - b * b, 1.0)), inside
+
+
+def factors(pn, NA, n, radiometric=False):
+    """M float64 [6,pn,pn], plane t = 2 c + j; zero where alpha^2 + beta^2 >= 1."""
+    a, b, g, inside = cosines(pn, NA, n)
+    M = np.stack([1.0 - a * a / (1.0 + g), -a * b / (1.0 + g), -a * b / (1.0 + g), 1.0 - b * b / (1.0 + g), -a, -b])
+    if radiometric:
+        M = M / np.sqrt(g)
+    return M * inside
+
+
+def defocus_phase(pn, NA, n, z, wavelength):
+    """exp(+2 pi i n z (1 - gamma) / lambda), 1 - gamma evaluated as s / (1 + gamma)."""
+    a, b, g, inside = cosines(pn, NA, n)
+    return np.exp(2j * np.pi * n * z * ((a * a + b * b) / (1.0 + g)) / wavelength) * inside
+
+
+def vector_pupils(P, NA, n, radiometric=False, defocus=None, wavelength=None):
+    """complex128 [6,pn,pn] of one pupil plane and one defocus value (None: no phase)."""
+    P = np.asarray(P, dtype=np.complex128)
+    pn = P.shape[0]
+    Q = P[None] * factors(pn, NA, n, radiometric)
+    return Q * defocus_phase(pn, NA, n, float(defocus), float(wavelength))[None] if defocus is not None else Q
+
+
+def directions(pn, mode):
+    """(e_x, e_y) float64 [pn,pn] of a named mode, or of a pair of numbers (the same direction everywhere, normalised);
+    "unpolarized" has no direction and gets x."""
+    if not isinstance(mode, str):
+        norm = float(np.hypot(mode[0], mode[1]))
+        return np.full((pn, pn), mode[0] / norm), np.full((pn, pn), mode[1] / norm)
+    k = np.arange(pn, dtype=np.float64) - pn // 2
+    phi = np.arctan2(np.broadcast_to(k[:, None], (pn, pn)), np.broadcast_to(k[None, :], (pn, pn)))
+    one, zero = np.ones((pn, pn)), np.zeros((pn, pn))
+    return {"x": (one, zero), "y": (zero, one), "tm": (np.cos(phi), np.sin(phi)), "te": (-np.sin(phi), np.cos(phi)),
+            "unpolarized": (one, zero)}[mode]
+
+
+def coherency(pn, mode, degree=1.0):
+    """(C_xx, C_yy, C_xy) float64 [pn,pn] per source-grid point."""
+    degree = 0.0 if isinstance(mode, str) and mode == "unpolarized" else float(degree)
+    ex, ey = directions(pn, mode)
+    return degree * ex * ex + (1 - degree) / 2, degree * ey * ey + (1 - degree) / 2, degree * ex * ey
+
+
+def weight_maps(W, mode, degree=1.0):
+    """float64 [3,pn,pn] = W . (C_xx, C_yy, C_xy)."""
+    W = np.asarray(W, dtype=np.float64)
+    return np.stack([W * c for c in coherency(W.shape[0], mode, degree)])
+
+
+def pure_states(W, mode, degree=1.0):
+    """Per lit source point, row-major: ((dy, dx), w, [(mu, e_x, e_y)]) -- the eigen-decomposition of its 2 x 2 coherency, states
+    with mu <= 1e-14 dropped."""
+    W = np.asarray(W, dtype=np.float64)
+    cxx, cyy, cxy = coherency(W.shape[0], mode, degree)
+    d, w = SO.source_points(W)
+    out = []
+    for (dy, dx), ws in zip(d.tolist(), w.tolist()):
+        r, c = dy + W.shape[0] // 2, dx + W.shape[0] // 2
+        mu, V = np.linalg.eigh(np.array([[cxx[r, c], cxy[r, c]], [cxy[r, c], cyy[r, c]]]))
+        out.append(((dy, dx), ws, [(float(mu[m]), float(V[0, m]), float(V[1, m])) for m in (1, 0) if mu[m] > 1e-14]))
+    return out
+
+
+def explicit_rows(Q, W, mode, degree=1.0):
+    """R x F: the rows a_smc, s-major, then m, then c."""
+    Q = np.asarray(Q, dtype=np.complex128)
+    rows = []
+    for (dy, dx), ws, states in pure_states(W, mode, degree):
+        for mu, ex, ey in states:
+            for c in range(3):
+                rows.append(np.sqrt(ws * mu) * np.roll(ex * Q[2 * c] + ey * Q[2 * c + 1], (dy, dx), axis=(0, 1)).ravel())
+    return np.stack(rows)
+
+
+def fft_apply(Q, Wmaps, X):
+    """T X by the 14-transform formula in complex128 (torch's transforms on the CPU, numpy in and out); X [..., pn, pn]."""
+    qh = torch.fft.fft2(torch.from_numpy(np.asarray(Q, dtype=np.complex128)))                       # [6,pn,pn]
+    wsh = torch.fft.ifftshift(torch.from_numpy(np.asarray(Wmaps, dtype=np.float64)), dim=(-2, -1))  # xx, yy, xy
+    X = torch.from_numpy(np.asarray(X, dtype=np.complex128))
+    u = torch.fft.ifft2(qh.conj() * torch.fft.fft2(X)[..., None, :, :])                            # [...,6,pn,pn]
+    v = torch.empty_like(u)
+    v[..., 0::2, :, :] = wsh[0] * u[..., 0::2, :, :] + wsh[2] * u[..., 1::2, :, :]
+    v[..., 1::2, :, :] = wsh[2] * u[..., 0::2, :, :] + wsh[1] * u[..., 1::2, :, :]
+    return torch.fft.ifft2((qh * torch.fft.fft2(v)).sum(dim=-3)).numpy()
+
+
+def apply_as_applier(Q, Wmaps):
+    """fft_apply as vectorSocsKernels' `applier`: complex64 torch [J,pn,pn] in and out, the operator itself in float64."""
+    def applier(X):
+        return torch.from_numpy(fft_apply(Q, Wmaps, X.detach().cpu().numpy())).to(torch.complex64)
+    return applier
+
+
+def trace(Q, Wmaps):
+    """sum_jj' (sum W_jj') sum_c <Q_cj', Q_cj>."""
+    Q, s = np.asarray(Q, dtype=np.complex128), np.asarray(Wmaps, dtype=np.float64).sum(axis=(1, 2))
+    gxx, gyy = (np.abs(Q[0::2]) ** 2).sum(), (np.abs(Q[1::2]) ** 2).sum()
+    return float(s[0] * gxx + s[1] * gyy + 2.0 * s[2] * (Q[0::2] * Q[1::2].conj()).sum().real)
+
+
+def abbe_truth(Q, M, W, mode, degree, N):
+    """float64 I = sum_smc |L_N(a_smc . M)|^2 through the closed form of the reference's op chain (oracle.field_closed_form's
+    F A F^T, the six planes of a source point in one batched product)."""
+    Qt = torch.from_numpy(np.asarray(Q, dtype=np.complex128))
+    Mt = torch.as_tensor(M).to(torch.complex128)
+    pn = Mt.shape[0]
+    F = O.centred_dft_matrix(pn, N)
+    out = torch.zeros((pn, pn), dtype=torch.float64)
+    for (dy, dx), ws, states in pure_states(np.asarray(W, dtype=np.float64), mode, degree):
+        E = F @ (torch.roll(Qt, shifts=(dy, dx), dims=(1, 2)) * Mt) @ F.T                           # [6,pn,pn]
+        for mu, ex, ey in states:
+            Ec = ex * E[0::2] + ey * E[1::2]
+            out += ws * mu * (Ec.real ** 2 + Ec.imag ** 2).sum(dim=0)
+    return out
+
+
+# ---- the cases the CPU and the GPU tests share ----------------------------------------------------------------------------------
+_cases = {}
+
+
+def six_points():
+    """(P, W, M, N) at (pn, N) = (32, 64): demo-aberration pupil, 6 strided points of the annular 0.3-0.9 source with grey
+    weights, the Bernoulli mask's spectrum."""
+    if "six" not in _cases:
+        from helpers import DEMO_AB, NA, PS, WL, f16
+        from lithographysimulator_amd.synthetic import bernoulli_mask
+        P = O.pupil_function(f16(DEMO_AB), 32, NA, WL)
+        W = SO.grey_weights(SO.strided_points(O.source_annular(0.3, 0.9, 32), 6))
+        _cases["six"] = (P, W, O.mask_spectrum(bernoulli_mask(32), PS, WL), 64)
+    return _cases["six"]
+
+
+def rank_of(Q, W, mode, degree=1.0):
+    return int(np.linalg.matrix_rank(explicit_rows(Q, W, mode, degree)))
