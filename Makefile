@@ -47,11 +47,11 @@ build/contour.o: $(CSRC)/contour.hip $(CSRC)/engine_common.hpp include/litho_abb
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 # the SOCS set-up transforms run the line FFT of fft_core.hpp: the FFT kernels' flags
-build/socs.o: $(CSRC)/socs.hip $(CSRC)/fft_core.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
+build/socs.o: $(CSRC)/socs.hip $(CSRC)/plane_fft.hpp $(CSRC)/fft_core.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(FFTFLAGS) -c $< -o $@
 # mask gradients: the centred pruned line transforms of the fields and of their adjoint, the same line FFT and flags
-build/socs_grad.o: $(CSRC)/socs_grad.hip $(CSRC)/fft_core.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
+build/socs_grad.o: $(CSRC)/socs_grad.hip $(CSRC)/plane_fft.hpp $(CSRC)/fft_core.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(FFTFLAGS) -c $< -o $@
 build/common.o: $(CSRC)/common.hip $(CSRC)/engine_common.hpp include/litho_abbe.h

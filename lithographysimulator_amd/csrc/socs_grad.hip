@@ -12,7 +12,8 @@
 // once, kept in registers, and pn outputs are written; m = 1 is one centred transform.  L^H is the same code with the other sign.
 //
 // Layout as socs.hip: rows, tiled transpose, rows, tiled transpose -- every global access of a row pass is a contiguous line
-// (thread t of a line owns samples t + T e, fft_core.hpp).  The elementwise products of both directions ride on the first row
+// (thread t of a line owns samples t + T e, fft_core.hpp); the twiddle table, the line geometry, the transpose and the dispatch on
+// the line size are plane_fft.hpp's, shared with socs.hip.  The elementwise products of both directions ride on the first row
 // pass's load (phi . M on the way in, G . E on the way back), the reduction over the batch is one running fp32 sum per element
 // in ascending item order: no atomics, so the result is deterministic and a chunked call gives the chunk-ordered sum.
 // No reference counterpart; checked against tests/socs_grad_oracle.py.
@@ -23,32 +24,9 @@
 
 #include "../../include/litho_abbe.h"
 #include "engine_common.hpp"
-#include "fft_core.hpp"
+#include "plane_fft.hpp"
 
 namespace litho {
-
-static constexpr int GRAD_MAX_N = 4096;
-// exp(+2 pi i k / 4096): the table of socs.hip, same fill, same bits.  The library is built without relocatable device code, so a
-// translation unit cannot name another's __device__ symbols; this is this unit's copy, rewritten by every call on its own stream.
-__device__ float2 g_grad_twiddles[GRAD_MAX_N];
-
-__global__ __launch_bounds__(256) void k_grad_twiddles()
-{
-    const int k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= GRAD_MAX_N) return;
-    double s, c;
-    sincospi(2.0 * (double)k / (double)GRAD_MAX_N, &s, &c);
-    g_grad_twiddles[k] = make_float2((float)c, (float)s);
-}
-
-template <int LOG2P>
-struct LineShape {
-    using F = LineFFT<LOG2P, +1>;
-    static constexpr int L = (F::T >= 64) ? 1 : 64 / F::T;      // lines per workgroup: at least one full wave
-    static constexpr int THREADS = F::T * L;
-    static constexpr size_t LDS_EXCH = (size_t)L * F::LDS_LINE;
-    static constexpr size_t LDS_BYTES = sizeof(float2) * (LDS_EXCH + F::LDS_TW);
-};
 
 // What the row pass multiplies into the line as it loads it.
 enum : int { LOAD_PLAIN = 0, LOAD_TIMES_MASK = 1, LOAD_TIMES_GRAD = 2 };
@@ -73,7 +51,7 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
     const int lt = threadIdx.x % F::T, lg = threadIdx.x / F::T;
     float2* lds = smem + (size_t)lg * F::LDS_LINE;
     typename F::Twiddles tw;
-    F::load_twiddles(tw, g_grad_twiddles, lt, smem + LS::LDS_EXCH, threadIdx.x, LS::THREADS, GRAD_MAX_N / PN);
+    F::load_twiddles(tw, g_twiddles, lt, smem + LS::LDS_EXCH, threadIdx.x, LS::THREADS, FFT_MAX_N / PN);
     const long long line = (long long)blockIdx.x * LS::L + lg;
     const bool active = line < lines;                       // every thread runs the transforms: they hold workgroup barriers
     const long long l = active ? line : 0;
@@ -108,7 +86,7 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
         for (int e = 0; e < 16; ++e) {
             const int n = lt + F::T * e;
             const int s = n < C ? n : n - PN;
-            float2 w = g_grad_twiddles[((s * r) & nmask) << tshift];
+            float2 w = g_twiddles[((s * r) & nmask) << tshift];
             if (SIGN < 0) w.y = -w.y;
             x[e] = r == 0 ? x0[e] : cmul(x0[e], w);
         }
@@ -124,34 +102,8 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
     }
 }
 
-// In-place transpose of n x n complex matrices (grid.z): the workgroup of tile (bi, bj), bi <= bj, swaps it with tile (bj, bi)
-// through LDS.  32 x 32 tiles, rows padded by one sample; 256 threads move 8 tile rows per step (socs.hip's scheme).
-static constexpr int GT_TILE = 32;
-__global__ __launch_bounds__(256) void k_grad_transpose(float2* __restrict__ data, int n)
-{
-    const int bi = blockIdx.y, bj = blockIdx.x;
-    if (bi > bj) return;
-    __shared__ float2 a[GT_TILE][GT_TILE + 1], b[GT_TILE][GT_TILE + 1];
-    float2* mtx = data + (size_t)blockIdx.z * n * n;
-    const int tx = threadIdx.x % GT_TILE, ty = threadIdx.x / GT_TILE;
-    for (int r = ty; r < GT_TILE; r += 256 / GT_TILE) {
-        const int ra = bi * GT_TILE + r, ca = bj * GT_TILE + tx;
-        const int rb = bj * GT_TILE + r, cb = bi * GT_TILE + tx;
-        if (ra < n && ca < n) a[r][tx] = mtx[(size_t)ra * n + ca];
-        if (rb < n && cb < n) b[r][tx] = mtx[(size_t)rb * n + cb];
-    }
-    __syncthreads();
-    for (int r = ty; r < GT_TILE; r += 256 / GT_TILE) {
-        const int ra = bi * GT_TILE + r, ca = bj * GT_TILE + tx;
-        const int rb = bj * GT_TILE + r, cb = bi * GT_TILE + tx;
-        if (ra < n && ca < n) mtx[(size_t)ra * n + ca] = b[tx][r];
-        if (bi != bj && rb < n && cb < n) mtx[(size_t)rb * n + cb] = a[tx][r];
-    }
-}
-
 // grad[i] (+)= sum_b 2 conj(kernels[b][i]) adj[b][i], b ascending, one running fp32 sum per component.  Bandwidth-bound: two
-// complex elements per thread in one 16-byte access (complex64 arrays promise 8-byte alignment only); cells is even.
-typedef float float4c __attribute__((ext_vector_type(4), aligned(8)));
+// complex elements per thread in one 16-byte access (float4c, plane_fft.hpp); cells is even.
 __global__ __launch_bounds__(256) void k_vjp_reduce(const float2* __restrict__ kernels, const float2* __restrict__ adj, int batch,
                                                     long long cells, float2* __restrict__ grad, int accumulate)
 {
@@ -173,15 +125,6 @@ __global__ __launch_bounds__(256) void k_vjp_reduce(const float2* __restrict__ k
     }
 }
 
-static int grad_log2(int n)
-{
-    int l = 0;
-    while ((1 << l) < n) ++l;
-    return (1 << l) == n ? l : -1;
-}
-
-static bool grad_size_ok(int n) { return n >= 16 && n <= GRAD_MAX_N && grad_log2(n) > 0; }
-
 struct RowArgs {
     const float2* src;
     float2* dst;
@@ -192,45 +135,20 @@ struct RowArgs {
     int log2m;
 };
 
-template <int LOG2P, int LOAD>
-static hipError_t launch_rows(const RowArgs& a, int sign, hipStream_t st)
-{
-    using LS = LineShape<LOG2P>;
-    const dim3 grid((unsigned)((a.lines + LS::L - 1) / LS::L));
-    if (sign > 0)
-        hipLaunchKernelGGL((k_centred_rows<LOG2P, +1, LOAD>), grid, dim3(LS::THREADS), LS::LDS_BYTES, st, a.src, a.dst, a.mul_c,
-                           a.mul_r, a.per_group, a.lines, a.log2m);
-    else
-        hipLaunchKernelGGL((k_centred_rows<LOG2P, -1, LOAD>), grid, dim3(LS::THREADS), LS::LDS_BYTES, st, a.src, a.dst, a.mul_c,
-                           a.mul_r, a.per_group, a.lines, a.log2m);
-    return hipGetLastError();
-}
-
 template <int LOAD>
 static hipError_t centred_rows(const RowArgs& a, int pn, int sign, hipStream_t st)
 {
-    switch (grad_log2(pn)) {
-    case 4: return launch_rows<4, LOAD>(a, sign, st);
-    case 5: return launch_rows<5, LOAD>(a, sign, st);
-    case 6: return launch_rows<6, LOAD>(a, sign, st);
-    case 7: return launch_rows<7, LOAD>(a, sign, st);
-    case 8: return launch_rows<8, LOAD>(a, sign, st);
-    case 9: return launch_rows<9, LOAD>(a, sign, st);
-    case 10: return launch_rows<10, LOAD>(a, sign, st);
-    case 11: return launch_rows<11, LOAD>(a, sign, st);
-    case 12: return launch_rows<12, LOAD>(a, sign, st);
-    default: return hipErrorInvalidValue;
-    }
-}
-
-static hipError_t grad_transpose(float2* data, int batch, int n, hipStream_t st)
-{
-    const unsigned tiles = (unsigned)((n + GT_TILE - 1) / GT_TILE);
-    for (int b0 = 0; b0 < batch; b0 += 65535) {                    // grid.z holds at most 65535 matrices
-        const int nb = batch - b0 < 65535 ? batch - b0 : 65535;
-        hipLaunchKernelGGL(k_grad_transpose, dim3(tiles, tiles, (unsigned)nb), dim3(256), 0, st, data + (size_t)b0 * n * n, n);
-    }
-    return hipGetLastError();
+    return for_log2(log2_exact(pn), [&](auto l2) {
+        constexpr int LOG2P = decltype(l2)::value;
+        using LS = LineShape<LOG2P>;
+        if (sign > 0)
+            hipLaunchKernelGGL((k_centred_rows<LOG2P, +1, LOAD>), LS::grid(a.lines), dim3(LS::THREADS), LS::LDS_BYTES, st, a.src, a.dst,
+                               a.mul_c, a.mul_r, a.per_group, a.lines, a.log2m);
+        else
+            hipLaunchKernelGGL((k_centred_rows<LOG2P, -1, LOAD>), LS::grid(a.lines), dim3(LS::THREADS), LS::LDS_BYTES, st, a.src, a.dst,
+                               a.mul_c, a.mul_r, a.per_group, a.lines, a.log2m);
+        return hipGetLastError();
+    });
 }
 
 // data <- L(first-pass product) for sign +1, L^H for sign -1: rows (with the product on the load), transpose, rows, transpose.
@@ -241,17 +159,17 @@ static hipError_t centred2d(const float2* src, float2* data, const float2* mul_c
     const long long lines = (long long)batch * pn;
     hipError_t e = centred_rows<LOAD>(RowArgs{src, data, mul_c, mul_r, per_group, lines, log2m}, pn, sign, st);
     if (e != hipSuccess) return e;
-    e = grad_transpose(data, batch, pn, st);
+    e = transpose(data, batch, pn, st);
     if (e != hipSuccess) return e;
     e = centred_rows<LOAD_PLAIN>(RowArgs{data, data, nullptr, nullptr, 1, lines, log2m}, pn, sign, st);
     if (e != hipSuccess) return e;
-    return grad_transpose(data, batch, pn, st);
+    return transpose(data, batch, pn, st);
 }
 
 // LITHO_OK, or the code of the first size rule broken (litho_fft2_c2c's domain for pn and for N, then N >= pn).
 static int check_sizes(long long batch, int pn, int N)
 {
-    if (batch < 1 || !grad_size_ok(pn) || !grad_size_ok(N)) return LITHO_E_ARG;
+    if (batch < 1 || !fft_size_ok(pn) || !fft_size_ok(N)) return LITHO_E_ARG;
     if (N < pn) return LITHO_E_NSMALL;
     if (batch * pn > INT_MAX) return LITHO_E_ARG;                   // one workgroup per line at the large sizes
     return LITHO_OK;
@@ -268,17 +186,16 @@ int litho_socs_fields(const void* kernels, const void* maskFT, int batch, int pn
     const int rc = check_sizes(batch, pn, N);
     if (rc != LITHO_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(k_grad_twiddles, dim3(GRAD_MAX_N / 256), dim3(256), 0, st);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(fill_twiddles(st));
     HIP_TRY(centred2d<LOAD_TIMES_MASK>((const float2*)kernels, (float2*)fields, (const float2*)maskFT, nullptr, 1, batch, pn,
-                                       grad_log2(N) - grad_log2(pn), +1, st));
+                                       log2_exact(N) - log2_exact(pn), +1, st));
     return LITHO_OK;
 }
 
 size_t litho_socs_vjp_work_bytes(int groups, int K, int pn)
 {
     using namespace litho;
-    if (groups < 1 || K < 1 || !grad_size_ok(pn) || (long long)groups * K * pn > INT_MAX) return 0;
+    if (groups < 1 || K < 1 || !fft_size_ok(pn) || (long long)groups * K * pn > INT_MAX) return 0;
     return (size_t)groups * K * pn * pn * sizeof(float2);
 }
 
@@ -293,9 +210,8 @@ int litho_socs_vjp(const void* kernels, const void* maskFT, const float* gradI, 
     if (work_bytes < litho_socs_vjp_work_bytes(groups, K, pn)) return LITHO_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float2* w = (float2*)work;
-    const int log2m = grad_log2(N) - grad_log2(pn);
-    hipLaunchKernelGGL(k_grad_twiddles, dim3(GRAD_MAX_N / 256), dim3(256), 0, st);
-    HIP_TRY(hipGetLastError());
+    const int log2m = log2_exact(N) - log2_exact(pn);
+    HIP_TRY(fill_twiddles(st));
     // the fields of the batch, then L^H of G . E in place
     HIP_TRY(centred2d<LOAD_TIMES_MASK>((const float2*)kernels, w, (const float2*)maskFT, nullptr, 1, (int)batch, pn, log2m, +1, st));
     HIP_TRY(centred2d<LOAD_TIMES_GRAD>(w, w, nullptr, gradI, K, (int)batch, pn, log2m, -1, st));

@@ -20,20 +20,12 @@ from . import _native as nat
 from . import socs as _socs
 from .socs import SOCSKernels
 
-MAX_N = 4096                      # litho_fft2_c2c's and litho_socs_fields' largest transform
+MAX_N = _socs.MAX_PN              # litho_fft2_c2c's and litho_socs_fields' largest transform: one limit, stated in socs.py
 
 
 def _checked(what, maskFT, socs):
-    """The argument checks hopkinsIntensity makes: (maskFT as contiguous complex64, device)."""
-    from .imageformation import ShapeError
-    if not isinstance(socs, SOCSKernels):
-        raise TypeError(f"{what}: socs must be the SOCSKernels socsKernels returned")
-    pn = socs.pn
-    if not isinstance(maskFT, torch.Tensor) or maskFT.dim() != 2 or tuple(maskFT.shape) != (pn, pn):
-        raise ShapeError(f"maskFT must be [{pn},{pn}] to match the kernels; got {tuple(getattr(maskFT, 'shape', ()))}")
-    dev = nat.require_gpu(maskFT.device)
-    if socs.kernels.device != dev:
-        raise ShapeError(f"the kernels live on {socs.kernels.device}, the mask spectrum on {dev}")
+    """socs._check_socs, and the spectrum as the kernels take it: (maskFT as contiguous complex64, device)."""
+    dev = _socs._check_socs(what, maskFT, socs)
     return maskFT.detach().to(torch.complex64).contiguous(), dev
 
 
@@ -58,27 +50,16 @@ def hopkinsGradient(maskFT, socs, N, gradIntensity, out=None, kernelChunk=None):
     only through the order of the fp32 sum.  `out`: accumulated into when given, as hopkinsIntensity does."""
     from .imageformation import ShapeError
     m, dev = _checked("hopkinsGradient", maskFT, socs)
-    pn, planes, K = socs.pn, socs.planes, socs.K
+    pn, planes = socs.pn, socs.planes
     want = (planes, pn, pn) if socs.stacked else (pn, pn)
     if (not isinstance(gradIntensity, torch.Tensor) or tuple(gradIntensity.shape) != want or gradIntensity.is_complex()
             or gradIntensity.device != dev):
         raise ShapeError(f"gradIntensity must be a real tensor of shape {want} on {dev} (hopkinsIntensity's image); got "
                          f"{getattr(gradIntensity, 'dtype', type(gradIntensity).__name__)} "
                          f"{tuple(getattr(gradIntensity, 'shape', ()))} on {getattr(gradIntensity, 'device', None)}")
-    if kernelChunk is None:
-        kernelChunk = max(1, _socs.STACK_BYTES // (planes * pn * pn * 8))
-    kernelChunk = int(kernelChunk)
-    if kernelChunk < 1:
-        raise ValueError(f"hopkinsGradient: kernelChunk must be >= 1; got {kernelChunk}")
-    given = out is not None
-    if not given:
-        out = torch.empty((pn, pn), dtype=torch.complex64, device=dev)
-    elif (not isinstance(out, torch.Tensor) or out.dtype != torch.complex64 or not out.is_contiguous() or out.device != dev
-          or tuple(out.shape) != (pn, pn)):
-        raise ShapeError(f"out must be a contiguous complex64 tensor of shape {(pn, pn)} on {dev}; got "
-                         f"{getattr(out, 'dtype', type(out).__name__)} {tuple(getattr(out, 'shape', ()))}")
+    size = _socs._kernel_chunk("hopkinsGradient", kernelChunk, socs, 8)
+    out, given = _socs._accumulate_into(out, (pn, pn), torch.complex64, dev)
     G = gradIntensity.detach().to(torch.float32).contiguous()
-    size = min(kernelChunk, K)
     work = None
     for i, (stack, _, k) in enumerate(socs.chunks(size)):
         nbytes = int(nat.lib().litho_socs_vjp_work_bytes(planes, k, pn))

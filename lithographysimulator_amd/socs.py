@@ -15,6 +15,8 @@ fraction sum_k lambda_k / trace T that the kept kernels carry, and nothing promi
 `socsKernels` factors T by subspace iteration (the operator on the device: litho_tcc_apply, four pn^2 transforms per vector
 whatever the number of source points; the J x J eigenproblems in float64 on the host); `hopkinsIntensity` runs the kernels as a
 pupil STACK through the unchanged Abbe engine and folds the K planes (litho_socs_fold)."""
+from functools import partial
+
 import numpy as np
 import torch
 
@@ -191,46 +193,110 @@ def socsKernels(pupilF, lightsource, kernels=64, oversample=16, iterations=2, se
     algebra then runs wherever the pupil lives, CPU included."""
     if not isinstance(pupilF, torch.Tensor) or pupilF.dim() not in (2, 3) or pupilF.shape[-1] != pupilF.shape[-2]:
         raise ValueError(f"socsKernels: pupilF must be [pn,pn] or [planes,pn,pn]; got {tuple(getattr(pupilF, 'shape', ()))}")
-    pn = int(pupilF.shape[-1])
+    pn, stacked = int(pupilF.shape[-1]), pupilF.dim() == 3
+    planes = int(pupilF.shape[0]) if stacked else 1
+
+    def planes_of(W, dev):
+        P = pupilF.detach().to(dtype=torch.complex64).reshape(planes, pn, pn).contiguous()
+        wsh = torch.fft.ifftshift(W).to(torch.float32).to(dev).contiguous()
+        wsum = float(W.sum())
+        for Pp in P:
+            yield Pp, wsum * float((Pp.real.double() ** 2 + Pp.imag.double() ** 2).sum()), partial(_DeviceOperator, Pp, wsh)
+
+    return _factorise("socsKernels", pupilF.device, pn, planes, stacked, lightsource, 1, planes_of, kernels=kernels,
+                      oversample=oversample, iterations=iterations, seed=seed, applier=applier)
+
+
+def _factorise(who, device, pn, planes, stacked, lightsource, rank, planes_of, *, kernels, oversample, iterations, seed, applier):
+    """The driver of socsKernels and vectorSocsKernels (`who` in the messages): the checks, the weight map and its lit points,
+    J = min(kernels + oversample, rank * lit points) with `rank` the caller's bound on rank T per lit point, the appliers, the
+    planes through _factor_plane with seed + p, the SOCSKernels.  The caller's part is `planes_of(W, dev)`, which yields per
+    plane (the support handed to _factor_plane, trace T, a callable that makes the device operator)."""
     if pn < MIN_PN or pn > MAX_PN or pn & (pn - 1):
-        raise ValueError(f"socsKernels: pn must be a power of two, {MIN_PN} ... {MAX_PN}; got {pn}")
+        raise ValueError(f"{who}: pn must be a power of two, {MIN_PN} ... {MAX_PN}; got {pn}")
     kernels, oversample, iterations = int(kernels), int(oversample), int(iterations)
     if kernels < 1 or oversample < 0 or iterations < 1:
-        raise ValueError(f"socsKernels: kernels >= 1, oversample >= 0, iterations >= 1; got {kernels}, {oversample}, {iterations}")
+        raise ValueError(f"{who}: kernels >= 1, oversample >= 0, iterations >= 1; got {kernels}, {oversample}, {iterations}")
     W = _weight_map(lightsource, pn)
     lit = W > 0
     S = int(lit.sum())
     if S == 0:
-        raise ValueError("socsKernels: the source has no lit point")
-    J = min(kernels + oversample, S)
+        raise ValueError(f"{who}: the source has no lit point")
+    J = min(kernels + oversample, rank * S)
     K = min(kernels, J)
-    stacked = pupilF.dim() == 3
-    planes = int(pupilF.shape[0]) if stacked else 1
     if applier is None:
-        dev = nat.require_gpu(pupilF.device)
+        dev = nat.require_gpu(device)
         appliers = None
     else:
-        dev = pupilF.device
+        dev = device
         appliers = list(applier) if isinstance(applier, (list, tuple)) else [applier]
         if len(appliers) != planes:
-            raise ValueError(f"socsKernels: {len(appliers)} appliers for {planes} pupil planes")
-    P = pupilF.detach().to(dtype=torch.complex64).reshape(planes, pn, pn).contiguous()
-    wsh = torch.fft.ifftshift(W).to(torch.float32).to(dev).contiguous()
-    wsum = float(W.sum())
+            raise ValueError(f"{who}: {len(appliers)} appliers for {planes} pupil planes")
     phis, lams, traces, boxes = [], [], [], []
-    for p in range(planes):
-        apply = appliers[p] if appliers is not None else _DeviceOperator(P[p], wsh)
-        phi, lam, box = _factor_plane(P[p], W, lit, J, K, iterations, seed + p, apply, dev)
+    for p, (support, trace, operator) in enumerate(planes_of(W, dev)):
+        apply = appliers[p] if appliers is not None else operator()
+        phi, lam, box = _factor_plane(support, W, lit, J, K, iterations, seed + p, apply, dev)
         phis.append(phi)
         lams.append(lam)
         boxes.append(box)
-        traces.append(wsum * float((P[p].real.double() ** 2 + P[p].imag.double() ** 2).sum()))
+        traces.append(trace)
     trace = torch.tensor(traces, dtype=torch.float64)
     lam = torch.stack(lams)
     captured = lam.sum(dim=1) / trace
+    wsum = float(W.sum())
     if stacked:
         return SOCSKernels(torch.stack(phis), lam, trace, captured, wsum, S, boxes)
     return SOCSKernels(phis[0], lam[0], float(trace[0]), float(captured[0]), wsum, S, boxes)
+
+
+def _check_socs(who, maskFT, socs):
+    """What every consumer of a kernel set checks of `socs` and `maskFT`; returns the device both live on."""
+    from .imageformation import ShapeError
+    if not isinstance(socs, SOCSKernels):
+        raise TypeError(f"{who}: socs must be the SOCSKernels socsKernels returned")
+    pn = socs.pn
+    if not isinstance(maskFT, torch.Tensor) or maskFT.dim() != 2 or tuple(maskFT.shape) != (pn, pn):
+        raise ShapeError(f"maskFT must be [{pn},{pn}] to match the kernels; got {tuple(getattr(maskFT, 'shape', ()))}")
+    dev = nat.require_gpu(maskFT.device)
+    if socs.kernels.device != dev:
+        raise ShapeError(f"the kernels live on {socs.kernels.device}, the mask spectrum on {dev}")
+    return dev
+
+
+def _kernel_chunk(who, kernelChunk, socs, itemsize):
+    """Kernels per chunk: `kernelChunk`, or by default what keeps a stack of `itemsize` bytes per sample under STACK_BYTES."""
+    if kernelChunk is None:
+        kernelChunk = max(1, STACK_BYTES // (socs.planes * socs.pn * socs.pn * itemsize))
+    kernelChunk = int(kernelChunk)
+    if kernelChunk < 1:
+        raise ValueError(f"{who}: kernelChunk must be >= 1; got {kernelChunk}")
+    return min(kernelChunk, socs.K)
+
+
+def _accumulate_into(out, want, dtype, dev):
+    """(out, given): the tensor a result is written to, allocated when `out` is None and accumulated into when it is given."""
+    from .imageformation import ShapeError
+    if out is None:
+        return torch.empty(want, dtype=dtype, device=dev), False
+    name = str(dtype).split(".")[-1]
+    if not isinstance(out, torch.Tensor):
+        raise ShapeError(f"out must be a contiguous {name} tensor of shape {want} on {dev}; got {type(out).__name__}")
+    if out.dtype != dtype or not out.is_contiguous() or out.device != dev or tuple(out.shape) != want:
+        raise ShapeError(f"out must be a contiguous {name} tensor of shape {want} on {dev}; got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}, contiguous={out.is_contiguous()}")
+    return out, True
+
+
+def _stack_and_fold(maskFT, stack, shifts, N, planes, k, out, accumulate, **engine):
+    """out[g] (+)= sum_j |field of stack[g k + j]|^2: the pupil stack [planes * k, pn, pn] through abbeIntensity into a zeroed
+    fp32 stack (`engine`: its plan, options, weights), then litho_socs_fold."""
+    from .imageformation import abbeIntensity
+    pn, dev = int(stack.shape[-1]), out.device
+    fields = torch.zeros((planes * k, pn, pn), dtype=torch.float32, device=dev)
+    abbeIntensity(maskFT, stack, shifts, N, out=fields, **engine)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_socs_fold(nat.ptr(fields), planes, k, pn * pn, nat.ptr(out), 1 if accumulate else 0,
+                                            nat.stream_ptr(dev)), "litho_socs_fold")
 
 
 def hopkinsIntensity(maskFT, socs, N, out=None, options=None, kernelChunk=None):
@@ -241,33 +307,12 @@ def hopkinsIntensity(maskFT, socs, N, out=None, options=None, kernelChunk=None):
     the intermediate stack, chunk * planes * pn^2 * 4 bytes (default: the whole set, or what keeps it under 1 GiB); the result
     depends on it only through the order of the fp32 fold.  `out`: accumulated into when given, as abbeIntensity does.
     `options`: launch-planner options for the engine calls."""
-    from .imageformation import ShapeError, abbeIntensity
-    if not isinstance(socs, SOCSKernels):
-        raise TypeError("hopkinsIntensity: socs must be the SOCSKernels socsKernels returned")
-    pn, planes, K = socs.pn, socs.planes, socs.K
-    if maskFT.dim() != 2 or tuple(maskFT.shape) != (pn, pn):
-        raise ShapeError(f"maskFT must be [{pn},{pn}] to match the kernels; got {tuple(maskFT.shape)}")
-    dev = nat.require_gpu(maskFT.device)
-    if socs.kernels.device != dev:
-        raise ShapeError(f"the kernels live on {socs.kernels.device}, the mask spectrum on {dev}")
-    if kernelChunk is None:
-        kernelChunk = max(1, STACK_BYTES // (planes * pn * pn * 4))
-    kernelChunk = int(kernelChunk)
-    if kernelChunk < 1:
-        raise ValueError(f"hopkinsIntensity: kernelChunk must be >= 1; got {kernelChunk}")
-    want = (planes, pn, pn) if socs.stacked else (pn, pn)
-    given = out is not None
-    if not given:
-        out = torch.empty(want, dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or tuple(out.shape) != want:
-        raise ShapeError(f"out must be a contiguous float32 tensor of shape {want} on {dev}; got {out.dtype} "
-                         f"{tuple(out.shape)} on {out.device}, contiguous={out.is_contiguous()}")
-    for i, (stack, cache, k) in enumerate(socs.chunks(min(kernelChunk, K))):
-        fields = torch.zeros((planes * k, pn, pn), dtype=torch.float32, device=dev)
-        abbeIntensity(maskFT, stack, socs.shifts(), N, out=fields, plan=cache, options=options)
-        with torch.cuda.device(dev):
-            nat.check(nat.lib().litho_socs_fold(nat.ptr(fields), planes, k, pn * pn, nat.ptr(out), 1 if (given or i > 0) else 0,
-                                                nat.stream_ptr(dev)), "litho_socs_fold")
+    dev = _check_socs("hopkinsIntensity", maskFT, socs)
+    pn, planes = socs.pn, socs.planes
+    size = _kernel_chunk("hopkinsIntensity", kernelChunk, socs, 4)
+    out, given = _accumulate_into(out, (planes, pn, pn) if socs.stacked else (pn, pn), torch.float32, dev)
+    for i, (stack, cache, k) in enumerate(socs.chunks(size)):
+        _stack_and_fold(maskFT, stack, socs.shifts(), N, planes, k, out, given or i > 0, plan=cache, options=options)
     return out
 
 

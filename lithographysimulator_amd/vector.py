@@ -20,6 +20,7 @@ their K fields with polarisation included.  The operator on the device is litho_
 engine.  Out of scope: thick-mask polarisation effects, a resist film stack (one homogeneous image medium), TCC interpolation."""
 import ctypes
 import math
+from functools import partial
 
 import numpy as np
 import torch
@@ -201,56 +202,28 @@ def vectorSocsKernels(pupilF, lightsource, NA, polarization="unpolarized", degre
     NA, n = _check_optics(who, NA, mediumIndex)
     zs, as_list = _defocus_list(who, defocus, wavelength)
     pn, pp, planes, stacked = _pupil_planes(who, pupilF, zs, as_list)
-    if pn < _socs.MIN_PN or pn > _socs.MAX_PN or pn & (pn - 1):
-        raise ValueError(f"{who}: pn must be a power of two, {_socs.MIN_PN} ... {_socs.MAX_PN}; got {pn}")
-    kernels, oversample, iterations = int(kernels), int(oversample), int(iterations)
-    if kernels < 1 or oversample < 0 or iterations < 1:
-        raise ValueError(f"{who}: kernels >= 1, oversample >= 0, iterations >= 1; got {kernels}, {oversample}, {iterations}")
-    pol = sourcePolarization(lightsource, polarization, degree)
-    W = _socs._weight_map(lightsource, pn)
-    lit = W > 0
-    S = int(lit.sum())
-    if S == 0:
-        raise ValueError(f"{who}: the source has no lit point")
     pure = not (isinstance(polarization, str) and polarization == "unpolarized") and float(degree) == 1.0
-    J = min(kernels + oversample, (3 if pure else 5) * S)
-    K = min(kernels, J)
-    if applier is None:
-        dev = nat.require_gpu(pupilF.device)
-        appliers = None
-    else:
-        dev = pupilF.device
-        appliers = list(applier) if isinstance(applier, (list, tuple)) else [applier]
-        if len(appliers) != planes:
-            raise ValueError(f"{who}: {len(appliers)} appliers for {planes} pupil planes")
-    if dev.type == "cuda":
-        Q = vectorPupils(pupilF.reshape(pp, pn, pn), NA, n, radiometric, zs if zs is not None else None, wavelength)
-        Q = Q.expand(planes, PLANES, pn, pn) if Q.shape[0] != planes else Q
-    else:
-        P = pupilF.detach().to(torch.complex64).reshape(pp, pn, pn).expand(planes, pn, pn)
-        Q = _host_vector_pupils(P, NA, n, radiometric, zs, wavelength)
-    wsh = torch.fft.ifftshift(pol, dim=(-2, -1)).to(dev).contiguous()
-    sums = pol.to(torch.float64).sum(dim=(1, 2))
-    wsum = float(W.sum())
-    phis, lams, traces, boxes = [], [], [], []
-    for p in range(planes):
-        Qp = Q[p].contiguous()
-        apply = appliers[p] if appliers is not None else _VectorOperator(Qp, wsh, applyBytes)
-        phi, lam, box = _socs._factor_plane((Qp != 0).any(dim=0), W, lit, J, K, iterations, seed + p, apply, dev)
-        phis.append(phi)
-        lams.append(lam)
-        boxes.append(box)
-        q = Qp.to(torch.complex128)
-        gxx = float((q[0::2].abs() ** 2).sum())
-        gyy = float((q[1::2].abs() ** 2).sum())
-        gxy = float((q[0::2] * q[1::2].conj()).sum().real)
-        traces.append(float(sums[0]) * gxx + float(sums[1]) * gyy + 2.0 * float(sums[2]) * gxy)
-    trace = torch.tensor(traces, dtype=torch.float64)
-    lam = torch.stack(lams)
-    captured = lam.sum(dim=1) / trace
-    if stacked:
-        return _socs.SOCSKernels(torch.stack(phis), lam, trace, captured, wsum, S, boxes)
-    return _socs.SOCSKernels(phis[0], lam[0], float(trace[0]), float(captured[0]), wsum, S, boxes)
+
+    def planes_of(W, dev):
+        pol = sourcePolarization(lightsource, polarization, degree)
+        if dev.type == "cuda":
+            Q = vectorPupils(pupilF.reshape(pp, pn, pn), NA, n, radiometric, zs, wavelength)
+            Q = Q.expand(planes, PLANES, pn, pn) if Q.shape[0] != planes else Q
+        else:
+            P = pupilF.detach().to(torch.complex64).reshape(pp, pn, pn).expand(planes, pn, pn)
+            Q = _host_vector_pupils(P, NA, n, radiometric, zs, wavelength)
+        wsh = torch.fft.ifftshift(pol, dim=(-2, -1)).to(dev).contiguous()
+        sxx, syy, sxy = pol.to(torch.float64).sum(dim=(1, 2)).tolist()
+        for Qp in Q:
+            Qp = Qp.contiguous()
+            q = Qp.to(torch.complex128)
+            gxx = float((q[0::2].abs() ** 2).sum())
+            gyy = float((q[1::2].abs() ** 2).sum())
+            gxy = float((q[0::2] * q[1::2].conj()).sum().real)
+            yield (Qp != 0).any(dim=0), sxx * gxx + syy * gyy + 2.0 * sxy * gxy, partial(_VectorOperator, Qp, wsh, applyBytes)
+
+    return _socs._factorise(who, pupilF.device, pn, planes, stacked, lightsource, 3 if pure else 5, planes_of, kernels=kernels,
+                            oversample=oversample, iterations=iterations, seed=seed, applier=applier)
 
 
 def _uniform_states(polarization, degree):
@@ -284,7 +257,7 @@ def vectorAbbeIntensity(maskFT, vectorPupils, shifts, N, polarization="unpolariz
     (`shifts`, `weights`, `plan`, `options` as there) and litho_socs_fold sums them, per plane.  `polarization`: "x", "y",
     "unpolarized" or a pair of numbers (e_x, e_y); "te", "tm" and maps raise ValueError -- a per-point state needs the
     fields, which the engine does not keep (vectorSocsKernels images those).  `out`: accumulated into when given."""
-    from .imageformation import ShapeError, abbeIntensity
+    from .imageformation import ShapeError
     states = _uniform_states(polarization, degree)
     Q = vectorPupils
     if not isinstance(Q, torch.Tensor) or Q.dim() not in (3, 4) or Q.shape[-3] != PLANES or Q.shape[-1] != Q.shape[-2]:
@@ -292,13 +265,7 @@ def vectorAbbeIntensity(maskFT, vectorPupils, shifts, N, polarization="unpolariz
     dev = nat.require_gpu(maskFT.device)
     pn, stacked = int(Q.shape[-1]), Q.dim() == 4
     planes = int(Q.shape[0]) if stacked else 1
-    want = (planes, pn, pn) if stacked else (pn, pn)
-    given = out is not None
-    if not given:
-        out = torch.empty(want, dtype=torch.float32, device=dev)
-    elif out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev or tuple(out.shape) != want:
-        raise ShapeError(f"out must be a contiguous float32 tensor of shape {want} on {dev}; got {out.dtype} "
-                         f"{tuple(out.shape)} on {out.device}, contiguous={out.is_contiguous()}")
+    out, given = _socs._accumulate_into(out, (planes, pn, pn) if stacked else (pn, pn), torch.float32, dev)
     key = (Q.data_ptr(), Q._version, tuple(Q.shape), tuple(states))
     stack = getattr(plan, "_vector_stack", (None, None))
     if stack[0] != key:                                    # a PlanCache keeps the stack it planned for
@@ -307,10 +274,6 @@ def vectorAbbeIntensity(maskFT, vectorPupils, shifts, N, polarization="unpolariz
         stack = (key, eff.reshape(planes * 3 * len(states), pn, pn).contiguous())
         if plan is not None:
             plan._vector_stack = stack
-    k = 3 * len(states)
-    fields = torch.zeros((planes * k, pn, pn), dtype=torch.float32, device=dev)
-    abbeIntensity(maskFT, stack[1], shifts, N, out=fields, plan=plan, options=options, weights=weights)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_socs_fold(nat.ptr(fields), planes, k, pn * pn, nat.ptr(out), 1 if given else 0,
-                                            nat.stream_ptr(dev)), "litho_socs_fold")
+    _socs._stack_and_fold(maskFT, stack[1], shifts, N, planes, 3 * len(states), out, given, plan=plan, options=options,
+                          weights=weights)
     return out
