@@ -11,7 +11,14 @@ socs_oracle.TRUNCATION_RULE and TOL_EIG; gradients socs_grad_oracle's.  Every te
 Measured on an MI355X: planes 5.2e-8 ... 5.9e-8 relative (bound 2.4e-7); operator 1.01 ... 1.35 of the complex64 formula's own
 error (bound 4), in place, a second call and chunks of one vector equal bit for bit; full-rank images max 3.4e-7 ... 1.5e-6, l2
 1.6e-7 ... 6.4e-7 (bounds 2e-5, 5e-6), captured within 3e-7 of 1; vectorAbbeIntensity 2.1e-7 ... 3.3e-7 max; truncated K 64 of 1140:
-residual 1.149 lambda_65 (bound 1.5); gradient 2.3e-7 max.  The whole file takes five seconds."""
+residual 1.149 lambda_65 (bound 1.5); gradient 2.3e-7 max.  Planes with cells exactly on alpha^2 + beta^2 = 1 (NA 0.72 / 1.44 at
+pn 64, 0.5 / 1 at pn 32): 5.6e-8 ... 5.9e-8, the two boundary cells exact zeros, everything finite.  vectorAbbeIntensity on a
+[3,6,pn,pn] stack 2.2e-7 ... 2.8e-7 max, 1.5e-7 ... 1.9e-7 l2 per plane (unpolarised and 45 degrees at degree 0.5), plane 1 equal bit
+for bit to the unstacked call; "y" 1.9e-7 max, 0.136 of the maximum (6,800 x the tolerance) away from "x"; with a PlanCache the
+second call, the call after a change of polarisation and the call after Qd.mul_(0.5) equal the calls without a plan bit for
+bit, the last exactly a quarter of the one before.  Polarisation as a pair of maps (vector_oracle.twisted_maps, degree 0.7):
+K 30, max 5.3e-7, l2 3.7e-7, captured within 3e-7 of 1.  The operator at every size class and with walking batches:
+test_gpu_vector_sizes.py.  The whole file takes six seconds."""
 import ctypes
 
 import numpy as np
@@ -96,6 +103,34 @@ def test_vector_pupils_against_the_oracle(L, nat, dev, pn):
         _planes_check(f"pn {pn} stack plane {i}", got[i], VO.vector_pupils(pupils[name].numpy().astype(np.complex128), *WATER, True, z, WL))
 
 
+@pytest.mark.parametrize("na,n,pn", [(0.72, 1.44, 64), (0.5, 1.0, 32)])
+def test_vector_pupils_on_the_evanescent_boundary(L, dev, na, n, pn):
+    """Two further cases of the test above, kept apart because their optics are not VO.OPTICS: NA sigma / n is exactly +-1 at
+    the grid edge (0.72 . 2 = 1.44 exactly in binary64), so alpha^2 + beta^2 is exactly 1.0 at cells (pn/2, 0) and (0, pn/2),
+    where `!(s < 1.0)` decides between an exact zero and 1 / sqrt(0).  The smallest gamma inside is 0.054 and 0.153, so
+    1 / sqrt(gamma) stays below 4.4 and the bound of _planes_check holds unchanged.
+    Only these exactly representable cases: NA 0.8, n 1.0, pn 64 puts 8 further cells within 1e-12 of the boundary, where the
+    compiler's contraction of a*a + b*b may legitimately classify a cell differently from numpy -- a test of rounding, not of
+    the kernel."""
+    a, b, gamma, inside = VO.cosines(pn, na, n)
+    on = (a * a + b * b) == 1.0
+    assert int(on.sum()) == 2 and bool(on[pn // 2, 0]) and bool(on[0, pn // 2]) and not inside[on].any()
+    print(f"NA {na} n {n} pn {pn}: 2 cells with alpha^2 + beta^2 == 1.0 exactly, smallest gamma inside {gamma[inside].min():.3f}")
+    g = torch.Generator().manual_seed(pn)
+    P = torch.view_as_complex(torch.randn((pn, pn, 2), generator=g, dtype=torch.float32) + 0.1)
+    assert bool((P != 0).all())
+    p = P.numpy().astype(np.complex128)
+    for rad in (False, True):
+        got = L.vectorPupils(P.to(dev), na, n, rad)
+        assert bool(torch.isfinite(torch.view_as_real(got)).all())
+        assert not got.cpu()[:, torch.from_numpy(on)].any()                                          # exact zeros, all six planes
+        _planes_check(f"pn {pn} random NA {na} n {n} radiometric {rad}", got, VO.vector_pupils(p, na, n, rad))
+        stack = L.vectorPupils(P.to(dev), na, n, rad, defocus=[-100.0, 100.0], wavelength=WL)
+        assert bool(torch.isfinite(torch.view_as_real(stack)).all()) and not stack.cpu()[:, :, torch.from_numpy(on)].any()
+        for i, z in enumerate((-100.0, 100.0)):
+            _planes_check(f"pn {pn} random NA {na} n {n} radiometric {rad} z {z:+.0f}", stack[i], VO.vector_pupils(p, na, n, rad, z, WL))
+
+
 def test_vector_pupils_argument_errors(nat, dev):
     pn = 16
     P = torch.ones((pn, pn), dtype=torch.complex64, device=dev)
@@ -115,16 +150,7 @@ def test_vector_pupils_argument_errors(nat, dev):
 
 
 # ---- 2. litho_tcc_apply_vector ---------------------------------------------------------------------------------------------------
-def _formula64(Q, maps, X):
-    """The 14-transform formula in torch CPU complex64: the floor of the bound.  The inverse transforms are taken unscaled and
-    their n^-4, a power of two, goes onto the weight maps, where the kernel puts it (as test_gpu_tcc_sizes.py does)."""
-    n = Q.shape[-1]
-    qh, wsh = torch.fft.fft2(Q), torch.fft.ifftshift(maps, dim=(-2, -1)) * (1.0 / float(n) ** 4)
-    u = torch.fft.ifft2(qh.conj() * torch.fft.fft2(X)[:, None], norm="forward")
-    v = torch.empty_like(u)
-    v[:, 0::2] = wsh[0] * u[:, 0::2] + wsh[2] * u[:, 1::2]
-    v[:, 1::2] = wsh[2] * u[:, 0::2] + wsh[1] * u[:, 1::2]
-    return torch.fft.ifft2((qh * torch.fft.fft2(v)).sum(dim=1), norm="forward").numpy()
+_formula64 = VO.formula64        # the floor of the bound, shared with test_gpu_vector_sizes.py
 
 
 def _device_apply(nat, dev, qh, wsh, X, Y, work=None, work_bytes=None):
@@ -189,23 +215,9 @@ def test_tcc_apply_vector_against_the_explicit_operator(L, nat, dev, name, batch
     assert bool((keep == 3.0).all()) and int(torch.count_nonzero(torch.view_as_real(both))) == 0
 
 
-def _random_setting(n):
-    """Six random complex planes inside an ellipse off the grid centre and three weight maps inside an off-centre disc (W_xx,
-    W_yy >= 0, |W_xy| below both): nothing is symmetric under transposition, nor under an exchange of planes."""
-    g = torch.Generator().manual_seed(31 * n)
-    r, c = torch.meshgrid(torch.arange(n, dtype=torch.float64), torch.arange(n, dtype=torch.float64), indexing="ij")
-    ellipse = ((r - 0.44 * n) / (0.30 * n)) ** 2 + ((c - 0.57 * n) / (0.17 * n)) ** 2 <= 1.0
-    disc = (r - 0.58 * n) ** 2 + (c - 0.39 * n) ** 2 <= (0.21 * n) ** 2
-    Q = (torch.view_as_complex(torch.randn((6, n, n, 2), generator=g, dtype=torch.float32)) * ellipse).contiguous()
-    w = torch.rand((3, n, n), generator=g, dtype=torch.float32)
-    maps = torch.stack([1.0 + w[0], 0.5 + w[1], w[2] - 0.5]) * disc
-    X = torch.view_as_complex(torch.randn((1, n, n, 2), generator=g, dtype=torch.float32))
-    return Q, maps.contiguous(), X
-
-
 @pytest.mark.parametrize("n", [16, 1024])
 def test_tcc_apply_vector_at_the_smallest_and_a_multi_pass_size(nat, dev, n):
-    Q, maps, X = _random_setting(n)
+    Q, maps, X = VO.random_setting(n)
     want = VO.fft_apply(Q.numpy(), maps.numpy(), X.numpy())
     floor = _rel(_formula64(Q, maps, X), want)
     moved = _rel(VO.fft_apply(Q.numpy().transpose(0, 2, 1), maps.numpy(), X.numpy()), want)        # the inputs can tell a transpose
@@ -234,7 +246,10 @@ def test_tcc_apply_vector_refusals(nat, dev):
         a = list(args)
         a[i] = bad
         assert f(*a) == nat.E_ARG, (i, bad)
-    for batch, size in ((0, n), (1, 8), (1, 48), (1, 8192)):
+    a = list(args)
+    a[4] = (1 << 20) + 1                                                       # one vector more than the entry takes
+    assert f(*a) == nat.E_ARG
+    for batch, size in ((0, n), (1, 8), (1, 48), (1, 8192), ((1 << 20) + 1, n)):
         assert lib.litho_tcc_apply_vector_work_bytes(batch, size) == 0
     torch.cuda.synchronize()
     assert bool((X == 1).all()) and bool((Y == 2).all()) and not work.any()
@@ -353,6 +368,94 @@ def test_vector_abbe_intensity(L, dev, pn, N):
             hop = L.hopkinsIntensity(mft, k, N)
             print(f"  {mode}: full-rank Hopkins K {rank}, captured {k.captured:.8f}")
             _check(f"  {mode}: full-rank Hopkins vs vectorAbbeIntensity", hop, images[mode].cpu().double())
+
+
+def test_vector_abbe_intensity_plane_stack(L, dev):
+    """vectorPupils [3,6,pn,pn] through vectorAbbeIntensity: planes x 3 (pure) or planes x 6 (mixed) effective pupils reach
+    litho_socs_fold in the group-major order [planes, states, 3]."""
+    pn, N = 32, 64
+    mft, pf, sel, w, W = _strided_problem(L, dev, pn, N)
+    zs = [-100.0, 0.0, 100.0]
+    Qd = L.vectorPupils(pf, *WATER, True, defocus=zs, wavelength=WL)
+    assert tuple(Qd.shape) == (3, 6, pn, pn)
+    flat = L.vectorPupils(pf, *WATER, True)
+    assert torch.equal(Qd[1], flat)                                            # z = 0: the phase factor is exactly 1
+    Qs = [VO.vector_pupils(pf.cpu().numpy(), *WATER, True, z, WL) for z in zs]
+    for mode, degree in (("unpolarized", 1.0), ((1.0, 1.0), 0.5)):
+        got = L.vectorAbbeIntensity(mft, Qd, sel, N, polarization=mode, degree=degree, weights=w)
+        assert tuple(got.shape) == (3, pn, pn)
+        for i, z in enumerate(zs):
+            _check(f"stack {mode} degree {degree} plane {i} z {z:+.0f}: vectorAbbeIntensity vs float64 truth", got[i],
+                   VO.abbe_truth(Qs[i], mft.cpu(), W.cpu().numpy(), mode, degree, N))
+        # The effective pupils of plane 1 are the same bits as those of the unstacked call, and every plane's fp32 sum runs
+        # over the source points in list order; only a launch plan that splits the 18 items of the stack differently from the
+        # 6 of the single plane could reorder that sum, and then by roundings of the sum alone.
+        single = L.vectorAbbeIntensity(mft, flat, sel, N, polarization=mode, degree=degree, weights=w)
+        same, e = torch.equal(got[1], single), rel_max(got[1], single)
+        print(f"stack {mode} degree {degree}: plane 1 {'==' if same else '!='} the unstacked call at z = 0 (max {e:.2e})")
+        assert same or e <= 1e-6
+        acc = torch.ones_like(got)
+        assert L.vectorAbbeIntensity(mft, Qd, sel, N, polarization=mode, degree=degree, weights=w, out=acc) is acc
+        assert rel_max(acc - 1.0, got) < 1e-5
+
+
+def test_vector_abbe_intensity_y(L, dev):
+    pn, N = 32, 64
+    mft, pf, sel, w, W = _strided_problem(L, dev, pn, N)
+    Qd = L.vectorPupils(pf, *WATER, True)
+    Q = VO.vector_pupils(pf.cpu().numpy(), *WATER, True)
+    y = L.vectorAbbeIntensity(mft, Qd, sel, N, polarization="y", weights=w)
+    _check("y: vectorAbbeIntensity vs float64 truth", y, VO.abbe_truth(Q, mft.cpu(), W.cpu().numpy(), "y", 1.0, N))
+    x = L.vectorAbbeIntensity(mft, Qd, sel, N, polarization="x", weights=w)
+    apart = rel_max(y, x)
+    print(f"y differs from x by {apart:.2e} of the maximum ({apart / TOL_IMAGE_MAX:.0f} x the tolerance)")
+    assert apart > 100 * TOL_IMAGE_MAX                                          # a swapped index cannot pass
+
+
+def test_vector_abbe_intensity_with_a_plan(L, dev):
+    """One PlanCache: the effective-pupil stack is kept while (data_ptr, _version, shape, states) stay, and rebuilt when the
+    polarisation changes or the planes are written in place."""
+    pn, N = 32, 64
+    mft, pf, sel, w, W = _strided_problem(L, dev, pn, N)
+    Qd = L.vectorPupils(pf, *WATER, True)
+    Q = VO.vector_pupils(pf.cpu().numpy(), *WATER, True)
+    truth = {m: VO.abbe_truth(Q, mft.cpu(), W.cpu().numpy(), m, 1.0, N) for m in ("x", "y")}
+    plan = L.PlanCache()
+    first = L.vectorAbbeIntensity(mft, Qd, sel, N, polarization="x", weights=w, plan=plan)
+    kept = plan._vector_stack[1]
+    second = L.vectorAbbeIntensity(mft, Qd, sel, N, polarization="x", weights=w, plan=plan)
+    assert torch.equal(first, second) and plan._vector_stack[1] is kept
+    _check("plan, x: vs float64 truth", first, truth["x"])
+    other = L.vectorAbbeIntensity(mft, Qd, sel, N, polarization="y", weights=w, plan=plan)       # same shape, other states
+    assert plan._vector_stack[1] is not kept
+    _check("plan, then y with the same cache: vs float64 truth", other, truth["y"])
+    free = {"x": L.vectorAbbeIntensity(mft, Qd, sel, N, polarization="x", weights=w),
+            "y": L.vectorAbbeIntensity(mft, Qd, sel, N, polarization="y", weights=w)}
+    version, kept = Qd._version, plan._vector_stack[1]
+    Qd.mul_(0.5)                                                               # same address and shape, _version moves
+    assert Qd._version != version
+    scaled = L.vectorAbbeIntensity(mft, Qd, sel, N, polarization="y", weights=w, plan=plan)
+    assert plan._vector_stack[1] is not kept
+    _check("plan, y after Qd.mul_(0.5): a quarter of the earlier image", scaled, other.cpu().double() / 4)
+    _check("plan, y after Qd.mul_(0.5): vs float64 truth / 4", scaled, truth["y"] / 4)
+    free_scaled = L.vectorAbbeIntensity(mft, Qd, sel, N, polarization="y", weights=w)
+    for tag, a, b in (("first", first, free["x"]), ("second", second, free["x"]), ("other polarisation", other, free["y"]),
+                      ("scaled", scaled, free_scaled)):
+        _check(f"plan, {tag}: vs the call without a plan", a, b.cpu().double())
+
+
+# ---- 4b. polarisation given as a pair of maps ---------------------------------------------------------------------------------------
+def test_full_rank_parity_with_polarisation_maps(L, dev):
+    """vector_oracle.twisted_maps on the six points: angle 2 phi + 0.3, un-normalised lengths, degree 0.7 -- a mixed state that
+    no named mode expresses, imaged through the kernels and compared with the float64 vector Abbe sum."""
+    P, W, M, N = VO.six_points()
+    ex, ey = VO.twisted_maps(32)
+    k, Q, rank = _full_rank(L, dev, ("six", WATER, "maps", 0.7), P, W, WATER, (ex, ey), 0.7)
+    assert k.K == rank == 30 and k.lit_points == 6
+    got = L.hopkinsIntensity(M.to(dev), k, N)
+    print(f"map pair degree 0.7: K {rank}, captured {k.captured:.8f}, box {k.boxes[0]}")
+    _check("  hopkins vs float64 vector Abbe", got, VO.abbe_truth(Q, M, W.numpy(), (ex, ey), 0.7, N))
+    assert abs(k.captured - 1.0) < 1e-5
 
 
 # ---- 5. through focus -------------------------------------------------------------------------------------------------------------

@@ -55,8 +55,15 @@ def vector_pupils(P, NA, n, radiometric=False, defocus=None, wavelength=None):
 
 
 def directions(pn, mode):
-    """(e_x, e_y) float64 [pn,pn] of a named mode, or of a pair of numbers (the same direction everywhere, normalised);
-    "unpolarized" has no direction and gets x."""
+    """(e_x, e_y) float64 [pn,pn] of a named mode, of a pair of numbers (the same direction everywhere, normalised) or of a
+    pair of real [pn,pn] arrays (normalised per point; where both vanish the direction is arbitrary and stays zero -- only lit
+    points matter); "unpolarized" has no direction and gets x."""
+    if not isinstance(mode, str) and np.ndim(mode[0]) == 2:
+        ex, ey = np.asarray(mode[0], dtype=np.float64), np.asarray(mode[1], dtype=np.float64)
+        assert ex.shape == ey.shape == (pn, pn)
+        norm = np.hypot(ex, ey)
+        norm = np.where(norm > 0, norm, 1.0)
+        return ex / norm, ey / norm
     if not isinstance(mode, str):
         norm = float(np.hypot(mode[0], mode[1]))
         return np.full((pn, pn), mode[0] / norm), np.full((pn, pn), mode[1] / norm)
@@ -115,6 +122,45 @@ def fft_apply(Q, Wmaps, X):
     v[..., 0::2, :, :] = wsh[0] * u[..., 0::2, :, :] + wsh[2] * u[..., 1::2, :, :]
     v[..., 1::2, :, :] = wsh[2] * u[..., 0::2, :, :] + wsh[1] * u[..., 1::2, :, :]
     return torch.fft.ifft2((qh * torch.fft.fft2(v)).sum(dim=-3)).numpy()
+
+
+def formula64(Q, maps, X):
+    """The 14-transform formula in torch CPU complex64: the floor of the operator's bound.  The inverse transforms are taken
+    unscaled and their n^-4, a power of two, goes onto the weight maps, where the kernel puts it (as test_gpu_tcc_sizes.py does)."""
+    n = Q.shape[-1]
+    qh, wsh = torch.fft.fft2(Q), torch.fft.ifftshift(maps, dim=(-2, -1)) * (1.0 / float(n) ** 4)
+    u = torch.fft.ifft2(qh.conj() * torch.fft.fft2(X)[:, None], norm="forward")
+    v = torch.empty_like(u)
+    v[:, 0::2] = wsh[0] * u[:, 0::2] + wsh[2] * u[:, 1::2]
+    v[:, 1::2] = wsh[2] * u[:, 0::2] + wsh[1] * u[:, 1::2]
+    return torch.fft.ifft2((qh * torch.fft.fft2(v)).sum(dim=1), norm="forward").numpy()
+
+
+def random_setting(n, batch=1):
+    """(Q complex64 [6,n,n], maps float32 [3,n,n], X complex64 [batch,n,n]), seeded on the CPU: six random complex planes inside
+    an ellipse off the grid centre and three weight maps inside an off-centre disc (W_xx != W_yy, both >= 0, W_xy of both signs
+    and below both): nothing is symmetric under transposition, nor under an exchange of the polarisation index.  The first
+    vector is drawn on its own and the others after it, so Q, maps and X[0] do not depend on `batch`."""
+    g = torch.Generator().manual_seed(31 * n)
+    r, c = torch.meshgrid(torch.arange(n, dtype=torch.float64), torch.arange(n, dtype=torch.float64), indexing="ij")
+    ellipse = ((r - 0.44 * n) / (0.30 * n)) ** 2 + ((c - 0.57 * n) / (0.17 * n)) ** 2 <= 1.0
+    disc = (r - 0.58 * n) ** 2 + (c - 0.39 * n) ** 2 <= (0.21 * n) ** 2
+    Q = (torch.view_as_complex(torch.randn((6, n, n, 2), generator=g, dtype=torch.float32)) * ellipse).contiguous()
+    w = torch.rand((3, n, n), generator=g, dtype=torch.float32)
+    maps = torch.stack([1.0 + w[0], 0.5 + w[1], w[2] - 0.5]) * disc
+    X = torch.randn((1, n, n, 2), generator=g, dtype=torch.float32)
+    if batch > 1:
+        X = torch.cat([X, torch.randn((batch - 1, n, n, 2), generator=g, dtype=torch.float32)])
+    return Q, maps.contiguous(), torch.view_as_complex(X)
+
+
+def twisted_maps(pn, seed=11):
+    """A polarisation given as a pair of maps that no named mode expresses: angle 2 phi + 0.3 (phi the azimuth of the source
+    point, as in `directions`), lengths un-normalised in (0.5, 2).  float64 numpy [pn,pn] each."""
+    k = np.arange(pn, dtype=np.float64) - pn // 2
+    theta = 2.0 * np.arctan2(np.broadcast_to(k[:, None], (pn, pn)), np.broadcast_to(k[None, :], (pn, pn))) + 0.3
+    length = 0.5 + 1.5 * np.random.default_rng(seed).uniform(0.001, 0.999, (pn, pn))
+    return length * np.cos(theta), length * np.sin(theta)
 
 
 def apply_as_applier(Q, Wmaps):
