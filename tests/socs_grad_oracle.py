@@ -16,7 +16,20 @@ below a quarter of helpers.TOL_IMAGE_MAX / TOL_IMAGE_L2 the project's image tole
 measured error (the factor covers the different summation order).  Measured:
     max|dg| / max|g| <= 7.9e-7 and ||dg||_2 / ||g||_2 <= 7.5e-7 over all of them (the largest at pn 1024 and at (16, 512)),
 both below a quarter of helpers.TOL_IMAGE_MAX (2e-5 / 4 = 5e-6) and TOL_IMAGE_L2 (5e-6 / 4 = 1.25e-6), so the gradient is held
-to the project's image tolerances themselves."""
+to the project's image tolerances themselves.
+
+Loop tolerances.  The same rule for optimizeMask's device model (tests/test_gpu_ilt.py): `model(..., dtype=complex64)` is this
+file's whole chain, transmission -> image and gradient on the image -> gradient on the transmission, with the same dense matrices
+cast to complex64 / float32, and test_socs_grad_cpu.py::test_fp32_floor_of_the_loop_chain compares it with the float64 chain on
+exactly the device tests' cases (ILT_DEVICE_CASES: pn 32 / 64, three epsilon regimes, one plane and two, gain 1 / 2.7 and 1;
+ILT_LOOP_CASES: the one-iteration loop with four kinds of mask).  Measured:
+    image    max|dI| / max I <= 5.7e-7, ||dI||_2 / ||I||_2 <= 3.6e-7;   adjoint  max 5.3e-7, l2 4.2e-7,
+all under a quarter of helpers.TOL_IMAGE_MAX / TOL_IMAGE_L2, so the device model's image and adjoint are held to those.  Through
+the loop the resist sigmoid multiplies a relative image error by about a_r . threshold = 25, so the image tolerances do not
+transfer; there the bound is four times the floor of the loop itself, complex64 chain against float64 chain:
+    losses[0], losses[1]  relative 1.9e-7  -> bound 7.6e-7;   (theta0 - theta1) / step, peak 1  absolute 5.8e-6  -> bound 2.3e-5
+(the update's floor holds eps32 max|theta| / step = 2e-6 from the fp32 subtraction alone; step 1 / 16).  A structural error -- a missing gain,
+a dropped plane, a count over one plane, a missing conjugate -- shows at order 0.1 ... 1 in all of them."""
 import math
 
 import numpy as np
@@ -33,6 +46,35 @@ TOL_GRAD_MAX, TOL_GRAD_L2 = TOL_IMAGE_MAX, TOL_IMAGE_L2
 # stages of these sizes is about 1.5e-6, which leaves a seven-fold margin; a structural error (a missing shift, a transposed R, a
 # wrong pad side) shows at order 1
 TOL_ADJOINT = 1e-5
+
+
+# Loop tolerances (see the head of the file): the measured complex64 floors of model(...) and of the one-iteration loop on it
+ILT_FLOOR_IMAGE_MAX, ILT_FLOOR_IMAGE_L2 = 5.7e-7, 3.6e-7
+ILT_FLOOR_ADJOINT_MAX, ILT_FLOOR_ADJOINT_L2 = 5.3e-7, 4.2e-7
+ILT_FLOOR_LOSS, ILT_FLOOR_UPDATE = 1.9e-7, 5.8e-6
+
+
+def _bound(floor, tol):
+    return tol if floor < tol / 4 else 4 * floor
+
+
+TOL_ILT_IMAGE_MAX, TOL_ILT_IMAGE_L2 = _bound(ILT_FLOOR_IMAGE_MAX, TOL_IMAGE_MAX), _bound(ILT_FLOOR_IMAGE_L2, TOL_IMAGE_L2)
+TOL_ILT_ADJOINT_MAX, TOL_ILT_ADJOINT_L2 = _bound(ILT_FLOOR_ADJOINT_MAX, TOL_IMAGE_MAX), _bound(ILT_FLOOR_ADJOINT_L2, TOL_IMAGE_L2)
+TOL_ILT_LOSS, TOL_ILT_UPDATE = 4 * ILT_FLOOR_LOSS, 4 * ILT_FLOOR_UPDATE
+
+
+def _c128(a):
+    return torch.as_tensor(a).detach().cpu().to(C128)
+
+
+def rel_max(a, b):
+    """max|a - b| / max|b| in float64, real or complex."""
+    return float((_c128(a) - _c128(b)).abs().max() / _c128(b).abs().max())
+
+
+def rel_l2(a, b):
+    """||a - b||_2 / ||b||_2 in float64, real or complex."""
+    return float(torch.linalg.norm(_c128(a) - _c128(b)) / torch.linalg.norm(_c128(b)))
 
 
 def _k4(kernels):
@@ -153,20 +195,71 @@ def epsilon_regimes(pn):
     return out
 
 
-def model(kernels, pn, epsilon, N, gain=1.0):
-    """(imager, adjoint) for optimizeMask on this file's float64 chain: transmission -> B t B^T -> gain . intensity -> Pp . Pp^T."""
-    B, Pp = spectrum_matrix(pn, epsilon, N), postprocess_matrix(pn, epsilon)
+def model(kernels, pn, epsilon, N, gain=1.0, dtype=C128):
+    """(imager, adjoint) for optimizeMask on this file's float64 chain: transmission -> B t B^T -> gain . intensity -> Pp . Pp^T.
+    `dtype` complex64 evaluates the same chain with the same dense matrices cast to complex64 / float32 in torch's CPU single
+    precision: the fp32 floor of the whole chain ("Loop tolerances" below), as gradient(..., dtype=complex64) is the formula's."""
+    real = torch.float64 if dtype == C128 else torch.float32
+    B, Pp = spectrum_matrix(pn, epsilon, N).to(dtype), postprocess_matrix(pn, epsilon).to(real)
     state = {}
 
     def imager(t):
-        state["M"] = B @ torch.as_tensor(t).to(C128) @ B.T
-        return Pp @ (gain * intensity(kernels, state["M"], N)) @ Pp.T
+        state["M"] = B @ torch.as_tensor(t).to(dtype) @ B.T
+        E = fields(kernels, state["M"], N, dtype=dtype)
+        return Pp @ (gain * (E.real ** 2 + E.imag ** 2).sum(dim=-3)) @ Pp.T
 
     def adjoint(g):
-        graw = gain * (Pp.T @ torch.as_tensor(g).double() @ Pp)
-        return B.conj().T @ gradient(kernels, state["M"], N, graw) @ B.conj()
+        graw = gain * (Pp.T @ torch.as_tensor(g).to(real) @ Pp)
+        return B.conj().T @ gradient(kernels, state["M"], N, graw, dtype=dtype) @ B.conj()
 
     return imager, adjoint
+
+
+# ---- the loss of optimizeMask and its pointwise derivatives, from its docstring -----------------------------------------------
+def _sigmoid(x):
+    return 1.0 / (1.0 + torch.exp(-x))
+
+
+def ilt_resist(image, threshold, dose, resistSteepness):
+    """float64 sigmoid(a_r (dose I - T))."""
+    return _sigmoid(float(resistSteepness) * (float(dose) * torch.as_tensor(image).double() - float(threshold)))
+
+
+def ilt_loss(image, target, threshold, dose, resistSteepness):
+    """float64 mean((sigmoid(a_r (dose I - T)) - target)^2) over the pixels and, for a stack [planes,n,n], over the planes."""
+    diff = ilt_resist(image, threshold, dose, resistSteepness) - torch.as_tensor(target).double()
+    return float((diff * diff).mean())
+
+
+def ilt_grad_image(image, target, threshold, dose, resistSteepness):
+    """float64 dl/dI of ilt_loss in closed form: 2 a_r dose / numel . (r - target) . r (1 - r), numel counting pixels and planes."""
+    r = ilt_resist(image, threshold, dose, resistSteepness)
+    return (2.0 * float(resistSteepness) * float(dose) / r.numel()) * (r - torch.as_tensor(target).double()) * r * (1.0 - r)
+
+
+def ilt_transmission(theta, background, feature, maskSteepness):
+    """complex128 t = background + (feature - background) sigmoid(a_m theta)."""
+    s = _sigmoid(float(maskSteepness) * torch.as_tensor(theta).double())
+    return complex(background) + (complex(feature) - complex(background)) * s.to(C128)
+
+
+def ilt_grad_theta(theta, grad_t, background, feature, maskSteepness):
+    """float64 dl/dtheta from grad_t = dl/dRe t + i dl/dIm t (dl = Re(conj(grad_t) dt)) and dt = span a_m s (1 - s) dtheta:
+    a_m s (1 - s) Re(grad_t conj(span))."""
+    s = _sigmoid(float(maskSteepness) * torch.as_tensor(theta).double())
+    span = complex(feature) - complex(background)
+    return float(maskSteepness) * s * (1.0 - s) * (torch.as_tensor(grad_t).to(C128) * span.conjugate()).real
+
+
+def socs_around(kernels, dev, weight_sum=1.0):
+    """A SOCSKernels around given kernels ([K,pn,pn] or [planes,K,pn,pn]) on `dev`: only the kernels, and `weight_sum` for
+    `normalize`, matter to the calls under test."""
+    from lithographysimulator_amd import SOCSKernels
+    k = torch.as_tensor(kernels).to(torch.complex64).to(dev).contiguous()
+    planes = k.shape[0] if k.dim() == 4 else 1
+    K = k.shape[-3]
+    lam = torch.ones((planes, K) if k.dim() == 4 else (K,), dtype=torch.float64)
+    return SOCSKernels(k, lam, 1.0, 1.0, float(weight_sum), K, [None] * planes)
 
 
 # ---- the cases the CPU floor measurement and the GPU tests share --------------------------------------------------------------
@@ -205,3 +298,94 @@ def sized_case(pn, N, K=5, planes=1):
         G = random_G((planes, pn, pn), pn + N)
         _cases[key] = ((k if planes > 1 else k[0]).contiguous(), M.contiguous(), G if planes > 1 else G[0])
     return _cases[key]
+
+
+# ---- settings of the inverse-lithography loop that the CPU and the GPU tests share -----------------------------------------------
+ILT_DOSE, ILT_WEIGHT_SUM, ILT_MASK_STEEPNESS, ILT_STEP = 1.1, 2.7, 4.0, 0.0625
+ILT_BACKGROUNDS = {"binary": 0, "attenuated": -math.sqrt(0.06), "complex": 0.1 + 0.2j}
+# the device model's cases (image and adjoint parity) and the loop's: kind -> (background, planes)
+ILT_DEVICE_CASES = [(pn, regime, planes, normalize) for pn in (32, 64) for regime in ("shrink", "crop", "copy") for planes in (1, 2)
+                    for normalize in (True, False)]
+ILT_LOOP_KINDS = {"binary": ("binary", 1), "attenuated": ("attenuated", 1), "complex": ("complex", 1), "stack": ("complex", 2)}
+ILT_LOOP_CASES = [(pn, regime, kind, normalize) for pn in (32, 64) for regime in ("shrink", "crop", "copy") for kind in ILT_LOOP_KINDS
+                  for normalize in (True, False)]
+_ilt = {}
+
+
+class Grid:
+    """What optimizeMask needs of `socs` when imager= / adjoint= replace the model."""
+
+    def __init__(self, pn):
+        self.pn = pn
+
+
+class IltCase:
+    """One setting of optimizeMask on this file's chain: K = 3 kernels of sized_case (one plane or a stack of two) at the pixel
+    size of an epsilon regime, deltaK = 4 / pn, 193 nm, dose 1.1; theta0 seeded normal of 0.5 sigma, a seeded Bernoulli target on
+    the post-processed grid (both values present), the threshold at the median of dose . image(theta0) so that the resist has
+    pixels on both sides and on the slope, the default resistSteepness 25 / threshold.  The planes of a stack are scaled to one
+    median, as the planes of a focus stack share their dose.  step 1 / 16: every case descends in its first step on this chain."""
+
+    def __init__(self, pn, regime, planes, background, gain):
+        self.pn, self.regime, self.planes, self.background, self.gain = pn, regime, planes, background, gain
+        self.ps, self.eps, self.N = epsilon_regimes(pn)[regime]
+        self.kernels = sized_case(pn, self.N, 3, planes)[0]
+        self.n_out = postprocess_matrix(pn, self.eps).shape[0]
+        g = torch.Generator().manual_seed(7000 + 10 * pn + planes + len(regime))
+        self.theta0 = (0.5 * torch.randn((pn, pn), generator=g, dtype=torch.float64)).to(torch.float32)
+        self.target = (torch.rand((self.n_out, self.n_out), generator=g, dtype=torch.float64) > 0.5).to(torch.float32)
+        assert 0 < int(self.target.sum()) < self.target.numel()
+        self.t0 = ilt_transmission(self.theta0, background, 1, ILT_MASK_STEEPNESS)
+        if planes > 1:
+            # the planes of a focus stack share their dose: random kernels do not, and a plane whose image lies far above the
+            # threshold everywhere would drop out of the gradient (r (1 - r) = 0), so each plane is scaled to the first one's median
+            med = self.model()[0](self.t0).flatten(1).median(dim=1).values
+            self.kernels = (self.kernels * torch.sqrt(med[0] / med).to(torch.float32)[:, None, None, None]).contiguous()
+        self.image0 = self.model()[0](self.t0)
+        self.threshold = ILT_DOSE * float(self.image0.median())
+        self.a_r = 25.0 / self.threshold
+        self.grad_image0 = ilt_grad_image(self.image0, self.target, self.threshold, ILT_DOSE, self.a_r)
+        # every plane carries a comparable share of the gradient
+        peaks = self.grad_image0.reshape(planes, -1).abs().max(dim=1).values
+        assert float(peaks.min()) > 0.1 * float(peaks.max()), peaks
+        self._reference = None
+
+    def model(self, dtype=C128):
+        """A fresh (imager, adjoint) pair: the adjoint belongs to the transmission its own imager saw last."""
+        return model(self.kernels, self.pn, self.eps, self.N, self.gain, dtype=dtype)
+
+    def loop(self, imager, adjoint, theta=None, target=None, **kw):
+        """optimizeMask through the public call with this setting and the given hooks, one iteration from theta0 (or `theta`)."""
+        from lithographysimulator_amd import optimizeMask
+        return optimizeMask(self.target if target is None else target, Grid(self.pn), self.ps, 4 / self.pn, 193.0, self.threshold,
+                            dose=ILT_DOSE, initial=self.theta0 if theta is None else theta, iterations=1, step=ILT_STEP,
+                            maskSteepness=ILT_MASK_STEEPNESS, background=self.background, imager=imager, adjoint=adjoint, **kw)
+
+    def reference(self):
+        """The one-iteration loop on the float64 chain, run once."""
+        if self._reference is None:
+            self._reference = self.loop(*self.model())
+        return self._reference
+
+
+def ilt_case(pn, regime, planes=1, background=0, gain=1.0):
+    key = (pn, regime, planes, complex(background), float(gain))
+    if key not in _ilt:
+        _ilt[key] = IltCase(pn, regime, planes, background, gain)
+    return _ilt[key]
+
+
+def device_case(pn, regime, planes, normalize):
+    """The setting of one of ILT_DEVICE_CASES: the complex background, so that t has both parts; gain 1 / weight_sum or 1."""
+    return ilt_case(pn, regime, planes, ILT_BACKGROUNDS["complex"], 1.0 / ILT_WEIGHT_SUM if normalize else 1.0)
+
+
+def loop_case(pn, regime, kind, normalize):
+    background, planes = ILT_LOOP_KINDS[kind]
+    return ilt_case(pn, regime, planes, ILT_BACKGROUNDS[background], 1.0 / ILT_WEIGHT_SUM if normalize else 1.0)
+
+
+def update_of(case, result):
+    """(theta0 - theta1) / step of a one-iteration result whose best iterate is the first update, in float64."""
+    assert result.best == 1 and result.losses[1] < result.losses[0]
+    return (case.theta0.double() - result.theta.detach().cpu().double()) / ILT_STEP

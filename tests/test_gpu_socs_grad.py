@@ -58,11 +58,7 @@ def nat():
 
 def _socs(L, kernels, dev):
     """A SOCSKernels around given kernels ([K,pn,pn] or [planes,K,pn,pn]): only the kernels matter to the calls under test."""
-    k = kernels.to(torch.complex64).to(dev).contiguous()
-    planes = k.shape[0] if k.dim() == 4 else 1
-    K = k.shape[-3]
-    lam = torch.ones((planes, K) if k.dim() == 4 else (K,), dtype=torch.float64)
-    return L.SOCSKernels(k, lam, 1.0, 1.0, 1.0, K, [None] * planes)
+    return GO.socs_around(kernels, dev)
 
 
 _named = {}

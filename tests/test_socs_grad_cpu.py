@@ -176,9 +176,7 @@ def test_package_adjoints_on_the_host(pn, name):
 
 # ---- argument errors ---------------------------------------------------------------------------------------------------------
 def _cpu_socs(pn=32, K=3, planes=1):
-    import lithographysimulator_amd as L
-    k = torch.zeros((planes, K, pn, pn) if planes > 1 else (K, pn, pn), dtype=torch.complex64)
-    return L.SOCSKernels(k, torch.ones(K, dtype=torch.float64), 1.0, 1.0, 1.0, K, [None] * planes)
+    return GO.socs_around(torch.zeros((planes, K, pn, pn) if planes > 1 else (K, pn, pn), dtype=torch.complex64), "cpu")
 
 
 def test_gradient_argument_errors():
@@ -287,6 +285,170 @@ def test_optimize_mask_the_setting_of_the_device_test():
     res2 = L.optimizeMask(target, _Grid(64), PS, 4 / 64, WL, threshold, iterations=4, background=-math.sqrt(0.06), imager=imager,
                           adjoint=adjoint, initial=res.theta)
     assert bool((res2.transmission.real < 0).any()) and all(math.isfinite(v) for v in res2.losses)
+
+
+# ---- the loop against the derivative of its own loss -------------------------------------------------------------------------
+LOOP_CASES = [(pn, regime, planes, bg) for pn in (16, 32) for regime in ("shrink", "crop", "copy") for planes in (1, 2)
+              for bg in GO.ILT_BACKGROUNDS]
+# eps32 = 2^-24, the relative rounding of one fp32 operation.  The loop forms s = sigmoid(a_m theta) in fp32 and, on the device's
+# types, theta1 = fl(theta0 - fl(step . fl(g / peak))) with |g / peak| <= 1.  Against g / peak in float64 that leaves, in units of
+# eps32: max(|theta0|, |theta1|) / step from the subtraction (the division by step, a power of two, is exact), 2 from the product
+# and the quotient, a_m max|theta0| from the rounding of a_m theta carried through s (1 - s) (|d log(s (1 - s)) / dx| = |1 - 2 s|
+# <= 1), and 4 from the sigmoid, 1 - s and the two products
+EPS32 = 2.0 ** -24
+
+
+def _update_bound(case, theta1):
+    top = max(float(case.theta0.abs().max()), float(theta1.abs().max()))
+    return EPS32 * (top / GO.ILT_STEP + 2.0 + GO.ILT_MASK_STEEPNESS * float(case.theta0.abs().max()) + 4.0)
+
+# the measured worst of |fd - <g, d>| / (||g|| ||d||) at h = 3e-3 over LOOP_CASES, 1.27e-4 (see the test's docstring), and the
+# bound, 4 times it
+FD_WORST_3E3 = 1.3e-4
+TOL_FD_3E3 = 4 * FD_WORST_3E3
+_runs = {}
+
+
+def _recorded_run(pn, regime, planes, bg):
+    """One optimizeMask(initial=theta0, iterations=1) on the float64 chain with hooks that record what crosses them; made once per
+    case and shared by the tests below: (case, result, {"t": transmissions imaged, "grad_image", "grad_t"})."""
+    key = (pn, regime, planes, bg)
+    if key not in _runs:
+        case = GO.ilt_case(pn, regime, planes, GO.ILT_BACKGROUNDS[bg], gain=1.0 / GO.ILT_WEIGHT_SUM)
+        imager, adjoint = case.model()
+        rec = {"t": [], "grad_image": [], "grad_t": []}
+
+        def rec_imager(t):
+            rec["t"].append(t.clone())
+            return imager(t)
+
+        def rec_adjoint(g):
+            rec["grad_image"].append(g.clone())
+            rec["grad_t"].append(adjoint(g))
+            return rec["grad_t"][-1]
+
+        _runs[key] = (case, case.loop(rec_imager, rec_adjoint), rec)
+    return _runs[key]
+
+
+@pytest.mark.parametrize("pn,regime,planes,bg", LOOP_CASES)
+def test_loop_loss_and_image_gradient_against_the_closed_form(pn, regime, planes, bg):
+    """losses[0] is GO.ilt_loss of the oracle image of t(theta0) computed here in float64.  The loop forms t in fp32 / complex64:
+    a_m theta rounds at eps32 . 8 under a slope of |span| / 4, the sigmoid, the product and the sum at eps32 |t| each, 5e-7 in
+    all (measured 1.4e-7), and the loss follows to 1e-6 relative, the bound of test_optimize_mask_descends_on_the_oracle_chain
+    (measured 1.4e-8).  The gradient the loop hands to the adjoint has the image's shape and is 2 a_r dose / numel . diff . r (1 - r)
+    with numel over pixels AND planes.  The loop forms it in float64 from the hook's float64 image, so only the rounded t separates
+    the two: 5e-7 on t is at most that, relatively, on the image, times the sigmoid's a_r . threshold = 25 on the slope, times 2 for
+    the two factors that move with it (diff and r (1 - r)): 2.5e-5 of the maximum (measured 1.7e-6); a count over one plane of
+    two is a factor 2."""
+    case, res, rec = _recorded_run(pn, regime, planes, bg)
+    assert len(res.losses) == 2 and len(rec["t"]) == 2 and len(rec["grad_image"]) == 1
+    assert rec["t"][0].dtype == torch.complex64 and tuple(rec["t"][0].shape) == (pn, pn)
+    e_t = float((rec["t"][0].to(torch.complex128) - case.t0).abs().max())
+    want = GO.ilt_loss(case.image0, case.target, case.threshold, GO.ILT_DOSE, case.a_r)
+    e_l = abs(res.losses[0] - want) / want
+    G = rec["grad_image"][0]
+    shape = (planes, case.n_out, case.n_out) if planes > 1 else (case.n_out, case.n_out)
+    assert tuple(G.shape) == shape and not G.is_complex()
+    G_want = GO.ilt_grad_image(case.image0, case.target, case.threshold, GO.ILT_DOSE, case.a_r)
+    e_g = float((G.double() - G_want).abs().max() / G_want.abs().max())
+    print(f"pn {pn} {regime} planes {planes} {bg}: loss {res.losses[0]:.9f} vs {want:.9f} ({e_l:.1e}, bound 1e-6), t {e_t:.1e} (bound 5e-7), "
+          f"grad_image {e_g:.1e} (bound 2.5e-5), signs {int((G_want < 0).sum())} / {int((G_want > 0).sum())}")
+    assert e_t < 5e-7 and e_l < 1e-6 and e_g < 2.5e-5
+    assert bool((G_want < 0).any()) and bool((G_want > 0).any())
+
+
+@pytest.mark.parametrize("pn,regime,planes,bg", LOOP_CASES)
+def test_loop_gradient_is_the_derivative_of_its_loss(pn, regime, planes, bg):
+    """g_theta = a_m s (1 - s) Re(grad_t conj(span)) from the recorded adjoint output against the central difference of the loop's
+    own loss, read through the public call (initial = theta0 +- h d, iterations = 1, losses[0]) along a seeded random d, at
+    h = 1e-2 and 3e-3; the error is |fd - <g, d>| / (||g||_2 ||d||_2).  Measured over the 36 cases:
+        h = 1e-2: worst 1.38e-3, median 6.9e-5;  h = 3e-3: worst 1.27e-4 (pn 32, crop, two planes, complex), median 5.7e-6,
+        smallest 3.8e-7
+    The worst cases fall as h^2 (1.38e-3 -> 1.27e-4); the small ones sit on the floor of the quotient, theta and t being rounded
+    to fp32 inside the call, so no convergence ratio between the two steps is asserted.  The bound at h = 3e-3 is 4 times that
+    worst, 5.2e-4.  Along a random d a gradient wrong by its own size shows at about 1 / pn of ||g|| ||d||, 0.03 ... 0.06, and a
+    count over one plane of two doubles <g, d>; the update test below sees a wrong direction element by element."""
+    case, res, rec = _recorded_run(pn, regime, planes, bg)
+    g = GO.ilt_grad_theta(case.theta0, rec["grad_t"][0], case.background, 1, GO.ILT_MASK_STEEPNESS)
+    d = torch.randn((pn, pn), generator=torch.Generator().manual_seed(pn + planes), dtype=torch.float64)
+    dd = float((g * d).sum())
+    scale = float(torch.linalg.norm(g) * torch.linalg.norm(d))
+    errs = {}
+    for h in (1e-2, 3e-3):
+        imager, adjoint = case.model()
+        lp = case.loop(imager, adjoint, theta=(case.theta0.double() + h * d).to(torch.float32)).losses[0]
+        lm = case.loop(imager, adjoint, theta=(case.theta0.double() - h * d).to(torch.float32)).losses[0]
+        errs[h] = abs((lp - lm) / (2 * h) - dd) / scale
+    print(f"pn {pn} {regime} planes {planes} {bg}: <g,d> {dd:+.6e}, ||g|| ||d|| {scale:.3e}, error {errs[1e-2]:.2e} at h 1e-2, "
+          f"{errs[3e-3]:.2e} at h 3e-3 (bound {TOL_FD_3E3:.1e})")
+    assert errs[3e-3] < TOL_FD_3E3
+
+
+@pytest.mark.parametrize("pn,regime,planes,bg", LOOP_CASES)
+def test_first_update_is_the_peak_normalised_gradient(pn, regime, planes, bg):
+    """Every case descends in its first step on the float64 chain (asserted: best == 1), so the returned theta is theta1 and
+    (theta0 - theta1) / step must be g_theta / max|g_theta| of the recorded adjoint output, to the fp32 rounding of the update
+    (EPS32 above; the float64 hooks make the loop's theta1 float64, which only lowers the error).  This is the one place where the
+    loop's own grad_theta shows: its conjugate on span, its a_m s (1 - s), the peak normalisation and the sign."""
+    case, res, rec = _recorded_run(pn, regime, planes, bg)
+    assert res.best == 1 and res.losses[1] < res.losses[0], res.losses
+    g = GO.ilt_grad_theta(case.theta0, rec["grad_t"][0], case.background, 1, GO.ILT_MASK_STEEPNESS)
+    got, want = GO.update_of(case, res), g / g.abs().max()
+    bound = _update_bound(case, res.theta)
+    e = float((got - want).abs().max())
+    print(f"pn {pn} {regime} planes {planes} {bg}: losses {res.losses[0]:.6f} -> {res.losses[1]:.6f}, update error {e:.2e} "
+          f"(bound {bound:.2e}), peak {float(got.abs().max()):.7f}")
+    assert e < bound
+    assert torch.equal(res.mask, res.theta > 0) and res.transmission.dtype == torch.complex64
+
+
+def _within(measured, recorded):
+    """The recorded floor is what this machine printed when the bound was chosen; another host BLAS sums in another order and
+    moves it by its own rounding, so the re-check allows a factor 2 -- a floor that has really moved (a changed case, another
+    chain) is caught before the device bound built on it means something else."""
+    return measured <= 2.0 * recorded
+
+
+def test_fp32_floor_of_the_loop_chain():
+    """The fp32 floors the bounds of tests/test_gpu_ilt.py are derived from (socs_grad_oracle.py, "Loop tolerances"): GO.model in
+    torch's CPU complex64 against float64 on exactly the device tests' cases -- the image and the adjoint over
+    GO.ILT_DEVICE_CASES, the one-iteration loop (both losses and the update) over GO.ILT_LOOP_CASES."""
+    im_max = im_l2 = ad_max = ad_l2 = 0.0
+    for key in GO.ILT_DEVICE_CASES:
+        case = GO.device_case(*key)
+        imager, adjoint = case.model(torch.complex64)
+        image = imager(case.t0.to(torch.complex64))
+        assert image.dtype == torch.float32
+        im_max, im_l2 = max(im_max, GO.rel_max(image, case.image0)), max(im_l2, GO.rel_l2(image, case.image0))
+        G = case.grad_image0.to(torch.float32)
+        imager64, adjoint64 = case.model()
+        imager64(case.t0.to(torch.complex64))
+        got, want = adjoint(G), adjoint64(G)
+        assert got.dtype == torch.complex64
+        ad_max, ad_l2 = max(ad_max, GO.rel_max(got, want)), max(ad_l2, GO.rel_l2(got, want))
+    loss = update = 0.0
+    for key in GO.ILT_LOOP_CASES:
+        case = GO.loop_case(*key)
+        ref, got = case.reference(), case.loop(*case.model(torch.complex64))
+        assert got.theta.dtype == torch.float32
+        loss = max(loss, abs(got.losses[0] - ref.losses[0]) / ref.losses[0], abs(got.losses[1] - ref.losses[1]) / ref.losses[1])
+        update = max(update, float((GO.update_of(case, got) - GO.update_of(case, ref)).abs().max()))
+    print(f"complex64 chain vs float64: image max {im_max:.2e} (recorded {GO.ILT_FLOOR_IMAGE_MAX:.1e}), l2 {im_l2:.2e} "
+          f"({GO.ILT_FLOOR_IMAGE_L2:.1e}); adjoint max {ad_max:.2e} ({GO.ILT_FLOOR_ADJOINT_MAX:.1e}), l2 {ad_l2:.2e} "
+          f"({GO.ILT_FLOOR_ADJOINT_L2:.1e}) over {len(GO.ILT_DEVICE_CASES)} cases; loss {loss:.2e} ({GO.ILT_FLOOR_LOSS:.1e}), update "
+          f"{update:.2e} ({GO.ILT_FLOOR_UPDATE:.1e}) over {len(GO.ILT_LOOP_CASES)} cases")
+    print(f"bounds: image {GO.TOL_ILT_IMAGE_MAX:.1e} / {GO.TOL_ILT_IMAGE_L2:.1e}, adjoint {GO.TOL_ILT_ADJOINT_MAX:.1e} / "
+          f"{GO.TOL_ILT_ADJOINT_L2:.1e}, loss {GO.TOL_ILT_LOSS:.1e}, update {GO.TOL_ILT_UPDATE:.1e}")
+    assert _within(im_max, GO.ILT_FLOOR_IMAGE_MAX) and _within(im_l2, GO.ILT_FLOOR_IMAGE_L2)
+    assert _within(ad_max, GO.ILT_FLOOR_ADJOINT_MAX) and _within(ad_l2, GO.ILT_FLOOR_ADJOINT_L2)
+    assert _within(loss, GO.ILT_FLOOR_LOSS) and _within(update, GO.ILT_FLOOR_UPDATE)
+    # the project's rule: the image tolerances where the floor is under a quarter of them, four times the floor otherwise
+    for floor, tol, bound in ((GO.ILT_FLOOR_IMAGE_MAX, TOL_IMAGE_MAX, GO.TOL_ILT_IMAGE_MAX), (GO.ILT_FLOOR_IMAGE_L2, TOL_IMAGE_L2, GO.TOL_ILT_IMAGE_L2),
+                              (GO.ILT_FLOOR_ADJOINT_MAX, TOL_IMAGE_MAX, GO.TOL_ILT_ADJOINT_MAX),
+                              (GO.ILT_FLOOR_ADJOINT_L2, TOL_IMAGE_L2, GO.TOL_ILT_ADJOINT_L2)):
+        assert bound == (tol if floor < tol / 4 else 4 * floor)
+    assert (GO.TOL_ILT_LOSS, GO.TOL_ILT_UPDATE) == (4 * GO.ILT_FLOOR_LOSS, 4 * GO.ILT_FLOOR_UPDATE)
 
 
 def test_optimize_mask_argument_errors():
