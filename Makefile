@@ -54,6 +54,10 @@ build/socs.o: $(CSRC)/socs.hip $(CSRC)/plane_fft.hpp $(CSRC)/fft_core.hpp $(CSRC
 build/socs_grad.o: $(CSRC)/socs_grad.hip $(CSRC)/plane_fft.hpp $(CSRC)/fft_core.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(FFTFLAGS) -c $< -o $@
+# the thin-film pupils: double precision per cell, no contraction (the cell classification s < 1 is then numpy's)
+build/film.o: $(CSRC)/film.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 build/common.o: $(CSRC)/common.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -65,7 +69,7 @@ build/plan_dry_run.o: $(CSRC)/plan_dry_run.cpp $(CSRC)/abbe_plan.hpp include/lit
 build/contour_link.o: $(CSRC)/contour_link.cpp include/litho_abbe.h
 	@mkdir -p build
 	g++ -O2 -std=c++17 -fPIC -Wall -Wextra -c $< -o $@
-$(OUT): build/abbe_engine.o build/optics.o build/layout.o build/metrology.o build/contour.o build/socs.o build/socs_grad.o build/common.o build/plan_dry_run.o build/contour_link.o $(INST) $(INSTW)
+$(OUT): build/abbe_engine.o build/optics.o build/layout.o build/metrology.o build/contour.o build/socs.o build/socs_grad.o build/film.o build/common.o build/plan_dry_run.o build/contour_link.o $(INST) $(INSTW)
 	@mkdir -p lithographysimulator_amd/lib
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 

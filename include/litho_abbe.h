@@ -419,6 +419,44 @@ size_t litho_tcc_apply_vector_work_bytes(int batch, int n);
 int litho_tcc_apply_vector(const void *q_hat, const float *w_shifted, const void *X, void *Y, int batch, int n, void *work,
                            size_t work_bytes, void *stream);
 
+/* ---- Resist film stack for vector imaging (csrc/film.hip; no reference counterpart, checked against tests/film_oracle.py;
+ * DESIGN.md section 10).  A film stack changes only the six planes Q_cj; the vector TCC above and every consumer take them as
+ * they are.  Conventions: the defocus phase exp(+2 pi i n z (1 - gamma) / lambda) above means that a wave advancing by z into
+ * the wafer carries exp(-i kappa z), so an absorbing medium (n, k), k >= 0, enters as nn = n - i k.
+ * Stack, top to bottom: the incident medium of real index n0 = `index` (NA < n0); L finite layers, 1 <= L <= 16, each
+ * (n_l, k_l, thickness d_l > 0 nm); a semi-infinite substrate (n_s, k_s).  Layer `resist` (0-based) is sampled at depths z in nm
+ * below its top, 0 <= z <= d_resist.
+ * Per pupil cell, (alpha, beta) as above with index = n0, s = NA^2 (sigma_x^2 + sigma_y^2) = n0^2 (alpha^2 + beta^2); every plane
+ * is exactly 0 where alpha^2 + beta^2 >= 1.  In each medium w = sqrt(nn^2 - s), the root with Im w <= 0 and Re w > 0 when
+ * Im w = 0; kappa = 2 pi w / lambda.  Two independent scalar problems share one recursion: a primary quantity
+ * u(z) = a exp(-i kappa z) + b exp(+i kappa z) with flux v = eta (a exp(-i kappa z) - b exp(+i kappa z)), u and v continuous at
+ * every interface, b = 0 in the substrate.
+ *   s-polarisation: u = E_s, eta = w, incident amplitude a0 = 1.
+ *   p-polarisation: u = H_s, eta = w / nn^2, incident amplitude a0 = n0; in the sampled layer
+ *     E_rad(z) = (w / nn^2) (a exp(-i kappa z) - b exp(+i kappa z)),   E_z(z) = -(sqrt(s) / nn^2) u(z).
+ * With r = (alpha, beta) / sqrt(alpha^2 + beta^2) and t = (-r_y, r_x), the planes at depth z are
+ *   Q_cj = P . f . [ t_c E_s t_j + (r_c E_rad + zhat_c E_z) r_j ],   c in {x, y, z}, j in {x, y}, plane 2 c + j;
+ * at s = 0, E_s on the diagonal and 0 elsewhere (E_rad = E_s there).  f = gamma0^(-1/2) with `radiometric`, gamma0 in the
+ * incident medium.  The pupil's own defocus (nm, in the incident medium: the phase litho_vector_pupils applies) rides on top and
+ * places best focus relative to the top of the stack.  No global phase is removed: with every index equal to n0 and k = 0 the
+ * planes equal litho_vector_pupils' at defocus z times exp(-2 pi i n0 z / lambda).
+ * Evaluation: the reflection ratio is swept upward from the substrate, the transmitted amplitude downward, and the upward wave
+ * of a layer is referenced to that layer's BOTTOM, so that no exponential with a positive real exponent is ever formed: every
+ * cell with alpha^2 + beta^2 < 1 gives finite planes whatever the thicknesses and absorptions.  The single degenerate point
+ * w = 0 exactly in a layer (grazing propagation in it) is NOT pinned.  Double precision per cell, each output component rounded
+ * to fp32 once.  Not modelled: absorbed-energy weighting (n k |E|^2 is a constant factor inside one layer), development,
+ * layers with a gradient in index.
+ *
+ * litho_film_pupils: out complex64 [planes, D, 6, pn, pn] from pupil complex64 [planes,pn,pn].  layers: L x {n, k, d_nm} on the
+ * host, depths_nm: D values on the host, defocus_nm_host: `planes` values on the host or NULL (all read before the call
+ * returns; the stack travels to the kernel by value).  One thread per cell runs the two recursions once and walks the depths;
+ * one launch per plane and per 16 depths.  pn even, 16..16384.  LITHO_E_ARG, before any launch: a null pointer, planes < 1,
+ * L or resist out of range, D < 1 or planes D > 65535, any non-finite value, k < 0, n <= 0, d <= 0, wavelength <= 0, a depth
+ * outside [0, d_resist], NA >= index.  Asynchronous, no allocation, no host wait. */
+int litho_film_pupils(const void *pupil, int planes, int pn, double NA, double index, int radiometric, const double *layers, int L,
+                      double substrate_n, double substrate_k, int resist, const double *depths_nm, int D,
+                      const double *defocus_nm_host, double wavelength, void *out, void *stream);
+
 /* ---- Mask gradients of Hopkins imaging (csrc/socs_grad.hip; no reference counterpart, checked against tests/socs_grad_oracle.py).
  * With F[q][i] = exp(+2 pi i (i - c)(q - c) / N), c = pn / 2, q, i in [0, pn), the engine's chain at shift (0,0) is L(X) = F X F^T,
  * the coherent fields are E_k = L(phi_k . M) and I = sum_k |E_k|^2.  For a real loss l with G = dl/dI,

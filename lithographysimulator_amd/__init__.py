@@ -16,6 +16,7 @@ from .ilt import (ILTResult, hopkinsFields, hopkinsGradient, hopkinsIntensityAD,
                   maskSpectrumAdjoint, optimizeMask, postProcessAdjoint)
 from .vector import (sourcePolarization, vectorAbbeIntensity, vectorPupils,            # noqa: F401
                      vectorSocsKernels)
+from .film import FilmStack, filmPupils                                                 # noqa: F401
 from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
@@ -27,4 +28,5 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "Contours", "contourVertices", "traceContours", "contoursToLayout", "simplifyContour", "contoursToGDSII", "doseFocusEnvelope",
            "processVariationBand", "SOCSKernels", "socsKernels", "hopkinsIntensity", "hopkinsImage",
            "hopkinsFields", "hopkinsGradient", "hopkinsIntensityAD", "maskSpectrumAdjoint", "postProcessAdjoint", "optimizeMask", "ILTResult",
-           "vectorPupils", "sourcePolarization", "vectorSocsKernels", "vectorAbbeIntensity"]
+           "vectorPupils", "sourcePolarization", "vectorSocsKernels", "vectorAbbeIntensity",
+           "FilmStack", "filmPupils"]

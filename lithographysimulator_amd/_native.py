@@ -63,6 +63,8 @@ _SIGNATURES = {
     "litho_tcc_apply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "litho_socs_fold": (c_int, [c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_void_p]),
     "litho_vector_pupils": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_int, POINTER(c_double), c_double, c_void_p, c_void_p]),
+    "litho_film_pupils": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_int, POINTER(c_double), c_int, c_double, c_double, c_int,
+                                  POINTER(c_double), c_int, POINTER(c_double), c_double, c_void_p, c_void_p]),
     "litho_tcc_apply_vector_work_bytes": (c_size_t, [c_int, c_int]),
     "litho_tcc_apply_vector": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "litho_socs_fields": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

@@ -17,7 +17,8 @@ SOCSKernels, and hopkinsIntensity / hopkinsImage / hopkinsFields / hopkinsGradie
 their K fields with polarisation included.  The operator on the device is litho_tcc_apply_vector: 14 pn^2 transforms per vector.
 
 `vectorAbbeIntensity` is the on-device truth for a UNIFORM polarisation: 3 or 6 effective pupils through the unchanged Abbe
-engine.  Out of scope: thick-mask polarisation effects, a resist film stack (one homogeneous image medium), TCC interpolation."""
+engine.  A resist film stack under the image medium changes only the six planes: film.py (`FilmStack`, `filmPupils`,
+`vectorSocsKernels(film=, depths=, depthWeights=)`).  Out of scope: thick-mask polarisation effects, TCC interpolation."""
 import ctypes
 import math
 from functools import partial
@@ -185,7 +186,7 @@ class _VectorOperator:
 
 def vectorSocsKernels(pupilF, lightsource, NA, polarization="unpolarized", degree=1.0, mediumIndex=1.0, radiometric=False,
                       defocus=None, wavelength=None, kernels=64, oversample=16, iterations=2, seed=0, applier=None,
-                      applyBytes=8 << 30):
+                      applyBytes=8 << 30, film=None, depths=None, depthWeights=None):
     """SOCS kernels of one optical setting with polarisation: an ordinary SOCSKernels for hopkinsIntensity and every other
     consumer.  `pupilF`, `lightsource`, `kernels`, `oversample`, `iterations`, `seed`, `applier` as socsKernels takes them (pn a
     power of two, 16 ... 4096); `NA`, `mediumIndex`, `radiometric`, `defocus`, `wavelength` as vectorPupils; `polarization`,
@@ -197,10 +198,26 @@ def vectorSocsKernels(pupilF, lightsource, NA, polarization="unpolarized", degre
     sum_jj' (sum W_jj') sum_c <Q_cj', Q_cj>, `captured` = sum_k lambda_k / trace, `weight_sum` = sum W.
 
     The device operator is litho_tcc_apply_vector, called on chunks of vectors so that its work buffer stays under `applyBytes`
-    (48 (chunk + 1) pn^2 bytes; never less than one vector).  The vectors are independent, so chunking changes no bit."""
+    (48 (chunk + 1) pn^2 bytes; never less than one vector).  The vectors are independent, so chunking changes no bit.
+
+    `film` (a FilmStack; film.py) images into the resist layer of a thin-film stack under the medium `mediumIndex` instead of
+    into that medium: the planes are filmPupils' at `depths` (nm below the top of the resist layer, D of them; `wavelength` is
+    then required, and `defocus` places best focus relative to the top of the stack).  Without `depthWeights` every (focus
+    plane f, depth d) is a plane of the result, at index f D + d.  With `depthWeights` (D non-negative numbers, not all zero) the
+    BULK operator X -> sum_d w_d T_d X is factored per focus plane -- support the union over depths, trace sum_d w_d trace_d,
+    rank bound (3 or 5) S D, the operator D calls of the unchanged litho_tcc_apply_vector summed in ascending d -- and the
+    result is an ordinary SOCSKernels whose image is sum_d w_d I(z_d): K fields per bulk image, not D K.  film=None is the
+    code path below, untouched."""
     who = "vectorSocsKernels"
     NA, n = _check_optics(who, NA, mediumIndex)
     zs, as_list = _defocus_list(who, defocus, wavelength)
+    if film is not None or depths is not None or depthWeights is not None:
+        if film is None:
+            raise ValueError(f"{who}: depths and depthWeights belong to a film stack; film is None")
+        from .film import _film_socs_kernels
+        return _film_socs_kernels(who, pupilF, lightsource, NA, n, polarization, degree, radiometric, zs, as_list, wavelength, film,
+                                  depths, depthWeights, applyBytes, kernels=kernels, oversample=oversample, iterations=iterations,
+                                  seed=seed, applier=applier)
     pn, pp, planes, stacked = _pupil_planes(who, pupilF, zs, as_list)
     pure = not (isinstance(polarization, str) and polarization == "unpolarized") and float(degree) == 1.0
 
