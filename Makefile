@@ -58,6 +58,11 @@ build/socs_grad.o: $(CSRC)/socs_grad.hip $(CSRC)/plane_fft.hpp $(CSRC)/fft_core.
 build/film.o: $(CSRC)/film.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
+# resist development: fixed sequences of single fp32 operations (the float64 restatement bounds every rounding), double per cell
+# in the rate kernel
+build/develop.o: $(CSRC)/develop.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 build/common.o: $(CSRC)/common.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -69,7 +74,7 @@ build/plan_dry_run.o: $(CSRC)/plan_dry_run.cpp $(CSRC)/abbe_plan.hpp include/lit
 build/contour_link.o: $(CSRC)/contour_link.cpp include/litho_abbe.h
 	@mkdir -p build
 	g++ -O2 -std=c++17 -fPIC -Wall -Wextra -c $< -o $@
-$(OUT): build/abbe_engine.o build/optics.o build/layout.o build/metrology.o build/contour.o build/socs.o build/socs_grad.o build/film.o build/common.o build/plan_dry_run.o build/contour_link.o $(INST) $(INSTW)
+$(OUT): build/abbe_engine.o build/optics.o build/layout.o build/metrology.o build/contour.o build/socs.o build/socs_grad.o build/film.o build/develop.o build/common.o build/plan_dry_run.o build/contour_link.o $(INST) $(INSTW)
 	@mkdir -p lithographysimulator_amd/lib
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 

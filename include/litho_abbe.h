@@ -34,6 +34,7 @@ extern "C" {
 #define LITHO_E_WORKSPACE (-3)  /* workspace too small                                        */
 #define LITHO_E_HIP (-4)        /* a HIP runtime call failed; see litho_last_error()           */
 #define LITHO_E_INDEX (-5)      /* aberration vector of length 4 (pupil.py:91-92)   */
+#define LITHO_E_NOCONV (-6)     /* litho_develop_time: the launch cap was reached before the fixed point */
 
 /* Library version and the gfx target it was compiled for ("gfx950"). */
 int litho_version(void);
@@ -456,6 +457,73 @@ int litho_tcc_apply_vector(const void *q_hat, const float *w_shifted, const void
 int litho_film_pupils(const void *pupil, int planes, int pn, double NA, double index, int radiometric, const double *layers, int L,
                       double substrate_n, double substrate_k, int resist, const double *depths_nm, int D,
                       const double *defocus_nm_host, double wavelength, void *out, void *stream);
+
+/* ---- Resist development (csrc/develop.hip; no reference counterpart, checked against tests/develop_oracle.py; DESIGN.md
+ * section 10): latent-image diffusion, Mack's dissolution rate and the arrival time of the development front.
+ * Grid: a volume is fp32 [D, n, n], 1 <= D <= 32 planes through ONE resist layer of `thickness` nm, plane d at depth
+ * z_d = (d + 1/2) hz, hz = thickness / D (the depths of litho_film_pupils' midpoint sampling), lateral pitch h = the image's
+ * pixel size in nm, x fastest.  A batch is [B, D, n, n], B D <= 65535, n any size 1..16384.
+ *
+ * 1. Latent-image diffusion.  A separable Gaussian on the intensity volume, along x, then y, then z.  Taps on each axis are
+ * exactly litho_postprocess_resist_diffused's: g[k] = exp(-k^2 / (2 sigma_px^2)), R = ceil(4 sigma_px) <= 32, normalised over
+ * -R..R in double, rounded to fp32; fp32 accumulation acc = g[0] c[0], then acc += g[k] (c[-k] + c[k]) in ascending k.  Laterally
+ * the volume is zero outside the grid (sigma_px = sigma_nm / h); in z the layer faces are mirrored, no flux: index -1 - k reads
+ * k and D + k reads D - 1 - k, repeated as often as needed (sigma_px = sigma_nm / hz) -- acid does not leave the layer.  sigma = 0
+ * on an axis is the identity on that axis, bit for bit.
+ *
+ * 2. Rate: Dill C exposure and Mack's model, per cell in double, rounded to fp32 once:
+ *   m = exp(-(C g) I), g the gain (dose);  x = (1 - m)^q;  a = (q + 1) / (q - 1) (1 - m_th)^q;
+ *   r = r_max (a + 1) x / (a + x) + r_min   [nm / s],  times the surface-inhibition factor 1 - (1 - r0) exp(-z_d / delta)
+ * (r0 = 1: the factor is exactly 1).  The kernel writes the slowness s = 1 / r.  Where 1 - m is negative or NaN (a negative
+ * product g I, a NaN intensity) it writes NaN explicitly -- (1 - m)^q alone is finite there for an integer q -- and the solver
+ * treats a NaN slowness as a wall.
+ *
+ * 3. Arrival time T in seconds: the first-order Godunov upwind solution of |grad T| = s with T = 0 on the resist top z = 0, which
+ * lies hz / 2 above plane 0.  There is no neighbour beyond the lateral edges of the grid or below plane D - 1; a missing neighbour
+ * counts as +inf.  A cell whose s is not finite and positive is a WALL: it keeps T = +inf and passes nothing on.  For a cell,
+ * on each axis a_i = the smaller of the two neighbours and h_i the spacing, (h, h, hz); for plane 0 the z-axis value is 0 at spacing
+ * hz / 2.  Sort the a_i ascending; with delta_i = a_i - a_1, w_i = 1 / h_i^2, solve for u = T - a_1 (the shifted form: the unshifted
+ * discriminant cancels once T >> h s), all in fp32:
+ *   one axis:    u = h_1 s; accepted if u <= delta_2;
+ *   two axes:    A = w_1 + w_2, Bq = w_2 delta_2, Cq = w_2 delta_2^2 - s^2, u = (Bq + sqrt(max(Bq^2 - A Cq, 0))) / A; accepted if
+ *                u <= delta_3;
+ *   three axes:  the same with w_3, w_3 delta_3, w_3 delta_3^2 added;
+ * the discriminant is evaluated in the algebraically equal form A s^2 - sum_{i<j} w_i w_j (delta_i - delta_j)^2 (delta_1 = 0), which
+ * subtracts nothing of size (w delta)^2 and so keeps its bits when hz << h;
+ * G = a_1 + u (+inf when a_1 is).  T is the fixed point of T <- min(T, G(T)) started from +inf.  s^2 must be finite in fp32.
+ *
+ * 4. Developed depth z* [B, n, n] in nm: the first crossing of T = t going down each column, fp32.  T_0 > t: z* = z_0 (t / T_0);
+ * first d >= 1 with T_d > t: z* = z_{d-1} + hz ((t - T_{d-1}) / (T_d - T_{d-1})); every plane developed: z* = thickness (cleared).
+ * The remaining resist height is thickness - z*.
+ *
+ * litho_latent_diffuse: image, out fp32 [B,D,n,n], not overlapping; one gather kernel per pass, up to three.  work: B D n^2
+ * floats on the device, needed (non-NULL, else LITHO_E_ARG; smaller: LITHO_E_WORKSPACE) when two or three passes run, and then
+ * overlapping neither image nor out (LITHO_E_ARG: a pass would read the buffer it writes).  A sigma
+ * that is negative, not finite or gives R > 32: LITHO_E_ARG.  Asynchronous, no allocation, no host wait.
+ * litho_develop_rate: image fp32 [volumes,D,n,n]; gains_host: n_gains <= 64 host floats, as litho_measure_cd; slowness fp32
+ * [n_gains volumes, D, n, n], gain-major; n_gains volumes D <= 65535.  LITHO_E_ARG unless C > 0, r_max > 0, r_min > 0, q > 1,
+ * 0 <= m_th < 1, 0 < surface_rate (r0) <= 1, surface_depth_nm (delta) > 0, thickness_nm > 0, all finite, no NaN gain.  One kernel,
+ * asynchronous, no allocation, no host wait.
+ * litho_develop_time: slowness, T fp32 [B,D,n,n], not overlapping each other or work (LITHO_E_ARG).  A tiled fast-iterative solver: a workgroup relaxes a 16 x 16 x D tile in
+ * LDS for a fixed number of rounds (columns in two colours, no races, no atomics: two calls give the same bits, and a batch
+ * equals its volumes solved one by one), launches ping-pong T between `T` and `work`, and a launch that lowers no cell ends the
+ * loop.  READS BACK: every fourth launch the call copies the launches' change flags to the host and waits for `stream`; it
+ * cannot be captured into a graph.  *launches_host = the number of launches up to and including the first that changed nothing.
+ * After max_iterations launches (1..65536) without one: LITHO_E_NOCONV, *launches_host = max_iterations, and T holds an
+ * unconverged upper bound that must not be used.  work: litho_develop_work_bytes(B, D, n, max_iterations) device bytes
+ * (0 for a bad argument), 16-byte aligned; less is LITHO_E_WORKSPACE.  No allocation.
+ * litho_developed_depth: T fp32 [B,D,n,n], depth fp32 [B,n,n]; develop_time_s >= 0 and finite.  One kernel, asynchronous.
+ * All five: a null pointer, D outside 1..32, n outside 1..16384, B < 1 or B D > 65535: LITHO_E_ARG before any GPU call. */
+int litho_latent_diffuse(const float *image, int B, int D, int n, double sigma_xy_px, double sigma_z_px, float *out, void *work,
+                         size_t work_bytes, void *stream);
+int litho_develop_rate(const float *image, int volumes, int D, int n, const float *gains_host, int n_gains, double C, double r_max,
+                       double r_min, double q, double m_th, double surface_rate, double surface_depth_nm, double thickness_nm,
+                       float *slowness, void *stream);
+size_t litho_develop_work_bytes(int B, int D, int n, int max_iterations);
+int litho_develop_time(const float *slowness, int B, int D, int n, double thickness_nm, double pixel_nm, int max_iterations,
+                       float *T, void *work, size_t work_bytes, int *launches_host, void *stream);
+int litho_developed_depth(const float *T, int B, int D, int n, double thickness_nm, double develop_time_s, float *depth,
+                          void *stream);
 
 /* ---- Mask gradients of Hopkins imaging (csrc/socs_grad.hip; no reference counterpart, checked against tests/socs_grad_oracle.py).
  * With F[q][i] = exp(+2 pi i (i - c)(q - c) / N), c = pn / 2, q, i in [0, pn), the engine's chain at shift (0,0) is L(X) = F X F^T,

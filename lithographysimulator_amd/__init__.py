@@ -17,6 +17,8 @@ from .ilt import (ILTResult, hopkinsFields, hopkinsGradient, hopkinsIntensityAD,
 from .vector import (sourcePolarization, vectorAbbeIntensity, vectorPupils,            # noqa: F401
                      vectorSocsKernels)
 from .film import FilmStack, filmPupils                                                 # noqa: F401
+from .develop import (MackResist, ResistProfile, developedDepth, developmentRate,      # noqa: F401
+                      developmentTime, latentDiffusion, resistProfile)
 from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
@@ -29,4 +31,5 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "processVariationBand", "SOCSKernels", "socsKernels", "hopkinsIntensity", "hopkinsImage",
            "hopkinsFields", "hopkinsGradient", "hopkinsIntensityAD", "maskSpectrumAdjoint", "postProcessAdjoint", "optimizeMask", "ILTResult",
            "vectorPupils", "sourcePolarization", "vectorSocsKernels", "vectorAbbeIntensity",
-           "FilmStack", "filmPupils"]
+           "FilmStack", "filmPupils",
+           "MackResist", "ResistProfile", "latentDiffusion", "developmentRate", "developmentTime", "developedDepth", "resistProfile"]

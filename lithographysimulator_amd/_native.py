@@ -13,7 +13,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LITHO_ABBE_LIB") or os.path.join(_HERE, "lib", "liblitho_abbe.so")
 
-LITHO_OK, E_ARG, E_NSMALL, E_WORKSPACE, E_HIP, E_INDEX = 0, -1, -2, -3, -4, -5
+LITHO_OK, E_ARG, E_NSMALL, E_WORKSPACE, E_HIP, E_INDEX, E_NOCONV = 0, -1, -2, -3, -4, -5, -6
 _lib = None
 
 _SIGNATURES = {
@@ -65,6 +65,13 @@ _SIGNATURES = {
     "litho_vector_pupils": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_int, POINTER(c_double), c_double, c_void_p, c_void_p]),
     "litho_film_pupils": (c_int, [c_void_p, c_int, c_int, c_double, c_double, c_int, POINTER(c_double), c_int, c_double, c_double, c_int,
                                   POINTER(c_double), c_int, POINTER(c_double), c_double, c_void_p, c_void_p]),
+    "litho_latent_diffuse": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "litho_develop_rate": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), c_int, c_double, c_double, c_double, c_double,
+                                   c_double, c_double, c_double, c_double, c_void_p, c_void_p]),
+    "litho_develop_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "litho_develop_time": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_size_t,
+                                   POINTER(c_int), c_void_p]),
+    "litho_developed_depth": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p]),
     "litho_tcc_apply_vector_work_bytes": (c_size_t, [c_int, c_int]),
     "litho_tcc_apply_vector": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "litho_socs_fields": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
@@ -123,6 +130,9 @@ def check(rc, what):
         raise RuntimeError(f"{what}: HIP error: {lib().litho_last_error().decode()}")
     if rc == E_WORKSPACE:
         raise RuntimeError(f"{what}: workspace too small")
+    if rc == E_NOCONV:
+        raise RuntimeError(f"{what}: the development front did not reach its fixed point within the launch cap (maxIterations); "
+                           "the arrival times are not a result")
     raise ValueError(f"{what}: unsupported or invalid argument (pn must be even, 2..16384; N a power of two, "
                      "16..16384)")
 

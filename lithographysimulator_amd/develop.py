@@ -1,0 +1,264 @@
+"""Resist development: Mack's dissolution rate and the propagation of the development front; no reference counterpart
+(include/litho_abbe.h; csrc/develop.hip).
+
+`vectorSocsKernels(film=, depths=)` gives the intensity at D depths inside the resist.  This module turns such a [D, n, n] stack
+into a resist PROFILE: the latent image is diffused (lateral and vertical acid diffusion, the vertical one with no flux through
+the layer faces -- what removes the standing-wave scallops a post-exposure bake removes), exposure and Mack's model give a
+dissolution rate per cell, and the arrival time T of the development front is the first-order upwind solution of |grad T| = 1 / r
+with T = 0 on the resist top.  The planes of T are [planes, n, n] fp32 like any image: `measureCD`, `measureEPE`, `traceContours`,
+`processVariationBand` and the GDSII writer take them unchanged, with the threshold = the development time and exposed=False
+(developed = T below the threshold).
+
+Grid: plane d of D sits at depth (d + 1/2) thickness / D, `FilmStack.depths(D)`; the lateral pitch is the image's pixel size.
+A batch is [B, D, n, n] with B = doses x focal planes, dose-major.
+
+NOT built: reaction-diffusion post-exposure bake with quencher, bleaching (Dill A, B: the intensity is taken as given),
+development of anything but one layer, gradients through development."""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from . import _native as nat
+from .film import FilmStack
+
+MAX_PLANES = 32
+
+
+class MackResist:
+    """Dill C exposure and Mack's dissolution model, a plain value class.
+
+    m = exp(-C dose I) is the inhibitor left after exposure; r = rMax (a + 1)(1 - m)^q / (a + (1 - m)^q) + rMin in nm / s with
+    a = (q + 1) / (q - 1) (1 - mTh)^q.  C > 0 (per unit of dose x intensity), rMax > 0, rMin > 0, q > 1, 0 <= mTh < 1.
+    `surfaceRate` r0 in (0, 1] and `surfaceDepth` delta > 0 (nm; None: the factor is switched off) give the surface inhibition
+    factor 1 - (1 - r0) exp(-z / delta).  `diffusionLength` / `verticalDiffusionLength` (nm, >= 0) are the lateral and vertical
+    standard deviations of the latent-image diffusion."""
+
+    def __init__(self, C, rMax, rMin, q, mTh, surfaceRate=1.0, surfaceDepth=None, diffusionLength=0.0, verticalDiffusionLength=0.0):
+        self.C, self.rMax, self.rMin, self.q, self.mTh = float(C), float(rMax), float(rMin), float(q), float(mTh)
+        self.surfaceRate = float(surfaceRate)
+        self.surfaceDepth = None if surfaceDepth is None else float(surfaceDepth)
+        self.diffusionLength, self.verticalDiffusionLength = float(diffusionLength), float(verticalDiffusionLength)
+        pos = lambda v: v > 0.0 and math.isfinite(v)                              # noqa: E731
+        if not (pos(self.C) and pos(self.rMax) and pos(self.rMin)):
+            raise ValueError("MackResist: C, rMax and rMin must be positive and finite")
+        if not (self.q > 1.0 and math.isfinite(self.q)):
+            raise ValueError(f"MackResist: q > 1 is required; got {q}")
+        if not 0.0 <= self.mTh < 1.0:
+            raise ValueError(f"MackResist: 0 <= mTh < 1 is required; got {mTh}")
+        if not 0.0 < self.surfaceRate <= 1.0:
+            raise ValueError(f"MackResist: 0 < surfaceRate <= 1 is required; got {surfaceRate}")
+        if self.surfaceDepth is not None and not pos(self.surfaceDepth):
+            raise ValueError(f"MackResist: surfaceDepth must be positive and finite (nm), or None; got {surfaceDepth}")
+        if self.surfaceDepth is None and self.surfaceRate != 1.0:
+            raise ValueError("MackResist: a surfaceRate below 1 needs a surfaceDepth (nm)")
+        for name in ("diffusionLength", "verticalDiffusionLength"):
+            v = getattr(self, name)
+            if not (v >= 0.0 and math.isfinite(v)):
+                raise ValueError(f"MackResist: {name} must be finite and >= 0 nm; got {v}")
+
+    def rate(self, m):
+        """Mack's rate at inhibitor concentration m (host, float64): rMin at m = 1, rMax + rMin at m = 0."""
+        a = (self.q + 1.0) / (self.q - 1.0) * (1.0 - self.mTh) ** self.q
+        x = (1.0 - np.asarray(m, dtype=np.float64)) ** self.q
+        return (self.rMax * (a + 1.0)) * x / (a + x) + self.rMin
+
+    def __repr__(self):
+        return (f"MackResist(C={self.C}, rMax={self.rMax}, rMin={self.rMin}, q={self.q}, mTh={self.mTh}, surfaceRate={self.surfaceRate}, "
+                f"surfaceDepth={self.surfaceDepth}, diffusionLength={self.diffusionLength}, "
+                f"verticalDiffusionLength={self.verticalDiffusionLength})")
+
+
+def _volume(who, t, what="image"):
+    """A float32 GPU tensor [D,n,n] or [B,D,n,n] as contiguous [B,D,n,n]; returns (tensor, B, D, n, batched, device)."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() not in (3, 4) or t.shape[-1] != t.shape[-2]:
+        raise ValueError(f"{who}: {what} must be a float32 tensor [D,n,n] or [B,D,n,n]; got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+    dev = nat.require_gpu(t.device)
+    batched = t.dim() == 4
+    v = t.detach().contiguous()
+    if not batched:
+        v = v[None]
+    B, D, n = int(v.shape[0]), int(v.shape[1]), int(v.shape[-1])
+    if not (1 <= D <= MAX_PLANES and 1 <= n <= 16384 and B >= 1 and B * D <= 65535):
+        raise ValueError(f"{who}: 1 <= D <= {MAX_PLANES} planes, 1 <= n <= 16384 and B D <= 65535 are required; got B {B}, D {D}, n {n}")
+    return v, B, D, n, batched, dev
+
+
+def _positive(who, name, v):
+    v = float(v)
+    if not (v > 0.0 and math.isfinite(v)):
+        raise ValueError(f"{who}: {name} must be positive and finite; got {v}")
+    return v
+
+
+def latentDiffusion(image, thickness, pixelSize, diffusionLength=0.0, verticalDiffusionLength=0.0):
+    """The intensity volume [D,n,n] or [B,D,n,n] convolved with a separable Gaussian (litho_latent_diffuse): standard deviation
+    `diffusionLength` nm along x and y with zeros outside the grid -- the taps of resistContour(diffusionLength=) -- and
+    `verticalDiffusionLength` nm along z with the layer faces mirrored.  4 sigma may span at most 32 cells on an axis; a length
+    of 0 leaves that axis untouched bit for bit."""
+    who = "latentDiffusion"
+    v, B, D, n, batched, dev = _volume(who, image)
+    thickness, h = _positive(who, "thickness", thickness), _positive(who, "pixelSize", pixelSize)
+    sxy, sz = float(diffusionLength) / h, float(verticalDiffusionLength) / (thickness / D)
+    for name, s in (("diffusionLength", sxy), ("verticalDiffusionLength", sz)):
+        if not (0.0 <= s <= 8.0):
+            raise ValueError(f"{who}: {name} must be >= 0 and span at most 8 cells (4 sigma <= 32 cells); got {s:g} cells")
+    out = torch.empty_like(v)
+    passes = (2 if sxy > 0 else 0) + (1 if sz > 0 else 0)
+    work = torch.empty_like(v) if passes >= 2 else None
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_latent_diffuse(nat.ptr(v), B, D, n, sxy, sz, nat.ptr(out), nat.ptr(work) if work is not None else None,
+                                                 work.numel() * 4 if work is not None else 0, nat.stream_ptr(dev)), "litho_latent_diffuse")
+        if work is not None:
+            work.record_stream(torch.cuda.current_stream(dev))
+    return out if batched else out[0]
+
+
+def developmentRate(image, resist, thickness, pixelSize, doses=(1.0,)):
+    """The slowness 1 / r in s / nm of `resist` (a MackResist) exposed by the intensity volume `image`, fp32 [D,n,n] or [F,D,n,n]
+    on the GPU, through a layer of `thickness` nm: the latent-image diffusion of `resist` first (latentDiffusion), then
+    litho_develop_rate.  Returns [len(doses) F, D, n, n], dose-major; at most 64 doses.  Where dose x intensity is negative or
+    NaN the slowness is NaN (written explicitly by the kernel, whatever q), a wall to developmentTime."""
+    who = "developmentRate"
+    if not isinstance(resist, MackResist):
+        raise TypeError(f"{who}: resist must be a MackResist")
+    v, F, D, n, _, dev = _volume(who, image)
+    thickness, h = _positive(who, "thickness", thickness), _positive(who, "pixelSize", pixelSize)
+    gains = [float(d) for d in doses]
+    if not 1 <= len(gains) <= 64:
+        raise ValueError(f"{who}: between 1 and 64 doses per call; got {len(gains)}")
+    if len(gains) * F * D > 65535:
+        raise ValueError(f"{who}: doses x volumes x planes exceeds 65535")
+    if resist.diffusionLength > 0.0 or resist.verticalDiffusionLength > 0.0:
+        v = latentDiffusion(v, thickness, h, resist.diffusionLength, resist.verticalDiffusionLength)
+    out = torch.empty((len(gains) * F, D, n, n), dtype=torch.float32, device=dev)
+    g = (ctypes.c_float * len(gains))(*gains)
+    delta = resist.surfaceDepth if resist.surfaceDepth is not None else thickness
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_develop_rate(nat.ptr(v), F, D, n, g, len(gains), resist.C, resist.rMax, resist.rMin, resist.q,
+                                               resist.mTh, resist.surfaceRate, delta, thickness, nat.ptr(out), nat.stream_ptr(dev)),
+                  "litho_develop_rate")
+        v.record_stream(torch.cuda.current_stream(dev))
+    return out
+
+
+def _development_time(slowness, thickness, pixelSize, maxIterations):
+    who = "developmentTime"
+    s, B, D, n, batched, dev = _volume(who, slowness, "slowness")
+    thickness, h = _positive(who, "thickness", thickness), _positive(who, "pixelSize", pixelSize)
+    maxIterations = int(maxIterations)
+    if not 1 <= maxIterations <= 65536:
+        raise ValueError(f"{who}: maxIterations must be 1 ... 65536; got {maxIterations}")
+    T = torch.empty_like(s)
+    nbytes = int(nat.lib().litho_develop_work_bytes(B, D, n, maxIterations))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    launches = ctypes.c_int(0)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_develop_time(nat.ptr(s), B, D, n, thickness, h, maxIterations, nat.ptr(T), nat.ptr(work), nbytes,
+                                               ctypes.byref(launches), nat.stream_ptr(dev)), "litho_develop_time")
+    return (T if batched else T[0]), launches.value
+
+
+def developmentTime(slowness, thickness, pixelSize, maxIterations=1024, returnLaunches=False):
+    """The arrival time T in seconds of the development front (litho_develop_time): the first-order upwind solution of
+    |grad T| = slowness with T = 0 on the resist top, half a plane spacing above plane 0.  `slowness` fp32 [D,n,n] or [B,D,n,n] in
+    s / nm on the GPU; a cell whose slowness is not finite and positive is a wall and keeps T = +inf, as does every cell the front
+    cannot reach.  The solver iterates to its fixed point and waits for the device while it does; if `maxIterations` launches do
+    not reach it, RuntimeError is raised -- an unconverged field is never returned.  Deterministic: the same bits on every call,
+    and a batch equals its volumes solved one at a time.  returnLaunches=True returns (T, launches)."""
+    T, launches = _development_time(slowness, thickness, pixelSize, maxIterations)
+    return (T, launches) if returnLaunches else T
+
+
+def developedDepth(T, thickness, developTime):
+    """How deep each column is developed after `developTime` seconds (litho_developed_depth): fp32 [n,n] or [B,n,n] in nm below the
+    resist top, the first crossing of T = developTime going down, linear between planes; `thickness` where the column has cleared
+    to the bottom of the layer.  The remaining resist height is thickness - depth."""
+    who = "developedDepth"
+    v, B, D, n, batched, dev = _volume(who, T, "T")
+    thickness = _positive(who, "thickness", thickness)
+    t = float(developTime)
+    if not (t >= 0.0 and math.isfinite(t)):
+        raise ValueError(f"{who}: developTime must be finite and >= 0; got {developTime}")
+    out = torch.empty((B, n, n), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_developed_depth(nat.ptr(v), B, D, n, thickness, t, nat.ptr(out), nat.stream_ptr(dev)),
+                  "litho_developed_depth")
+        v.record_stream(torch.cuda.current_stream(dev))
+    return out if batched else out[0]
+
+
+class ResistProfile:
+    """What resistProfile returns.  `T` fp32 [doses, F, D, n, n]: arrival times in seconds (+inf where the developer never
+    arrives); `depth` fp32 [doses, F, n, n]: developed depth in nm; `launches`: solver launches; `thickness`, `pixelSize`,
+    `developTime`, `doses` as given.
+
+    For the metrology helpers +inf in T is replaced by the finite value 2 developTime + 1 (`clampedT`), because measureCD and
+    traceContours interpolate linearly between samples: an edge next to a cell the developer never reaches then lies where a
+    cell of that arrival time would put it, not at a NaN."""
+
+    def __init__(self, T, depth, launches, thickness, pixelSize, developTime, doses):
+        self.T, self.depth, self.launches = T, depth, launches
+        self.thickness, self.pixelSize, self.developTime, self.doses = thickness, pixelSize, developTime, tuple(doses)
+
+    @property
+    def clampedT(self):
+        return torch.where(torch.isposinf(self.T), torch.full_like(self.T, 2.0 * self.developTime + 1.0), self.T)
+
+    def cd(self, gauges, exposed=False):
+        """measureCD on every plane of T with threshold developTime: fp32 [doses, F D, G, 5] = (cd_nm, x_lo, x_hi, ils_lo,
+        ils_hi).  exposed=False (the default) measures the developed run through the gauge -- a space or a contact."""
+        from .imageformation import measureCD
+        nd, F, D, n = self.T.shape[0], self.T.shape[1], self.T.shape[2], self.T.shape[-1]
+        out = measureCD(self.clampedT.reshape(nd * F * D, n, n), self.developTime, gauges, self.pixelSize, exposed=exposed)
+        return out.reshape(nd, F * D, out.shape[2], 5)
+
+    def sidewallAngle(self, gauge, exposed=False):
+        """Side-wall angles in degrees at one gauge (row, col, axis), float64 [doses, F, 2]: a least-squares line through the edge
+        positions x_lo(z_d) and x_hi(z_d) of `cd` over the depths where the feature exists, on the host.  The angle is measured
+        inside the resist from the substrate plane: 90 is a vertical wall, below 90 a developed space that narrows with depth;
+        NaN with fewer than two usable depths."""
+        nd, F, D = self.T.shape[0], self.T.shape[1], self.T.shape[2]
+        table = self.cd([tuple(int(v) for v in gauge)], exposed=exposed).cpu().numpy().astype(np.float64).reshape(nd, F, D, 5)
+        z = self.thickness * (np.arange(D) + 0.5) / D
+        out = np.full((nd, F, 2), np.nan)
+        for i in range(nd):
+            for f in range(F):
+                for e, sign in ((0, -1.0), (1, 1.0)):
+                    x = table[i, f, :, 1 + e] * self.pixelSize
+                    ok = np.isfinite(x) & (table[i, f, :, 0] > 0)
+                    if ok.sum() >= 2:
+                        slope = np.polyfit(z[ok], x[ok], 1)[0]                       # d(edge) / dz, nm per nm
+                        out[i, f, e] = 90.0 + sign * math.degrees(math.atan(slope))
+        return out
+
+    def contours(self, depth_index, exposed=False):
+        """traceContours of T at plane `depth_index` with threshold developTime: result[dose][focal plane] is a Contours."""
+        from .contours import traceContours
+        nd, F, n = self.T.shape[0], self.T.shape[1], self.T.shape[-1]
+        planes = self.clampedT[:, :, int(depth_index)].reshape(nd * F, n, n).contiguous()
+        flat = traceContours(planes, self.developTime, exposed=exposed)[0]
+        return [flat[i * F:(i + 1) * F] for i in range(nd)]
+
+
+def resistProfile(image, resist, stack_or_thickness, pixelSize, developTime, doses=(1.0,), focalPlanes=1, maxIterations=1024):
+    """The chain developmentRate -> developmentTime -> developedDepth on an intensity stack.  `image` fp32 [F D, n, n] in the plane
+    order hopkinsImage returns for vectorSocsKernels(film=, depths=stack.depths(D)) (plane f D + d), F = `focalPlanes`;
+    `stack_or_thickness` the FilmStack (its resist layer is developed) or the thickness in nm.  Returns a ResistProfile; before
+    its T goes to measureCD or traceContours, +inf is clamped to 2 developTime + 1 (ResistProfile)."""
+    who = "resistProfile"
+    thickness = stack_or_thickness.thickness if isinstance(stack_or_thickness, FilmStack) else float(stack_or_thickness)
+    F = int(focalPlanes)
+    if not isinstance(image, torch.Tensor) or image.dim() != 3 or F < 1 or image.shape[0] % F:
+        raise ValueError(f"{who}: image must be [focalPlanes x D, n, n]; got {tuple(getattr(image, 'shape', ()))} with focalPlanes {focalPlanes}")
+    t = float(developTime)
+    if not (t > 0.0 and math.isfinite(t)):
+        raise ValueError(f"{who}: developTime must be positive and finite; got {developTime}")
+    D, n = image.shape[0] // F, image.shape[-1]
+    s = developmentRate(image.reshape(F, D, n, n), resist, thickness, pixelSize, doses)
+    T, launches = _development_time(s, thickness, pixelSize, maxIterations)
+    depth = developedDepth(T, thickness, t)
+    nd = len(tuple(doses))
+    return ResistProfile(T.reshape(nd, F, D, n, n), depth.reshape(nd, F, n, n), launches, thickness, float(pixelSize), t, doses)

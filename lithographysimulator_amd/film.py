@@ -18,8 +18,9 @@ With every index equal to the incident one the planes are vectorPupils(defocus=z
 The depth-averaged ("bulk") image sum_d omega_d I(z_d) has the transmission cross coefficient sum_d omega_d T_d, which is
 factored as ONE kernel set (`depthWeights`): a bulk image costs K fields, not D K.
 
-NOT built: absorbed-energy weighting (n k |E|^2 is a constant factor inside one layer), development models, layers with a
-gradient in index, a per-depth vectorAbbeIntensity beyond reshaping the planes to [planes D, 6, pn, pn]."""
+NOT built: absorbed-energy weighting (n k |E|^2 is a constant factor inside one layer), layers with a gradient in index, a
+per-depth vectorAbbeIntensity beyond reshaping the planes to [planes D, 6, pn, pn].  Development of the resist from the
+per-depth images is develop.py."""
 import ctypes
 import math
 from functools import partial
