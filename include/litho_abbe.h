@@ -525,6 +525,72 @@ int litho_develop_time(const float *slowness, int B, int D, int n, double thickn
 int litho_developed_depth(const float *T, int B, int D, int n, double thickness_nm, double develop_time_s, float *depth,
                           void *stream);
 
+/* ---- Post-exposure bake of a chemically amplified resist (csrc/peb.hip; no reference counterpart, checked against the float64
+ * restatement tests/peb_oracle.py).  Acid h, base quencher q (both relative to the initial PAG) and the accumulated acid dose a
+ * [s] on the grid of the development calls: fp32 [B, D, n, n], plane d at depth (d + 1/2) hz, hz = thickness / D, lateral pitch
+ * `pixel`; lengths in nm, times in s.  A bake makes the slowness volume that litho_develop_time takes, in place of
+ * litho_latent_diffuse and litho_develop_rate.
+ *
+ * 1. Exposure: h0 = 1 - exp(-(C g) I), g the gain (dose), per cell in double, rounded to fp32 once; NaN where that is negative
+ * or NaN (a negative product g I, a NaN intensity), litho_develop_rate's convention.  q starts uniform at q0 >= 0, a at 0.
+ *
+ * 2. One bake step of length dt = bake_time / S, all in fp32, each line a fixed sequence of single operations:
+ *   diffusion       x' = x + lxy (((W + E) + (S + N)) - 4 x) + lz ((U + Dn) - 2 x)  for x = h and x = q, both from the values at
+ *                   the start of the step (Jacobi); W, E, S, N the lateral neighbours, U, Dn the planes above and below.  NO FLUX
+ *                   through any of the six faces: a neighbour outside the grid is the cell's mirror image, index -1 <-> 0 (the
+ *                   cell itself).  lxy = D_s dt / pixel^2 and lz = D_z dt / hz^2 per species, from the customary diffusion lengths
+ *                   sigma = sqrt(2 D_s bake_time) and sigma_z = vertical_scale sigma: lxy = sigma^2 / (2 S pixel^2),
+ *                   lz = sigma_z^2 / (2 S hz^2), formed in double and rounded to fp32.  A species with sigma = 0 skips this line
+ *                   and is left untouched bit for bit.
+ *   neutralisation  beta = fp32(k_quench dt); R = beta h' q' / (1 + beta (h' + q')) (left to right), or, when beta is +inf
+ *                   (k_quench = +inf, instantaneous), R = (h' < q') ? h' : q' -- written like this so that a NaN behaves as in
+ *                   numpy.where; h'' = h' - R, q'' = q' - R.  h - q is conserved; in exact arithmetic neither goes negative.
+ *   acid loss       h''' = h'' fl, fl = fp32(exp(-k_loss dt)) from the host.
+ *   amplification   a <- a + fp32(dt / 2) (h_at_the_start_of_the_step + h''')  (trapezoid).
+ * (Unlike litho_latent_diffuse, which puts zeros outside the grid laterally, the bake mirrors: mass is then conserved exactly
+ * and a bake does not drain acid out of the picture.)
+ *
+ * 3. After S steps: inhibitor m = exp(-k_amp a), Mack's rate r(m) of litho_develop_rate with x = (1 - m)^q, times the surface
+ * factor of the plane; slowness 1 / r.  Double per cell, rounded once; NaN where 1 - m is negative or NaN, a wall to
+ * litho_develop_time.  a = 0 gives m = 1 and r = r_min exactly.
+ *
+ * Steps.  litho_peb_min_steps: the smallest S with 4 lxy + 2 lz <= 1 (in double) for both species -- every diffusion update is
+ * then a convex combination: a maximum principle holds and no concentration goes negative; 0 for a bad argument (a negative or
+ * non-finite length or scale, thickness or pixel not positive and finite, D outside 1..32) or when that S exceeds the cap 65536.
+ * The reaction is first order in dt: raise S for a stiff finite k_quench.
+ *
+ * litho_peb_expose: image fp32 [volumes,D,n,n]; gains_host: n_gains <= 64 host floats; acid fp32 [n_gains volumes, D, n, n],
+ * gain-major, not overlapping image; n_gains volumes D <= 65535; C > 0 and finite, no NaN gain.  One kernel, asynchronous.
+ * litho_peb_bake: acid_in (h0), acid, quencher, acid_dose fp32 [B,D,n,n] and work, litho_peb_work_bytes(B, D, n) = two volumes
+ * of device bytes (0 for a bad argument), 16-byte aligned: none may overlap another (LITHO_E_ARG); less workspace is
+ * LITHO_E_WORKSPACE.  quencher0, k_loss, the two diffusion lengths and vertical_scale >= 0 and finite, k_quench >= 0 (+inf
+ * allowed; a finite k_quench whose beta overflows fp32 counts as +inf), bake_time_s > 0 and finite, steps from
+ * litho_peb_min_steps(...) to 65536; anything else is LITHO_E_ARG.  Two kernels run the one step function: a direct kernel, one
+ * step per launch with the neighbours from global memory, and a fused kernel that runs s = 2..4 steps per launch on a
+ * 16 x 16 x D tile with an s-cell halo in LDS, D (4 (16 + 2 s)^2 + 256) floats.  steps_per_launch = 0: the largest s <= 4 whose
+ * LDS fits the library's budget, else the direct kernel (litho_peb_steps_per_launch(D) tells which; 0 for a bad D) -- the
+ * budget is 0 today, the direct kernel being the faster one wherever it was timed (LABNOTES), so 0 means the direct kernel;
+ * 1: the direct kernel; 2..4: the fused kernel, LITHO_E_ARG if its LDS exceeds the 160 KiB of a workgroup (D = 32 always does).
+ * The steps left over by steps mod s run as a shorter last launch.  The result does NOT depend on steps_per_launch, bit for
+ * bit, two calls give the same bits, and a batch equals its volumes baked one at a time: no atomics, no workgroup reads what
+ * another writes.  Launches ping-pong h and q between the outputs and work.  Asynchronous, no allocation, no host wait: it can
+ * be captured into a graph (an explicit steps_per_launch whose LDS exceeds 64 KiB raises the fused kernel's dynamic-LDS limit
+ * on its first call per device: make that call once before capturing).
+ * litho_peb_rate: acid_dose, slowness and the optional inhibitor (NULL: not written) fp32 [B,D,n,n], not overlapping; k_amp > 0
+ * and finite, Mack's parameters and the surface factor as litho_develop_rate checks them.  One kernel, asynchronous.
+ * All: a null pointer, D outside 1..32, n outside 1..16384, B < 1 or B D > 65535: LITHO_E_ARG before any GPU call. */
+int litho_peb_expose(const float *image, int volumes, int D, int n, const float *gains_host, int n_gains, double C, float *acid,
+                     void *stream);
+int litho_peb_min_steps(double sigma_acid_nm, double sigma_quencher_nm, double vertical_scale, double thickness_nm, int D,
+                        double pixel_nm);
+size_t litho_peb_work_bytes(int B, int D, int n);
+int litho_peb_steps_per_launch(int D);
+int litho_peb_bake(const float *acid_in, int B, int D, int n, double thickness_nm, double pixel_nm, double quencher0, double k_quench,
+                   double k_loss, double sigma_acid_nm, double sigma_quencher_nm, double vertical_scale, double bake_time_s, int steps,
+                   int steps_per_launch, float *acid, float *quencher, float *acid_dose, void *work, size_t work_bytes, void *stream);
+int litho_peb_rate(const float *acid_dose, int B, int D, int n, double k_amp, double r_max, double r_min, double q, double m_th,
+                   double surface_rate, double surface_depth_nm, double thickness_nm, float *slowness, float *inhibitor, void *stream);
+
 /* ---- Mask gradients of Hopkins imaging (csrc/socs_grad.hip; no reference counterpart, checked against tests/socs_grad_oracle.py).
  * With F[q][i] = exp(+2 pi i (i - c)(q - c) / N), c = pn / 2, q, i in [0, pn), the engine's chain at shift (0,0) is L(X) = F X F^T,
  * the coherent fields are E_k = L(phi_k . M) and I = sum_k |E_k|^2.  For a real loss l with G = dl/dI,

@@ -19,6 +19,7 @@ from .vector import (sourcePolarization, vectorAbbeIntensity, vectorPupils,     
 from .film import FilmStack, filmPupils                                                 # noqa: F401
 from .develop import (MackResist, ResistProfile, developedDepth, developmentRate,      # noqa: F401
                       developmentTime, latentDiffusion, resistProfile)
+from .peb import BakeResult, ChemicallyAmplifiedResist, postExposureBake              # noqa: F401
 from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
@@ -32,4 +33,5 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "hopkinsFields", "hopkinsGradient", "hopkinsIntensityAD", "maskSpectrumAdjoint", "postProcessAdjoint", "optimizeMask", "ILTResult",
            "vectorPupils", "sourcePolarization", "vectorSocsKernels", "vectorAbbeIntensity",
            "FilmStack", "filmPupils",
-           "MackResist", "ResistProfile", "latentDiffusion", "developmentRate", "developmentTime", "developedDepth", "resistProfile"]
+           "MackResist", "ResistProfile", "latentDiffusion", "developmentRate", "developmentTime", "developedDepth", "resistProfile",
+           "ChemicallyAmplifiedResist", "BakeResult", "postExposureBake"]

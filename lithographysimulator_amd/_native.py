@@ -72,6 +72,14 @@ _SIGNATURES = {
     "litho_develop_time": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_void_p, c_void_p, c_size_t,
                                    POINTER(c_int), c_void_p]),
     "litho_developed_depth": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_void_p, c_void_p]),
+    "litho_peb_expose": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), c_int, c_double, c_void_p, c_void_p]),
+    "litho_peb_min_steps": (c_int, [c_double, c_double, c_double, c_double, c_int, c_double]),
+    "litho_peb_work_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "litho_peb_steps_per_launch": (c_int, [c_int]),
+    "litho_peb_bake": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_double,
+                               c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "litho_peb_rate": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_double,
+                               c_double, c_void_p, c_void_p, c_void_p]),
     "litho_tcc_apply_vector_work_bytes": (c_size_t, [c_int, c_int]),
     "litho_tcc_apply_vector": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "litho_socs_fields": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

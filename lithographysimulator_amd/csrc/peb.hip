@@ -1,0 +1,430 @@
+// peb.hip -- the post-exposure bake of a chemically amplified resist behind litho_peb_expose, litho_peb_bake and litho_peb_rate
+// (no reference counterpart; the definitions are in include/litho_abbe.h, the checker is their float64 restatement
+// tests/peb_oracle.py).  Built with -ffp-contract=off (Makefile): every fp32 result is a fixed sequence of single operations.
+//
+// Volumes are fp32 [B, D, n, n], D <= 32 planes through the resist, x fastest.  Four kernels:
+//   k_peb_expose   acid h0 = 1 - exp(-(C g) I) in double per cell, the gains in a loop inside
+//   k_peb_direct   one bake step per launch: a thread per cell, the six neighbours of both species from global memory
+//   k_peb_fused    s >= 2 bake steps per launch (temporal blocking, below)
+//   k_peb_rate     inhibitor m = exp(-kAmp a), Mack's rate and the surface factor in double per cell, slowness 1 / r out
+// The arithmetic of a step is peb_step and nothing else: both bake kernels call it with the same inputs in the same order, so
+// the bits of a bake do not depend on how its steps are cut into launches.  expose and rate move four consecutive x per thread
+// (16-byte accesses) when n is a multiple of 4 and the pointers are 16-byte aligned, one otherwise.
+//
+// k_peb_fused.  A workgroup owns a 16 x 16 lateral tile with all D planes.  It loads h and q of the tile and an s-cell lateral
+// halo into LDS, W = 16 + 2 s cells on a side; a cell beyond the grid is read from its mirror image (mirror_index, folding as
+// often as needed when n < s), so the LDS window is a piece of the mirror-extended lattice and a ghost cell takes exactly the
+// update of the cell it mirrors (the update pairs W + E and S + N).  Step j = 1 .. s updates the cells [j, W - j)^2 x D from
+// one LDS copy into the other (Jacobi; a barrier; the copies swap): the region that is still exact shrinks by one cell per
+// step and after s steps is the tile.  The amplification integral a is kept for the tile's own cells only, in LDS.  LDS:
+// D (4 W^2 + 256) floats.  Launches ping-pong h and q between the outputs and the caller's workspace; a is updated in place
+// by the one thread that owns the cell.  No workgroup reads what another writes in the same launch; no atomics.
+#include "engine_common.hpp"
+#include "../../include/litho_abbe.h"
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+
+namespace litho {
+
+static constexpr int PEB_DMAX = 32, PEB_GAINS = 64, PEB_TILE = 16, PEB_SMAX = 4, PEB_MAXSTEPS = 65536;
+static constexpr size_t PEB_LDS_MAX = 160 * 1024;         // what one workgroup can have on gfx950
+// The automatic choice of steps per launch takes the largest s <= PEB_SMAX whose LDS fits this budget, else the direct kernel.
+// It started at 64 KiB (two workgroups per CU of 160 KiB) and the first timing (scripts/peb_time.py, LABNOTES: 2048^2, S = 32)
+// set it to 0: the direct kernel runs at 87 - 91 % of the HBM rate, 0.22 ms per step at D = 8 against 0.46 / 0.39 / 0.35 for the
+// untuned fused kernel at s = 2 / 3 / 4 (D = 16: 0.43 against 1.60 / 1.38 / 1.27), which moves fewer bytes but is bound by its
+// index arithmetic and LDS traffic.  Until the fused kernel wins somewhere, the automatic choice is the direct kernel.
+static constexpr size_t PEB_LDS_BUDGET = 0;
+
+struct PebGains {
+    float g[PEB_GAINS];
+};
+struct PebSurface {
+    double f[PEB_DMAX];                                   // the surface-inhibition factor of plane d, from the host
+};
+// what one bake step needs, fp32 as the kernels use it; rides in the kernel arguments
+struct PebStep {
+    float lxy_h, lz_h, lxy_q, lz_q;                       // lambda = D_s dt / spacing^2 per species and direction
+    float beta, fl, half_dt;                              // kQuench dt, exp(-kLoss dt), dt / 2
+    int diffuse_h, diffuse_q, instant;                    // sigma > 0 per species; kQuench dt = +inf
+};
+struct PebNb {
+    float w, e, s, n, u, d;
+};
+
+template <int VEC>
+struct Pack {
+    float v[VEC];
+};
+template <int VEC>
+__device__ __forceinline__ Pack<VEC> load_pack(const float* p)
+{
+    Pack<VEC> r;
+    if constexpr (VEC == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(p);
+        r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w;
+    } else {
+        r.v[0] = *p;
+    }
+    return r;
+}
+template <int VEC>
+__device__ __forceinline__ void store_pack(float* p, const Pack<VEC>& r)
+{
+    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+    else *p = r.v[0];
+}
+
+// index -1 - k <-> k and n + k <-> n - 1 - k, repeated as needed
+__host__ __device__ __forceinline__ int mirror_index(int i, int n)
+{
+    int m = i % (2 * n);
+    if (m < 0) m += 2 * n;
+    return m < n ? m : 2 * n - 1 - m;
+}
+
+// ---- 1. exposure: h0 = 1 - exp(-(C g) I), NaN where that is negative or NaN (litho_develop_rate's convention).  Double per
+// cell, rounded once.  grid.y: the F D planes of the image.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_peb_expose(const float* __restrict__ image, float* __restrict__ out, int planes, int n,
+                                                    const PebGains gains, int n_gains, double C)
+{
+    const long long plane_elems = (long long)n * n;
+    const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
+    if (e >= plane_elems) return;
+    const int p = blockIdx.y;
+    const Pack<VEC> I = load_pack<VEC>(image + (size_t)p * plane_elems + e);
+    for (int gi = 0; gi < n_gains; ++gi) {
+        const double Cg = C * (double)gains.g[gi];
+        Pack<VEC> h;
+        for (int v = 0; v < VEC; ++v) {
+            const double h0 = 1.0 - exp(-(Cg * (double)I.v[v]));
+            h.v[v] = (h0 >= 0.0) ? (float)h0 : __builtin_nanf("");
+        }
+        store_pack<VEC>(out + ((size_t)gi * planes + p) * plane_elems + e, h);
+    }
+}
+
+// ---- 2. one bake step of one cell.  h, q: the cell at the start of the step; nb_h(), nb_q(): its six neighbours at the start
+// of the step, fetched only for a species that diffuses.  Diffusion (Jacobi, no flux), neutralisation, acid loss, and the
+// trapezoid of the amplification integral, in this order; every line is include/litho_abbe.h's.
+template <class FH, class FQ>
+__device__ __forceinline__ void peb_step(const PebStep& P, float h, float q, FH nb_h, FQ nb_q, float& h_new, float& q_new, float& a)
+{
+    float hd = h, qd = q;
+    if (P.diffuse_h) {
+        const PebNb b = nb_h();
+        hd = h + P.lxy_h * (((b.w + b.e) + (b.s + b.n)) - 4.f * h) + P.lz_h * ((b.u + b.d) - 2.f * h);
+    }
+    if (P.diffuse_q) {
+        const PebNb b = nb_q();
+        qd = q + P.lxy_q * (((b.w + b.e) + (b.s + b.n)) - 4.f * q) + P.lz_q * ((b.u + b.d) - 2.f * q);
+    }
+    const float R = P.instant ? ((hd < qd) ? hd : qd) : P.beta * hd * qd / (1.f + P.beta * (hd + qd));
+    h_new = (hd - R) * P.fl;
+    q_new = qd - R;
+    a = a + P.half_dt * (h + h_new);
+}
+
+// grid.x covers the n^2 cells of a plane, grid.y the B D planes.  q_in == nullptr: the first step, q = q0 everywhere and a = 0.
+__global__ __launch_bounds__(256) void k_peb_direct(const float* __restrict__ h_in, const float* __restrict__ q_in, float q0,
+                                                    float* __restrict__ h_out, float* __restrict__ q_out, float* __restrict__ a_io,
+                                                    int D, int n, const PebStep P)
+{
+    const long long plane_elems = (long long)n * n;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= plane_elems) return;
+    const int p = blockIdx.y, d = p % D, row = (int)(e / n), col = (int)(e - (long long)row * n);
+    const size_t at = (size_t)p * plane_elems + e;
+    // a neighbour outside the grid is the cell's mirror image: the cell itself
+    const long long w = col > 0 ? -1 : 0, ea = col + 1 < n ? 1 : 0, s = row > 0 ? -(long long)n : 0, nn = row + 1 < n ? n : 0;
+    const long long u = d > 0 ? -plane_elems : 0, dn = d + 1 < D ? plane_elems : 0;
+    auto around = [&](const float* c) -> PebNb { return PebNb{c[w], c[ea], c[s], c[nn], c[u], c[dn]}; };
+    const bool first = q_in == nullptr;
+    const float h = h_in[at], q = first ? q0 : q_in[at];
+    float a = first ? 0.f : a_io[at], h_new, q_new;
+    peb_step(P, h, q, [&] { return around(h_in + at); }, [&] { return first ? PebNb{q0, q0, q0, q0, q0, q0} : around(q_in + at); }, h_new,
+             q_new, a);
+    h_out[at] = h_new;
+    q_out[at] = q_new;
+    a_io[at] = a;
+}
+
+// grid: (tiles, tiles, B).  Dynamic LDS: D (4 W^2 + 256) floats, W = 16 + 2 s.
+__global__ __launch_bounds__(256) void k_peb_fused(const float* __restrict__ h_in, const float* __restrict__ q_in, float q0,
+                                                   float* __restrict__ h_out, float* __restrict__ q_out, float* __restrict__ a_io,
+                                                   int D, int n, int s, const PebStep P)
+{
+    extern __shared__ __attribute__((aligned(16))) float peb_lds[];
+    const int W = PEB_TILE + 2 * s, WW = W * W, cells = D * WW;
+    float* hc = peb_lds;                                  // [D][W][W]  the current copy of h, tile + halo
+    float* hn = hc + cells;                               //            the next one
+    float* qc = hn + cells;
+    float* qn = qc + cells;
+    float* al = qn + cells;                               // [D][16][16] a of the tile
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * PEB_TILE, y0 = blockIdx.y * PEB_TILE;
+    const size_t plane_elems = (size_t)n * n;
+    const size_t vol = (size_t)blockIdx.z * D * plane_elems;
+    const bool first = q_in == nullptr;
+    for (int i = tid; i < cells; i += 256) {
+        const int d = i / WW, r = i - d * WW, ly = r / W, lx = r - ly * W;
+        const size_t g = vol + (size_t)d * plane_elems + (size_t)mirror_index(y0 - s + ly, n) * n + mirror_index(x0 - s + lx, n);
+        hc[i] = h_in[g];
+        qc[i] = first ? q0 : q_in[g];
+    }
+    // thread tid owns the column (tid / 16, tid % 16) of the tile when a is loaded and when the results are stored
+    const int oy = tid >> 4, ox = tid & 15;
+    const bool inside = y0 + oy < n && x0 + ox < n;
+    const size_t own = vol + (size_t)(y0 + oy) * n + (x0 + ox);
+    for (int d = 0; d < D; ++d) al[d * 256 + tid] = (first || !inside) ? 0.f : a_io[own + (size_t)d * plane_elems];
+    __syncthreads();
+    for (int j = 1; j <= s; ++j) {
+        const int w = W - 2 * j, ww = w * w, todo = D * ww;
+        for (int i = tid; i < todo; i += 256) {
+            const int d = i / ww, r = i - d * ww, ry = r / w, ly = j + ry, lx = j + (r - ry * w);
+            const int c = (d * W + ly) * W + lx;
+            const int up = d > 0 ? -WW : 0, dn = d + 1 < D ? WW : 0;
+            auto around = [&](const float* b) -> PebNb { return PebNb{b[c - 1], b[c + 1], b[c - W], b[c + W], b[c + up], b[c + dn]}; };
+            const int ty = ly - s, tx = lx - s;
+            const bool mine = ty >= 0 && ty < PEB_TILE && tx >= 0 && tx < PEB_TILE;
+            const int ai = d * 256 + ty * PEB_TILE + tx;
+            float h_new, q_new, a = mine ? al[ai] : 0.f;                  // a halo cell's a is not kept
+            peb_step(P, hc[c], qc[c], [&] { return around(hc); }, [&] { return around(qc); }, h_new, q_new, a);
+            hn[c] = h_new;
+            qn[c] = q_new;
+            if (mine) al[ai] = a;
+        }
+        __syncthreads();
+        float* t = hc; hc = hn; hn = t;
+        t = qc; qc = qn; qn = t;
+    }
+    if (!inside) return;
+    for (int d = 0; d < D; ++d) {
+        const int c = (d * W + oy + s) * W + ox + s;
+        const size_t g = own + (size_t)d * plane_elems;
+        h_out[g] = hc[c];
+        q_out[g] = qc[c];
+        a_io[g] = al[d * 256 + tid];
+    }
+}
+
+// ---- 3. rate: m = exp(-kAmp a), x = (1 - m)^q, r = (rmax (a_m + 1)) x / (a_m + x) + rmin, times the surface factor of the
+// plane; slowness = fp32(1 / r), NaN where 1 - m is negative or NaN (k_develop_rate's lines, restated).  grid.y: the B D planes.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_peb_rate(const float* __restrict__ dose, float* __restrict__ slowness, float* __restrict__ inhibitor,
+                                                  int D, int n, double k_amp, double rmax_a1, double rmin, double q, double a_m,
+                                                  const PebSurface surface)
+{
+    const long long plane_elems = (long long)n * n;
+    const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
+    if (e >= plane_elems) return;
+    const int p = blockIdx.y;
+    const double f = surface.f[p % D];
+    const size_t at = (size_t)p * plane_elems + e;
+    const Pack<VEC> a = load_pack<VEC>(dose + at);
+    Pack<VEC> s, mi;
+    for (int v = 0; v < VEC; ++v) {
+        const double m = exp(-(k_amp * (double)a.v[v]));
+        const double x = pow(1.0 - m, q);
+        const double r = (rmax_a1 * x / (a_m + x) + rmin) * f;
+        s.v[v] = (1.0 - m >= 0.0) ? (float)(1.0 / r) : __builtin_nanf("");
+        mi.v[v] = (float)m;
+    }
+    store_pack<VEC>(slowness + at, s);
+    if (inhibitor) store_pack<VEC>(inhibitor + at, mi);
+}
+
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + b_bytes && pb < pa + a_bytes;
+}
+static bool finite_pos(double v) { return v > 0.0 && !std::isinf(v); }
+static bool finite_nonneg(double v) { return v >= 0.0 && !std::isinf(v); }
+static unsigned plane_blocks(int n, int vec) { return (unsigned)(((long long)n * n / vec + 255) / 256); }
+static bool volume_ok(int B, int D, int n) { return B >= 1 && D >= 1 && D <= PEB_DMAX && n >= 1 && n <= 16384 && (long long)B * D <= 65535; }
+static size_t lds_bytes(int D, int s)
+{
+    const size_t W = PEB_TILE + 2 * s;
+    return (size_t)D * (4 * W * W + PEB_TILE * PEB_TILE) * sizeof(float);
+}
+
+// lambda_xy = sigma^2 / (2 S pixel^2), lambda_z = (v sigma)^2 / (2 S hz^2): D_s dt / spacing^2 with sigma = sqrt(2 D_s bakeTime)
+static void lambdas(double sigma, double vscale, double pixel, double hz, int S, double& lxy, double& lz)
+{
+    const double sz = vscale * sigma;
+    lxy = sigma * sigma / (2.0 * S * (pixel * pixel));
+    lz = sz * sz / (2.0 * S * (hz * hz));
+}
+static bool stable(double sigma, double vscale, double pixel, double hz, int S)
+{
+    double lxy, lz;
+    lambdas(sigma, vscale, pixel, hz, S, lxy, lz);
+    return 4.0 * lxy + 2.0 * lz <= 1.0;
+}
+// the smallest S with 4 lambda_xy + 2 lambda_z <= 1 for both species; 0 when the arguments are bad or it exceeds the cap
+static int min_steps(double sigma_h, double sigma_q, double vscale, double thickness, int D, double pixel)
+{
+    if (!finite_nonneg(sigma_h) || !finite_nonneg(sigma_q) || !finite_nonneg(vscale) || !finite_pos(thickness) || !finite_pos(pixel) ||
+        D < 1 || D > PEB_DMAX)
+        return 0;
+    const double hz = thickness / D;
+    const double sigma = sigma_h > sigma_q ? sigma_h : sigma_q;       // both lambdas grow with sigma: the larger one decides
+    const double need = sigma * sigma * (2.0 / (pixel * pixel) + (vscale * vscale) / (hz * hz));
+    if (!(need <= (double)PEB_MAXSTEPS + 1.0)) return 0;              // too many, infinite or NaN
+    int S = (int)need - 1;                                            // the closed form, then settled with the test the kernels' lambdas pass
+    if (S < 1) S = 1;
+    while (S <= PEB_MAXSTEPS && !stable(sigma, vscale, pixel, hz, S)) ++S;
+    return S <= PEB_MAXSTEPS ? S : 0;
+}
+
+}  // namespace litho
+
+extern "C" {
+
+int litho_peb_expose(const float* image, int volumes, int D, int n, const float* gains_host, int n_gains, double C, float* acid,
+                     void* stream)
+{
+    using namespace litho;
+    if (!image || !gains_host || !acid || n_gains < 1 || n_gains > PEB_GAINS || !volume_ok(volumes, D, n)) return LITHO_E_ARG;
+    if ((long long)volumes * n_gains * D > 65535 || !finite_pos(C)) return LITHO_E_ARG;
+    PebGains gains;
+    memset(&gains, 0, sizeof(gains));
+    for (int i = 0; i < n_gains; ++i) {
+        if (!(gains_host[i] == gains_host[i])) return LITHO_E_ARG;
+        gains.g[i] = gains_host[i];
+    }
+    const size_t in_bytes = (size_t)volumes * D * n * n * sizeof(float);
+    if (overlap(image, in_bytes, acid, in_bytes * n_gains)) return LITHO_E_ARG;
+    const int planes = volumes * D;
+    const bool wide = (n & 3) == 0 && aligned16(image) && aligned16(acid);
+    const dim3 grid(plane_blocks(n, wide ? 4 : 1), (unsigned)planes);
+    if (wide) hipLaunchKernelGGL(k_peb_expose<4>, grid, dim3(256), 0, (hipStream_t)stream, image, acid, planes, n, gains, n_gains, C);
+    else hipLaunchKernelGGL(k_peb_expose<1>, grid, dim3(256), 0, (hipStream_t)stream, image, acid, planes, n, gains, n_gains, C);
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+int litho_peb_min_steps(double sigma_acid_nm, double sigma_quencher_nm, double vertical_scale, double thickness_nm, int D,
+                        double pixel_nm)
+{
+    return litho::min_steps(sigma_acid_nm, sigma_quencher_nm, vertical_scale, thickness_nm, D, pixel_nm);
+}
+
+size_t litho_peb_work_bytes(int B, int D, int n)
+{
+    using namespace litho;
+    if (!volume_ok(B, D, n)) return 0;
+    return 2 * (size_t)B * D * n * n * sizeof(float);
+}
+
+int litho_peb_steps_per_launch(int D)
+{
+    using namespace litho;
+    if (D < 1 || D > PEB_DMAX) return 0;
+    for (int s = PEB_SMAX; s >= 2; --s)
+        if (lds_bytes(D, s) <= PEB_LDS_BUDGET) return s;
+    return 1;
+}
+
+int litho_peb_bake(const float* acid_in, int B, int D, int n, double thickness_nm, double pixel_nm, double quencher0, double k_quench,
+                   double k_loss, double sigma_acid_nm, double sigma_quencher_nm, double vertical_scale, double bake_time_s, int steps,
+                   int steps_per_launch, float* acid, float* quencher, float* acid_dose, void* work, size_t work_bytes, void* stream)
+{
+    using namespace litho;
+    if (!acid_in || !acid || !quencher || !acid_dose || !work || !volume_ok(B, D, n)) return LITHO_E_ARG;
+    if (!finite_nonneg(quencher0) || !(k_quench >= 0.0) || !finite_nonneg(k_loss) || !finite_pos(bake_time_s)) return LITHO_E_ARG;
+    const int least = min_steps(sigma_acid_nm, sigma_quencher_nm, vertical_scale, thickness_nm, D, pixel_nm);
+    if (least == 0 || steps < least || steps > PEB_MAXSTEPS) return LITHO_E_ARG;
+    if (steps_per_launch < 0 || steps_per_launch > PEB_SMAX) return LITHO_E_ARG;
+    const int s = steps_per_launch ? steps_per_launch : litho_peb_steps_per_launch(D);
+    const size_t lds = s >= 2 ? lds_bytes(D, s) : 0;
+    if (lds > PEB_LDS_MAX) return LITHO_E_ARG;
+    const size_t vol_bytes = (size_t)B * D * n * n * sizeof(float), need = 2 * vol_bytes;
+    const void* bufs[5] = {acid_in, acid, quencher, acid_dose, work};
+    if (!aligned16(work)) return LITHO_E_ARG;
+    if (work_bytes < need) return LITHO_E_WORKSPACE;
+    for (int i = 0; i < 5; ++i)
+        for (int j = i + 1; j < 5; ++j)
+            if (overlap(bufs[i], i == 4 ? need : vol_bytes, bufs[j], j == 4 ? need : vol_bytes)) return LITHO_E_ARG;
+    const double hz = thickness_nm / D, dt = bake_time_s / steps;
+    double lxy_h, lz_h, lxy_q, lz_q;
+    lambdas(sigma_acid_nm, vertical_scale, pixel_nm, hz, steps, lxy_h, lz_h);
+    lambdas(sigma_quencher_nm, vertical_scale, pixel_nm, hz, steps, lxy_q, lz_q);
+    PebStep P;
+    P.lxy_h = (float)lxy_h; P.lz_h = (float)lz_h; P.lxy_q = (float)lxy_q; P.lz_q = (float)lz_q;
+    P.beta = (float)(k_quench * dt);
+    P.fl = (float)std::exp(-k_loss * dt);
+    P.half_dt = (float)(0.5 * dt);
+    P.diffuse_h = sigma_acid_nm > 0.0;
+    P.diffuse_q = sigma_quencher_nm > 0.0;
+    P.instant = std::isinf(P.beta);                       // kQuench = +inf, or kQuench dt beyond fp32
+    const float q0 = (float)quencher0;
+    if (std::isinf(q0) || std::isinf(P.half_dt)) return LITHO_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    if (lds > 64 * 1024) {                                // once per device; the automatic choice never gets here
+        static unsigned lds_done = 0;
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        const unsigned bit = 1u << (dev & 31);
+        if (!(__atomic_load_n(&lds_done, __ATOMIC_ACQUIRE) & bit)) {
+            HIP_TRY(hipFuncSetAttribute((const void*)k_peb_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PEB_LDS_MAX));
+            __atomic_fetch_or(&lds_done, bit, __ATOMIC_RELEASE);
+        }
+    }
+    // launch k of L reads what launch k - 1 wrote; the last one writes the outputs, the ones before it alternate
+    float* out_h[2] = {acid, (float*)work};
+    float* out_q[2] = {quencher, (float*)work + (size_t)B * D * n * n};
+    const int L = (steps + s - 1) / s;
+    const unsigned tiles = (unsigned)((n + PEB_TILE - 1) / PEB_TILE);
+    const float *src_h = acid_in, *src_q = nullptr;
+    int left = steps;
+    for (int k = 0; k < L; ++k) {
+        const int now = left < s ? left : s, to = (L - 1 - k) & 1;
+        if (now == 1)
+            hipLaunchKernelGGL(k_peb_direct, dim3(plane_blocks(n, 1), (unsigned)(B * D)), dim3(256), 0, st, src_h, src_q, q0, out_h[to],
+                               out_q[to], acid_dose, D, n, P);
+        else
+            hipLaunchKernelGGL(k_peb_fused, dim3(tiles, tiles, (unsigned)B), dim3(256), lds_bytes(D, now), st, src_h, src_q, q0, out_h[to],
+                               out_q[to], acid_dose, D, n, now, P);
+        src_h = out_h[to];
+        src_q = out_q[to];
+        left -= now;
+    }
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+int litho_peb_rate(const float* acid_dose, int B, int D, int n, double k_amp, double r_max, double r_min, double q, double m_th,
+                   double surface_rate, double surface_depth_nm, double thickness_nm, float* slowness, float* inhibitor, void* stream)
+{
+    using namespace litho;
+    if (!acid_dose || !slowness || !volume_ok(B, D, n)) return LITHO_E_ARG;
+    if (!finite_pos(k_amp) || !finite_pos(r_max) || !finite_pos(r_min) || !(q > 1.0) || std::isinf(q) || !(m_th >= 0.0) || !(m_th < 1.0) ||
+        !(surface_rate > 0.0) || !(surface_rate <= 1.0) || !finite_pos(surface_depth_nm) || !finite_pos(thickness_nm))
+        return LITHO_E_ARG;
+    const size_t bytes = (size_t)B * D * n * n * sizeof(float);
+    if (overlap(acid_dose, bytes, slowness, bytes)) return LITHO_E_ARG;
+    if (inhibitor && (overlap(acid_dose, bytes, inhibitor, bytes) || overlap(slowness, bytes, inhibitor, bytes))) return LITHO_E_ARG;
+    const double a_m = (q + 1.0) / (q - 1.0) * std::pow(1.0 - m_th, q);
+    PebSurface surface;
+    for (int d = 0; d < PEB_DMAX; ++d) {
+        const double z = thickness_nm * (d + 0.5) / D;
+        surface.f[d] = 1.0 - (1.0 - surface_rate) * std::exp(-z / surface_depth_nm);
+    }
+    const bool wide = (n & 3) == 0 && aligned16(acid_dose) && aligned16(slowness) && aligned16(inhibitor);
+    const dim3 grid(plane_blocks(n, wide ? 4 : 1), (unsigned)(B * D));
+    if (wide)
+        hipLaunchKernelGGL(k_peb_rate<4>, grid, dim3(256), 0, (hipStream_t)stream, acid_dose, slowness, inhibitor, D, n, k_amp,
+                           r_max * (a_m + 1.0), r_min, q, a_m, surface);
+    else
+        hipLaunchKernelGGL(k_peb_rate<1>, grid, dim3(256), 0, (hipStream_t)stream, acid_dose, slowness, inhibitor, D, n, k_amp,
+                           r_max * (a_m + 1.0), r_min, q, a_m, surface);
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+}  // extern "C"

@@ -12,8 +12,11 @@ with T = 0 on the resist top.  The planes of T are [planes, n, n] fp32 like any 
 Grid: plane d of D sits at depth (d + 1/2) thickness / D, `FilmStack.depths(D)`; the lateral pitch is the image's pixel size.
 A batch is [B, D, n, n] with B = doses x focal planes, dose-major.
 
-NOT built: reaction-diffusion post-exposure bake with quencher, bleaching (Dill A, B: the intensity is taken as given),
-development of anything but one layer, gradients through development."""
+A chemically amplified resist (peb.py: ChemicallyAmplifiedResist) takes the place of the Gaussian blur and of developmentRate with a
+reaction-diffusion post-exposure bake with quencher, `postExposureBake`; resistProfile accepts either kind of resist.
+
+NOT built: bleaching (Dill A, B: the intensity is taken as given), development of anything but one layer, gradients through
+development."""
 import ctypes
 import math
 
@@ -244,7 +247,8 @@ class ResistProfile:
 
 
 def resistProfile(image, resist, stack_or_thickness, pixelSize, developTime, doses=(1.0,), focalPlanes=1, maxIterations=1024):
-    """The chain developmentRate -> developmentTime -> developedDepth on an intensity stack.  `image` fp32 [F D, n, n] in the plane
+    """The chain developmentRate -> developmentTime -> developedDepth on an intensity stack; with a ChemicallyAmplifiedResist
+    (peb.py) the slowness comes from postExposureBake (its default steps) instead of developmentRate.  `image` fp32 [F D, n, n] in the plane
     order hopkinsImage returns for vectorSocsKernels(film=, depths=stack.depths(D)) (plane f D + d), F = `focalPlanes`;
     `stack_or_thickness` the FilmStack (its resist layer is developed) or the thickness in nm.  Returns a ResistProfile; before
     its T goes to measureCD or traceContours, +inf is clamped to 2 developTime + 1 (ResistProfile)."""
@@ -257,7 +261,11 @@ def resistProfile(image, resist, stack_or_thickness, pixelSize, developTime, dos
     if not (t > 0.0 and math.isfinite(t)):
         raise ValueError(f"{who}: developTime must be positive and finite; got {developTime}")
     D, n = image.shape[0] // F, image.shape[-1]
-    s = developmentRate(image.reshape(F, D, n, n), resist, thickness, pixelSize, doses)
+    from .peb import ChemicallyAmplifiedResist, postExposureBake
+    if isinstance(resist, ChemicallyAmplifiedResist):
+        s = postExposureBake(image.reshape(F, D, n, n), resist, thickness, pixelSize, doses).slowness
+    else:
+        s = developmentRate(image.reshape(F, D, n, n), resist, thickness, pixelSize, doses)
     T, launches = _development_time(s, thickness, pixelSize, maxIterations)
     depth = developedDepth(T, thickness, t)
     nd = len(tuple(doses))

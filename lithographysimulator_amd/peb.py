@@ -1,0 +1,168 @@
+"""Post-exposure bake of a chemically amplified resist: acid-quencher reaction-diffusion; no reference counterpart
+(include/litho_abbe.h; csrc/peb.hip).
+
+Exposure releases acid, h0 = 1 - exp(-C dose I) relative to the initial photo-acid generator.  During the bake the acid diffuses,
+is neutralised by the base quencher (which may diffuse too, usually far less), is lost, and catalyses the deprotection that lets
+the developer in: with a = the time integral of the acid, the inhibitor left is m = exp(-kAmp a), and Mack's rate of m gives the
+slowness volume that `developmentTime` takes -- everything downstream of `developmentRate` is unchanged.  The bake is an explicit
+scheme of `steps` steps on the grid of develop.py (plane d at depth (d + 1/2) thickness / D, lateral pitch `pixelSize`) with no
+flux through any of the six faces: unlike `latentDiffusion`, which puts zeros outside the grid laterally, the bake mirrors, so
+acid minus quencher is conserved exactly and a bake does not drain acid out of the picture.
+
+NOT built: bleaching, a diffusivity that depends on the deprotection, gradients through the bake."""
+import ctypes
+import math
+
+import torch
+
+from . import _native as nat
+from .develop import MackResist, _positive, _volume
+
+MAX_STEPS = 65536
+
+
+class ChemicallyAmplifiedResist:
+    """A chemically amplified resist, a plain value class (normalised concentrations, nm, s).
+
+    `C` > 0: Dill C, acid h0 = 1 - exp(-C dose I).  `quencher` >= 0: the base loading q0 relative to the initial PAG.  `kAmp` > 0:
+    amplification rate, m = exp(-kAmp integral of h dt).  `kQuench` >= 0 (1 / s per unit concentration; float('inf') =
+    instantaneous neutralisation), `kLoss` >= 0 (1 / s).  `acidDiffusionLength`, `quencherDiffusionLength` >= 0: the customary
+    sigma = sqrt(2 D bakeTime) in nm; the vertical one is `verticalScale` (>= 0) times the lateral.  `bakeTime` > 0 s.  `mack`:
+    the MackResist whose rMax, rMin, q, mTh and surface inhibition develop the baked resist; its C is not used and its own
+    diffusionLength fields must be 0 (the bake is the diffusion)."""
+
+    def __init__(self, C, quencher, kAmp, kQuench, kLoss, acidDiffusionLength, quencherDiffusionLength, verticalScale=1.0, *, bakeTime,
+                 mack):
+        self.C, self.quencher, self.kAmp, self.kQuench, self.kLoss = float(C), float(quencher), float(kAmp), float(kQuench), float(kLoss)
+        self.acidDiffusionLength, self.quencherDiffusionLength = float(acidDiffusionLength), float(quencherDiffusionLength)
+        self.verticalScale, self.bakeTime, self.mack = float(verticalScale), float(bakeTime), mack
+        pos = lambda v: v > 0.0 and math.isfinite(v)                              # noqa: E731
+        if not (pos(self.C) and pos(self.kAmp) and pos(self.bakeTime)):
+            raise ValueError("ChemicallyAmplifiedResist: C, kAmp and bakeTime must be positive and finite")
+        for name in ("quencher", "kLoss", "acidDiffusionLength", "quencherDiffusionLength", "verticalScale"):
+            v = getattr(self, name)
+            if not (v >= 0.0 and math.isfinite(v)):
+                raise ValueError(f"ChemicallyAmplifiedResist: {name} must be finite and >= 0; got {v}")
+        if not self.kQuench >= 0.0:
+            raise ValueError(f"ChemicallyAmplifiedResist: kQuench must be >= 0 (inf: instantaneous); got {kQuench}")
+        if not isinstance(mack, MackResist):
+            raise TypeError("ChemicallyAmplifiedResist: mack must be a MackResist")
+        if mack.diffusionLength != 0.0 or mack.verticalDiffusionLength != 0.0:
+            raise ValueError("ChemicallyAmplifiedResist: the MackResist's own diffusion lengths must be 0; the bake is the diffusion")
+
+    def minSteps(self, thickness, D, pixelSize):
+        """The smallest number of bake steps at which every diffusion update is a convex combination (litho_peb_min_steps)."""
+        S = int(nat.lib().litho_peb_min_steps(self.acidDiffusionLength, self.quencherDiffusionLength, self.verticalScale, float(thickness),
+                                              int(D), float(pixelSize)))
+        if S == 0:
+            raise ValueError(f"ChemicallyAmplifiedResist: the diffusion lengths need more than {MAX_STEPS} bake steps on this grid "
+                             f"(thickness {thickness} nm at {D} planes, pixel {pixelSize} nm), or the grid is invalid")
+        return S
+
+    def __repr__(self):
+        return (f"ChemicallyAmplifiedResist(C={self.C}, quencher={self.quencher}, kAmp={self.kAmp}, kQuench={self.kQuench}, kLoss={self.kLoss}, "
+                f"acidDiffusionLength={self.acidDiffusionLength}, quencherDiffusionLength={self.quencherDiffusionLength}, "
+                f"verticalScale={self.verticalScale}, bakeTime={self.bakeTime}, mack={self.mack!r})")
+
+
+class BakeResult:
+    """What postExposureBake returns, all fp32 [len(doses) F, D, n, n], dose-major: `acid` and `quencher` after the bake,
+    `acidDose` a = the time integral of the acid in s, `inhibitor` m = exp(-kAmp a), `slowness` 1 / r in s / nm (NaN: a wall to
+    developmentTime); `steps`: the bake steps that ran."""
+
+    def __init__(self, acid, quencher, acidDose, inhibitor, slowness, steps):
+        self.acid, self.quencher, self.acidDose, self.inhibitor, self.slowness, self.steps = acid, quencher, acidDose, inhibitor, slowness, steps
+
+
+def _steps(who, resist, thickness, D, pixel, steps):
+    least = resist.minSteps(thickness, D, pixel)
+    S = max(least, 8) if steps is None else int(steps)
+    if not least <= S <= MAX_STEPS:
+        raise ValueError(f"{who}: steps must be {least} (the smallest stable number on this grid) ... {MAX_STEPS}; got {steps}")
+    return S
+
+
+def exposeAcid(image, C, doses=(1.0,)):
+    """The acid released by exposure (litho_peb_expose): h0 = 1 - exp(-C dose I) for the intensity volume `image`, fp32 [D,n,n] or
+    [F,D,n,n] on the GPU; returns [len(doses) F, D, n, n], dose-major, at most 64 doses; NaN where dose x intensity is negative
+    or NaN."""
+    who = "exposeAcid"
+    v, F, D, n, _, dev = _volume(who, image)
+    gains = [float(d) for d in doses]
+    if not 1 <= len(gains) <= 64:
+        raise ValueError(f"{who}: between 1 and 64 doses per call; got {len(gains)}")
+    if len(gains) * F * D > 65535:
+        raise ValueError(f"{who}: doses x volumes x planes exceeds 65535")
+    out = torch.empty((len(gains) * F, D, n, n), dtype=torch.float32, device=dev)
+    g = (ctypes.c_float * len(gains))(*gains)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_peb_expose(nat.ptr(v), F, D, n, g, len(gains), _positive(who, "C", C), nat.ptr(out), nat.stream_ptr(dev)),
+                  "litho_peb_expose")
+        v.record_stream(torch.cuda.current_stream(dev))
+    return out
+
+
+def bakeAcid(acid, resist, thickness, pixelSize, steps=None, stepsPerLaunch=0):
+    """The bake alone (litho_peb_bake) from the acid volume `acid`, fp32 [D,n,n] or [B,D,n,n] on the GPU, with the quencher uniform
+    at resist.quencher: returns (acid, quencher, acidDose, steps), the volumes shaped like the input.  `steps` and
+    `stepsPerLaunch` as in postExposureBake."""
+    who = "bakeAcid"
+    if not isinstance(resist, ChemicallyAmplifiedResist):
+        raise TypeError(f"{who}: resist must be a ChemicallyAmplifiedResist")
+    v, B, D, n, batched, dev = _volume(who, acid, "acid")
+    thickness, h = _positive(who, "thickness", thickness), _positive(who, "pixelSize", pixelSize)
+    S = _steps(who, resist, thickness, D, h, steps)
+    spl = int(stepsPerLaunch)
+    if not 0 <= spl <= 4:
+        raise ValueError(f"{who}: stepsPerLaunch must be 0 (automatic) ... 4; got {stepsPerLaunch}")
+    lib = nat.lib()
+    out_h, out_q, out_a = (torch.empty_like(v) for _ in range(3))
+    nbytes = int(lib.litho_peb_work_bytes(B, D, n))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(lib.litho_peb_bake(nat.ptr(v), B, D, n, thickness, h, resist.quencher, resist.kQuench, resist.kLoss,
+                                     resist.acidDiffusionLength, resist.quencherDiffusionLength, resist.verticalScale, resist.bakeTime, S, spl,
+                                     nat.ptr(out_h), nat.ptr(out_q), nat.ptr(out_a), nat.ptr(work), nbytes, nat.stream_ptr(dev)),
+                  "litho_peb_bake")
+        for t in (v, work):
+            t.record_stream(torch.cuda.current_stream(dev))
+    if not batched:
+        out_h, out_q, out_a = out_h[0], out_q[0], out_a[0]
+    return out_h, out_q, out_a, S
+
+
+def amplifiedRate(acidDose, resist, thickness):
+    """(inhibitor, slowness) of the baked resist (litho_peb_rate) from the acid dose a, fp32 [D,n,n] or [B,D,n,n] on the GPU:
+    m = exp(-kAmp a) and 1 / (Mack's rate of m x the surface factor) with resist.mack's parameters.  A NaN or negative a gives a
+    NaN slowness, a wall to developmentTime."""
+    who = "amplifiedRate"
+    if not isinstance(resist, ChemicallyAmplifiedResist):
+        raise TypeError(f"{who}: resist must be a ChemicallyAmplifiedResist")
+    v, B, D, n, batched, dev = _volume(who, acidDose, "acidDose")
+    thickness, mack = _positive(who, "thickness", thickness), resist.mack
+    slow, m = torch.empty_like(v), torch.empty_like(v)
+    delta = mack.surfaceDepth if mack.surfaceDepth is not None else thickness
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_peb_rate(nat.ptr(v), B, D, n, resist.kAmp, mack.rMax, mack.rMin, mack.q, mack.mTh, mack.surfaceRate, delta,
+                                           thickness, nat.ptr(slow), nat.ptr(m), nat.stream_ptr(dev)), "litho_peb_rate")
+        v.record_stream(torch.cuda.current_stream(dev))
+    return (m, slow) if batched else (m[0], slow[0])
+
+
+def postExposureBake(image, resist, thickness, pixelSize, doses=(1.0,), steps=None, stepsPerLaunch=0):
+    """Exposure, bake and rate of `resist` (a ChemicallyAmplifiedResist) on the intensity volume `image`, fp32 [D,n,n] or [F,D,n,n]
+    on the GPU, in a layer of `thickness` nm: exposeAcid, bakeAcid, amplifiedRate.  Returns a BakeResult, [len(doses) F, D, n, n];
+    at most 64 doses.  Where dose x intensity is negative or NaN the acid starts as NaN, which the bake spreads one cell per
+    step.
+
+    `steps`: None takes max(resist.minSteps(...), 8); a value below minSteps raises (the explicit diffusion would lose its
+    maximum principle), the cap is 65536.  The reaction terms are first order in the step length: RAISE `steps` for a stiff
+    finite kQuench (kQuench x bakeTime / steps well above 1) until the result stops moving.  `stepsPerLaunch`: 0 lets the
+    library choose between its direct kernel (1) and its fused kernel (2 ... 4 steps per launch); the result does not depend
+    on it, bit for bit."""
+    if not isinstance(resist, ChemicallyAmplifiedResist):
+        raise TypeError("postExposureBake: resist must be a ChemicallyAmplifiedResist")
+    h0 = exposeAcid(image, resist.C, doses)
+    acid, quencher, dose, S = bakeAcid(h0, resist, thickness, pixelSize, steps, stepsPerLaunch)
+    m, slow = amplifiedRate(dose, resist, thickness)
+    return BakeResult(acid, quencher, dose, m, slow, S)
