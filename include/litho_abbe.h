@@ -611,6 +611,29 @@ size_t litho_socs_vjp_work_bytes(int groups, int K, int pn);
 int litho_socs_vjp(const void *kernels, const void *maskFT, const float *gradI, int groups, int K, int pn, int N, void *grad,
                    int accumulate, void *work, size_t work_bytes, void *stream);
 
+/* ---- Source gradients of Abbe imaging (csrc/socs_grad.hip; no reference counterpart, checked against tests/source_grad_oracle.py).
+ * The weighted Abbe sum I = sum_s w_s |E_s|^2 is linear in the weights, and source point s is the coherent kernel roll(P, d_s) of
+ * the field code above: E_s = L(roll(P, d_s) . M), L as documented for litho_socs_fields.  For a real loss l with G = dl/dI,
+ *   dl/dw_s = <G, |E_s|^2> = sum_q G[q] |E_s[q]|^2:
+ * one number per source point, independent of the weights, and no adjoint transform -- one forward field and a reduction.
+ *
+ * litho_source_sensitivity:
+ *   sens[s] = sum_{g < groups} sum_{k < K} sum_q gradI[g][q] . | L( roll(pupils[g K + k], (dy_s, dx_s)) . maskFT )[q] |^2,   s < count,
+ * roll(P, (dy, dx))[r][c] = P[(r - dy) mod pn][(c - dx) mod pn] (torch.roll(P, (dy, dx), (0, 1)), the reference's
+ * imageformation.py:63).  shifts: device int32 [count][2] = (dy, dx), what litho_source_compact writes; any integers, a wrapping
+ * shift is the modular index.  pupils complex64 [groups K,pn,pn] with item g K + k = pupil k of plane g (K > 1: pupil stacks that
+ * share one image plane, such as the effective pupils of vector imaging; the (groups, K) convention of litho_socs_vjp), maskFT
+ * complex64 [pn,pn], gradI fp32 [groups,pn,pn], sens fp32 [count], overwritten.  The list is walked in chunks of `batch` points and
+ * work holds one chunk: litho_source_sensitivity_work_bytes(groups, K, batch, pn) device bytes, 8-byte aligned (batch groups K field
+ * planes, one partial per line of them, one transposed copy of gradI; 0 for a bad argument), less is LITHO_E_WORKSPACE.  No
+ * atomics and one fixed order for every sum: sens[s] depends on point s alone -- its bits do not change with batch, count, the
+ * point's place in the list or the other points.  Domain as litho_socs_fields: pn, N powers of two, 16..4096, else LITHO_E_ARG;
+ * N < pn: LITHO_E_NSMALL; count < 0, batch, groups or K < 1, a null pointer, or batch groups K pn > INT_MAX lines: LITHO_E_ARG;
+ * every check is made before any launch.  count == 0: LITHO_OK, nothing is launched.  Asynchronous, no allocation, no host wait. */
+size_t litho_source_sensitivity_work_bytes(int groups, int K, int batch, int pn);
+int litho_source_sensitivity(const void *pupils, const void *maskFT, const float *gradI, int groups, int K, const int32_t *shifts,
+                             int64_t count, int pn, int N, float *sens, int batch, void *work, size_t work_bytes, void *stream);
+
 /* ---- Layout rasteriser: the device side of the GDSII import (lithographysimulator_amd/layout.py).  SURVEY.md section
  * 8(f) row 4: the reference has NO counterpart (README.md:20-22 lists GDSII import among its unbuilt goals), it is the
  * caller side of Mask(geometry, pixelSize) (mask.py:5-30), so there is no parity target; checked bit for bit against

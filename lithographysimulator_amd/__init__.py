@@ -14,6 +14,8 @@ from .contours import (Contours, contourVertices, contoursToGDSII, contoursToLay
 from .socs import SOCSKernels, hopkinsImage, hopkinsIntensity, socsKernels          # noqa: F401
 from .ilt import (ILTResult, hopkinsFields, hopkinsGradient, hopkinsIntensityAD,       # noqa: F401
                   maskSpectrumAdjoint, optimizeMask, postProcessAdjoint)
+from .smo import (SourceResult, optimizeSource, optimizeSourceMask, projectedStep,      # noqa: F401
+                  sourceGradient, sourceLossGradient, sourceSensitivities)
 from .vector import (sourcePolarization, vectorAbbeIntensity, vectorPupils,            # noqa: F401
                      vectorSocsKernels)
 from .film import FilmStack, filmPupils                                                 # noqa: F401
@@ -31,6 +33,8 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "Contours", "contourVertices", "traceContours", "contoursToLayout", "simplifyContour", "contoursToGDSII", "doseFocusEnvelope",
            "processVariationBand", "SOCSKernels", "socsKernels", "hopkinsIntensity", "hopkinsImage",
            "hopkinsFields", "hopkinsGradient", "hopkinsIntensityAD", "maskSpectrumAdjoint", "postProcessAdjoint", "optimizeMask", "ILTResult",
+           "sourceSensitivities", "sourceGradient", "sourceLossGradient", "projectedStep", "optimizeSource", "optimizeSourceMask",
+           "SourceResult",
            "vectorPupils", "sourcePolarization", "vectorSocsKernels", "vectorAbbeIntensity",
            "FilmStack", "filmPupils",
            "MackResist", "ResistProfile", "latentDiffusion", "developmentRate", "developmentTime", "developedDepth", "resistProfile",

@@ -17,6 +17,12 @@
 // pass's load (phi . M on the way in, G . E on the way back), the reduction over the batch is one running fp32 sum per element
 // in ascending item order: no atomics, so the result is deterministic and a chunked call gives the chunk-ordered sum.
 // No reference counterpart; checked against tests/socs_grad_oracle.py.
+//
+// Source sensitivities (litho_source_sensitivity) are the same field code with two other ends: a source point is the coherent
+// kernel roll(P, d_s), so the first row pass reads the one pupil plane rolled (LOAD_ROLLED) instead of a stored kernel, and the
+// second row pass reduces G^T . |E|^2 over its line (STORE_REDUCE) instead of writing the field; a small kernel sums a point's
+// line partials.  Every sum has one fixed order and nothing is atomic, so a point's number depends on that point alone.
+// Checked against tests/source_grad_oracle.py.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -29,7 +35,9 @@
 namespace litho {
 
 // What the row pass multiplies into the line as it loads it.
-enum : int { LOAD_PLAIN = 0, LOAD_TIMES_MASK = 1, LOAD_TIMES_GRAD = 2 };
+enum : int { LOAD_PLAIN = 0, LOAD_TIMES_MASK = 1, LOAD_TIMES_GRAD = 2, LOAD_ROLLED = 3 };
+// What it does with the outputs: writes them, or reduces mul_r . |y|^2 over the line to one number.
+enum : int { STORE_FIELD = 0, STORE_REDUCE = 1 };
 
 // `lines` lines of pn = 2^LOG2P samples, line l = row (l mod pn) of item (l / pn); each becomes its centred pruned transform
 //   dst[q] = sum_i src[i] exp(SIGN 2 pi i (i - c)(q - c) / N),  q in [0, pn),  N = pn << log2m.
@@ -37,11 +45,18 @@ enum : int { LOAD_PLAIN = 0, LOAD_TIMES_MASK = 1, LOAD_TIMES_GRAD = 2 };
 // LOAD_TIMES_GRAD: by mul_r[item / per_group][row][i] (real).  dst may BE src: a line is in registers before any of its outputs
 // is written (every write follows a barrier that the line's threads reach with their loads consumed; a 16-point line has one
 // thread), and no workgroup touches another's lines.
-template <int LOG2P, int SIGN, int LOAD>
+// LOAD_ROLLED: item b is plane (b mod per_point) of source point (b / per_point); src holds the per_point planes once and
+//   src[i] = plane[(row - dy) mod pn][(i - dx) mod pn] . mul_c[row][i],  (dy, dx) = shifts[point], read once per line.
+// STORE_REDUCE: nothing is written to dst; partial[line] = sum_q mul_r[(item mod per_point) / per_group][row][q] |dst[q]|^2, each
+// thread over the outputs it owns (r ascending, then e), then the line's threads in a fixed order: the xor butterfly of a wave's
+// shuffles, every lane ending with the same bits, and for a line of several waves their sums through LDS, added in wave order.
+template <int LOG2P, int SIGN, int LOAD, int STORE = STORE_FIELD>
 __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(const float2* src, float2* dst,
                                                                             const float2* __restrict__ mul_c,
                                                                             const float* __restrict__ mul_r, int per_group,
-                                                                            long long lines, int log2m)
+                                                                            long long lines, int log2m,
+                                                                            const int32_t* __restrict__ shifts, int per_point,
+                                                                            float* __restrict__ partial)
 {
     using F = LineFFT<LOG2P, SIGN>;
     using LS = LineShape<LOG2P>;
@@ -58,6 +73,13 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
     const int row = (int)(l & (PN - 1));
     const float2* in = src + (size_t)l * PN;
     float2* out = dst + (size_t)l * PN;
+    unsigned dx = 0;
+    if (LOAD == LOAD_ROLLED) {
+        const long long item = l >> LOG2P, point = item / per_point;
+        const unsigned dy = (unsigned)shifts[2 * point];    // unsigned: the modular index of any integer, no overflow
+        dx = (unsigned)shifts[2 * point + 1];
+        in = src + ((size_t)(item - point * per_point) * PN + (((unsigned)row - dy) & (PN - 1))) * PN;
+    }
     // transform index n = lt + T e stands for the sample at signed offset s = n (n < c) or n - pn from the centre: i = s + c
     float2 x0[16];
 #pragma unroll
@@ -66,8 +88,8 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
         const int i = (n + C) & (PN - 1);
         float2 v = make_float2(0.f, 0.f);
         if (active) {
-            v = in[i];
-            if (LOAD == LOAD_TIMES_MASK) v = cmul(v, mul_c[(size_t)row * PN + i]);
+            v = LOAD == LOAD_ROLLED ? in[((unsigned)i - dx) & (PN - 1)] : in[i];
+            if (LOAD == LOAD_TIMES_MASK || LOAD == LOAD_ROLLED) v = cmul(v, mul_c[(size_t)row * PN + i]);
             if (LOAD == LOAD_TIMES_GRAD) {
                 const float g = mul_r[((size_t)(l >> LOG2P) / per_group * PN + row) * PN + i];
                 v = make_float2(v.x * g, v.y * g);
@@ -79,6 +101,9 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
     const int nmask = (PN << log2m) - 1;                   // N - 1
     const int tshift = 12 - LOG2P - log2m;                 // table stride 4096 / N
     int flip = 0;
+    float acc = 0.f;
+    const float* gt = mul_r;
+    if (STORE == STORE_REDUCE) gt = mul_r + ((size_t)((l >> LOG2P) % per_point / per_group) * PN + row) * PN;
     for (int r = 0; r < m; ++r) {
         if (m > PN && r >= C && r < m - C) continue;       // no q in [0, pn) is congruent to c + r (uniform over the workgroup)
         float2 x[16];
@@ -97,9 +122,56 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
             const int u = lt + F::T * e;
             const int t = u < C ? u : u - PN;
             const int q = C + (t << log2m) + r;
-            if (q >= 0 && q < PN) out[q] = x[e];
+            if (q >= 0 && q < PN) {
+                if (STORE == STORE_REDUCE) acc = fmaf(gt[q], fmaf(x[e].x, x[e].x, x[e].y * x[e].y), acc);
+                else out[q] = x[e];
+            }
         }
     }
+    if (STORE == STORE_REDUCE) {
+        constexpr int W = F::T < 64 ? F::T : 64;           // the line's lanes within one wave: an aligned group of W
+#pragma unroll
+        for (int o = W / 2; o >= 1; o /= 2) acc += __shfl_xor(acc, o);
+        if (F::T > 64) {                                   // one line per workgroup, T / 64 waves
+            float* red = reinterpret_cast<float*>(smem);   // the exchange buffer, free once every thread has left the transforms
+            __syncthreads();
+            if ((lt & 63) == 0) red[lt >> 6] = acc;
+            __syncthreads();
+            acc = red[0];
+            for (int w = 1; w < F::T / 64; ++w) acc += red[w];
+        }
+        if (active && lt == 0) partial[l] = acc;
+    }
+}
+
+// out[g][c][r] = in[g][r][c] for `gridDim.z` real n x n planes, through a 32 x 32 LDS tile: the copy of gradI whose lines the
+// reducing row pass reads contiguously.
+__global__ __launch_bounds__(256) void k_transpose_real(const float* __restrict__ in, float* __restrict__ out, int n)
+{
+    __shared__ float tile[TR_TILE][TR_TILE + 1];
+    const size_t plane = (size_t)blockIdx.z * n * n;
+    const int tx = threadIdx.x % TR_TILE, ty = threadIdx.x / TR_TILE;
+    for (int r = ty; r < TR_TILE; r += 256 / TR_TILE) {
+        const int ri = blockIdx.y * TR_TILE + r, ci = blockIdx.x * TR_TILE + tx;
+        if (ri < n && ci < n) tile[r][tx] = in[plane + (size_t)ri * n + ci];
+    }
+    __syncthreads();
+    for (int r = ty; r < TR_TILE; r += 256 / TR_TILE) {
+        const int ro = blockIdx.x * TR_TILE + r, co = blockIdx.y * TR_TILE + tx;
+        if (ro < n && co < n) out[plane + (size_t)ro * n + co] = tile[tx][r];
+    }
+}
+
+// sens[p] = sum of the `n` line partials of point p: one wave per point, lane t over t, t + 64, ... ascending, then the xor
+// butterfly.  n is a multiple of 16.
+__global__ __launch_bounds__(64) void k_sum_partials(const float* __restrict__ partial, int n, float* __restrict__ sens)
+{
+    const float* p = partial + (size_t)blockIdx.x * n;
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < n; i += 64) acc += p[i];
+#pragma unroll
+    for (int o = 32; o >= 1; o /= 2) acc += __shfl_xor(acc, o);
+    if (threadIdx.x == 0) sens[blockIdx.x] = acc;
 }
 
 // grad[i] (+)= sum_b 2 conj(kernels[b][i]) adj[b][i], b ascending, one running fp32 sum per component.  Bandwidth-bound: two
@@ -133,20 +205,23 @@ struct RowArgs {
     int per_group;
     long long lines;
     int log2m;
+    const int32_t* shifts = nullptr;                       // LOAD_ROLLED / STORE_REDUCE only
+    int per_point = 1;
+    float* partial = nullptr;
 };
 
-template <int LOAD>
+template <int LOAD, int STORE = STORE_FIELD>
 static hipError_t centred_rows(const RowArgs& a, int pn, int sign, hipStream_t st)
 {
     return for_log2(log2_exact(pn), [&](auto l2) {
         constexpr int LOG2P = decltype(l2)::value;
         using LS = LineShape<LOG2P>;
         if (sign > 0)
-            hipLaunchKernelGGL((k_centred_rows<LOG2P, +1, LOAD>), LS::grid(a.lines), dim3(LS::THREADS), LS::LDS_BYTES, st, a.src, a.dst,
-                               a.mul_c, a.mul_r, a.per_group, a.lines, a.log2m);
+            hipLaunchKernelGGL((k_centred_rows<LOG2P, +1, LOAD, STORE>), LS::grid(a.lines), dim3(LS::THREADS), LS::LDS_BYTES, st, a.src,
+                               a.dst, a.mul_c, a.mul_r, a.per_group, a.lines, a.log2m, a.shifts, a.per_point, a.partial);
         else
-            hipLaunchKernelGGL((k_centred_rows<LOG2P, -1, LOAD>), LS::grid(a.lines), dim3(LS::THREADS), LS::LDS_BYTES, st, a.src, a.dst,
-                               a.mul_c, a.mul_r, a.per_group, a.lines, a.log2m);
+            hipLaunchKernelGGL((k_centred_rows<LOG2P, -1, LOAD, STORE>), LS::grid(a.lines), dim3(LS::THREADS), LS::LDS_BYTES, st, a.src,
+                               a.dst, a.mul_c, a.mul_r, a.per_group, a.lines, a.log2m, a.shifts, a.per_point, a.partial);
         return hipGetLastError();
     });
 }
@@ -173,6 +248,23 @@ static int check_sizes(long long batch, int pn, int N)
     if (N < pn) return LITHO_E_NSMALL;
     if (batch * pn > INT_MAX) return LITHO_E_ARG;                   // one workgroup per line at the large sizes
     return LITHO_OK;
+}
+
+// The three parts of litho_source_sensitivity's workspace, in float2 / float / float elements.
+struct SensWork {
+    size_t fields, gt, partial;
+    size_t bytes() const { return fields * sizeof(float2) + (gt + partial) * sizeof(float); }
+};
+
+static bool sens_work(int groups, int K, int batch, int pn, SensWork& w)
+{
+    if (groups < 1 || K < 1 || batch < 1 || !fft_size_ok(pn)) return false;
+    const long long items = (long long)groups * K;
+    if (items > INT_MAX || items * batch > INT_MAX || items * batch * pn > INT_MAX) return false;
+    w.partial = (size_t)(items * batch * pn);
+    w.fields = w.partial * pn;
+    w.gt = (size_t)groups * pn * pn;
+    return true;
 }
 
 }  // namespace litho
@@ -221,6 +313,48 @@ int litho_socs_vjp(const void* kernels, const void* maskFT, const float* gradI, 
     hipLaunchKernelGGL(k_vjp_reduce, dim3((unsigned)blocks), dim3(256), 0, st, (const float2*)kernels, (const float2*)w, (int)batch,
                        cells, (float2*)grad, accumulate ? 1 : 0);
     HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+size_t litho_source_sensitivity_work_bytes(int groups, int K, int batch, int pn)
+{
+    litho::SensWork w;
+    return litho::sens_work(groups, K, batch, pn, w) ? w.bytes() : 0;
+}
+
+int litho_source_sensitivity(const void* pupils, const void* maskFT, const float* gradI, int groups, int K, const int32_t* shifts,
+                             int64_t count, int pn, int N, float* sens, int batch, void* work, size_t work_bytes, void* stream)
+{
+    using namespace litho;
+    if (!pupils || !maskFT || !gradI || !shifts || !sens || !work || groups < 1 || K < 1 || batch < 1 || count < 0) return LITHO_E_ARG;
+    if (!fft_size_ok(pn) || !fft_size_ok(N)) return LITHO_E_ARG;
+    if (N < pn) return LITHO_E_NSMALL;
+    SensWork w;
+    if (!sens_work(groups, K, batch, pn, w)) return LITHO_E_ARG;   // more than INT_MAX lines in a chunk
+    if (work_bytes < w.bytes()) return LITHO_E_WORKSPACE;
+    if (count == 0) return LITHO_OK;
+    hipStream_t st = (hipStream_t)stream;
+    float2* fields = (float2*)work;
+    float* gt = (float*)(fields + w.fields);
+    float* partial = gt + w.gt;
+    const int log2m = log2_exact(N) - log2_exact(pn), per_point = groups * K;
+    HIP_TRY(fill_twiddles(st));
+    const unsigned tiles = (unsigned)((pn + TR_TILE - 1) / TR_TILE);
+    hipLaunchKernelGGL(k_transpose_real, dim3(tiles, tiles, (unsigned)groups), dim3(256), 0, st, gradI, gt, pn);
+    HIP_TRY(hipGetLastError());
+    for (int64_t p0 = 0; p0 < count; p0 += batch) {
+        const int nb = count - p0 < batch ? (int)(count - p0) : batch;
+        const int items = nb * per_point;
+        const long long lines = (long long)items * pn;
+        // rows of roll(P, d) . M, transpose, then the columns, each reduced against its line of G^T as it comes out
+        HIP_TRY(centred_rows<LOAD_ROLLED>(RowArgs{(const float2*)pupils, fields, (const float2*)maskFT, nullptr, 1, lines, log2m,
+                                                  shifts + 2 * p0, per_point, nullptr}, pn, +1, st));
+        HIP_TRY(transpose(fields, items, pn, st));
+        HIP_TRY((centred_rows<LOAD_PLAIN, STORE_REDUCE>(RowArgs{fields, fields, nullptr, gt, K, lines, log2m, nullptr, per_point,
+                                                                partial}, pn, +1, st)));
+        hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)nb), dim3(64), 0, st, (const float*)partial, per_point * pn, sens + p0);
+        HIP_TRY(hipGetLastError());
+    }
     return LITHO_OK;
 }
 

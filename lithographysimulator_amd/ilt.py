@@ -9,7 +9,8 @@ of a SOCS kernel set are E_k = L(phi_k . M) and hopkinsIntensity returns I = sum
 torch's convention for the gradient of a complex leaf (dl = Re <g, dM>).  `hopkinsGradient` computes g on the device
 (litho_socs_vjp: K fields and K adjoint fields per call, csrc/socs_grad.hip); `maskSpectrumAdjoint` and `postProcessAdjoint` are
 the adjoints of the two linear bookends (mask transmission -> spectrum, raw intensity -> image), and `optimizeMask` descends a
-pixel mask through all of it.  Mask gradients only: the source and the pupil are constants here."""
+pixel mask through all of it.  Mask gradients only: the source and the pupil are constants here (source gradients: smo.py;
+DESIGN.md section 10)."""
 import ctypes
 import math
 
