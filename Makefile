@@ -50,7 +50,8 @@ build/contour.o: $(CSRC)/contour.hip $(CSRC)/engine_common.hpp include/litho_abb
 build/socs.o: $(CSRC)/socs.hip $(CSRC)/plane_fft.hpp $(CSRC)/fft_core.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(FFTFLAGS) -c $< -o $@
-# mask gradients: the centred pruned line transforms of the fields and of their adjoint, the same line FFT and flags
+# mask, source and pupil gradients: the centred pruned line transforms of the fields and of their adjoint, the same line FFT and
+# flags; the pupil gradient's reducing and projecting kernels live in the same unit (they share its row passes and its table)
 build/socs_grad.o: $(CSRC)/socs_grad.hip $(CSRC)/plane_fft.hpp $(CSRC)/fft_core.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) $(FFTFLAGS) -c $< -o $@

@@ -634,6 +634,50 @@ size_t litho_source_sensitivity_work_bytes(int groups, int K, int batch, int pn)
 int litho_source_sensitivity(const void *pupils, const void *maskFT, const float *gradI, int groups, int K, const int32_t *shifts,
                              int64_t count, int pn, int N, float *sens, int batch, void *work, size_t work_bytes, void *stream);
 
+/* ---- Pupil gradients of Abbe imaging (csrc/socs_grad.hip; no reference counterpart, checked against tests/pupil_grad_oracle.py).
+ * Notation of the source-gradient block: L(X) = F X F^T, L^H(Y) = conj(F) Y conj(F)^T, roll(P, (dy, dx))[r][c] =
+ * P[(r - dy) mod pn][(c - dx) mod pn], M the mask spectrum [pn,pn], pupils P_j, j < groups K, plane g = j / K with image I_g,
+ * weights w_s.  Forward model:  E_{s,j} = L(roll(P_j, d_s) . M),   I_g = sum_s w_s sum_{k < K} |E_{s,g K + k}|^2.
+ * For a real loss l with G_g = dl/dI_g, in torch's convention for a complex leaf (dl = Re <g, dP>),
+ *   g_j[r][c] = dl/dRe P_j + i dl/dIm P_j = 2 sum_s w_s conj(M[r'][c']) A_{s,j}[r'][c'],
+ *   r' = (r + dy_s) mod pn,  c' = (c + dx_s) mod pn,   A_{s,j} = L^H(G_{j / K} . E_{s,j}):
+ * each point's adjoint is multiplied by conj(M) in the mask frame, rolled back by -d_s, and summed.  SOCS cannot give this (its
+ * kernels are eigenvectors of a TCC that depends on the pupil), so it costs one forward and one adjoint field per source point.
+ * Wavefront gradient, where P = a . exp(2 pi i W) with a real and independent of W:  dl/dW = 2 pi Im(g . conj(P)), real [pn,pn]
+ * per pupil.  Coefficient gradient, for W_p = W0_p + sum_j c_j B_j with real basis maps B_j shared by all planes:
+ *   dl/dc_j = sum_p sum_cells (dl/dW_p) . B_j.
+ *
+ * litho_pupil_vjp: grad (+)= g of the list.  pupils complex64 [groups K,pn,pn], maskFT complex64 [pn,pn], gradI fp32 [groups,pn,pn],
+ * shifts device int32 [count][2] = (dy, dx) (any integers), weights device fp32 [count] or NULL = all 1, grad complex64
+ * [groups K,pn,pn].  The list is walked in chunks of `batch` points, items of a chunk point-major (item = point groups K + j); a
+ * chunk is: the fields (rolled load, rows, transpose, rows, transpose: natural layout), L^H of G . E in place, then one reducing
+ * pass in which every cell of every plane keeps one running fp32 sum over the chunk's points in ascending order, each term
+ *   re += fma(2 w, fma(M.re, A.re, M.im A.im), .),   im += fma(2 w, fma(M.re, A.im, -(M.im A.re)), .)   read at (r', c'),
+ * starting from grad for every chunk after the first or when accumulate != 0, from 0 otherwise.  Nothing is atomic and the
+ * additions into a cell are the list's order: grad's bits do not depend on `batch`, and a list split over two calls, the second with
+ * accumulate != 0, gives the bits of one call (another ORDER of the list is another rounding).  work holds one chunk:
+ * litho_pupil_vjp_work_bytes(groups, K, batch, pn) = batch groups K pn^2 complex64 (0 for a bad argument), nothing of size count
+ * pn^2; less is LITHO_E_WORKSPACE.  Sizes and codes as litho_source_sensitivity: pn, N powers of two, 16..4096, else LITHO_E_ARG;
+ * N < pn: LITHO_E_NSMALL; count < 0, batch, groups or K < 1, a null pointer other than weights (and than shifts when count == 0), or batch groups K pn >
+ * INT_MAX lines: LITHO_E_ARG; every check is made before any launch.  count == 0: grad is zeroed when accumulate == 0 and left alone
+ * otherwise.  Asynchronous, no allocation, no host wait. */
+size_t litho_pupil_vjp_work_bytes(int groups, int K, int batch, int pn);
+int litho_pupil_vjp(const void *pupils, const void *maskFT, const float *gradI, int groups, int K, const int32_t *shifts,
+                    const float *weights, int64_t count, int pn, int N, void *grad, int accumulate, int batch, void *work,
+                    size_t work_bytes, void *stream);
+/* litho_pupil_project: out[j] = sum_{p < planes} sum_cells 2 pi Im(grad[p] . conj(pupils[p])) . basis[j], j < J: the coefficient
+ * gradient.  grad, pupils complex64 [planes,pn,pn], basis fp32 [J,pn,pn], out fp32 [J], overwritten; 1 <= J <=
+ * LITHO_PUPIL_PROJECT_MAX_TERMS, pn a power of two, 16..4096, planes >= 1 (else, or for a null pointer, LITHO_E_ARG).  Two stages
+ * with one fixed order and no atomics: per workgroup and term a partial (threads over their cells in ascending order, a wave's
+ * lanes in the xor butterfly of its shuffles, the waves in order), then per term the partials in a fixed order; the number of
+ * workgroups depends on the sizes alone, so two calls give the same bits.  grad and pupils are read once per tile of 16 terms,
+ * not once per term.  work: litho_pupil_project_work_bytes(planes, J, pn) device bytes (the partials; 0 for a bad argument), less
+ * is LITHO_E_WORKSPACE.  Asynchronous, no allocation, no host wait. */
+#define LITHO_PUPIL_PROJECT_MAX_TERMS 1024
+size_t litho_pupil_project_work_bytes(int planes, int J, int pn);
+int litho_pupil_project(const void *grad, const void *pupils, int planes, const float *basis, int J, int pn, float *out, void *work,
+                        size_t work_bytes, void *stream);
+
 /* ---- Layout rasteriser: the device side of the GDSII import (lithographysimulator_amd/layout.py).  SURVEY.md section
  * 8(f) row 4: the reference has NO counterpart (README.md:20-22 lists GDSII import among its unbuilt goals), it is the
  * caller side of Mask(geometry, pixelSize) (mask.py:5-30), so there is no parity target; checked bit for bit against

@@ -16,6 +16,8 @@ from .ilt import (ILTResult, hopkinsFields, hopkinsGradient, hopkinsIntensityAD,
                   maskSpectrumAdjoint, optimizeMask, postProcessAdjoint)
 from .smo import (SourceResult, optimizeSource, optimizeSourceMask, projectedStep,      # noqa: F401
                   sourceGradient, sourceLossGradient, sourceSensitivities)
+from .aberrations import (AberrationResult, aberrationGradient, fitAberrations,         # noqa: F401
+                          pupilGradient, wavefrontGradient, zernikeBasis)
 from .vector import (sourcePolarization, vectorAbbeIntensity, vectorPupils,            # noqa: F401
                      vectorSocsKernels)
 from .film import FilmStack, filmPupils                                                 # noqa: F401
@@ -35,6 +37,7 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "hopkinsFields", "hopkinsGradient", "hopkinsIntensityAD", "maskSpectrumAdjoint", "postProcessAdjoint", "optimizeMask", "ILTResult",
            "sourceSensitivities", "sourceGradient", "sourceLossGradient", "projectedStep", "optimizeSource", "optimizeSourceMask",
            "SourceResult",
+           "pupilGradient", "wavefrontGradient", "zernikeBasis", "aberrationGradient", "fitAberrations", "AberrationResult",
            "vectorPupils", "sourcePolarization", "vectorSocsKernels", "vectorAbbeIntensity",
            "FilmStack", "filmPupils",
            "MackResist", "ResistProfile", "latentDiffusion", "developmentRate", "developmentTime", "developedDepth", "resistProfile",

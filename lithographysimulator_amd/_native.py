@@ -89,6 +89,11 @@ _SIGNATURES = {
     "litho_source_sensitivity_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "litho_source_sensitivity": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p,
                                          c_int, c_void_p, c_size_t, c_void_p]),
+    "litho_pupil_vjp_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "litho_pupil_vjp": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p,
+                                c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "litho_pupil_project_work_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "litho_pupil_project": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "litho_mask_spectrum": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "litho_mask_spectrum_complex": (c_int, [c_void_p, c_int, c_double, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
     "litho_rasterize_work_bytes": (c_size_t, [c_int]),

@@ -23,6 +23,11 @@
 // second row pass reduces G^T . |E|^2 over its line (STORE_REDUCE) instead of writing the field; a small kernel sums a point's
 // line partials.  Every sum has one fixed order and nothing is atomic, so a point's number depends on that point alone.
 // Checked against tests/source_grad_oracle.py.
+//
+// Pupil gradients (litho_pupil_vjp) join the two: the rolled load with the stored field (the field in natural layout), the
+// adjoint transform of the mask-gradient path with the G of the item's plane, and a reducing pass that undoes each point's roll
+// and sums the points in list order (k_pupil_reduce); litho_pupil_project pairs the result with a basis of wavefront maps in a
+// two-stage reduction of fixed order.  Checked against tests/pupil_grad_oracle.py.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -42,8 +47,9 @@ enum : int { STORE_FIELD = 0, STORE_REDUCE = 1 };
 // `lines` lines of pn = 2^LOG2P samples, line l = row (l mod pn) of item (l / pn); each becomes its centred pruned transform
 //   dst[q] = sum_i src[i] exp(SIGN 2 pi i (i - c)(q - c) / N),  q in [0, pn),  N = pn << log2m.
 // LOAD_TIMES_MASK: src[i] is first multiplied by mul_c[row][i] (complex [pn][pn], the same for every item);
-// LOAD_TIMES_GRAD: by mul_r[item / per_group][row][i] (real).  dst may BE src: a line is in registers before any of its outputs
-// is written (every write follows a barrier that the line's threads reach with their loads consumed; a 16-point line has one
+// LOAD_TIMES_GRAD: by mul_r[(item mod per_point) / per_group][row][i] (real; per_point = the batch for litho_socs_vjp, whose items
+// are the planes themselves, groups K for the point-major chunks of litho_pupil_vjp).  dst may BE src: a line is in registers
+// before any of its outputs is written (every write follows a barrier that the line's threads reach with their loads consumed; a 16-point line has one
 // thread), and no workgroup touches another's lines.
 // LOAD_ROLLED: item b is plane (b mod per_point) of source point (b / per_point); src holds the per_point planes once and
 //   src[i] = plane[(row - dy) mod pn][(i - dx) mod pn] . mul_c[row][i],  (dy, dx) = shifts[point], read once per line.
@@ -91,7 +97,7 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
             v = LOAD == LOAD_ROLLED ? in[((unsigned)i - dx) & (PN - 1)] : in[i];
             if (LOAD == LOAD_TIMES_MASK || LOAD == LOAD_ROLLED) v = cmul(v, mul_c[(size_t)row * PN + i]);
             if (LOAD == LOAD_TIMES_GRAD) {
-                const float g = mul_r[((size_t)(l >> LOG2P) / per_group * PN + row) * PN + i];
+                const float g = mul_r[((size_t)((l >> LOG2P) % per_point / per_group) * PN + row) * PN + i];
                 v = make_float2(v.x * g, v.y * g);
             }
         }
@@ -197,6 +203,94 @@ __global__ __launch_bounds__(256) void k_vjp_reduce(const float2* __restrict__ k
     }
 }
 
+// The reducing pass of litho_pupil_vjp.  adj holds the chunk's adjoints A[p][j] = L^H(G . E) in the mask frame, item p per_point + j;
+//   grad[j][r][c] (+)= sum_p 2 w_p conj(M[r'][c']) A[p][j][r'][c'],   r' = (r + dy_p) mod pn,  c' = (c + dx_p) mod pn,
+// p ascending: the roll undone per point, as unsigned modular indices (any integer shift, no overflow).  One thread per cell and
+// plane keeps the running fp32 sum; each term is added as
+//   re = fma(2 w, fma(M.re, A.re, M.im A.im), re),   im = fma(2 w, fma(M.re, A.im, -(M.im A.re)), im)
+// (w = 1 without weights), so the additions into a cell are the list's, whatever chunk a point falls into: a chunk that starts
+// from grad (`accumulate`) continues the same sequence, an fp32 store and load changing nothing.  A gather: the reads of one
+// point are a rolled copy of the thread order, contiguous except at the wrap.  cells = pn^2 is a multiple of 256.
+__global__ __launch_bounds__(256) void k_pupil_reduce(const float2* __restrict__ adj, const float2* __restrict__ M,
+                                                      const int32_t* __restrict__ shifts, const float* __restrict__ weights, int points,
+                                                      int per_point, int log2pn, float2* __restrict__ grad, int accumulate)
+{
+    const unsigned pn = 1u << log2pn, wrap = pn - 1;
+    const size_t cells = (size_t)pn << log2pn;
+    const size_t cell = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (cell >= cells) return;
+    const unsigned r = (unsigned)(cell >> log2pn), c = (unsigned)cell & wrap;
+    for (int j = blockIdx.y; j < per_point; j += gridDim.y) {
+        float2* g = grad + (size_t)j * cells + cell;
+        float2 acc = accumulate ? *g : make_float2(0.f, 0.f);
+        for (int p = 0; p < points; ++p) {
+            const unsigned dy = (unsigned)shifts[2 * p], dx = (unsigned)shifts[2 * p + 1];
+            const size_t at = ((size_t)((r + dy) & wrap) << log2pn) | ((c + dx) & wrap);
+            const float2 a = adj[((size_t)p * per_point + j) * cells + at];
+            const float2 m = M[at];
+            const float tw = weights ? 2.0f * weights[p] : 2.0f;
+            acc.x = fmaf(tw, fmaf(m.x, a.x, m.y * a.y), acc.x);
+            acc.y = fmaf(tw, fmaf(m.x, a.y, -(m.y * a.x)), acc.y);
+        }
+        *g = acc;
+    }
+}
+
+// litho_pupil_project, stage 1: workgroup (x, y) sums d . basis_j for the PROJ_JT terms j = y PROJ_JT ... over its grid-stride share
+// of the planes' cells, d = 2 pi Im(grad conj(P)) = 2 pi (g.im P.re - g.re P.im).  grad and the pupils are read once per tile of
+// PROJ_JT terms, two cells per thread and access; each thread adds its cells in ascending order, the lanes of a wave meet in the
+// xor butterfly, the four waves through LDS in wave order.  partial[x][j]; nothing is atomic.
+static constexpr int PROJ_JT = 16;
+static constexpr int PROJ_MAX_BLOCKS = 1024;
+typedef float float2u __attribute__((ext_vector_type(2), aligned(4)));     // two fp32 of a 4-byte aligned array in one access
+
+__global__ __launch_bounds__(256) void k_project_partial(const float2* __restrict__ grad, const float2* __restrict__ pupils,
+                                                         const float* __restrict__ basis, int J, long long cells, long long pairs,
+                                                         float* __restrict__ partial)
+{
+    constexpr float TWO_PI = 6.28318530717958647692f;
+    const int j0 = blockIdx.y * PROJ_JT;
+    const int nj = J - j0 < PROJ_JT ? J - j0 : PROJ_JT;
+    float acc[PROJ_JT];
+#pragma unroll
+    for (int t = 0; t < PROJ_JT; ++t) acc[t] = 0.f;
+    for (long long q = (long long)blockIdx.x * 256 + threadIdx.x; q < pairs; q += (long long)gridDim.x * 256) {
+        const long long e = 2 * q, cell = e & (cells - 1);                 // cells is a power of two: the basis is shared by the planes
+        const float4c g = *reinterpret_cast<const float4c*>(grad + e);
+        const float4c p = *reinterpret_cast<const float4c*>(pupils + e);
+        const float d0 = TWO_PI * fmaf(g.y, p.x, -(g.x * p.y));
+        const float d1 = TWO_PI * fmaf(g.w, p.z, -(g.z * p.w));
+#pragma unroll
+        for (int t = 0; t < PROJ_JT; ++t) {
+            if (t < nj) {
+                const float2u b = *reinterpret_cast<const float2u*>(basis + (size_t)(j0 + t) * cells + cell);
+                acc[t] = fmaf(d1, b.y, fmaf(d0, b.x, acc[t]));
+            }
+        }
+    }
+    __shared__ float red[4][PROJ_JT];
+#pragma unroll
+    for (int t = 0; t < PROJ_JT; ++t) {
+#pragma unroll
+        for (int o = 32; o >= 1; o /= 2) acc[t] += __shfl_xor(acc[t], o);
+        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][t] = acc[t];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nj)
+        partial[(size_t)blockIdx.x * J + j0 + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// stage 2: out[j] = the sum of the `blocks` partials of term j: one wave per term, lane t over t, t + 64, ... ascending, then the
+// xor butterfly.
+__global__ __launch_bounds__(64) void k_project_final(const float* __restrict__ partial, int blocks, int J, float* __restrict__ out)
+{
+    float acc = 0.f;
+    for (int b = threadIdx.x; b < blocks; b += 64) acc += partial[(size_t)b * J + blockIdx.x];
+#pragma unroll
+    for (int o = 32; o >= 1; o /= 2) acc += __shfl_xor(acc, o);
+    if (threadIdx.x == 0) out[blockIdx.x] = acc;
+}
+
 struct RowArgs {
     const float2* src;
     float2* dst;
@@ -227,12 +321,14 @@ static hipError_t centred_rows(const RowArgs& a, int pn, int sign, hipStream_t s
 }
 
 // data <- L(first-pass product) for sign +1, L^H for sign -1: rows (with the product on the load), transpose, rows, transpose.
+// The `batch` items are `per_point` planes per source point, point-major (LOAD_ROLLED reads shifts[point]; LOAD_TIMES_GRAD takes
+// the plane's G); a plain batch of planes is one point of `batch` planes.
 template <int LOAD>
 static hipError_t centred2d(const float2* src, float2* data, const float2* mul_c, const float* mul_r, int per_group, int batch, int pn,
-                            int log2m, int sign, hipStream_t st)
+                            int log2m, int sign, hipStream_t st, int per_point, const int32_t* shifts = nullptr)
 {
     const long long lines = (long long)batch * pn;
-    hipError_t e = centred_rows<LOAD>(RowArgs{src, data, mul_c, mul_r, per_group, lines, log2m}, pn, sign, st);
+    hipError_t e = centred_rows<LOAD>(RowArgs{src, data, mul_c, mul_r, per_group, lines, log2m, shifts, per_point}, pn, sign, st);
     if (e != hipSuccess) return e;
     e = transpose(data, batch, pn, st);
     if (e != hipSuccess) return e;
@@ -267,6 +363,17 @@ static bool sens_work(int groups, int K, int batch, int pn, SensWork& w)
     return true;
 }
 
+// Workgroups of litho_pupil_project's first stage: a function of the sizes alone, so the order of every sum is too.  0 for a
+// bad argument.
+static int project_blocks(int planes, int J, int pn)
+{
+    if (planes < 1 || J < 1 || J > LITHO_PUPIL_PROJECT_MAX_TERMS || !fft_size_ok(pn)) return 0;
+    const long long pairs = (long long)planes * pn * pn / 2;
+    if ((long long)planes * pn > INT_MAX) return 0;
+    const long long blocks = (pairs + 255) / 256;
+    return (int)(blocks < PROJ_MAX_BLOCKS ? blocks : PROJ_MAX_BLOCKS);
+}
+
 }  // namespace litho
 
 extern "C" {
@@ -280,7 +387,7 @@ int litho_socs_fields(const void* kernels, const void* maskFT, int batch, int pn
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(fill_twiddles(st));
     HIP_TRY(centred2d<LOAD_TIMES_MASK>((const float2*)kernels, (float2*)fields, (const float2*)maskFT, nullptr, 1, batch, pn,
-                                       log2_exact(N) - log2_exact(pn), +1, st));
+                                       log2_exact(N) - log2_exact(pn), +1, st, batch));
     return LITHO_OK;
 }
 
@@ -305,8 +412,9 @@ int litho_socs_vjp(const void* kernels, const void* maskFT, const float* gradI, 
     const int log2m = log2_exact(N) - log2_exact(pn);
     HIP_TRY(fill_twiddles(st));
     // the fields of the batch, then L^H of G . E in place
-    HIP_TRY(centred2d<LOAD_TIMES_MASK>((const float2*)kernels, w, (const float2*)maskFT, nullptr, 1, (int)batch, pn, log2m, +1, st));
-    HIP_TRY(centred2d<LOAD_TIMES_GRAD>(w, w, nullptr, gradI, K, (int)batch, pn, log2m, -1, st));
+    HIP_TRY(centred2d<LOAD_TIMES_MASK>((const float2*)kernels, w, (const float2*)maskFT, nullptr, 1, (int)batch, pn, log2m, +1, st,
+                                       (int)batch));
+    HIP_TRY(centred2d<LOAD_TIMES_GRAD>(w, w, nullptr, gradI, K, (int)batch, pn, log2m, -1, st, (int)batch));
     const long long cells = (long long)pn * pn, pairs = cells / 2;
     long long blocks = (pairs + 255) / 256;
     if (blocks > 65536) blocks = 65536;                            // grid-stride beyond that
@@ -355,6 +463,71 @@ int litho_source_sensitivity(const void* pupils, const void* maskFT, const float
         hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)nb), dim3(64), 0, st, (const float*)partial, per_point * pn, sens + p0);
         HIP_TRY(hipGetLastError());
     }
+    return LITHO_OK;
+}
+
+size_t litho_pupil_vjp_work_bytes(int groups, int K, int batch, int pn)
+{
+    litho::SensWork w;
+    return litho::sens_work(groups, K, batch, pn, w) ? w.fields * sizeof(float2) : 0;
+}
+
+int litho_pupil_vjp(const void* pupils, const void* maskFT, const float* gradI, int groups, int K, const int32_t* shifts,
+                    const float* weights, int64_t count, int pn, int N, void* grad, int accumulate, int batch, void* work,
+                    size_t work_bytes, void* stream)
+{
+    using namespace litho;
+    if (!pupils || !maskFT || !gradI || !grad || !work || groups < 1 || K < 1 || batch < 1 || count < 0) return LITHO_E_ARG;
+    if (!shifts && count > 0) return LITHO_E_ARG;                  // an empty list has no address
+    if (!fft_size_ok(pn) || !fft_size_ok(N)) return LITHO_E_ARG;
+    if (N < pn) return LITHO_E_NSMALL;
+    SensWork w;
+    if (!sens_work(groups, K, batch, pn, w)) return LITHO_E_ARG;   // more than INT_MAX lines in a chunk
+    if (work_bytes < w.fields * sizeof(float2)) return LITHO_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const int log2pn = log2_exact(pn), log2m = log2_exact(N) - log2pn, per_point = groups * K;
+    const size_t cells = (size_t)pn * pn;
+    if (count == 0) {
+        if (!accumulate) HIP_TRY(hipMemsetAsync(grad, 0, (size_t)per_point * cells * sizeof(float2), st));
+        return LITHO_OK;
+    }
+    float2* fields = (float2*)work;
+    HIP_TRY(fill_twiddles(st));
+    const dim3 rgrid((unsigned)(cells / 256), (unsigned)(per_point < 65535 ? per_point : 65535));
+    for (int64_t p0 = 0; p0 < count; p0 += batch) {
+        const int nb = count - p0 < batch ? (int)(count - p0) : batch;
+        const int items = nb * per_point;
+        // the fields of the chunk in natural layout, L^H of G . E in place, then the roll undone and the points summed
+        HIP_TRY(centred2d<LOAD_ROLLED>((const float2*)pupils, fields, (const float2*)maskFT, nullptr, 1, items, pn, log2m, +1, st,
+                                       per_point, shifts + 2 * p0));
+        HIP_TRY(centred2d<LOAD_TIMES_GRAD>(fields, fields, nullptr, gradI, K, items, pn, log2m, -1, st, per_point));
+        hipLaunchKernelGGL(k_pupil_reduce, rgrid, dim3(256), 0, st, (const float2*)fields, (const float2*)maskFT, shifts + 2 * p0,
+                           weights ? weights + p0 : nullptr, nb, per_point, log2pn, (float2*)grad, (accumulate || p0 > 0) ? 1 : 0);
+        HIP_TRY(hipGetLastError());
+    }
+    return LITHO_OK;
+}
+
+size_t litho_pupil_project_work_bytes(int planes, int J, int pn)
+{
+    return (size_t)litho::project_blocks(planes, J, pn) * (size_t)(J > 0 ? J : 0) * sizeof(float);
+}
+
+int litho_pupil_project(const void* grad, const void* pupils, int planes, const float* basis, int J, int pn, float* out, void* work,
+                        size_t work_bytes, void* stream)
+{
+    using namespace litho;
+    if (!grad || !pupils || !basis || !out || !work) return LITHO_E_ARG;
+    const int blocks = project_blocks(planes, J, pn);
+    if (blocks == 0) return LITHO_E_ARG;
+    if (work_bytes < (size_t)blocks * J * sizeof(float)) return LITHO_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const long long cells = (long long)pn * pn;
+    hipLaunchKernelGGL(k_project_partial, dim3((unsigned)blocks, (unsigned)((J + PROJ_JT - 1) / PROJ_JT)), dim3(256), 0, st,
+                       (const float2*)grad, (const float2*)pupils, basis, J, cells, (long long)planes * cells / 2, (float*)work);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_project_final, dim3((unsigned)J), dim3(64), 0, st, (const float*)work, blocks, J, out);
+    HIP_TRY(hipGetLastError());
     return LITHO_OK;
 }
 
