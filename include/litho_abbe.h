@@ -591,6 +591,51 @@ int litho_peb_bake(const float *acid_in, int B, int D, int n, double thickness_n
 int litho_peb_rate(const float *acid_dose, int B, int D, int n, double k_amp, double r_max, double r_min, double q, double m_th,
                    double surface_rate, double surface_depth_nm, double thickness_nm, float *slowness, float *inhibitor, void *stream);
 
+/* ---- Gradients through the bake (csrc/peb.hip; checked against the float64 restatement tests/peb_grad_oracle.py, itself pinned to
+ * central differences of tests/peb_oracle.py).  The discrete adjoint of the S bake steps above, for a real loss l on the bake's
+ * outputs (h_S, q_S, a_S) with cotangents gh = dl/dh_S, gq = dl/dq_S, ga = dl/da_S (any may be absent = zero, not all).
+ *
+ * Forward step k = 0 .. S-1, (h_k, q_k, a_k) -> (h_k+1, q_k+1, a_k+1):  hd = A_h h_k, qd = A_q q_k with A_s the diffusion line
+ * (A_s = I when sigma_s = 0);  R = beta hd qd / (1 + beta (hd + qd)), or (hd < qd) ? hd : qd when beta = +inf;
+ * h_k+1 = (hd - R) fl;  q_k+1 = qd - R;  a_k+1 = a_k + half_dt (h_k + h_k+1).  With mirror faces A_s = I + lambda (graph
+ * Laplacian of the grid) is symmetric: its transpose is the same stencil with the same face rule.
+ *
+ * Backward step.  abar = ga throughout.  hbar_S = gh, qbar_S = gq; for k = S-1 .. 0, with the step's own (hd, qd), all fp32, each
+ * line a fixed sequence of single operations, per cell:
+ *   hp  = hbar_k+1 + half_dt abar
+ *   finite beta:    Dn = 1 + beta (hd + qd);  R_h = beta qd (1 + beta qd) / (Dn Dn);  R_q = beta hd (1 + beta hd) / (Dn Dn)
+ *                   (each left to right: ((beta qd) (1 + beta qd)) / (Dn Dn))
+ *   instantaneous:  R_h = (hd < qd) ? 1 : 0;  R_q = 1 - R_h                 (the forward's own comparison)
+ *   f = fl hp;  u = f (1 - R_h) - qbar_k+1 R_h;  v = qbar_k+1 (1 - R_q) - f R_q
+ *   hbar_k = A_h u + half_dt abar,  qbar_k = A_q v:  x + lxy (((W + E) + (S + N)) - 4 x) + lz ((U + Dn) - 2 x) on u and on v, the
+ *   neighbours' u, v evaluated by the same lines at the neighbour cells (a gather; a cell at a face takes itself).
+ * Results: dl/dh_0 = hbar_0 and qbar_0; the initial quencher is uniform, so dl/dquencher0 of a volume is the sum of its qbar_0.
+ * u and v are convex combinations of (f, -qbar) and (-f, qbar) and A_s has non-negative rows that sum to 1, so
+ * |hbar_0|, |qbar_0| <= G = max(|gh|_inf, |gq|_inf) + bake_time |ga|_inf.
+ *
+ * litho_peb_bake_vjp is stateless: it runs its own forward sweep from acid_in and keeps (h_k, q_k) at k = c, 2c, .. < S, c =
+ * checkpoint_every in 1 .. S; the backward sweep takes the segments of c steps last to first, re-runs each from its checkpoint
+ * through the one step function while taping (hd, qd), then runs its backward steps -- one launch per step, a thread per cell,
+ * no atomics and no scatter: two calls give the same bits, the bits do not depend on c, and a batch equals its volumes one at a
+ * time.  work: litho_peb_vjp_work_bytes(B, D, n, steps, c) = (2 (ceil(S / c) - 1) + 2 c + 8) volumes of B D n n floats (the
+ * checkpoints, one segment's tape, the ping-pong of (h, q) and of (hbar, qbar)); 0 for a bad argument; 16-byte aligned, less is
+ * LITHO_E_WORKSPACE.  The physical arguments are litho_peb_bake's, checked alike.  grad_acid, grad_quencher, grad_acid_dose
+ * (gh, gq, ga; NULL = zero) and the outputs grad_acid_in (hbar_0) and grad_quencher_in (qbar_0, NULL: not returned) are fp32
+ * [B,D,n,n].  LITHO_E_ARG: all three cotangents NULL, steps below litho_peb_min_steps(...) or above 65536, c outside 1 .. steps,
+ * a bad volume, an output overlapping an input, the other output or work, an input overlapping work.  NaN in the acid propagates
+ * by arithmetic and is not otherwise specified.  Asynchronous, no allocation, no host wait.
+ *
+ * litho_peb_expose_vjp: the exposure h0[g] = 1 - exp(-(C gain_g) I) backwards, grad_image = sum_g (C gain_g) exp(-(C gain_g) I)
+ * grad_acid[g], the gains in ascending order, double per cell, rounded to fp32 once; image, grad_image fp32 [volumes,D,n,n],
+ * grad_acid fp32 [n_gains volumes,D,n,n] gain-major, grad_image overlapping neither; otherwise litho_peb_expose's checks. */
+size_t litho_peb_vjp_work_bytes(int B, int D, int n, int steps, int checkpoint_every);
+int litho_peb_bake_vjp(const float *acid_in, int B, int D, int n, double thickness_nm, double pixel_nm, double quencher0, double k_quench,
+                       double k_loss, double sigma_acid_nm, double sigma_quencher_nm, double vertical_scale, double bake_time_s, int steps,
+                       int checkpoint_every, const float *grad_acid, const float *grad_quencher, const float *grad_acid_dose,
+                       float *grad_acid_in, float *grad_quencher_in, void *work, size_t work_bytes, void *stream);
+int litho_peb_expose_vjp(const float *image, int volumes, int D, int n, const float *gains_host, int n_gains, double C,
+                         const float *grad_acid, float *grad_image, void *stream);
+
 /* ---- Mask gradients of Hopkins imaging (csrc/socs_grad.hip; no reference counterpart, checked against tests/socs_grad_oracle.py).
  * With F[q][i] = exp(+2 pi i (i - c)(q - c) / N), c = pn / 2, q, i in [0, pn), the engine's chain at shift (0,0) is L(X) = F X F^T,
  * the coherent fields are E_k = L(phi_k . M) and I = sum_k |E_k|^2.  For a real loss l with G = dl/dI,

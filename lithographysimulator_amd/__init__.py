@@ -12,8 +12,8 @@ from .metrology import (LayoutSites, OPCResult, biasLayout, correctLayout,      
 from .contours import (Contours, contourVertices, contoursToGDSII, contoursToLayout,   # noqa: F401
                        doseFocusEnvelope, processVariationBand, simplifyContour, traceContours)
 from .socs import SOCSKernels, hopkinsImage, hopkinsIntensity, socsKernels          # noqa: F401
-from .ilt import (ILTResult, hopkinsFields, hopkinsGradient, hopkinsIntensityAD,       # noqa: F401
-                  maskSpectrumAdjoint, optimizeMask, postProcessAdjoint)
+from .ilt import (ILTResult, bakedResistModel, hopkinsFields, hopkinsGradient,         # noqa: F401
+                  hopkinsIntensityAD, maskSpectrumAdjoint, optimizeMask, postProcessAdjoint)
 from .smo import (SourceResult, optimizeSource, optimizeSourceMask, projectedStep,      # noqa: F401
                   sourceGradient, sourceLossGradient, sourceSensitivities)
 from .aberrations import (AberrationResult, aberrationGradient, fitAberrations,         # noqa: F401
@@ -23,7 +23,8 @@ from .vector import (sourcePolarization, vectorAbbeIntensity, vectorPupils,     
 from .film import FilmStack, filmPupils                                                 # noqa: F401
 from .develop import (MackResist, ResistProfile, developedDepth, developmentRate,      # noqa: F401
                       developmentTime, latentDiffusion, resistProfile)
-from .peb import BakeResult, ChemicallyAmplifiedResist, postExposureBake              # noqa: F401
+from .peb import (BakeResult, ChemicallyAmplifiedResist, bakeGradient,                 # noqa: F401
+                  exposeAcidGradient, postExposureBake, postExposureBakeGradient)
 from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
@@ -41,4 +42,5 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "vectorPupils", "sourcePolarization", "vectorSocsKernels", "vectorAbbeIntensity",
            "FilmStack", "filmPupils",
            "MackResist", "ResistProfile", "latentDiffusion", "developmentRate", "developmentTime", "developedDepth", "resistProfile",
-           "ChemicallyAmplifiedResist", "BakeResult", "postExposureBake"]
+           "ChemicallyAmplifiedResist", "BakeResult", "postExposureBake",
+           "bakeGradient", "exposeAcidGradient", "postExposureBakeGradient", "bakedResistModel"]

@@ -78,7 +78,12 @@ _SIGNATURES = {
     "litho_peb_steps_per_launch": (c_int, [c_int]),
     "litho_peb_bake": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_double,
                                c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
-    "litho_peb_rate": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_double,
+    "litho_peb_vjp_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "litho_peb_bake_vjp": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_double,
+                                   c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                   c_void_p]),
+    "litho_peb_expose_vjp": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    "litho_peb_rate": (c_int,[c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_double,
                                c_double, c_void_p, c_void_p, c_void_p]),
     "litho_tcc_apply_vector_work_bytes": (c_size_t, [c_int, c_int]),
     "litho_tcc_apply_vector": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),

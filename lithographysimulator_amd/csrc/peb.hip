@@ -7,6 +7,10 @@
 //   k_peb_direct   one bake step per launch: a thread per cell, the six neighbours of both species from global memory
 //   k_peb_fused    s >= 2 bake steps per launch (temporal blocking, below)
 //   k_peb_rate     inhibitor m = exp(-kAmp a), Mack's rate and the surface factor in double per cell, slowness 1 / r out
+// and behind litho_peb_bake_vjp and litho_peb_expose_vjp, the bake and the exposure backwards (section 2b):
+//   k_peb_taped       one bake step per launch through peb_step, without a, storing the step's (hd, qd) when a tape is given
+//   k_peb_adjoint     one backward step per launch: a thread per cell gathers (u, v) at the cell and its six neighbours
+//   k_peb_expose_vjp  gI = sum_g (C g) exp(-(C g) I) gh0[g] in double per cell
 // The arithmetic of a step is peb_step and nothing else: both bake kernels call it with the same inputs in the same order, so
 // the bits of a bake do not depend on how its steps are cut into launches.  expose and rate move four consecutive x per thread
 // (16-byte accesses) when n is a multiple of 4 and the pointers are 16-byte aligned, one otherwise.
@@ -108,11 +112,14 @@ __global__ __launch_bounds__(256) void k_peb_expose(const float* __restrict__ im
 
 // ---- 2. one bake step of one cell.  h, q: the cell at the start of the step; nb_h(), nb_q(): its six neighbours at the start
 // of the step, fetched only for a species that diffuses.  Diffusion (Jacobi, no flux), neutralisation, acid loss, and the
-// trapezoid of the amplification integral, in this order; every line is include/litho_abbe.h's.
+// trapezoid of the amplification integral, in this order; every line is include/litho_abbe.h's.  hd, qd: the two species after
+// the diffusion line, what the reaction saw -- the tape of the backward sweep (k_peb_taped), a dead store elsewhere.
 template <class FH, class FQ>
-__device__ __forceinline__ void peb_step(const PebStep& P, float h, float q, FH nb_h, FQ nb_q, float& h_new, float& q_new, float& a)
+__device__ __forceinline__ void peb_step(const PebStep& P, float h, float q, FH nb_h, FQ nb_q, float& h_new, float& q_new, float& a,
+                                         float& hd, float& qd)
 {
-    float hd = h, qd = q;
+    hd = h;
+    qd = q;
     if (P.diffuse_h) {
         const PebNb b = nb_h();
         hd = h + P.lxy_h * (((b.w + b.e) + (b.s + b.n)) - 4.f * h) + P.lz_h * ((b.u + b.d) - 2.f * h);
@@ -143,9 +150,9 @@ __global__ __launch_bounds__(256) void k_peb_direct(const float* __restrict__ h_
     auto around = [&](const float* c) -> PebNb { return PebNb{c[w], c[ea], c[s], c[nn], c[u], c[dn]}; };
     const bool first = q_in == nullptr;
     const float h = h_in[at], q = first ? q0 : q_in[at];
-    float a = first ? 0.f : a_io[at], h_new, q_new;
+    float a = first ? 0.f : a_io[at], h_new, q_new, hd, qd;
     peb_step(P, h, q, [&] { return around(h_in + at); }, [&] { return first ? PebNb{q0, q0, q0, q0, q0, q0} : around(q_in + at); }, h_new,
-             q_new, a);
+             q_new, a, hd, qd);
     h_out[at] = h_new;
     q_out[at] = q_new;
     a_io[at] = a;
@@ -190,8 +197,8 @@ __global__ __launch_bounds__(256) void k_peb_fused(const float* __restrict__ h_i
             const int ty = ly - s, tx = lx - s;
             const bool mine = ty >= 0 && ty < PEB_TILE && tx >= 0 && tx < PEB_TILE;
             const int ai = d * 256 + ty * PEB_TILE + tx;
-            float h_new, q_new, a = mine ? al[ai] : 0.f;                  // a halo cell's a is not kept
-            peb_step(P, hc[c], qc[c], [&] { return around(hc); }, [&] { return around(qc); }, h_new, q_new, a);
+            float h_new, q_new, hd, qd, a = mine ? al[ai] : 0.f;          // a halo cell's a is not kept
+            peb_step(P, hc[c], qc[c], [&] { return around(hc); }, [&] { return around(qc); }, h_new, q_new, a, hd, qd);
             hn[c] = h_new;
             qn[c] = q_new;
             if (mine) al[ai] = a;
@@ -208,6 +215,118 @@ __global__ __launch_bounds__(256) void k_peb_fused(const float* __restrict__ h_i
         q_out[g] = qc[c];
         a_io[g] = al[d * 256 + tid];
     }
+}
+
+// ---- 2b. the backward sweep of the bake (litho_peb_bake_vjp; the definitions are include/litho_abbe.h's "Gradients through the
+// bake").  k_peb_taped is k_peb_direct without the amplification integral (nothing in the adjoint needs a): one step through
+// peb_step, the step's (hd, qd) to the tape when one is given, the new state when one is wanted.  q_in == nullptr: q = q0.
+__global__ __launch_bounds__(256) void k_peb_taped(const float* __restrict__ h_in, const float* __restrict__ q_in, float q0,
+                                                   float* __restrict__ h_out, float* __restrict__ q_out, float* __restrict__ hd_out,
+                                                   float* __restrict__ qd_out, int D, int n, const PebStep P)
+{
+    const long long plane_elems = (long long)n * n;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= plane_elems) return;
+    const int p = blockIdx.y, d = p % D, row = (int)(e / n), col = (int)(e - (long long)row * n);
+    const size_t at = (size_t)p * plane_elems + e;
+    const long long w = col > 0 ? -1 : 0, ea = col + 1 < n ? 1 : 0, s = row > 0 ? -(long long)n : 0, nn = row + 1 < n ? n : 0;
+    const long long u = d > 0 ? -plane_elems : 0, dn = d + 1 < D ? plane_elems : 0;
+    auto around = [&](const float* c) -> PebNb { return PebNb{c[w], c[ea], c[s], c[nn], c[u], c[dn]}; };
+    const bool first = q_in == nullptr;
+    const float h = h_in[at], q = first ? q0 : q_in[at];
+    float a = 0.f, h_new, q_new, hd, qd;
+    peb_step(P, h, q, [&] { return around(h_in + at); }, [&] { return first ? PebNb{q0, q0, q0, q0, q0, q0} : around(q_in + at); }, h_new,
+             q_new, a, hd, qd);
+    if (h_out) {
+        h_out[at] = h_new;
+        q_out[at] = q_new;
+    }
+    if (hd_out) {
+        hd_out[at] = hd;
+        qd_out[at] = qd;
+    }
+}
+
+// The pointwise half of the backward step: (u, v) of one cell from hp = hbar + half_dt abar, qbar and the step's (hd, qd).
+struct PebUV {
+    float u, v;
+};
+__device__ __forceinline__ PebUV peb_react_adjoint(const PebStep& P, float hp, float qb, float hd, float qd)
+{
+    float Rh, Rq;
+    if (P.instant) {
+        Rh = (hd < qd) ? 1.f : 0.f;                      // the forward's own comparison
+        Rq = 1.f - Rh;
+    } else {
+        const float Dn = 1.f + P.beta * (hd + qd), DD = Dn * Dn;
+        Rh = P.beta * qd * (1.f + P.beta * qd) / DD;
+        Rq = P.beta * hd * (1.f + P.beta * hd) / DD;
+    }
+    const float fhp = P.fl * hp;
+    return PebUV{fhp * (1.f - Rh) - qb * Rh, qb * (1.f - Rq) - fhp * Rq};
+}
+// One backward step of one cell.  uv(i): (u, v) at the cell (i = 0) and at its neighbours W, E, S, N, U, Dn (i = 1 .. 6, the cell
+// itself beyond a face), asked for only when a species diffuses; ha = half_dt abar at the cell.  A_s is symmetric, so the
+// transposed stencil is the forward's line on u and v: a gather.
+template <class F>
+__device__ __forceinline__ void peb_step_adjoint(const PebStep& P, F uv, float ha, float& hb, float& qb)
+{
+    const PebUV c = uv(0);
+    float hu = c.u, qv = c.v;
+    if (P.diffuse_h || P.diffuse_q) {
+        const PebUV w = uv(1), e = uv(2), s = uv(3), n = uv(4), up = uv(5), dn = uv(6);
+        if (P.diffuse_h) hu = c.u + P.lxy_h * (((w.u + e.u) + (s.u + n.u)) - 4.f * c.u) + P.lz_h * ((up.u + dn.u) - 2.f * c.u);
+        if (P.diffuse_q) qv = c.v + P.lxy_q * (((w.v + e.v) + (s.v + n.v)) - 4.f * c.v) + P.lz_q * ((up.v + dn.v) - 2.f * c.v);
+    }
+    hb = hu + ha;
+    qb = qv;
+}
+
+// grid as k_peb_direct.  hb_in, qb_in, abar: the cotangents after the step, nullptr = zero; hd, qd: the step's tape.
+__global__ __launch_bounds__(256) void k_peb_adjoint(const float* __restrict__ hb_in, const float* __restrict__ qb_in,
+                                                     const float* __restrict__ abar, const float* __restrict__ hd,
+                                                     const float* __restrict__ qd, float* __restrict__ hb_out, float* __restrict__ qb_out,
+                                                     int D, int n, const PebStep P)
+{
+    const long long plane_elems = (long long)n * n;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= plane_elems) return;
+    const int p = blockIdx.y, d = p % D, row = (int)(e / n), col = (int)(e - (long long)row * n);
+    const size_t at = (size_t)p * plane_elems + e;
+    const long long off[7] = {0, col > 0 ? -1 : 0, col + 1 < n ? 1 : 0, row > 0 ? -(long long)n : 0, row + 1 < n ? n : 0,
+                              d > 0 ? -plane_elems : 0, d + 1 < D ? plane_elems : 0};
+    auto uv = [&](int i) -> PebUV {
+        const size_t c = (size_t)((long long)at + off[i]);
+        const float hp = (hb_in ? hb_in[c] : 0.f) + P.half_dt * (abar ? abar[c] : 0.f);
+        return peb_react_adjoint(P, hp, qb_in ? qb_in[c] : 0.f, hd[c], qd[c]);
+    };
+    float hb, qb;
+    peb_step_adjoint(P, uv, P.half_dt * (abar ? abar[at] : 0.f), hb, qb);
+    hb_out[at] = hb;
+    qb_out[at] = qb;
+}
+
+// The exposure's VJP: gI = sum_g (C g) exp(-(C g) I) gh0[g], the gains in ascending order, double per cell, rounded once.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_peb_expose_vjp(const float* __restrict__ image, const float* __restrict__ grad_acid,
+                                                        float* __restrict__ grad_image, int planes, int n, const PebGains gains,
+                                                        int n_gains, double C)
+{
+    const long long plane_elems = (long long)n * n;
+    const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
+    if (e >= plane_elems) return;
+    const int p = blockIdx.y;
+    const Pack<VEC> I = load_pack<VEC>(image + (size_t)p * plane_elems + e);
+    double sum[VEC];
+    for (int v = 0; v < VEC; ++v) sum[v] = 0.0;
+    for (int gi = 0; gi < n_gains; ++gi) {
+        const double Cg = C * (double)gains.g[gi];
+        const Pack<VEC> g = load_pack<VEC>(grad_acid + ((size_t)gi * planes + p) * plane_elems + e);
+        for (int v = 0; v < VEC; ++v) sum[v] = sum[v] + Cg * exp(-(Cg * (double)I.v[v])) * (double)g.v[v];
+    }
+    Pack<VEC> out;
+    for (int v = 0; v < VEC; ++v) out.v[v] = (float)sum[v];
+    store_pack<VEC>(grad_image + (size_t)p * plane_elems + e, out);
 }
 
 // ---- 3. rate: m = exp(-kAmp a), x = (1 - m)^q, r = (rmax (a_m + 1)) x / (a_m + x) + rmin, times the surface factor of the
@@ -281,6 +400,28 @@ static int min_steps(double sigma_h, double sigma_q, double vscale, double thick
     return S <= PEB_MAXSTEPS ? S : 0;
 }
 
+// the step's parameters as the kernels take them: formed in double, rounded to fp32 once
+static PebStep step_of(double thickness_nm, double pixel_nm, double k_quench, double k_loss, double sigma_acid_nm, double sigma_quencher_nm,
+                       double vertical_scale, double bake_time_s, int D, int steps)
+{
+    const double hz = thickness_nm / D, dt = bake_time_s / steps;
+    double lxy_h, lz_h, lxy_q, lz_q;
+    lambdas(sigma_acid_nm, vertical_scale, pixel_nm, hz, steps, lxy_h, lz_h);
+    lambdas(sigma_quencher_nm, vertical_scale, pixel_nm, hz, steps, lxy_q, lz_q);
+    PebStep P;
+    P.lxy_h = (float)lxy_h; P.lz_h = (float)lz_h; P.lxy_q = (float)lxy_q; P.lz_q = (float)lz_q;
+    P.beta = (float)(k_quench * dt);
+    P.fl = (float)std::exp(-k_loss * dt);
+    P.half_dt = (float)(0.5 * dt);
+    P.diffuse_h = sigma_acid_nm > 0.0;
+    P.diffuse_q = sigma_quencher_nm > 0.0;
+    P.instant = std::isinf(P.beta);                       // kQuench = +inf, or kQuench dt beyond fp32
+    return P;
+}
+// the workspace of litho_peb_bake_vjp in volumes: the checkpoints (h, q) at c, 2 c, ... < S, one segment's tape (hd, qd) of c steps,
+// the ping-pong of the re-run's (h, q) and the ping-pong of (hbar, qbar)
+static size_t vjp_volumes(int steps, int c) { return 2 * (size_t)((steps + c - 1) / c - 1) + 2 * (size_t)c + 8; }
+
 }  // namespace litho
 
 extern "C" {
@@ -350,18 +491,7 @@ int litho_peb_bake(const float* acid_in, int B, int D, int n, double thickness_n
     for (int i = 0; i < 5; ++i)
         for (int j = i + 1; j < 5; ++j)
             if (overlap(bufs[i], i == 4 ? need : vol_bytes, bufs[j], j == 4 ? need : vol_bytes)) return LITHO_E_ARG;
-    const double hz = thickness_nm / D, dt = bake_time_s / steps;
-    double lxy_h, lz_h, lxy_q, lz_q;
-    lambdas(sigma_acid_nm, vertical_scale, pixel_nm, hz, steps, lxy_h, lz_h);
-    lambdas(sigma_quencher_nm, vertical_scale, pixel_nm, hz, steps, lxy_q, lz_q);
-    PebStep P;
-    P.lxy_h = (float)lxy_h; P.lz_h = (float)lz_h; P.lxy_q = (float)lxy_q; P.lz_q = (float)lz_q;
-    P.beta = (float)(k_quench * dt);
-    P.fl = (float)std::exp(-k_loss * dt);
-    P.half_dt = (float)(0.5 * dt);
-    P.diffuse_h = sigma_acid_nm > 0.0;
-    P.diffuse_q = sigma_quencher_nm > 0.0;
-    P.instant = std::isinf(P.beta);                       // kQuench = +inf, or kQuench dt beyond fp32
+    const PebStep P = step_of(thickness_nm, pixel_nm, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps);
     const float q0 = (float)quencher0;
     if (std::isinf(q0) || std::isinf(P.half_dt)) return LITHO_E_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -394,6 +524,121 @@ int litho_peb_bake(const float* acid_in, int B, int D, int n, double thickness_n
         src_q = out_q[to];
         left -= now;
     }
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+size_t litho_peb_vjp_work_bytes(int B, int D, int n, int steps, int checkpoint_every)
+{
+    using namespace litho;
+    if (!volume_ok(B, D, n) || steps < 1 || steps > PEB_MAXSTEPS || checkpoint_every < 1 || checkpoint_every > steps) return 0;
+    return vjp_volumes(steps, checkpoint_every) * ((size_t)B * D * n * n * sizeof(float));
+}
+
+int litho_peb_bake_vjp(const float* acid_in, int B, int D, int n, double thickness_nm, double pixel_nm, double quencher0, double k_quench,
+                       double k_loss, double sigma_acid_nm, double sigma_quencher_nm, double vertical_scale, double bake_time_s, int steps,
+                       int checkpoint_every, const float* grad_acid, const float* grad_quencher, const float* grad_acid_dose,
+                       float* grad_acid_in, float* grad_quencher_in, void* work, size_t work_bytes, void* stream)
+{
+    using namespace litho;
+    if (!acid_in || !grad_acid_in || !work || !volume_ok(B, D, n)) return LITHO_E_ARG;
+    if (!grad_acid && !grad_quencher && !grad_acid_dose) return LITHO_E_ARG;
+    if (!finite_nonneg(quencher0) || !(k_quench >= 0.0) || !finite_nonneg(k_loss) || !finite_pos(bake_time_s)) return LITHO_E_ARG;
+    const int least = min_steps(sigma_acid_nm, sigma_quencher_nm, vertical_scale, thickness_nm, D, pixel_nm);
+    if (least == 0 || steps < least || steps > PEB_MAXSTEPS) return LITHO_E_ARG;
+    const int c = checkpoint_every;
+    if (c < 1 || c > steps) return LITHO_E_ARG;
+    const size_t V = (size_t)B * D * n * n, vol_bytes = V * sizeof(float), need = vjp_volumes(steps, c) * vol_bytes;
+    if (!aligned16(work)) return LITHO_E_ARG;
+    if (work_bytes < need) return LITHO_E_WORKSPACE;
+    // the outputs may overlap neither an input, nor the workspace, nor each other; the inputs are only read
+    const void* ins[4] = {acid_in, grad_acid, grad_quencher, grad_acid_dose};
+    const void* outs[2] = {grad_acid_in, grad_quencher_in};
+    for (int o = 0; o < 2; ++o) {
+        if (!outs[o]) continue;
+        for (int i = 0; i < 4; ++i)
+            if (ins[i] && overlap(outs[o], vol_bytes, ins[i], vol_bytes)) return LITHO_E_ARG;
+        if (overlap(outs[o], vol_bytes, work, need)) return LITHO_E_ARG;
+    }
+    if (grad_quencher_in && overlap(grad_acid_in, vol_bytes, grad_quencher_in, vol_bytes)) return LITHO_E_ARG;
+    for (int i = 0; i < 4; ++i)
+        if (ins[i] && overlap(ins[i], vol_bytes, work, need)) return LITHO_E_ARG;
+    const PebStep P = step_of(thickness_nm, pixel_nm, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps);
+    const float q0 = (float)quencher0;
+    if (std::isinf(q0) || std::isinf(P.half_dt)) return LITHO_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int nc = (steps + c - 1) / c;                   // segments; checkpoint j = (h, q) at step j c, j = 1 .. nc - 1, kept in work
+    float* base = (float*)work;
+    auto ck_h = [&](int j) { return base + (size_t)(2 * (j - 1)) * V; };
+    auto ck_q = [&](int j) { return base + (size_t)(2 * (j - 1) + 1) * V; };
+    float* tape = base + (size_t)(2 * (nc - 1)) * V;      // step i of the segment: hd at tape + 2 i V, qd one volume on
+    float* state = tape + (size_t)(2 * c) * V;            // (h, q) x 2
+    float* bar = state + 4 * V;                           // (hbar, qbar) x 2
+    const dim3 grid(plane_blocks(n, 1), (unsigned)(B * D)), block(256);
+    // the forward sweep to the last checkpoint: step k writes checkpoint (k + 1) / c when k + 1 is a multiple of c
+    const float *src_h = acid_in, *src_q = nullptr;
+    for (int k = 0; k < (nc - 1) * c; ++k) {
+        const bool keep = (k + 1) % c == 0;
+        float* to_h = keep ? ck_h((k + 1) / c) : state + (size_t)(2 * (k & 1)) * V;
+        float* to_q = keep ? ck_q((k + 1) / c) : to_h + V;
+        hipLaunchKernelGGL(k_peb_taped, grid, block, 0, st, src_h, src_q, q0, to_h, to_q, (float*)nullptr, (float*)nullptr, D, n, P);
+        src_h = to_h;
+        src_q = to_q;
+    }
+    // the segments last to first: the taped steps from the checkpoint, then their backward steps
+    const float *hb = grad_acid, *qb = grad_quencher;
+    int flip = 0;
+    for (int j = nc - 1; j >= 0; --j) {
+        const int k0 = j * c, k1 = (k0 + c < steps) ? k0 + c : steps;
+        src_h = j ? ck_h(j) : acid_in;
+        src_q = j ? ck_q(j) : nullptr;
+        for (int k = k0; k < k1; ++k) {
+            const bool last = k + 1 == k1;                // its new state is the next checkpoint, or of no use
+            float* to_h = last ? nullptr : state + (size_t)(2 * ((k - k0) & 1)) * V;
+            float* to_q = last ? nullptr : to_h + V;
+            float* t = tape + (size_t)(2 * (k - k0)) * V;
+            hipLaunchKernelGGL(k_peb_taped, grid, block, 0, st, src_h, src_q, q0, to_h, to_q, t, t + V, D, n, P);
+            src_h = to_h;
+            src_q = to_q;
+        }
+        for (int k = k1 - 1; k >= k0; --k) {
+            float* to_h = k == 0 ? grad_acid_in : bar + (size_t)(2 * flip) * V;
+            float* to_q = (k == 0 && grad_quencher_in) ? grad_quencher_in : bar + (size_t)(2 * flip + 1) * V;
+            const float* t = tape + (size_t)(2 * (k - k0)) * V;
+            hipLaunchKernelGGL(k_peb_adjoint, grid, block, 0, st, hb, qb, grad_acid_dose, t, t + V, to_h, to_q, D, n, P);
+            hb = to_h;
+            qb = to_q;
+            flip ^= 1;
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+int litho_peb_expose_vjp(const float* image, int volumes, int D, int n, const float* gains_host, int n_gains, double C,
+                         const float* grad_acid, float* grad_image, void* stream)
+{
+    using namespace litho;
+    if (!image || !gains_host || !grad_acid || !grad_image || n_gains < 1 || n_gains > PEB_GAINS || !volume_ok(volumes, D, n))
+        return LITHO_E_ARG;
+    if ((long long)volumes * n_gains * D > 65535 || !finite_pos(C)) return LITHO_E_ARG;
+    PebGains gains;
+    memset(&gains, 0, sizeof(gains));
+    for (int i = 0; i < n_gains; ++i) {
+        if (!(gains_host[i] == gains_host[i])) return LITHO_E_ARG;
+        gains.g[i] = gains_host[i];
+    }
+    const size_t in_bytes = (size_t)volumes * D * n * n * sizeof(float);
+    if (overlap(image, in_bytes, grad_image, in_bytes) || overlap(grad_acid, in_bytes * n_gains, grad_image, in_bytes)) return LITHO_E_ARG;
+    const int planes = volumes * D;
+    const bool wide = (n & 3) == 0 && aligned16(image) && aligned16(grad_acid) && aligned16(grad_image);
+    const dim3 grid(plane_blocks(n, wide ? 4 : 1), (unsigned)planes);
+    if (wide)
+        hipLaunchKernelGGL(k_peb_expose_vjp<4>, grid, dim3(256), 0, (hipStream_t)stream, image, grad_acid, grad_image, planes, n, gains,
+                           n_gains, C);
+    else
+        hipLaunchKernelGGL(k_peb_expose_vjp<1>, grid, dim3(256), 0, (hipStream_t)stream, image, grad_acid, grad_image, planes, n, gains,
+                           n_gains, C);
     HIP_TRY(hipGetLastError());
     return LITHO_OK;
 }

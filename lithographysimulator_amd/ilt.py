@@ -9,7 +9,8 @@ of a SOCS kernel set are E_k = L(phi_k . M) and hopkinsIntensity returns I = sum
 torch's convention for the gradient of a complex leaf (dl = Re <g, dM>).  `hopkinsGradient` computes g on the device
 (litho_socs_vjp: K fields and K adjoint fields per call, csrc/socs_grad.hip); `maskSpectrumAdjoint` and `postProcessAdjoint` are
 the adjoints of the two linear bookends (mask transmission -> spectrum, raw intensity -> image), and `optimizeMask` descends a
-pixel mask through all of it.  Mask gradients only: the source and the pupil are constants here (source gradients: smo.py;
+pixel mask through all of it; `bakedResistModel` replaces its constant-threshold resist by the post-exposure bake of a chemically
+amplified resist and its adjoint (peb.py), through optimizeMask's imager= / adjoint= pair.  Mask gradients only: the source and the pupil are constants here (source gradients: smo.py;
 DESIGN.md section 10)."""
 import ctypes
 import math
@@ -223,6 +224,41 @@ def _device_model(socs, pn, pixelSize, deltaK, wavelength, normalize, dev):
         if gain != 1.0:
             graw *= gain
         return maskSpectrumAdjoint(hopkinsGradient(state["M"], socs, N, graw), pn, epsilon, N)
+
+    return imager, adjoint
+
+
+def bakedResistModel(socs, resist, thickness, pixelSize, deltaK, wavelength, intensityScale=1.0, normalize=True, steps=None):
+    """(imager, adjoint) for optimizeMask(imager=, adjoint=): inverse lithography against a chemically amplified resist instead of
+    a constant threshold.  imager(t) is the device model's image (spectrum -> hopkinsIntensity -> postProcess) x `intensityScale`
+    -> postExposureBake, and returns the deprotection 1 - m after the bake as [planes, n_out, n_out]; the planes of `socs` are the
+    depths of the resist, top first, as vectorSocsKernels(film=, depths=) makes them (a single kernel set is one plane).
+    adjoint(g) is postExposureBakeGradient with gradInhibitor = -g, x `intensityScale`, then the device model's adjoint.  With it
+    optimizeMask's `threshold` is a deprotection level (for example 1 - mTh of the Mack resist that develops it), its `dose`
+    stays 1 and the exposure dose rides in `intensityScale` (the image is in the engine's units: intensityScale = dose / clear
+    field puts C in units of the clear-field dose).  `resist`: a ChemicallyAmplifiedResist; `steps`: postExposureBake's.
+    Development is not differentiated: the loss sits on the latent image that development thresholds."""
+    from .peb import ChemicallyAmplifiedResist, postExposureBake, postExposureBakeGradient
+    if not isinstance(socs, SOCSKernels):
+        raise TypeError("bakedResistModel: socs must be the SOCSKernels socsKernels returned")
+    if not isinstance(resist, ChemicallyAmplifiedResist):
+        raise TypeError("bakedResistModel: resist must be a ChemicallyAmplifiedResist")
+    scale = float(intensityScale)
+    if not (scale > 0.0 and math.isfinite(scale)):
+        raise ValueError(f"bakedResistModel: intensityScale must be positive and finite; got {intensityScale}")
+    dev = nat.require_gpu(socs.kernels.device)
+    optics, optics_adjoint = _device_model(socs, int(socs.pn), pixelSize, deltaK, wavelength, normalize, dev)
+    state = {}
+
+    def imager(transmission):
+        image = optics(transmission) * scale
+        state["I"] = image if image.dim() == 3 else image[None]
+        return 1.0 - postExposureBake(state["I"], resist, thickness, pixelSize, steps=steps).inhibitor[0]
+
+    def adjoint(gradDeprotection):
+        g = gradDeprotection.detach().to(torch.float32).reshape(state["I"].shape)
+        gI = postExposureBakeGradient(state["I"], resist, thickness, pixelSize, gradInhibitor=-g[None], steps=steps) * scale
+        return optics_adjoint(gI if socs.stacked else gI[0])
 
     return imager, adjoint
 

@@ -9,7 +9,11 @@ scheme of `steps` steps on the grid of develop.py (plane d at depth (d + 1/2) th
 flux through any of the six faces: unlike `latentDiffusion`, which puts zeros outside the grid laterally, the bake mirrors, so
 acid minus quencher is conserved exactly and a bake does not drain acid out of the picture.
 
-NOT built: bleaching, a diffusivity that depends on the deprotection, gradients through the bake."""
+Gradients: `bakeGradient`, `exposeAcidGradient` and their chain `postExposureBakeGradient` are the discrete adjoint of exactly this
+scheme, for a loss on the acid, the quencher, the acid dose or the inhibitor after the bake (litho_peb_bake_vjp: a checkpointed
+forward sweep, then one backward step per launch); `ilt.bakedResistModel` hands them to `optimizeMask`.
+
+NOT built: bleaching, a diffusivity that depends on the deprotection, gradients through development."""
 import ctypes
 import math
 
@@ -166,3 +170,106 @@ def postExposureBake(image, resist, thickness, pixelSize, doses=(1.0,), steps=No
     acid, quencher, dose, S = bakeAcid(h0, resist, thickness, pixelSize, steps, stepsPerLaunch)
     m, slow = amplifiedRate(dose, resist, thickness)
     return BakeResult(acid, quencher, dose, m, slow, S)
+
+
+# ---- gradients through the bake ----------------------------------------------------------------------------------------------------
+def _cotangent(who, name, g, like, batched):
+    """A cotangent shaped like the volume it belongs to, as contiguous fp32 [B,D,n,n] on its device; None stays None."""
+    if g is None:
+        return None
+    want = tuple(like.shape) if batched else tuple(like.shape[1:])
+    if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or tuple(g.shape) != want or g.device != like.device:
+        raise ValueError(f"{who}: {name} must be a float32 tensor {want} on {like.device}; got {getattr(g, 'dtype', type(g))} "
+                         f"{tuple(getattr(g, 'shape', ()))} on {getattr(g, 'device', None)}")
+    g = g.detach().contiguous()
+    return g if batched else g[None]
+
+
+def bakeGradient(acid, resist, thickness, pixelSize, gradAcid=None, gradQuencher=None, gradAcidDose=None, steps=None, checkpointEvery=None):
+    """The bake backwards (litho_peb_bake_vjp): for a real loss l on bakeAcid's outputs with gradAcid = dl/d acid, gradQuencher =
+    dl/d quencher, gradAcidDose = dl/d acidDose (each shaped like `acid`, None = zero, at least one given), returns
+    (gradAcid0, gradQuencher0) = (dl/d h0, qbar_0), shaped like `acid` ([D,n,n] or [B,D,n,n]).  The initial quencher is one number
+    per volume, so dl/d resist.quencher of a volume is gradQuencher0.sum() over it.  `steps` as in bakeAcid -- the same default,
+    so that forward and backward describe one function.  The discrete adjoint of the explicit scheme, step by step (the header's
+    "Gradients through the bake"); the call runs its own forward sweep and keeps the state every `checkpointEvery` steps (1 ...
+    steps; None: ceil(sqrt(steps))), re-running each segment once: the result does not depend on it, bit for bit, only the
+    workspace does, (2 (ceil(steps / c) - 1) + 2 c + 8) volumes.  With instantaneous neutralisation the loss is differentiable
+    only where acid and quencher do not tie; a tie takes the forward's branch."""
+    who = "bakeGradient"
+    if not isinstance(resist, ChemicallyAmplifiedResist):
+        raise TypeError(f"{who}: resist must be a ChemicallyAmplifiedResist")
+    v, B, D, n, batched, dev = _volume(who, acid, "acid")
+    thickness, h = _positive(who, "thickness", thickness), _positive(who, "pixelSize", pixelSize)
+    S = _steps(who, resist, thickness, D, h, steps)
+    c = math.isqrt(S - 1) + 1 if checkpointEvery is None else int(checkpointEvery)    # ceil(sqrt(S))
+    if not 1 <= c <= S:
+        raise ValueError(f"{who}: checkpointEvery must be 1 ... steps ({S}); got {checkpointEvery}")
+    gh, gq, ga = (_cotangent(who, name, g, v, batched) for name, g in (("gradAcid", gradAcid), ("gradQuencher", gradQuencher),
+                                                                        ("gradAcidDose", gradAcidDose)))
+    if gh is None and gq is None and ga is None:
+        raise ValueError(f"{who}: give at least one of gradAcid, gradQuencher, gradAcidDose")
+    lib = nat.lib()
+    out_h, out_q = torch.empty_like(v), torch.empty_like(v)
+    nbytes = int(lib.litho_peb_vjp_work_bytes(B, D, n, S, c))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    opt = lambda t: nat.ptr(t) if t is not None else None                       # noqa: E731
+    with torch.cuda.device(dev):
+        nat.check(lib.litho_peb_bake_vjp(nat.ptr(v), B, D, n, thickness, h, resist.quencher, resist.kQuench, resist.kLoss,
+                                         resist.acidDiffusionLength, resist.quencherDiffusionLength, resist.verticalScale, resist.bakeTime, S, c,
+                                         opt(gh), opt(gq), opt(ga), nat.ptr(out_h), nat.ptr(out_q), nat.ptr(work), nbytes,
+                                         nat.stream_ptr(dev)), "litho_peb_bake_vjp")
+        for t in (v, gh, gq, ga, work):
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(dev))
+    return (out_h, out_q) if batched else (out_h[0], out_q[0])
+
+
+def exposeAcidGradient(image, C, doses, gradAcid):
+    """exposeAcid backwards (litho_peb_expose_vjp): gradImage = sum over the doses of (C dose) exp(-C dose I) gradAcid[dose],
+    shaped like `image` ([D,n,n] or [F,D,n,n]); gradAcid fp32 [len(doses) F, D, n, n], dose-major, as exposeAcid returns."""
+    who = "exposeAcidGradient"
+    v, F, D, n, batched, dev = _volume(who, image)
+    gains = [float(d) for d in doses]
+    if not 1 <= len(gains) <= 64:
+        raise ValueError(f"{who}: between 1 and 64 doses per call; got {len(gains)}")
+    if len(gains) * F * D > 65535:
+        raise ValueError(f"{who}: doses x volumes x planes exceeds 65535")
+    want = (len(gains) * F, D, n, n)
+    if not isinstance(gradAcid, torch.Tensor) or gradAcid.dtype != torch.float32 or tuple(gradAcid.shape) != want or gradAcid.device != dev:
+        raise ValueError(f"{who}: gradAcid must be a float32 tensor {want} on {dev}; got {getattr(gradAcid, 'dtype', type(gradAcid))} "
+                         f"{tuple(getattr(gradAcid, 'shape', ()))} on {getattr(gradAcid, 'device', None)}")
+    ga = gradAcid.detach().contiguous()
+    out = torch.empty_like(v)
+    g = (ctypes.c_float * len(gains))(*gains)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_peb_expose_vjp(nat.ptr(v), F, D, n, g, len(gains), _positive(who, "C", C), nat.ptr(ga), nat.ptr(out),
+                                                 nat.stream_ptr(dev)), "litho_peb_expose_vjp")
+        for t in (v, ga):
+            t.record_stream(torch.cuda.current_stream(dev))
+    return out if batched else out[0]
+
+
+def postExposureBakeGradient(image, resist, thickness, pixelSize, doses=(1.0,), gradInhibitor=None, gradAcidDose=None, gradAcid=None,
+                             gradQuencher=None, steps=None, checkpointEvery=None):
+    """postExposureBake backwards, down to the intensity: gradImage shaped like `image` for a real loss on the BakeResult's
+    `inhibitor`, `acidDose`, `acid` and `quencher` (cotangents [len(doses) F, D, n, n], dose-major; None = zero, at least one
+    given).  The chain of three pieces: the inhibitor m = exp(-kAmp a) gives abar = gradAcidDose - kAmp m gradInhibitor (pointwise,
+    torch on the device, m from the forward bake that this call runs), then bakeGradient, then exposeAcidGradient.  `steps`:
+    the default of postExposureBake.  Nothing is differentiated through development (the slowness and what follows it)."""
+    who = "postExposureBakeGradient"
+    if not isinstance(resist, ChemicallyAmplifiedResist):
+        raise TypeError(f"{who}: resist must be a ChemicallyAmplifiedResist")
+    if gradInhibitor is None and gradAcidDose is None and gradAcid is None and gradQuencher is None:
+        raise ValueError(f"{who}: give at least one of gradInhibitor, gradAcidDose, gradAcid, gradQuencher")
+    h0 = exposeAcid(image, resist.C, doses)
+    ga = gradAcidDose
+    if gradInhibitor is not None:
+        _, _, a, _ = bakeAcid(h0, resist, thickness, pixelSize, steps)
+        if (not isinstance(gradInhibitor, torch.Tensor) or gradInhibitor.dtype != torch.float32 or gradInhibitor.shape != a.shape
+                or gradInhibitor.device != a.device):
+            raise ValueError(f"{who}: gradInhibitor must be a float32 tensor {tuple(a.shape)} on {a.device}; got "
+                             f"{getattr(gradInhibitor, 'dtype', type(gradInhibitor))} {tuple(getattr(gradInhibitor, 'shape', ()))}")
+        from_m = (-resist.kAmp) * torch.exp(-resist.kAmp * a) * gradInhibitor.detach()
+        ga = from_m if ga is None else ga + from_m
+    gh0, _ = bakeGradient(h0, resist, thickness, pixelSize, gradAcid, gradQuencher, ga, steps, checkpointEvery)
+    return exposeAcidGradient(image, resist.C, doses, gh0)
