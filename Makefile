@@ -64,6 +64,11 @@ build/film.o: $(CSRC)/film.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
 build/develop.o: $(CSRC)/develop.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
+# gradients through development: the link coefficients in double per cell, the gather iteration a fixed sequence of single fp32
+# operations (what makes its bits independent of the tile schedule)
+build/develop_grad.o: $(CSRC)/develop_grad.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 # the post-exposure bake: the same, and what makes a bake's bits independent of how its steps are cut into launches
 build/peb.o: $(CSRC)/peb.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
@@ -79,7 +84,7 @@ build/plan_dry_run.o: $(CSRC)/plan_dry_run.cpp $(CSRC)/abbe_plan.hpp include/lit
 build/contour_link.o: $(CSRC)/contour_link.cpp include/litho_abbe.h
 	@mkdir -p build
 	g++ -O2 -std=c++17 -fPIC -Wall -Wextra -c $< -o $@
-$(OUT): build/abbe_engine.o build/optics.o build/layout.o build/metrology.o build/contour.o build/socs.o build/socs_grad.o build/film.o build/develop.o build/peb.o build/common.o build/plan_dry_run.o build/contour_link.o $(INST) $(INSTW)
+$(OUT): build/abbe_engine.o build/optics.o build/layout.o build/metrology.o build/contour.o build/socs.o build/socs_grad.o build/film.o build/develop.o build/develop_grad.o build/peb.o build/common.o build/plan_dry_run.o build/contour_link.o $(INST) $(INSTW)
 	@mkdir -p lithographysimulator_amd/lib
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 

@@ -636,6 +636,63 @@ int litho_peb_bake_vjp(const float *acid_in, int B, int D, int n, double thickne
 int litho_peb_expose_vjp(const float *image, int volumes, int D, int n, const float *gains_host, int n_gains, double C,
                          const float *grad_acid, float *grad_image, void *stream);
 
+/* ---- Gradients through development (csrc/develop_grad.hip; checked against the float64 restatement
+ * tests/develop_grad_oracle.py, itself pinned to central differences of tests/develop_oracle.py).  The arrival time T of
+ * litho_develop_time is the fixed point T_i = G_i(T at i's neighbours, s_i) of the Godunov update of section 3 above.  For a
+ * reached cell i that is no wall the update used k = 1, 2 or 3 axes; on a used axis j the upwind value is a_j, the smaller of the
+ * two neighbours (plane 0's z axis: the resist top, a = 0 at spacing hz / 2, no upstream cell).  T_i satisfies
+ * sum_j w_j (T_i - a_j)^2 = s_i^2, w_j = 1 / h_j^2; with P_i = sum_j w_j (T_i - a_j), implicit differentiation gives
+ *   dT_i / da_j = alpha_ij = w_j (T_i - a_j) / P_i   (non-negative, summing to 1 over the used axes),
+ *   dT_i / ds_i = sigma_i = s_i / P_i               (= h_1 in the one-axis branch).
+ * For a real loss l with cotangent g = dl/dT the adjoint variable solves lambda_i = g_i + sum_j alpha_ji lambda_j, the sum over
+ * those of i's six neighbours j whose update took i as the upwind cell of its axis, and dl/ds_i = lambda_i sigma_i.  The rules
+ * that make this well defined:
+ *   branch     k and the T_i in the coefficients are recomputed from the neighbours' STORED T and from s_i as the update decides
+ *              (axes sorted by a, u <= delta_2, u <= delta_3), in double from the fp32 inputs with h = fp32(pixel),
+ *              hz = fp32(thickness / D); alpha and sigma are rounded to fp32 once.  (The stored fp32 fixed point may differ from
+ *              G_i(T) by an ulp.  The derivative is continuous across a branch switch -- alpha -> 0 for the axis that drops out --
+ *              so a near-tie decided differently in fp32 and in double moves the result by rounding, not by a jump.)
+ *   axis ties  a tie between the two neighbours of one axis goes to the LOWER-index neighbour: on the symmetry line of a
+ *              symmetric pattern the result is a valid but one-sided subgradient.
+ *   strict     a link counts only if the upwind cell's stored T is strictly below the stored T_i, otherwise it is dropped: the
+ *              dependency graph is then acyclic (ordered by T) and the iteration below reaches its fixed point in finitely
+ *              many sweeps.
+ *   no gradient  a wall (s not finite and positive) or a cell with T = +inf gets gradient 0, and its cotangent is ignored
+ *              whatever it holds, NaN and inf included.
+ *
+ * litho_develop_time_vjp: slowness, T, grad_T, grad_slowness fp32 [B,D,n,n]; T MUST be the converged output of
+ * litho_develop_time for the same slowness and geometry (documented, not verifiable).  Three stages.  A pointwise kernel writes
+ * four fp32 per cell into work, the signed link weights of the three axes (positive: the upwind cell is the lower-index
+ * neighbour) and sigma.  Then the tiled gather iteration, the decomposition of litho_develop_time: a workgroup holds lambda and
+ * the links of a 16 x 16 x D tile with a one-cell halo in LDS, D (3 . 18 . 18 + 16 . 16) floats = 4912 D bytes (153.5 KiB at D = 32;
+ * every D from 1 to 32 works), the cotangent read from global memory by the thread that owns the column; columns in two colours, a Gauss-Seidel sweep up and down each column, 8 rounds per launch, lambda ping-ponged between
+ * grad_slowness and work.  A cell's update is a pure gather, lambda_i = g_i + the terms of the neighbours whose link points at
+ * i, added in the fixed order x-, x+, y-, y+, z-, z+, each one fp32 multiplication and one addition: no atomics, no scatter.  A
+ * launch in which no cell's BIT PATTERN changed ends the loop; a closing pointwise kernel writes lambda sigma (0 where sigma is
+ * 0).  Each cell's final value is that fixed expression on the final values of cells with strictly larger T, so the bits depend
+ * on neither the tile schedule, nor the batch, nor the launch at which the loop stops: two calls give the same bits, and a batch
+ * equals its volumes one at a time.  READS BACK every fourth launch like litho_develop_time and cannot be captured into a graph.
+ * *launches_host = the gather launches up to and including the first that changed nothing; after max_iterations (1..65536)
+ * without one: LITHO_E_NOCONV, *launches_host = max_iterations and grad_slowness holds nothing usable.  work:
+ * litho_develop_vjp_work_bytes(B, D, n, max_iterations) device bytes (the flag words and five volumes; 0 for a bad argument),
+ * 16-byte aligned; less is LITHO_E_WORKSPACE.  LITHO_E_ARG: a null pointer, a bad volume (as above), thickness or pixel not
+ * positive and finite, grad_slowness overlapping an input, work overlapping anything.  No allocation.
+ *
+ * litho_develop_rate_vjp: the rate law backwards, for litho_develop_rate (kappa = C, x = the intensity, the doses as gains) and for
+ * litho_peb_rate (kappa = k_amp, x = the acid dose, one gain of 1) alike.  With m = exp(-(kappa g) x), X = (1 - m)^q,
+ * r = (R X / (a + X) + r_min) f, R = r_max (a + 1), f the surface factor of the plane, s = 1 / r:
+ *   grad_x = sum over the gains of grad_slowness[gain] . (-s^2 f R a / (a + X)^2 . q (1 - m)^(q-1) . (kappa g) m),
+ * double per cell, the gains in ascending order, rounded to fp32 once; a cell whose slowness is NaN (1 - m negative or NaN: a wall)
+ * contributes 0 whatever its cotangent holds.  x, grad_x fp32 [volumes,D,n,n], grad_slowness fp32 [n_gains volumes,D,n,n]
+ * gain-major, grad_x overlapping neither; the parameters as litho_develop_rate checks them.  One kernel, asynchronous. */
+size_t litho_develop_vjp_work_bytes(int B, int D, int n, int max_iterations);
+int litho_develop_time_vjp(const float *slowness, const float *T, const float *grad_T, int B, int D, int n, double thickness_nm,
+                           double pixel_nm, int max_iterations, float *grad_slowness, void *work, size_t work_bytes,
+                           int *launches_host, void *stream);
+int litho_develop_rate_vjp(const float *x, int volumes, int D, int n, const float *gains_host, int n_gains, double kappa, double r_max,
+                           double r_min, double q, double m_th, double surface_rate, double surface_depth_nm, double thickness_nm,
+                           const float *grad_slowness, float *grad_x, void *stream);
+
 /* ---- Mask gradients of Hopkins imaging (csrc/socs_grad.hip; no reference counterpart, checked against tests/socs_grad_oracle.py).
  * With F[q][i] = exp(+2 pi i (i - c)(q - c) / N), c = pn / 2, q, i in [0, pn), the engine's chain at shift (0,0) is L(X) = F X F^T,
  * the coherent fields are E_k = L(phi_k . M) and I = sum_k |E_k|^2.  For a real loss l with G = dl/dI,

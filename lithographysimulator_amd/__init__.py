@@ -12,8 +12,8 @@ from .metrology import (LayoutSites, OPCResult, biasLayout, correctLayout,      
 from .contours import (Contours, contourVertices, contoursToGDSII, contoursToLayout,   # noqa: F401
                        doseFocusEnvelope, processVariationBand, simplifyContour, traceContours)
 from .socs import SOCSKernels, hopkinsImage, hopkinsIntensity, socsKernels          # noqa: F401
-from .ilt import (ILTResult, bakedResistModel, hopkinsFields, hopkinsGradient,         # noqa: F401
-                  hopkinsIntensityAD, maskSpectrumAdjoint, optimizeMask, postProcessAdjoint)
+from .ilt import (ILTResult, bakedResistModel, developedResistModel, hopkinsFields,     # noqa: F401
+                  hopkinsGradient, hopkinsIntensityAD, maskSpectrumAdjoint, optimizeMask, postProcessAdjoint)
 from .smo import (SourceResult, optimizeSource, optimizeSourceMask, projectedStep,      # noqa: F401
                   sourceGradient, sourceLossGradient, sourceSensitivities)
 from .aberrations import (AberrationResult, aberrationGradient, fitAberrations,         # noqa: F401
@@ -22,9 +22,10 @@ from .vector import (sourcePolarization, vectorAbbeIntensity, vectorPupils,     
                      vectorSocsKernels)
 from .film import FilmStack, filmPupils                                                 # noqa: F401
 from .develop import (MackResist, ResistProfile, developedDepth, developmentRate,      # noqa: F401
-                      developmentTime, latentDiffusion, resistProfile)
-from .peb import (BakeResult, ChemicallyAmplifiedResist, bakeGradient,                 # noqa: F401
-                  exposeAcidGradient, postExposureBake, postExposureBakeGradient)
+                      developmentRateGradient, developmentTime, developmentTimeGradient,
+                      latentDiffusion, resistProfile, resistProfileGradient)
+from .peb import (BakeResult, ChemicallyAmplifiedResist, amplifiedRateGradient,        # noqa: F401
+                  bakeGradient, exposeAcidGradient, postExposureBake, postExposureBakeGradient)
 from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
@@ -43,4 +44,5 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "FilmStack", "filmPupils",
            "MackResist", "ResistProfile", "latentDiffusion", "developmentRate", "developmentTime", "developedDepth", "resistProfile",
            "ChemicallyAmplifiedResist", "BakeResult", "postExposureBake",
-           "bakeGradient", "exposeAcidGradient", "postExposureBakeGradient", "bakedResistModel"]
+           "bakeGradient", "exposeAcidGradient", "postExposureBakeGradient", "bakedResistModel",
+           "developmentTimeGradient", "developmentRateGradient", "resistProfileGradient", "amplifiedRateGradient", "developedResistModel"]

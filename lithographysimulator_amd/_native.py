@@ -85,6 +85,11 @@ _SIGNATURES = {
     "litho_peb_expose_vjp": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), c_int, c_double, c_void_p, c_void_p, c_void_p]),
     "litho_peb_rate": (c_int,[c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_double,
                                c_double, c_void_p, c_void_p, c_void_p]),
+    "litho_develop_vjp_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "litho_develop_time_vjp": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_double, c_double, c_int, c_void_p, c_void_p,
+                                       c_size_t, POINTER(c_int), c_void_p]),
+    "litho_develop_rate_vjp": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), c_int, c_double, c_double, c_double, c_double,
+                                       c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p]),
     "litho_tcc_apply_vector_work_bytes": (c_size_t, [c_int, c_int]),
     "litho_tcc_apply_vector": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "litho_socs_fields": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),

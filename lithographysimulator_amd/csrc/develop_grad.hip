@@ -1,0 +1,481 @@
+// develop_grad.hip -- gradients through resist development, behind litho_develop_time_vjp and litho_develop_rate_vjp (no
+// reference counterpart; the definitions are in include/litho_abbe.h, "Gradients through development"; the checker is their
+// float64 restatement tests/develop_grad_oracle.py).  Built with -ffp-contract=off (Makefile): every fp32 result is a fixed
+// sequence of single operations.
+//
+// The arrival time T of develop.hip is the fixed point T_i = G_i(T_N(i), s_i) of the Godunov update.  For a reached cell that is
+// no wall, sum_j w_j (T_i - a_j)^2 = s_i^2 over the axes the update used, and with P_i = sum_j w_j (T_i - a_j)
+//   dT_i / da_j = alpha_ij = w_j (T_i - a_j) / P_i   (non-negative, summing to 1),     dT_i / ds_i = sigma_i = s_i / P_i.
+// For a cotangent g = dl/dT the adjoint variable solves lambda_i = g_i + sum_j alpha_ji lambda_j over the neighbours j whose
+// update took i as the upwind cell of its axis, and dl/ds_i = lambda_i sigma_i.  Four kernels:
+//   k_develop_links     per cell, in double, rounded once: the branch of the update, its three link weights and sigma
+//   k_develop_time_vjp  the tiled gather iteration for lambda (below)
+//   k_develop_scale     grad_s = lambda sigma, exactly 0 where the cell has no gradient
+//   k_develop_rate_vjp  the rate law of k_develop_rate / k_peb_rate backwards, double per cell, the gains summed inside
+// The pointwise kernels move four consecutive x per thread (16-byte accesses) when n is a multiple of 4 and the pointers are
+// 16-byte aligned, one otherwise.
+//
+// Links.  Four fp32 per cell, (lx, ly, lz, sigma).  |l| is alpha on that axis; the sign carries the direction: positive when the
+// upwind cell is the lower-index neighbour (a tie of the two neighbours goes there), negative when it is the higher-index one.
+// A weight is 0 when the axis was not used, when the upwind "cell" is the resist top (plane 0's z axis) and when the upwind
+// cell's stored T is not strictly below the cell's own stored T: the links then point strictly down in T, the dependency graph
+// is acyclic and the iteration below is nilpotent.  sigma = 0 marks a cell with no gradient (a wall, or T = +inf): all of its
+// weights are 0, nothing gathers from it and it gathers from nothing.
+//
+// k_develop_time_vjp.  The decomposition of k_develop_time: a workgroup owns a 16 x 16 lateral tile with all D planes.  In LDS:
+// lambda, lx and ly of tile + one-cell halo as [D][18][18] (of a halo cell only lambda and the one link that points into the
+// tile are loaded and read; the corners are never touched) and lz of the tile as [D][16][16]: D (3 . 324 + 256) floats = 4912 B
+// per plane, 38.4 KiB at D = 8 (four workgroups per CU), 76.8 KiB at D = 16 (two), 153.5 KiB at D = 32 (one).  The cotangent g
+// is read from global memory by the thread that owns the column: keeping it in LDS as well (5936 B per plane, possible up to
+// D = 27) costs a workgroup per CU at D = 8 and at D = 16 and was slower in a same-box A/B at 2048^2, 2.80 against 2.31 ms per
+// launch at D = 8 and 16.3 against 9.0 at D = 16 (LABNOTES).  A round is two phases, the columns with (row + col) even, a barrier, the odd ones,
+// a barrier; in a phase 128 threads own one column each and sweep it up and then down (Gauss-Seidel along z: the front mostly
+// ran downwards, so lambda flows upwards).  A cell's update is a pure gather,
+//   lambda_i = g_i (+) w lambda_j  over x-, x+, y-, y+, z-, z+ in this order, a term only where the neighbour's link points at i,
+// each term one fp32 multiplication and one addition.  The lateral neighbours of a column have the other colour and are not
+// written in that phase; halo cells are read-only: no race, no atomics.  Launches ping-pong lambda between two global buffers,
+// so no workgroup reads what another writes.  A cell "changed" when the new value's bit pattern differs from the old one (never
+// `!=`, which does not settle on a NaN); a thread that changed one stores 1 into the launch's own flag word with a plain store.
+// The host reads the flag words every DG_CHECK launches and stops at the first launch that changed nothing.  Every loop has a
+// trip count fixed by D; the launch count is capped by the caller.
+//
+// Determinism.  Each cell's final value is the fixed expression above on the final values of cells with strictly larger T.  By
+// induction from the sinks of the graph the bits depend on neither the tile schedule, nor the batch, nor the start value, nor
+// the launch at which the iteration stops.
+#include "engine_common.hpp"
+#include "../../include/litho_abbe.h"
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+
+namespace litho {
+
+static constexpr int DG_DMAX = 32, DG_GAINS = 64;
+static constexpr int DG_TILE = 16, DG_HALO = DG_TILE + 2, DG_INNER = 8, DG_CHECK = 4, DG_MAXIT = 65536;
+static constexpr int DG_HCELLS = DG_HALO * DG_HALO, DG_TCELLS = DG_TILE * DG_TILE;
+static constexpr size_t DG_PLANE_BYTES = (size_t)(3 * DG_HCELLS + DG_TCELLS) * sizeof(float);
+static_assert((size_t)DG_DMAX * DG_PLANE_BYTES <= 160 * 1024, "the tile of the deepest volume must fit a gfx950 workgroup's LDS");
+
+struct DgGains {
+    float g[DG_GAINS];
+};
+struct DgSurface {
+    double f[DG_DMAX];                                   // the surface-inhibition factor of plane d, from the host
+};
+
+template <int VEC>
+struct DgPack {
+    float v[VEC];
+};
+template <int VEC>
+__device__ __forceinline__ DgPack<VEC> dg_load(const float* p)
+{
+    DgPack<VEC> r;
+    if constexpr (VEC == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(p);
+        r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w;
+    } else {
+        r.v[0] = *p;
+    }
+    return r;
+}
+template <int VEC>
+__device__ __forceinline__ DgPack<VEC> dg_fill(float x)
+{
+    DgPack<VEC> r;
+    for (int v = 0; v < VEC; ++v) r.v[v] = x;
+    return r;
+}
+template <int VEC>
+__device__ __forceinline__ void dg_store(float* p, const DgPack<VEC>& r)
+{
+    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+    else *p = r.v[0];
+}
+
+// ---- 1. the links of one cell.  s, Ti: the cell's slowness and stored T; (xm, xp), (ym, yp), (zm, zp): the stored T of the two
+// neighbours per axis, +inf where there is none; top: plane 0, whose z axis is the resist top (a = 0 at hz / 2).  The branch and
+// T_i are recomputed from these as godunov (develop.hip) decides -- sorted axes, u <= d1, u <= d2 -- in double.
+__device__ __forceinline__ float4 link_cell(float s, float Ti, float xm, float xp, float ym, float yp, float zm, float zp, bool top,
+                                            double h, double hz)
+{
+    const float4 none = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!(s > 0.f && s < INFINITY) || !(Ti < INFINITY)) return none;      // a wall, or never reached
+    const bool xlo = xm <= xp, ylo = ym <= yp, zlo = zm <= zp;            // a tie goes to the lower-index neighbour
+    const float ux = xlo ? xm : xp, uy = ylo ? ym : yp, uz = zlo ? zm : zp;
+    double a0 = ux, a1 = uy, a2 = top ? 0.0 : (double)uz;
+    double h0 = h, h1 = h, h2 = top ? 0.5 * hz : hz;
+    int k0 = 0, k1 = 1, k2 = 2;
+    double t;
+    int ti;
+#define DG_SWAP(i, j)                                                                          \
+    if (a##i > a##j) {                                                                         \
+        t = a##i; a##i = a##j; a##j = t; t = h##i; h##i = h##j; h##j = t; ti = k##i; k##i = k##j; k##j = ti; \
+    }
+    DG_SWAP(0, 1)
+    DG_SWAP(1, 2)
+    DG_SWAP(0, 1)
+#undef DG_SWAP
+    if (!(a0 < (double)INFINITY)) return none;
+    const double w0 = 1.0 / (h0 * h0), w1 = 1.0 / (h1 * h1), w2 = 1.0 / (h2 * h2);
+    const double sd = s, ss = sd * sd;
+    double u = h0 * sd, p0, p1 = 0.0, p2 = 0.0;
+    const double d1 = a1 - a0;                           // +inf where that axis has no finite neighbour
+    if (!(u <= d1)) {
+        double A = w0 + w1;
+        u = (w1 * d1 + sqrt(fmax(A * ss - (w0 * w1) * (d1 * d1), 0.0))) / A;
+        const double d2 = a2 - a0;
+        if (!(u <= d2)) {
+            const double d21 = d2 - d1;
+            A = A + w2;
+            const double cross = ((w0 * w1) * (d1 * d1) + (w0 * w2) * (d2 * d2)) + (w1 * w2) * (d21 * d21);
+            u = ((w1 * d1 + w2 * d2) + sqrt(fmax(A * ss - cross, 0.0))) / A;
+            p2 = w2 * (u - d2);
+        }
+        p1 = w1 * (u - d1);
+    }
+    p0 = w0 * u;
+    const double P = (p0 + p1) + p2;
+    if (!(P > 0.0)) return none;                         // cannot happen for a positive finite s; never divide by 0
+    const double al0 = p0 / P, al1 = p1 / P, al2 = p2 / P;
+    const double ax = k0 == 0 ? al0 : (k1 == 0 ? al1 : al2);
+    const double ay = k0 == 1 ? al0 : (k1 == 1 ? al1 : al2);
+    const double az = k0 == 2 ? al0 : (k1 == 2 ? al1 : al2);
+    float4 out;
+    // strict upwind: a link counts only where the upwind cell's stored T is below the cell's own
+    out.x = (ux < Ti) ? (float)(xlo ? ax : -ax) : 0.f;
+    out.y = (uy < Ti) ? (float)(ylo ? ay : -ay) : 0.f;
+    out.z = (!top && uz < Ti) ? (float)(zlo ? az : -az) : 0.f;
+    out.w = (float)(sd / P);
+    return out;
+}
+
+// grid.x covers the n^2 / VEC packs of a plane, grid.y the B D planes
+template <int VEC>
+__global__ __launch_bounds__(256) void k_develop_links(const float* __restrict__ slow, const float* __restrict__ T,
+                                                       float4* __restrict__ links, int D, int n, double h, double hz)
+{
+    const long long plane_elems = (long long)n * n;
+    const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
+    if (e >= plane_elems) return;
+    const int p = blockIdx.y, d = p % D;
+    const int row = (int)(e / n), col = (int)(e % n);
+    const size_t at = (size_t)p * plane_elems + e;
+    const float inf = INFINITY;
+    const DgPack<VEC> s = dg_load<VEC>(slow + at), c = dg_load<VEC>(T + at);
+    const DgPack<VEC> ym = row > 0 ? dg_load<VEC>(T + at - n) : dg_fill<VEC>(inf);
+    const DgPack<VEC> yp = row + 1 < n ? dg_load<VEC>(T + at + n) : dg_fill<VEC>(inf);
+    const DgPack<VEC> zm = d > 0 ? dg_load<VEC>(T + at - plane_elems) : dg_fill<VEC>(inf);
+    const DgPack<VEC> zp = d + 1 < D ? dg_load<VEC>(T + at + plane_elems) : dg_fill<VEC>(inf);
+    const float left = col > 0 ? T[at - 1] : inf, right = col + VEC < n ? T[at + VEC] : inf;
+    for (int v = 0; v < VEC; ++v) {
+        const float xm = v > 0 ? c.v[v - 1] : left, xp = v + 1 < VEC ? c.v[v + 1] : right;
+        links[at + v] = link_cell(s.v[v], c.v[v], xm, xp, ym.v[v], yp.v[v], zm.v[v], zp.v[v], d == 0, h, hz);
+    }
+}
+
+// ---- 2. the gather iteration
+__device__ __forceinline__ unsigned bits_of(float x) { return __float_as_uint(x); }
+
+// One cell: lam/lx/ly point at it in the [18][18] planes, lz in the [16][16] planes; true when its bits changed.
+__device__ __forceinline__ bool gather_cell(float* lam, const float* lx, const float* ly, const float* lz, float g, int d, int D)
+{
+    float acc = g, w;
+    w = lx[-1];
+    if (w < 0.f) acc = acc + (-w) * lam[-1];
+    w = lx[1];
+    if (w > 0.f) acc = acc + w * lam[1];
+    w = ly[-DG_HALO];
+    if (w < 0.f) acc = acc + (-w) * lam[-DG_HALO];
+    w = ly[DG_HALO];
+    if (w > 0.f) acc = acc + w * lam[DG_HALO];
+    if (d > 0) {
+        w = lz[-DG_TCELLS];
+        if (w < 0.f) acc = acc + (-w) * lam[-DG_HCELLS];
+    }
+    if (d + 1 < D) {
+        w = lz[DG_TCELLS];
+        if (w > 0.f) acc = acc + w * lam[DG_HCELLS];
+    }
+    const bool changed = bits_of(acc) != bits_of(*lam);
+    *lam = acc;
+    return changed;
+}
+
+__global__ __launch_bounds__(256) void k_develop_time_vjp(const float* __restrict__ links, const float* __restrict__ g,
+                                                          const float* __restrict__ lin, float* __restrict__ lout, int D, int n,
+                                                          int* __restrict__ flag)
+{
+    extern __shared__ __attribute__((aligned(16))) float dg_lds[];
+    float* lam = dg_lds;                                 // [D][18][18]  tile + halo
+    float* lx = lam + D * DG_HCELLS;                     // [D][18][18]
+    float* ly = lx + D * DG_HCELLS;                      // [D][18][18]
+    float* lz = ly + D * DG_HCELLS;                      // [D][16][16]  tile
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * DG_TILE, y0 = blockIdx.y * DG_TILE;
+    const size_t plane_elems = (size_t)n * n;
+    const size_t vol = (size_t)blockIdx.z * D * plane_elems;
+    // the tile: all three links and lambda; a tile cell outside the grid has no links and lambda 0
+    for (int i = tid; i < D * DG_TCELLS; i += 256) {
+        const int d = i / DG_TCELLS, r = i - d * DG_TCELLS, ty = r / DG_TILE, tx = r - ty * DG_TILE;
+        const int gy = y0 + ty, gx = x0 + tx;
+        const int q = d * DG_HCELLS + (ty + 1) * DG_HALO + tx + 1;
+        float4 L = make_float4(0.f, 0.f, 0.f, 0.f);
+        float l0 = 0.f;
+        if (gy < n && gx < n) {
+            const size_t cell = vol + (size_t)d * plane_elems + (size_t)gy * n + gx;
+            L = *reinterpret_cast<const float4*>(links + 4 * cell);
+            l0 = lin[cell];
+        }
+        lam[q] = l0;
+        lx[q] = L.x;
+        ly[q] = L.y;
+        lz[i] = L.z;
+    }
+    // the 64 edge cells of the halo per plane: lambda and the one link that can point into the tile
+    for (int i = tid; i < D * 4 * DG_TILE; i += 256) {
+        const int d = i / (4 * DG_TILE), r = i - d * (4 * DG_TILE), side = r / DG_TILE, k = r - side * DG_TILE;
+        int hy, hx;                                      // position in the [18][18] plane
+        if (side == 0) { hy = k + 1; hx = 0; }
+        else if (side == 1) { hy = k + 1; hx = DG_HALO - 1; }
+        else if (side == 2) { hy = 0; hx = k + 1; }
+        else { hy = DG_HALO - 1; hx = k + 1; }
+        const int gy = y0 + hy - 1, gx = x0 + hx - 1;
+        float l0 = 0.f, w = 0.f;
+        if (gy >= 0 && gy < n && gx >= 0 && gx < n) {
+            const size_t cell = vol + (size_t)d * plane_elems + (size_t)gy * n + gx;
+            l0 = lin[cell];
+            w = links[4 * cell + (side < 2 ? 0 : 1)];
+        }
+        const int q = d * DG_HCELLS + hy * DG_HALO + hx;
+        lam[q] = l0;
+        if (side < 2) lx[q] = w;
+        else ly[q] = w;
+    }
+    __syncthreads();
+    // compute threads: 128, row = tid / 8, the columns of this phase's colour in that row
+    const int row = (tid >> 3) & (DG_TILE - 1), pair = tid & 7;
+    bool changed = false;
+    for (int round = 0; round < DG_INNER; ++round) {
+        for (int colour = 0; colour < 2; ++colour) {
+            const int col = 2 * pair + ((row + colour) & 1);
+            if (tid < 128 && y0 + row < n && x0 + col < n) {
+                const int q = (row + 1) * DG_HALO + (col + 1), t = row * DG_TILE + col;
+                const float* gc = g + vol + (size_t)(y0 + row) * n + (x0 + col);     // the column's cotangent, from global memory
+                for (int d = D - 1; d >= 0; --d)
+                    changed |= gather_cell(lam + d * DG_HCELLS + q, lx + d * DG_HCELLS + q, ly + d * DG_HCELLS + q,
+                                           lz + d * DG_TCELLS + t, gc[d * plane_elems], d, D);
+                for (int d = 1; d < D; ++d)
+                    changed |= gather_cell(lam + d * DG_HCELLS + q, lx + d * DG_HCELLS + q, ly + d * DG_HCELLS + q,
+                                           lz + d * DG_TCELLS + t, gc[d * plane_elems], d, D);
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < D * DG_TCELLS; i += 256) {
+        const int d = i / DG_TCELLS, r = i - d * DG_TCELLS, ty = r / DG_TILE, tx = r - ty * DG_TILE;
+        const int gy = y0 + ty, gx = x0 + tx;
+        if (gy < n && gx < n)
+            lout[vol + (size_t)d * plane_elems + (size_t)gy * n + gx] = lam[d * DG_HCELLS + (ty + 1) * DG_HALO + tx + 1];
+    }
+    if (changed) *flag = 1;
+}
+
+// ---- 3. grad_s = lambda sigma; a cell with no gradient (sigma = 0) gets exactly 0 whatever its cotangent held
+template <int VEC>
+__global__ __launch_bounds__(256) void k_develop_scale(const float* __restrict__ lambda, const float* __restrict__ links,
+                                                       float* __restrict__ out, int n)
+{
+    const long long plane_elems = (long long)n * n;
+    const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
+    if (e >= plane_elems) return;
+    const size_t at = (size_t)blockIdx.y * plane_elems + e;
+    const DgPack<VEC> l = dg_load<VEC>(lambda + at);
+    DgPack<VEC> r;
+    for (int v = 0; v < VEC; ++v) {
+        const float sigma = links[4 * (at + v) + 3];
+        r.v[v] = sigma > 0.f ? l.v[v] * sigma : 0.f;
+    }
+    dg_store<VEC>(out + at, r);
+}
+
+// ---- 4. the rate law backwards: m = exp(-(kappa g) x), X = (1 - m)^q, r = (R X / (a + X) + rmin) f, s = 1 / r;
+// ds/dx = -s^2 f R a / (a + X)^2 q (1 - m)^(q - 1) (kappa g) m.  A wall (1 - m negative or NaN) contributes 0.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_develop_rate_vjp(const float* __restrict__ x, const float* __restrict__ grad_s,
+                                                          float* __restrict__ grad_x, int planes, int D, int n, const DgGains gains,
+                                                          int n_gains, double kappa, double rmax_a1, double rmin, double q, double a,
+                                                          const DgSurface surface)
+{
+    const long long plane_elems = (long long)n * n;
+    const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
+    if (e >= plane_elems) return;
+    const int p = blockIdx.y;
+    const double f = surface.f[p % D];
+    const size_t at = (size_t)p * plane_elems + e;
+    const DgPack<VEC> xv = dg_load<VEC>(x + at);
+    double acc[VEC];
+    for (int v = 0; v < VEC; ++v) acc[v] = 0.0;
+    for (int gi = 0; gi < n_gains; ++gi) {
+        const double kg = kappa * (double)gains.g[gi];
+        const DgPack<VEC> gs = dg_load<VEC>(grad_s + ((size_t)gi * planes + p) * plane_elems + e);
+        for (int v = 0; v < VEC; ++v) {
+            const double m = exp(-(kg * (double)xv.v[v]));
+            const double b = 1.0 - m;
+            if (!(b >= 0.0)) continue;                   // a wall
+            const double X = pow(b, q);
+            const double r = (rmax_a1 * X / (a + X) + rmin) * f;
+            const double s = 1.0 / r;
+            const double dX = q * pow(b, q - 1.0) * (kg * m);
+            acc[v] += (double)gs.v[v] * (-(s * s) * f * (rmax_a1 * a / ((a + X) * (a + X))) * dX);
+        }
+    }
+    DgPack<VEC> out;
+    for (int v = 0; v < VEC; ++v) out.v[v] = (float)acc[v];
+    dg_store<VEC>(grad_x + at, out);
+}
+
+static bool dg_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static bool dg_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + b_bytes && pb < pa + a_bytes;
+}
+static bool dg_finite_pos(double v) { return v > 0.0 && !std::isinf(v); }
+static unsigned dg_plane_blocks(int n, int vec) { return (unsigned)(((long long)n * n / vec + 255) / 256); }
+static bool dg_volume_ok(int B, int D, int n)
+{
+    return B >= 1 && D >= 1 && D <= DG_DMAX && n >= 1 && n <= 16384 && (long long)B * D <= 65535;
+}
+static size_t dg_flag_bytes(int max_iterations) { return ((size_t)max_iterations * sizeof(int) + 255) & ~(size_t)255; }
+
+}  // namespace litho
+
+extern "C" {
+
+size_t litho_develop_vjp_work_bytes(int B, int D, int n, int max_iterations)
+{
+    using namespace litho;
+    if (!dg_volume_ok(B, D, n) || max_iterations < 1 || max_iterations > DG_MAXIT) return 0;
+    return dg_flag_bytes(max_iterations) + 5 * (size_t)B * D * n * n * sizeof(float);     // flags, links (4), lambda (1)
+}
+
+int litho_develop_time_vjp(const float* slowness, const float* T, const float* grad_T, int B, int D, int n, double thickness_nm,
+                           double pixel_nm, int max_iterations, float* grad_slowness, void* work, size_t work_bytes,
+                           int* launches_host, void* stream)
+{
+    using namespace litho;
+    if (launches_host) *launches_host = 0;
+    if (!slowness || !T || !grad_T || !grad_slowness || !work || !launches_host || !dg_volume_ok(B, D, n)) return LITHO_E_ARG;
+    if (max_iterations < 1 || max_iterations > DG_MAXIT || !dg_finite_pos(thickness_nm) || !dg_finite_pos(pixel_nm)) return LITHO_E_ARG;
+    const size_t cells = (size_t)B * D * n * n, vol_bytes = cells * sizeof(float);
+    const size_t need = litho_develop_vjp_work_bytes(B, D, n, max_iterations);
+    if (!dg_aligned16(work)) return LITHO_E_ARG;
+    const void* in[3] = {slowness, T, grad_T};
+    for (int i = 0; i < 3; ++i)
+        if (dg_overlap(grad_slowness, vol_bytes, in[i], vol_bytes)) return LITHO_E_ARG;     // lambda lives in the output meanwhile
+    if (work_bytes < need) return LITHO_E_WORKSPACE;
+    for (int i = 0; i < 3; ++i)
+        if (dg_overlap(work, need, in[i], vol_bytes)) return LITHO_E_ARG;
+    if (dg_overlap(work, need, grad_slowness, vol_bytes)) return LITHO_E_ARG;
+    // the geometry as litho_develop_time rounds it
+    const float hf = (float)pixel_nm, hzf = (float)(thickness_nm / D);
+    const float wxy = 1.f / (hf * hf), wz = 1.f / (hzf * hzf);
+    if (!(hf > 0.f) || !(hzf > 0.f) || std::isinf(wxy) || std::isinf(wz) || !(wxy > 0.f) || !(wz > 0.f)) return LITHO_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    int* flags = (int*)work;
+    float* links = (float*)((char*)work + dg_flag_bytes(max_iterations));
+    float* buf[2] = {links + 4 * cells, grad_slowness};
+    const size_t lds = (size_t)D * DG_PLANE_BYTES;
+    if (lds > 64 * 1024) {                               // once per device: the worst case, D = 32
+        static unsigned lds_done = 0;
+        int dev = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        const unsigned bit = 1u << (dev & 31);
+        if (!(__atomic_load_n(&lds_done, __ATOMIC_ACQUIRE) & bit)) {
+            HIP_TRY(hipFuncSetAttribute((const void*)k_develop_time_vjp, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)((size_t)DG_DMAX * DG_PLANE_BYTES)));
+            __atomic_fetch_or(&lds_done, bit, __ATOMIC_RELEASE);
+        }
+    }
+    HIP_TRY(hipMemsetAsync(flags, 0, dg_flag_bytes(max_iterations), st));
+    HIP_TRY(hipMemsetAsync(buf[0], 0, vol_bytes, st));
+    const bool wide = (n & 3) == 0 && dg_aligned16(slowness) && dg_aligned16(T) && dg_aligned16(grad_slowness);
+    const dim3 pgrid(dg_plane_blocks(n, wide ? 4 : 1), (unsigned)(B * D));
+    if (wide)
+        hipLaunchKernelGGL(k_develop_links<4>, pgrid, dim3(256), 0, st, slowness, T, (float4*)links, D, n, (double)hf, (double)hzf);
+    else
+        hipLaunchKernelGGL(k_develop_links<1>, pgrid, dim3(256), 0, st, slowness, T, (float4*)links, D, n, (double)hf, (double)hzf);
+    HIP_TRY(hipGetLastError());
+    const unsigned tiles = (unsigned)((n + DG_TILE - 1) / DG_TILE);
+    const dim3 grid(tiles, tiles, (unsigned)B);
+    int done = 0, launches = 0;
+    while (done < max_iterations && !launches) {
+        const int group = max_iterations - done < DG_CHECK ? max_iterations - done : DG_CHECK;
+        for (int j = 0; j < group; ++j) {
+            const int it = done + j;                     // launch `it` reads buf[it & 1] and writes the other
+            hipLaunchKernelGGL(k_develop_time_vjp, grid, dim3(256), lds, st, (const float*)links, grad_T, (const float*)buf[it & 1],
+                               buf[(it + 1) & 1], D, n, flags + it);
+        }
+        HIP_TRY(hipGetLastError());
+        int seen[DG_CHECK] = {1, 1, 1, 1};
+        HIP_TRY(hipMemcpyAsync(seen, flags + done, (size_t)group * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int j = 0; j < group && !launches; ++j)
+            if (seen[j] == 0) launches = done + j + 1;   // this launch changed nothing: its output equals its input
+        done += group;
+    }
+    if (!launches) {
+        *launches_host = max_iterations;
+        return LITHO_E_NOCONV;
+    }
+    *launches_host = launches;
+    // both buffers hold the fixed point: read the workspace's, write the output
+    if (wide)
+        hipLaunchKernelGGL(k_develop_scale<4>, pgrid, dim3(256), 0, st, (const float*)buf[0], (const float*)links, grad_slowness, n);
+    else
+        hipLaunchKernelGGL(k_develop_scale<1>, pgrid, dim3(256), 0, st, (const float*)buf[0], (const float*)links, grad_slowness, n);
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+int litho_develop_rate_vjp(const float* x, int volumes, int D, int n, const float* gains_host, int n_gains, double kappa, double r_max,
+                           double r_min, double q, double m_th, double surface_rate, double surface_depth_nm, double thickness_nm,
+                           const float* grad_slowness, float* grad_x, void* stream)
+{
+    using namespace litho;
+    if (!x || !gains_host || !grad_slowness || !grad_x || n_gains < 1 || n_gains > DG_GAINS || !dg_volume_ok(volumes, D, n))
+        return LITHO_E_ARG;
+    if ((long long)volumes * n_gains * D > 65535) return LITHO_E_ARG;
+    if (!dg_finite_pos(kappa) || !dg_finite_pos(r_max) || !dg_finite_pos(r_min) || !(q > 1.0) || std::isinf(q) || !(m_th >= 0.0) ||
+        !(m_th < 1.0) || !(surface_rate > 0.0) || !(surface_rate <= 1.0) || !dg_finite_pos(surface_depth_nm) || !dg_finite_pos(thickness_nm))
+        return LITHO_E_ARG;
+    const size_t x_bytes = (size_t)volumes * D * n * n * sizeof(float);
+    if (dg_overlap(grad_x, x_bytes, x, x_bytes) || dg_overlap(grad_x, x_bytes, grad_slowness, x_bytes * n_gains)) return LITHO_E_ARG;
+    DgGains gains;
+    memset(&gains, 0, sizeof(gains));
+    for (int i = 0; i < n_gains; ++i) {
+        if (!(gains_host[i] == gains_host[i])) return LITHO_E_ARG;
+        gains.g[i] = gains_host[i];
+    }
+    const double a = (q + 1.0) / (q - 1.0) * std::pow(1.0 - m_th, q);
+    DgSurface surface;
+    for (int d = 0; d < DG_DMAX; ++d) {
+        const double z = thickness_nm * (d + 0.5) / D;
+        surface.f[d] = 1.0 - (1.0 - surface_rate) * std::exp(-z / surface_depth_nm);
+    }
+    const int planes = volumes * D;
+    const bool wide = (n & 3) == 0 && dg_aligned16(x) && dg_aligned16(grad_slowness) && dg_aligned16(grad_x);
+    const dim3 grid(dg_plane_blocks(n, wide ? 4 : 1), (unsigned)planes);
+    if (wide)
+        hipLaunchKernelGGL(k_develop_rate_vjp<4>, grid, dim3(256), 0, (hipStream_t)stream, x, grad_slowness, grad_x, planes, D, n, gains,
+                           n_gains, kappa, r_max * (a + 1.0), r_min, q, a, surface);
+    else
+        hipLaunchKernelGGL(k_develop_rate_vjp<1>, grid, dim3(256), 0, (hipStream_t)stream, x, grad_slowness, grad_x, planes, D, n, gains,
+                           n_gains, kappa, r_max * (a + 1.0), r_min, q, a, surface);
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+}  // extern "C"

@@ -15,8 +15,14 @@ A batch is [B, D, n, n] with B = doses x focal planes, dose-major.
 A chemically amplified resist (peb.py: ChemicallyAmplifiedResist) takes the place of the Gaussian blur and of developmentRate with a
 reaction-diffusion post-exposure bake with quencher, `postExposureBake`; resistProfile accepts either kind of resist.
 
-NOT built: bleaching (Dill A, B: the intensity is taken as given), development of anything but one layer, gradients through
-development."""
+Gradients: `developmentTimeGradient` differentiates the solver itself -- the adjoint of the Godunov fixed point, an iteration
+of the same tiled kind as the forward (litho_develop_time_vjp) -- `developmentRateGradient` the rate law and the latent-image
+diffusion, and `resistProfileGradient` chains them from a cotangent on the arrival times T down to the intensity stack, for
+either kind of resist; `ilt.developedResistModel` hands that to `optimizeMask`.  On the symmetry line of a symmetric pattern,
+where the two neighbours of an axis tie, the gradient is a valid but one-sided subgradient (the tie goes to the lower index).
+
+NOT built: bleaching (Dill A, B: the intensity is taken as given), development of anything but one layer, the gradient of
+`developedDepth`, gradients with respect to the resist's parameters, a fused or coarser-grained backward solver."""
 import ctypes
 import math
 
@@ -270,3 +276,118 @@ def resistProfile(image, resist, stack_or_thickness, pixelSize, developTime, dos
     depth = developedDepth(T, thickness, t)
     nd = len(tuple(doses))
     return ResistProfile(T.reshape(nd, F, D, n, n), depth.reshape(nd, F, n, n), launches, thickness, float(pixelSize), t, doses)
+
+
+# ---- gradients through development -----------------------------------------------------------------------------------------------
+def _like(who, name, g, shape, dev):
+    """A float32 tensor of exactly `shape` on `dev`, detached and contiguous."""
+    if not isinstance(g, torch.Tensor) or g.dtype != torch.float32 or tuple(g.shape) != tuple(shape) or g.device != dev:
+        raise ValueError(f"{who}: {name} must be a float32 tensor {tuple(shape)} on {dev}; got {getattr(g, 'dtype', type(g))} "
+                         f"{tuple(getattr(g, 'shape', ()))} on {getattr(g, 'device', None)}")
+    return g.detach().contiguous()
+
+
+def developmentTimeGradient(slowness, T, gradT, thickness, pixelSize, maxIterations=1024, returnLaunches=False):
+    """developmentTime backwards (litho_develop_time_vjp): for a real loss l on the arrival times with gradT = dl/dT, returns
+    gradSlowness = dl/d slowness, shaped like `slowness` ([D,n,n] or [B,D,n,n], fp32 on the GPU).  `T` must be what
+    developmentTime returned for this slowness, thickness and pixelSize.  The adjoint of the Godunov fixed point: every reached
+    cell hands its lambda on to the upwind cells of its update with the weights alpha = w (T - a) / P, and dl/ds = lambda s / P
+    (the header's "Gradients through development").  A wall or a cell the front never reached gets 0 and its gradT is ignored,
+    NaN and inf included.  Where the two neighbours of an axis tie -- the symmetry line of a symmetric pattern -- the lower-index
+    one is taken: a valid but one-sided subgradient.  The solver iterates to a bitwise fixed point and waits for the device while
+    it does; if `maxIterations` launches do not reach it, RuntimeError is raised -- an unconverged gradient is never returned.
+    Deterministic: the same bits on every call, and a batch equals its volumes solved one at a time.  returnLaunches=True returns
+    (gradSlowness, launches)."""
+    who = "developmentTimeGradient"
+    s, B, D, n, batched, dev = _volume(who, slowness, "slowness")
+    thickness, h = _positive(who, "thickness", thickness), _positive(who, "pixelSize", pixelSize)
+    maxIterations = int(maxIterations)
+    if not 1 <= maxIterations <= 65536:
+        raise ValueError(f"{who}: maxIterations must be 1 ... 65536; got {maxIterations}")
+    Tv = _like(who, "T", T, slowness.shape, dev).reshape(s.shape)
+    g = _like(who, "gradT", gradT, slowness.shape, dev).reshape(s.shape)
+    out = torch.empty_like(s)
+    nbytes = int(nat.lib().litho_develop_vjp_work_bytes(B, D, n, maxIterations))
+    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    launches = ctypes.c_int(0)
+    with torch.cuda.device(dev):
+        rc = nat.lib().litho_develop_time_vjp(nat.ptr(s), nat.ptr(Tv), nat.ptr(g), B, D, n, thickness, h, maxIterations, nat.ptr(out),
+                                              nat.ptr(work), nbytes, ctypes.byref(launches), nat.stream_ptr(dev))
+        if rc == nat.E_NOCONV:
+            raise RuntimeError(f"{who}: the adjoint iteration did not reach its fixed point within the launch cap (maxIterations = "
+                               f"{maxIterations}); the gradient is not a result")
+        nat.check(rc, "litho_develop_time_vjp")
+        for t in (s, Tv, g, work):
+            t.record_stream(torch.cuda.current_stream(dev))
+    out = out if batched else out[0]
+    return (out, launches.value) if returnLaunches else out
+
+
+def _rate_vjp(who, x, gains, kappa, mack, thickness, gradSlowness):
+    """litho_develop_rate_vjp on the volume x ([D,n,n] or [F,D,n,n]) with Mack's parameters of `mack`; shaped like x."""
+    v, F, D, n, batched, dev = _volume(who, x)
+    if not 1 <= len(gains) <= 64:
+        raise ValueError(f"{who}: between 1 and 64 doses per call; got {len(gains)}")
+    if len(gains) * F * D > 65535:
+        raise ValueError(f"{who}: doses x volumes x planes exceeds 65535")
+    gs = _like(who, "gradSlowness", gradSlowness, (len(gains) * F, D, n, n), dev)
+    out = torch.empty_like(v)
+    g = (ctypes.c_float * len(gains))(*gains)
+    delta = mack.surfaceDepth if mack.surfaceDepth is not None else thickness
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_develop_rate_vjp(nat.ptr(v), F, D, n, g, len(gains), kappa, mack.rMax, mack.rMin, mack.q, mack.mTh,
+                                                   mack.surfaceRate, delta, thickness, nat.ptr(gs), nat.ptr(out), nat.stream_ptr(dev)),
+                  "litho_develop_rate_vjp")
+        for t in (v, gs):
+            t.record_stream(torch.cuda.current_stream(dev))
+    return out if batched else out[0]
+
+
+def developmentRateGradient(image, resist, thickness, pixelSize, doses, gradSlowness):
+    """developmentRate backwards: gradImage = dl/d image, shaped like `image` ([D,n,n] or [F,D,n,n]), from gradSlowness =
+    dl/d slowness, fp32 [len(doses) F, D, n, n], dose-major, as developmentRate returns it.  The rate law backwards
+    (litho_develop_rate_vjp, evaluated on the diffused image when `resist` diffuses) and then latentDiffusion on the result: the
+    diffusion is its own adjoint (symmetric taps with zeros outside the grid laterally, and the half-sample mirror in z has a
+    symmetric matrix).  A cell whose slowness is NaN (a wall) contributes 0."""
+    who = "developmentRateGradient"
+    if not isinstance(resist, MackResist):
+        raise TypeError(f"{who}: resist must be a MackResist")
+    vv, _, _, _, batched, _ = _volume(who, image)
+    v = vv if batched else vv[0]
+    thickness, h = _positive(who, "thickness", thickness), _positive(who, "pixelSize", pixelSize)
+    diffuses = resist.diffusionLength > 0.0 or resist.verticalDiffusionLength > 0.0
+    lat = latentDiffusion(v, thickness, h, resist.diffusionLength, resist.verticalDiffusionLength) if diffuses else v
+    out = _rate_vjp(who, lat, [float(d) for d in doses], resist.C, resist, thickness, gradSlowness)
+    return latentDiffusion(out, thickness, h, resist.diffusionLength, resist.verticalDiffusionLength) if diffuses else out
+
+
+def resistProfileGradient(image, resist, stack_or_thickness, pixelSize, gradT, doses=(1.0,), focalPlanes=1, maxIterations=1024):
+    """resistProfile backwards, from the arrival times down to the intensity: gradImage = dl/d image, shaped like `image`
+    ([focalPlanes x D, n, n]), for a real loss l on ResistProfile.T with gradT = dl/dT, fp32 [doses, F, D, n, n].  The call runs
+    its own forward (the slowness and developmentTime), then developmentTimeGradient, then the rate backwards: with a MackResist
+    developmentRateGradient, with a ChemicallyAmplifiedResist amplifiedRateGradient into postExposureBakeGradient(gradAcidDose=)
+    (its default steps, as resistProfile).  gradT is ignored where T is +inf; the developed depth is not differentiated."""
+    who = "resistProfileGradient"
+    thickness = stack_or_thickness.thickness if isinstance(stack_or_thickness, FilmStack) else float(stack_or_thickness)
+    F = int(focalPlanes)
+    if not isinstance(image, torch.Tensor) or image.dim() != 3 or F < 1 or image.shape[0] % F:
+        raise ValueError(f"{who}: image must be [focalPlanes x D, n, n]; got {tuple(getattr(image, 'shape', ()))} with focalPlanes {focalPlanes}")
+    D, n = image.shape[0] // F, image.shape[-1]
+    doses = tuple(doses)
+    vol = image.reshape(F, D, n, n)
+    dev = nat.require_gpu(image.device)
+    g = _like(who, "gradT", gradT, (len(doses), F, D, n, n), dev).reshape(len(doses) * F, D, n, n)
+    from .peb import ChemicallyAmplifiedResist, amplifiedRateGradient, postExposureBake, postExposureBakeGradient
+    if isinstance(resist, ChemicallyAmplifiedResist):
+        bake = postExposureBake(vol, resist, thickness, pixelSize, doses)
+        s = bake.slowness
+    else:
+        s = developmentRate(vol, resist, thickness, pixelSize, doses)
+    T, _ = _development_time(s, thickness, pixelSize, maxIterations)
+    gs = developmentTimeGradient(s, T, g, thickness, pixelSize, maxIterations)
+    if isinstance(resist, ChemicallyAmplifiedResist):
+        ga = amplifiedRateGradient(bake.acidDose, resist, thickness, gs)
+        out = postExposureBakeGradient(vol, resist, thickness, pixelSize, doses, gradAcidDose=ga)
+    else:
+        out = developmentRateGradient(vol, resist, thickness, pixelSize, doses, gs)
+    return out.reshape(image.shape)

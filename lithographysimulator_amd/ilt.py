@@ -237,7 +237,8 @@ def bakedResistModel(socs, resist, thickness, pixelSize, deltaK, wavelength, int
     optimizeMask's `threshold` is a deprotection level (for example 1 - mTh of the Mack resist that develops it), its `dose`
     stays 1 and the exposure dose rides in `intensityScale` (the image is in the engine's units: intensityScale = dose / clear
     field puts C in units of the clear-field dose).  `resist`: a ChemicallyAmplifiedResist; `steps`: postExposureBake's.
-    Development is not differentiated: the loss sits on the latent image that development thresholds."""
+    Development is not differentiated here: the loss sits on the latent image that development thresholds.  developedResistModel
+    is the model whose loss sits on the developed profile."""
     from .peb import ChemicallyAmplifiedResist, postExposureBake, postExposureBakeGradient
     if not isinstance(socs, SOCSKernels):
         raise TypeError("bakedResistModel: socs must be the SOCSKernels socsKernels returned")
@@ -258,6 +259,64 @@ def bakedResistModel(socs, resist, thickness, pixelSize, deltaK, wavelength, int
     def adjoint(gradDeprotection):
         g = gradDeprotection.detach().to(torch.float32).reshape(state["I"].shape)
         gI = postExposureBakeGradient(state["I"], resist, thickness, pixelSize, gradInhibitor=-g[None], steps=steps) * scale
+        return optics_adjoint(gI if socs.stacked else gI[0])
+
+    return imager, adjoint
+
+
+def developedResistModel(socs, resist, thickness, pixelSize, deltaK, wavelength, developTime, intensityScale=1.0, normalize=True,
+                         steps=None, maxIterations=1024):
+    """(imager, adjoint) for optimizeMask(imager=, adjoint=): inverse lithography against the DEVELOPED profile.  imager(t) is the
+    device model's image x `intensityScale` -> the slowness of `resist` (a MackResist: developmentRate; a
+    ChemicallyAmplifiedResist: postExposureBake with `steps`) -> developmentTime, and returns the development margin
+    1 - min(T, 2 developTime) / developTime as [planes, n_out, n_out]: positive where the plane is developed at `developTime`, -1
+    where the developer arrives late or never.  The planes of `socs` are the depths of the resist, top first, as in
+    bakedResistModel.  adjoint(g) carries g through the margin (zero where it is clamped), developmentTimeGradient, the rate and,
+    for a chemically amplified resist, the bake backwards, x `intensityScale`, then the device model's adjoint.  Use it with
+    optimizeMask(threshold=0), whose default resistSteepness is then 25 (per unit of margin), and dose 1; the exposure dose rides
+    in `intensityScale`.  `maxIterations` caps the launches of the forward and of the adjoint solver alike."""
+    from .develop import (MackResist, _development_time, developmentRate, developmentRateGradient, developmentTimeGradient)
+    from .peb import ChemicallyAmplifiedResist, amplifiedRateGradient, postExposureBake, postExposureBakeGradient
+    who = "developedResistModel"
+    if not isinstance(socs, SOCSKernels):
+        raise TypeError(f"{who}: socs must be the SOCSKernels socsKernels returned")
+    if not isinstance(resist, (MackResist, ChemicallyAmplifiedResist)):
+        raise TypeError(f"{who}: resist must be a MackResist or a ChemicallyAmplifiedResist")
+    scale, t_dev = float(intensityScale), float(developTime)
+    if not (scale > 0.0 and math.isfinite(scale)):
+        raise ValueError(f"{who}: intensityScale must be positive and finite; got {intensityScale}")
+    if not (t_dev > 0.0 and math.isfinite(t_dev)):
+        raise ValueError(f"{who}: developTime must be positive and finite; got {developTime}")
+    if not 1 <= int(maxIterations) <= 65536:
+        raise ValueError(f"{who}: maxIterations must be 1 ... 65536; got {maxIterations}")
+    amplified = isinstance(resist, ChemicallyAmplifiedResist)
+    dev = nat.require_gpu(socs.kernels.device)
+    optics, optics_adjoint = _device_model(socs, int(socs.pn), pixelSize, deltaK, wavelength, normalize, dev)
+    state = {}
+
+    def imager(transmission):
+        image = optics(transmission) * scale
+        I = state["I"] = image if image.dim() == 3 else image[None]
+        if amplified:
+            bake = postExposureBake(I, resist, thickness, pixelSize, steps=steps)
+            state["a"], s = bake.acidDose, bake.slowness
+        else:
+            s = developmentRate(I, resist, thickness, pixelSize)
+        state["s"] = s
+        state["T"] = _development_time(s, thickness, pixelSize, maxIterations)[0]
+        return 1.0 - torch.clamp(state["T"][0], max=2.0 * t_dev) / t_dev
+
+    def adjoint(gradMargin):
+        T = state["T"]
+        g = gradMargin.detach().to(torch.float32).reshape(T.shape)
+        gT = torch.where(T < 2.0 * t_dev, g * (-1.0 / t_dev), torch.zeros_like(g))
+        gs = developmentTimeGradient(state["s"], T, gT, thickness, pixelSize, maxIterations)
+        if amplified:
+            ga = amplifiedRateGradient(state["a"], resist, thickness, gs)
+            gI = postExposureBakeGradient(state["I"], resist, thickness, pixelSize, gradAcidDose=ga, steps=steps)
+        else:
+            gI = developmentRateGradient(state["I"], resist, thickness, pixelSize, (1.0,), gs)
+        gI = gI * scale
         return optics_adjoint(gI if socs.stacked else gI[0])
 
     return imager, adjoint

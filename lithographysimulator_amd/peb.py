@@ -11,9 +11,11 @@ acid minus quencher is conserved exactly and a bake does not drain acid out of t
 
 Gradients: `bakeGradient`, `exposeAcidGradient` and their chain `postExposureBakeGradient` are the discrete adjoint of exactly this
 scheme, for a loss on the acid, the quencher, the acid dose or the inhibitor after the bake (litho_peb_bake_vjp: a checkpointed
-forward sweep, then one backward step per launch); `ilt.bakedResistModel` hands them to `optimizeMask`.
+forward sweep, then one backward step per launch); `ilt.bakedResistModel` hands them to `optimizeMask`.  `amplifiedRateGradient` is amplifiedRate backwards, the link from
+develop.py's gradients through development (`resistProfileGradient`, `ilt.developedResistModel`) to the bake's.
 
-NOT built: bleaching, a diffusivity that depends on the deprotection, gradients through development."""
+NOT built: bleaching, a diffusivity that depends on the deprotection, gradients with respect to resist parameters other than
+the quencher loading."""
 import ctypes
 import math
 
@@ -153,6 +155,19 @@ def amplifiedRate(acidDose, resist, thickness):
     return (m, slow) if batched else (m[0], slow[0])
 
 
+def amplifiedRateGradient(acidDose, resist, thickness, gradSlowness):
+    """amplifiedRate backwards (litho_develop_rate_vjp with kappa = kAmp and a single gain of 1): gradAcidDose = dl/d acidDose from
+    gradSlowness = dl/d slowness, both shaped like `acidDose` ([D,n,n] or [B,D,n,n]).  A cell whose slowness is NaN contributes 0.
+    What postExposureBakeGradient(gradAcidDose=) takes."""
+    who = "amplifiedRateGradient"
+    if not isinstance(resist, ChemicallyAmplifiedResist):
+        raise TypeError(f"{who}: resist must be a ChemicallyAmplifiedResist")
+    from .develop import _rate_vjp
+    if isinstance(acidDose, torch.Tensor) and acidDose.dim() == 3 and isinstance(gradSlowness, torch.Tensor) and gradSlowness.dim() == 3:
+        gradSlowness = gradSlowness[None]                                         # one volume: the single gain's cotangent
+    return _rate_vjp(who, acidDose, [1.0], resist.kAmp, resist.mack, _positive(who, "thickness", thickness), gradSlowness)
+
+
 def postExposureBake(image, resist, thickness, pixelSize, doses=(1.0,), steps=None, stepsPerLaunch=0):
     """Exposure, bake and rate of `resist` (a ChemicallyAmplifiedResist) on the intensity volume `image`, fp32 [D,n,n] or [F,D,n,n]
     on the GPU, in a layer of `thickness` nm: exposeAcid, bakeAcid, amplifiedRate.  Returns a BakeResult, [len(doses) F, D, n, n];
@@ -255,7 +270,8 @@ def postExposureBakeGradient(image, resist, thickness, pixelSize, doses=(1.0,), 
     `inhibitor`, `acidDose`, `acid` and `quencher` (cotangents [len(doses) F, D, n, n], dose-major; None = zero, at least one
     given).  The chain of three pieces: the inhibitor m = exp(-kAmp a) gives abar = gradAcidDose - kAmp m gradInhibitor (pointwise,
     torch on the device, m from the forward bake that this call runs), then bakeGradient, then exposeAcidGradient.  `steps`:
-    the default of postExposureBake.  Nothing is differentiated through development (the slowness and what follows it)."""
+    the default of postExposureBake.  The slowness is not differentiated here: develop.resistProfileGradient carries a cotangent on
+    the arrival times through development and the rate and enters this call through gradAcidDose."""
     who = "postExposureBakeGradient"
     if not isinstance(resist, ChemicallyAmplifiedResist):
         raise TypeError(f"{who}: resist must be a ChemicallyAmplifiedResist")
