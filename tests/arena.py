@@ -1,0 +1,158 @@
+"""A guarded, poisoned arena for calls through the raw C ABI: every device buffer of ONE call -- inputs, outputs and the
+workspace -- lies in a single uint8 allocation, so that what a kernel reads or writes outside a buffer is seen.
+
+    poison      every byte of the arena is 0xFF before the inputs are copied in: as fp32 or complex64 that is a NaN (a read outside
+                a buffer contaminates the result instead of looking plausible), as int32 it is -1 (a flag word that nobody
+                initialised reads as "changed").
+    guards      in front of and behind every buffer lie at least `guard_bytes` bytes of poison, rounded up to 256: the caller
+                passes one plane + one row + one pack of the call's volume, (n n + n + 4) elements, the farthest a one-off error in
+                a plane, row or pack index can reach.
+    alignment   a buffer starts `mod` bytes (0, 4, 8 or 12) past a 16-byte boundary; the arena asserts data_ptr() % 16 == mod.
+    exact sizes a buffer is exactly as long as it was asked for -- a workspace exactly what its *_work_bytes function returned --
+                and the next byte is guard.
+
+After the call `report(reference)` lists, as (buffer name, byte offset from the start of that buffer): every guard byte that
+changed (a negative offset lies in front of the buffer, one >= its size behind it; a byte between two buffers goes to the nearer
+one), every input byte that changed, and every 4-byte word of an output that still holds the poison pattern where the reference
+result does not.  All comparisons are of bit patterns, through uint8 or int32 views: a result may hold NaN (walls) and a NaN
+never equals itself as a float.  Works on CPU tensors as well (tests/test_arena_cpu.py)."""
+import torch
+
+POISON = 0xFF
+POISON_WORD = -1                                                               # 0xFFFFFFFF as int32
+ROLES = ("in", "out", "work")
+
+
+class Buf:
+    """One buffer of the call: `role` "in" (must not change), "out" (must be written completely) or "work" (scratch: its
+    contents are nobody's business, its borders are); `mod` = the start offset in bytes modulo 16."""
+
+    def __init__(self, name, role, dtype, shape, mod=0):
+        assert role in ROLES and mod in (0, 4, 8, 12), (name, role, mod)
+        self.name, self.role, self.dtype, self.shape, self.mod = name, role, dtype, tuple(int(v) for v in shape), mod
+        count = 1
+        for v in self.shape:
+            count *= v
+        self.nbytes = count * torch.empty((), dtype=dtype).element_size()
+        assert self.nbytes > 0, name
+        self.start = self.end = None
+
+
+def words(t):
+    """The bit patterns of a tensor as a flat int32 tensor (fp32, int32, complex64) or uint8 tensor (uint8)."""
+    t = t.contiguous()
+    if t.is_complex():
+        t = torch.view_as_real(t)
+    t = t.reshape(-1)
+    return t if t.dtype == torch.uint8 else t.view(torch.int32)
+
+
+def differing(a, b):
+    """Byte offsets of the 4-byte words (bytes, for uint8) in which a and b differ as bit patterns; a shape mismatch is an error."""
+    wa, wb = words(a), words(b.to(a.device))
+    assert wa.shape == wb.shape and wa.dtype == wb.dtype, (tuple(a.shape), tuple(b.shape))
+    step = 1 if wa.dtype == torch.uint8 else 4
+    return [step * i for i in (wa != wb).nonzero().flatten().cpu().tolist()]
+
+
+class Report:
+    """What report() found; each entry is (buffer name, byte offset from the start of that buffer)."""
+
+    def __init__(self, guards, inputs, unwritten):
+        self.guards, self.inputs, self.unwritten = guards, inputs, unwritten
+
+    @property
+    def clean(self):
+        return not (self.guards or self.inputs or self.unwritten)
+
+    def __str__(self):
+        def some(items):
+            return f"{len(items)}: {items[:8]}{' ...' if len(items) > 8 else ''}"
+        return f"guard bytes changed {some(self.guards)}; input bytes changed {some(self.inputs)}; output words never written {some(self.unwritten)}"
+
+
+class Arena:
+    def __init__(self, bufs, guard_bytes, device="cpu"):
+        self.bufs = {b.name: b for b in bufs}
+        assert len(self.bufs) == len(bufs), "buffer names must differ"
+        self.guard = (int(guard_bytes) + 255) // 256 * 256
+        assert self.guard >= 256
+        at = 0
+        for b in bufs:                                                         # [guard][mod][buffer][pad to 256] ... [guard]
+            b.start = at + self.guard + b.mod
+            b.end = b.start + b.nbytes
+            at = (b.end + 255) // 256 * 256
+        self.size = at + self.guard
+        raw = torch.full((self.size + 256,), POISON, dtype=torch.uint8, device=device)
+        shift = -raw.data_ptr() % 256
+        self.bytes = raw[shift:shift + self.size]
+        assert self.bytes.data_ptr() % 256 == 0 and shift % 16 == 0
+        outside = torch.ones(self.size, dtype=torch.bool)
+        inside_in = torch.zeros(self.size, dtype=torch.bool)
+        for b in bufs:
+            outside[b.start:b.end] = False
+            if b.role == "in":
+                inside_in[b.start:b.end] = True
+            assert self[b.name].data_ptr() % 16 == b.mod, (b.name, self[b.name].data_ptr() % 16, b.mod)
+        self._guard_mask, self._input_mask = outside.to(device), inside_in.to(device)
+        self._sealed = None
+
+    def __getitem__(self, name):
+        """The buffer as a tensor of its own dtype and shape, a view of the arena."""
+        b = self.bufs[name]
+        return self.bytes[b.start:b.end].view(b.dtype).view(b.shape)
+
+    def ptr(self, name):
+        return self[name].data_ptr()
+
+    def leading_guard(self, name):
+        """Bytes of poison between this buffer and the one in front of it (or the start of the arena)."""
+        b = self.bufs[name]
+        return b.start - max([o.end for o in self.bufs.values() if o.end <= b.start], default=0)
+
+    def trailing_guard(self, name):
+        b = self.bufs[name]
+        return min([o.start for o in self.bufs.values() if o.start >= b.end], default=self.size) - b.end
+
+    def fill(self, name, value):
+        """Copy an input in (bit for bit: same dtype, same shape)."""
+        view = self[name]
+        assert value.dtype == view.dtype and tuple(value.shape) == tuple(view.shape), (name, value.dtype, tuple(value.shape))
+        view.copy_(value)
+
+    def seal(self):
+        """Remember the arena as it is now, inputs in place: what report() compares the inputs with."""
+        self._sealed = self.bytes.clone()
+
+    def _locate(self, positions):
+        """(name, offset) per arena byte position: inside a buffer that buffer, outside the nearer one."""
+        out = []
+        for p in positions:
+            best = None
+            for b in self.bufs.values():
+                dist = 0 if b.start <= p < b.end else (b.start - p if p < b.start else p - b.end + 1)
+                if best is None or dist < best[0]:
+                    best = (dist, b)
+            out.append((best[1].name, p - best[1].start))
+        return out
+
+    def still_poison(self, name):
+        """True when every byte of the buffer is still 0xFF: nothing was launched on it."""
+        b = self.bufs[name]
+        return bool((self.bytes[b.start:b.end] == POISON).all())
+
+    def report(self, reference):
+        """`reference`: {output name: the tensor the output is expected to equal}; every "out" buffer needs one."""
+        assert self._sealed is not None, "seal() the arena after the inputs are in"
+        cur = self.bytes
+        guards = self._locate(((cur != POISON) & self._guard_mask).nonzero().flatten().cpu().tolist())
+        inputs = self._locate(((cur != self._sealed) & self._input_mask).nonzero().flatten().cpu().tolist())
+        unwritten = []
+        for b in self.bufs.values():
+            if b.role != "out":
+                continue
+            got, want = words(self[b.name]), words(reference[b.name].to(cur.device))
+            assert got.shape == want.shape and got.dtype == torch.int32, (b.name, tuple(got.shape), tuple(want.shape))
+            left = (got == POISON_WORD) & (want != POISON_WORD)
+            unwritten += [(b.name, 4 * i) for i in left.nonzero().flatten().cpu().tolist()]
+        return Report(guards, inputs, unwritten)

@@ -1,0 +1,118 @@
+"""tests/arena.py can fail: the layout it promises and every kind of damage it is there to report, on CPU tensors (no GPU)."""
+import pytest
+import torch
+
+from arena import POISON, Arena, Buf, differing, words
+
+N, D = 5, 2
+GUARD = (N * N + N + 4) * 4                                                    # one plane + one row + one pack, in bytes: 136
+
+
+def make(mod_x=0, mod_y=0, mod_w=0, work_bytes=100):
+    a = Arena([Buf("x", "in", torch.float32, (D, N, N), mod_x), Buf("y", "out", torch.float32, (D, N, N), mod_y),
+               Buf("work", "work", torch.uint8, (work_bytes,), mod_w)], GUARD)
+    x = torch.arange(D * N * N, dtype=torch.float32).reshape(D, N, N) + 1.0
+    a.fill("x", x)
+    a.seal()
+    return a, x
+
+
+def answer(a, x):
+    """What a correct call would do: y = 2 x, and scribble over all of the workspace."""
+    a["y"].copy_(2.0 * x)
+    a["work"].fill_(0x11)
+    return {"y": 2.0 * x}
+
+
+@pytest.mark.parametrize("mod", [0, 4, 8, 12])
+def test_offsets_and_guard_sizes(mod):
+    a, x = make(mod_x=mod, mod_y=(mod + 4) % 16, mod_w=mod)
+    assert a.guard == 256 and a.guard >= GUARD                                  # 136 bytes rounded up to 256
+    assert a.bytes.data_ptr() % 256 == 0 and bool((a.bytes[:a.bufs["x"].start] == POISON).all())
+    for name, m in (("x", mod), ("y", (mod + 4) % 16), ("work", mod)):
+        b = a.bufs[name]
+        assert a.ptr(name) % 16 == m and a.ptr(name) == a.bytes.data_ptr() + b.start
+        assert b.end - b.start == b.nbytes == a[name].numel() * a[name].element_size()
+        assert a.leading_guard(name) >= a.guard and a.trailing_guard(name) >= a.guard
+    assert a.bufs["x"].end <= a.bufs["y"].start - a.guard and a.size - a.bufs["work"].end >= a.guard
+    assert torch.equal(a["x"], x) and a.still_poison("y") and a.still_poison("work")
+    assert words(a["y"]).dtype == torch.int32 and bool((words(a["y"]) == -1).all()) and bool(torch.isnan(a["y"]).all())
+    rep = a.report(answer(a, x))
+    assert rep.clean and not a.still_poison("y"), str(rep)
+
+
+def test_a_complex_buffer_at_8_mod_16():
+    a = Arena([Buf("p", "in", torch.complex64, (3, 4), 8), Buf("q", "out", torch.complex64, (3, 4), 8)], 64)
+    assert a.ptr("p") % 16 == 8 and a.ptr("q") % 16 == 8 and a["q"].dtype == torch.complex64
+    assert bool(torch.isnan(torch.view_as_real(a["q"])).all())
+    p = torch.complex(torch.arange(12.0).reshape(3, 4), torch.ones(3, 4))
+    a.fill("p", p)
+    a.seal()
+    a["q"].copy_(p)
+    a["q"].view(torch.float32).reshape(-1)[5] = float("nan")                    # one real part written as an ordinary NaN
+    a["q"].view(torch.int32).reshape(-1)[7] = -1                                # one imaginary part left as poison
+    want = p.clone()
+    torch.view_as_real(want).reshape(-1)[5] = float("nan")
+    rep = a.report({"q": want})
+    assert rep.unwritten == [("q", 28)] and not rep.guards and not rep.inputs, str(rep)
+
+
+@pytest.mark.parametrize("mod", [0, 12])
+def test_a_flipped_byte_is_reported_where_it_is(mod):
+    a, x = make(mod_x=mod, mod_y=mod)
+    want = answer(a, x)
+    y, w = a.bufs["y"], a.bufs["work"]
+    a.bytes[y.start - 1] = 0                                                   # the last byte in front of y
+    a.bytes[y.end] = 7                                                         # the first byte behind y
+    a.bytes[w.start - 100] = 1                                                 # inside the guard in front of the workspace
+    a.bytes[a.size - 1] = 2                                                    # the last byte of the arena
+    a.bytes[a.bufs["x"].start + 9] ^= 0x40                                     # an input byte
+    rep = a.report(want)
+    assert rep.guards == [("y", -1), ("y", y.nbytes), ("work", -100), ("work", a.size - 1 - w.start)], str(rep)
+    assert rep.inputs == [("x", 9)] and rep.unwritten == [] and not rep.clean
+
+
+def test_a_byte_in_front_of_the_first_buffer():
+    a, x = make()
+    want = answer(a, x)
+    a.bytes[0] = 0
+    assert a.report(want).guards == [("x", -a.guard)]
+
+
+def test_an_output_element_left_as_poison_is_reported_and_a_nan_result_is_not():
+    a, x = make(mod_y=4)
+    want = answer(a, x)
+    nan_other_payload = torch.tensor([0x7FC00001], dtype=torch.int32).view(torch.float32)[0]
+    want["y"][1, 2, 3] = float("nan")                                          # the reference: the canonical NaN, 0x7fc00000
+    a["y"][1, 2, 3] = nan_other_payload                                        # the call: a NaN of another payload -- written
+    a["y"].view(torch.int32)[0, 4, 1] = -1                                     # never written: still 0xFFFFFFFF
+    rep = a.report(want)
+    assert rep.unwritten == [("y", 4 * (4 * N + 1))] and not rep.guards and not rep.inputs, str(rep)
+    # as floats the two could not be told apart: both are NaN, and neither equals the reference
+    assert bool(torch.isnan(a["y"][1, 2, 3])) and bool(torch.isnan(a["y"][0, 4, 1]))
+    # bitwise comparison sees both, and only those
+    assert differing(a["y"], want["y"]) == [4 * (4 * N + 1), 4 * (N * N + 2 * N + 3)]
+    want["y"][1, 2, 3] = nan_other_payload
+    assert differing(a["y"], want["y"]) == [4 * (4 * N + 1)]
+    # where the reference itself holds the poison pattern, an equal word is no finding
+    want["y"].view(torch.int32)[0, 4, 1] = -1
+    assert a.report(want).clean and differing(a["y"], want["y"]) == []
+
+
+@pytest.mark.parametrize("nbytes", [1, 100, 256, 4 * 50 + 256])
+def test_a_workspace_of_exact_size(nbytes):
+    a, x = make(work_bytes=nbytes)
+    w = a.bufs["work"]
+    assert a["work"].numel() == nbytes and w.end - w.start == nbytes and a["work"].dtype == torch.uint8
+    want = answer(a, x)                                                        # writes every byte of the workspace
+    assert a.report(want).clean
+    a.bytes[w.end] = 0x11                                                      # one byte more than was asked for
+    assert a.report(want).guards == [("work", nbytes)]
+
+
+def test_nothing_launched_leaves_everything_poison():
+    a, x = make(mod_w=8)
+    assert a.ptr("work") % 16 == 8
+    assert a.still_poison("y") and a.still_poison("work") and a.report({"y": 2.0 * x}).unwritten[0] == ("y", 0)
+    a["work"][3] = 0
+    assert not a.still_poison("work")

@@ -51,6 +51,11 @@ def L():
     return L
 
 
+def same_bits(a, b):
+    """Equal as bit patterns (int32 views): a NaN-bearing result compares like any other, and -0 is not +0."""
+    return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
 def solver_bound(n, D, t_max):
     return C_SOLVER * (D + 2 * n) * U * t_max
 
@@ -191,9 +196,9 @@ def test_second_call_and_batch_are_bit_identical(L, dev, n, D):
     s, T, launches, _, _ = random_case(L, dev, n, D)
     sd = torch.from_numpy(s).to(dev)
     again, l2 = L.developmentTime(sd, THICK, H, returnLaunches=True)
-    assert torch.equal(again, T) and l2 == launches
+    assert same_bits(again, T) and l2 == launches
     singles = [L.developmentTime(sd[b], THICK, H, returnLaunches=True) for b in range(3)]
-    assert all(torch.equal(t, T[b]) for b, (t, _) in enumerate(singles))
+    assert all(same_bits(t, T[b]) for b, (t, _) in enumerate(singles))
     assert max(l for _, l in singles) == launches                               # the batch runs until its slowest volume is done
     print(f"n {n} D {D}: second call and 3 single calls equal the batch bit for bit; launches {launches} vs {[l for _, l in singles]}")
 
