@@ -61,16 +61,16 @@ build/film.o: $(CSRC)/film.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 # resist development: fixed sequences of single fp32 operations (the float64 restatement bounds every rounding), double per cell
 # in the rate kernel
-build/develop.o: $(CSRC)/develop.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
+build/develop.o: $(CSRC)/develop.hip $(CSRC)/resist_volume.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 # gradients through development: the link coefficients in double per cell, the gather iteration a fixed sequence of single fp32
 # operations (what makes its bits independent of the tile schedule)
-build/develop_grad.o: $(CSRC)/develop_grad.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
+build/develop_grad.o: $(CSRC)/develop_grad.hip $(CSRC)/resist_volume.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 # the post-exposure bake: the same, and what makes a bake's bits independent of how its steps are cut into launches
-build/peb.o: $(CSRC)/peb.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
+build/peb.o: $(CSRC)/peb.hip $(CSRC)/resist_volume.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 build/common.o: $(CSRC)/common.hip $(CSRC)/engine_common.hpp include/litho_abbe.h

@@ -47,6 +47,17 @@ int device_cus()
     }
     return n;
 }
+hipError_t lds_opt_in(unsigned& done, const void* kernel, size_t bytes)
+{
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    const unsigned bit = 1u << (dev & 31);
+    if (__atomic_load_n(&done, __ATOMIC_ACQUIRE) & bit) return hipSuccess;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) __atomic_fetch_or(&done, bit, __ATOMIC_RELEASE);
+    return e;
+}
 }  // namespace litho
 
 extern "C" {

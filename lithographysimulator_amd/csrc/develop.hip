@@ -2,7 +2,8 @@
 // (no reference counterpart; the definitions are in include/litho_abbe.h, the checker is their float64 restatement
 // tests/develop_oracle.py).  Built with -ffp-contract=off (Makefile): every fp32 result is a fixed sequence of single operations.
 //
-// Volumes are fp32 [B, D, n, n], D <= 32 planes through the resist, x fastest.  Four kernels:
+// Volumes are fp32 [B, D, n, n], D <= 32 planes through the resist, x fastest.  The limits, the packs, the host predicates, the
+// gains, Mack's rate law and the solver's host loop are resist_volume.hpp's, shared with peb.hip and develop_grad.hip.  Four kernels:
 //   k_latent_diffuse   one pass of the separable Gaussian along x, y (zero outside the grid) or z (mirrored layer faces); a gather
 //                      per output element, lanes along x, so every load of a wave is one contiguous run of a row
 //   k_develop_rate     Dill C exposure and Mack's rate in double per cell, the gains in a loop inside, slowness 1 / r out
@@ -12,68 +13,25 @@
 // 16-byte aligned, one otherwise.
 //
 // k_develop_time.  A workgroup owns a 16 x 16 lateral tile with all D planes: T of tile + one-cell halo and s of the tile live in
-// LDS, D (18 . 18 + 16 . 16) floats = 72.5 KiB at D = 32.  It relaxes the tile DEV_INNER rounds; a round is two phases, the columns
+// LDS, D (18 . 18 + 16 . 16) floats = 72.5 KiB at D = 32.  It relaxes the tile VOL_INNER rounds; a round is two phases, the columns
 // with (row + col) even, a barrier, the odd ones, a barrier.  In a phase 128 threads own one column each and sweep it down and
 // up (Gauss-Seidel along z, where the front mostly runs); the four lateral neighbours of a column have the other colour and are
 // not written in that phase, so there is no race and the result does not depend on scheduling.  Halo cells are read-only, cells
 // outside the grid hold +inf.  Launches ping-pong T between two global buffers: no workgroup reads what another writes.  A cell
 // "changed" when it took a strictly smaller value (new < old: false for a NaN); a thread that changed one stores 1 into the
-// launch's own flag word with a plain store.  The host reads the flag words every DEV_CHECK launches and stops at the first
+// launch's own flag word with a plain store.  The host reads the flag words every VOL_CHECK launches and stops at the first
 // launch that changed nothing: its output equals its input, so both buffers hold the fixed point.  Values only ever decrease and
 // every loop has a trip count fixed by D: a launch cannot hang, and the launch count is capped by the caller.
-#include "engine_common.hpp"
-#include "../../include/litho_abbe.h"
-
-#include <cmath>
-#include <cstdint>
-#include <cstring>
+#include "resist_volume.hpp"
 
 namespace litho {
 
-static constexpr int DEV_DMAX = 32, DEV_RMAX = 32, DEV_GAINS = 64;
-static constexpr int DEV_TILE = 16, DEV_HALO = DEV_TILE + 2, DEV_INNER = 8, DEV_CHECK = 4, DEV_MAXIT = 65536;
-static constexpr int DEV_TCELLS = DEV_HALO * DEV_HALO, DEV_SCELLS = DEV_TILE * DEV_TILE;
+static constexpr int DEV_RMAX = 32;
+static constexpr int DEV_TCELLS = VOL_HALO * VOL_HALO, DEV_SCELLS = VOL_TILE * VOL_TILE;
 
 struct DevTaps {
     float g[DEV_RMAX + 1];                               // g[|k|], normalised over k = -R .. R; rides in the kernel arguments
 };
-struct DevGains {
-    float g[DEV_GAINS];
-};
-struct DevSurface {
-    double f[DEV_DMAX];                                  // the surface-inhibition factor of plane d, from the host
-};
-
-template <int VEC>
-struct Pack {
-    float v[VEC];
-};
-template <int VEC>
-__device__ __forceinline__ Pack<VEC> load_pack(const float* p)
-{
-    Pack<VEC> r;
-    if constexpr (VEC == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w;
-    } else {
-        r.v[0] = *p;
-    }
-    return r;
-}
-template <int VEC>
-__device__ __forceinline__ void store_pack(float* p, const Pack<VEC>& r)
-{
-    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    else *p = r.v[0];
-}
-
-// index -1 - k <-> k and D + k <-> D - 1 - k, repeated as needed
-__host__ __device__ __forceinline__ int mirror_index(int i, int D)
-{
-    int m = i % (2 * D);
-    if (m < 0) m += 2 * D;
-    return m < D ? m : 2 * D - 1 - m;
-}
 
 // ---- 1. one pass of the latent-image diffusion.  axis 0: along x, 1: along y (zero outside), 2: along z (mirror).  grid.x covers
 // the n^2 / VEC packs of a plane, grid.y the B D planes.  Symmetric taps are paired, acc = g[0] c; acc += g[k] (c[-k] + c[k]),
@@ -112,13 +70,12 @@ __global__ __launch_bounds__(256) void k_latent_diffuse(const float* __restrict_
     store_pack<VEC>(out + (size_t)p * plane_elems + e, acc);
 }
 
-// ---- 2. Dill C exposure and Mack's rate: m = exp(-(C g) I), x = (1 - m)^q, r = (rmax (a + 1)) x / (a + x) + rmin, times the
-// surface factor of the plane; slowness = fp32(1 / r), NaN where 1 - m is negative or NaN.  Double per cell, rounded once.
-// grid.y: the F D planes of the image.
+// ---- 2. Dill C exposure and Mack's rate: m = exp(-(C g) I), then mack_slowness of 1 - m with the surface factor of the plane
+// (resist_volume.hpp): NaN where 1 - m is negative or NaN.  Double per cell, rounded once.  grid.y: the F D planes of the image.
 template <int VEC>
 __global__ __launch_bounds__(256) void k_develop_rate(const float* __restrict__ image, float* __restrict__ out, int planes, int D, int n,
-                                                      const DevGains gains, int n_gains, double C, double rmax_a1, double rmin, double q,
-                                                      double a, const DevSurface surface)
+                                                      const VolGains gains, int n_gains, double C, double rmax_a1, double rmin, double q,
+                                                      double a, const VolSurface surface)
 {
     const long long plane_elems = (long long)n * n;
     const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
@@ -131,10 +88,7 @@ __global__ __launch_bounds__(256) void k_develop_rate(const float* __restrict__ 
         Pack<VEC> s;
         for (int v = 0; v < VEC; ++v) {
             const double m = exp(-(Cg * (double)I.v[v]));
-            const double x = pow(1.0 - m, q);
-            const double r = (rmax_a1 * x / (a + x) + rmin) * f;
-            // 1 - m < 0 under a negative product g I: pow is finite there for an integer q, so the NaN is written explicitly
-            s.v[v] = (1.0 - m >= 0.0) ? (float)(1.0 / r) : __builtin_nanf("");
+            s.v[v] = mack_slowness(1.0 - m, rmax_a1, rmin, q, a, f);
         }
         store_pack<VEC>(out + ((size_t)gi * planes + p) * plane_elems + e, s);
     }
@@ -176,7 +130,7 @@ __device__ __forceinline__ float godunov(float a0, float h0, float w0, float a1,
 __device__ __forceinline__ bool relax_cell(float* q, float s, int d, int D, float h, float hz, float wxy, float wz)
 {
     if (!(s > 0.f && s < INFINITY)) return false;        // a wall keeps +inf
-    const float ax = fminf(q[-1], q[1]), ay = fminf(q[-DEV_HALO], q[DEV_HALO]);
+    const float ax = fminf(q[-1], q[1]), ay = fminf(q[-VOL_HALO], q[VOL_HALO]);
     const float below = d + 1 < D ? q[DEV_TCELLS] : INFINITY;
     float az = 0.f, hd = 0.5f * hz, wd = 4.f * wz;       // plane 0: the resist top, T = 0, half a step above
     if (d > 0) {
@@ -200,30 +154,30 @@ __global__ __launch_bounds__(256) void k_develop_time(const float* __restrict__ 
     float* Tl = dev_lds;                                 // [D][18][18]  tile + halo
     float* sl = dev_lds + D * DEV_TCELLS;                // [D][16][16]  tile
     const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * DEV_TILE, y0 = blockIdx.y * DEV_TILE;
+    const int x0 = blockIdx.x * VOL_TILE, y0 = blockIdx.y * VOL_TILE;
     const size_t plane_elems = (size_t)n * n;
     const size_t vol = (size_t)blockIdx.z * D * plane_elems;
     const float inf = INFINITY, nan = __builtin_nanf("");
     for (int i = tid; i < D * DEV_TCELLS; i += 256) {
-        const int d = i / DEV_TCELLS, r = i - d * DEV_TCELLS, ly = r / DEV_HALO, lx = r - ly * DEV_HALO;
+        const int d = i / DEV_TCELLS, r = i - d * DEV_TCELLS, ly = r / VOL_HALO, lx = r - ly * VOL_HALO;
         const int gy = y0 + ly - 1, gx = x0 + lx - 1;
         Tl[i] = (gy >= 0 && gy < n && gx >= 0 && gx < n) ? Tin[vol + (size_t)d * plane_elems + (size_t)gy * n + gx] : inf;
     }
     for (int i = tid; i < D * DEV_SCELLS; i += 256) {
-        const int d = i / DEV_SCELLS, r = i - d * DEV_SCELLS, ly = r / DEV_TILE, lx = r - ly * DEV_TILE;
+        const int d = i / DEV_SCELLS, r = i - d * DEV_SCELLS, ly = r / VOL_TILE, lx = r - ly * VOL_TILE;
         const int gy = y0 + ly, gx = x0 + lx;
         sl[i] = (gy < n && gx < n) ? slow[vol + (size_t)d * plane_elems + (size_t)gy * n + gx] : nan;   // outside the grid: a wall
     }
     __syncthreads();
     // compute threads: 128, row = tid / 8, the columns of this phase's colour in that row
-    const int row = (tid >> 3) & (DEV_TILE - 1), pair = tid & 7;
+    const int row = (tid >> 3) & (VOL_TILE - 1), pair = tid & 7;
     bool changed = false;
-    for (int round = 0; round < DEV_INNER; ++round) {
+    for (int round = 0; round < VOL_INNER; ++round) {
         for (int colour = 0; colour < 2; ++colour) {
             if (tid < 128) {
                 const int col = 2 * pair + ((row + colour) & 1);
-                float* Tc = Tl + (row + 1) * DEV_HALO + (col + 1);
-                const float* sc = sl + row * DEV_TILE + col;
+                float* Tc = Tl + (row + 1) * VOL_HALO + (col + 1);
+                const float* sc = sl + row * VOL_TILE + col;
                 for (int d = 0; d < D; ++d) changed |= relax_cell(Tc + d * DEV_TCELLS, sc[d * DEV_SCELLS], d, D, h, hz, wxy, wz);
                 for (int d = D - 2; d >= 0; --d) changed |= relax_cell(Tc + d * DEV_TCELLS, sc[d * DEV_SCELLS], d, D, h, hz, wxy, wz);
             }
@@ -231,9 +185,9 @@ __global__ __launch_bounds__(256) void k_develop_time(const float* __restrict__ 
         }
     }
     for (int i = tid; i < D * DEV_SCELLS; i += 256) {
-        const int d = i / DEV_SCELLS, r = i - d * DEV_SCELLS, ly = r / DEV_TILE, lx = r - ly * DEV_TILE;
+        const int d = i / DEV_SCELLS, r = i - d * DEV_SCELLS, ly = r / VOL_TILE, lx = r - ly * VOL_TILE;
         const int gy = y0 + ly, gx = x0 + lx;
-        if (gy < n && gx < n) Tout[vol + (size_t)d * plane_elems + (size_t)gy * n + gx] = Tl[d * DEV_TCELLS + (ly + 1) * DEV_HALO + lx + 1];
+        if (gy < n && gx < n) Tout[vol + (size_t)d * plane_elems + (size_t)gy * n + gx] = Tl[d * DEV_TCELLS + (ly + 1) * VOL_HALO + lx + 1];
     }
     if (changed) *flag = 1;
 }
@@ -267,17 +221,6 @@ __global__ __launch_bounds__(256) void k_developed_depth(const float* __restrict
     }
     store_pack<VEC>(out + (size_t)blockIdx.y * plane_elems + e, z);
 }
-
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + b_bytes && pb < pa + a_bytes;
-}
-static bool finite_pos(double v) { return v > 0.0 && !std::isinf(v); }
-static unsigned plane_blocks(int n, int vec) { return (unsigned)(((long long)n * n / vec + 255) / 256); }
-static bool volume_ok(int B, int D, int n) { return B >= 1 && D >= 1 && D <= DEV_DMAX && n >= 1 && n <= 16384 && (long long)B * D <= 65535; }
-static size_t flag_bytes(int max_iterations) { return ((size_t)max_iterations * sizeof(int) + 255) & ~(size_t)255; }
 
 // taps of litho_postprocess_resist_diffused; false when R = ceil(4 sigma) > 32 or sigma is negative or not finite
 static bool make_taps(double sigma_px, DevTaps& taps, int& R)
@@ -328,10 +271,7 @@ int litho_latent_diffuse(const float* image, int B, int D, int n, double sigma_x
     int left = passes;
     auto pass = [&](int axis, const DevTaps& taps, int R) {
         float* dst = (left & 1) ? out : (float*)work;
-        const int vec = (wide && axis != 0) ? 4 : 1;
-        const dim3 grid(plane_blocks(n, vec), (unsigned)(B * D));
-        if (vec == 4) hipLaunchKernelGGL(k_latent_diffuse<4>, grid, dim3(256), 0, st, src, dst, D, n, axis, taps, R);
-        else hipLaunchKernelGGL(k_latent_diffuse<1>, grid, dim3(256), 0, st, src, dst, D, n, axis, taps, R);
+        LAUNCH_PACKED(k_latent_diffuse, wide && axis != 0, n, B * D, st, src, dst, D, n, axis, taps, R);
         src = dst;
         --left;
     };
@@ -349,32 +289,15 @@ int litho_develop_rate(const float* image, int volumes, int D, int n, const floa
                        float* slowness, void* stream)
 {
     using namespace litho;
-    if (!image || !gains_host || !slowness || n_gains < 1 || n_gains > DEV_GAINS || !volume_ok(volumes, D, n)) return LITHO_E_ARG;
-    if ((long long)volumes * n_gains * D > 65535) return LITHO_E_ARG;
-    if (!finite_pos(C) || !finite_pos(r_max) || !finite_pos(r_min) || !(q > 1.0) || std::isinf(q) || !(m_th >= 0.0) || !(m_th < 1.0) ||
-        !(surface_rate > 0.0) || !(surface_rate <= 1.0) || !finite_pos(surface_depth_nm) || !finite_pos(thickness_nm))
+    VolGains gains;
+    MackLaw law;
+    if (!image || !slowness || !volume_ok(volumes, D, n) || !make_gains(gains_host, n_gains, volumes, D, gains) || !finite_pos(C) ||
+        !make_mack(r_max, r_min, q, m_th, surface_rate, surface_depth_nm, thickness_nm, D, law))
         return LITHO_E_ARG;
-    DevGains gains;
-    memset(&gains, 0, sizeof(gains));
-    for (int i = 0; i < n_gains; ++i) {
-        if (!(gains_host[i] == gains_host[i])) return LITHO_E_ARG;
-        gains.g[i] = gains_host[i];
-    }
-    const double a = (q + 1.0) / (q - 1.0) * std::pow(1.0 - m_th, q);
-    DevSurface surface;
-    for (int d = 0; d < DEV_DMAX; ++d) {
-        const double z = thickness_nm * (d + 0.5) / D;
-        surface.f[d] = 1.0 - (1.0 - surface_rate) * std::exp(-z / surface_depth_nm);
-    }
     const int planes = volumes * D;
     const bool wide = (n & 3) == 0 && aligned16(image) && aligned16(slowness);
-    const dim3 grid(plane_blocks(n, wide ? 4 : 1), (unsigned)planes);
-    if (wide)
-        hipLaunchKernelGGL(k_develop_rate<4>, grid, dim3(256), 0, (hipStream_t)stream, image, slowness, planes, D, n, gains, n_gains, C,
-                           r_max * (a + 1.0), r_min, q, a, surface);
-    else
-        hipLaunchKernelGGL(k_develop_rate<1>, grid, dim3(256), 0, (hipStream_t)stream, image, slowness, planes, D, n, gains, n_gains, C,
-                           r_max * (a + 1.0), r_min, q, a, surface);
+    LAUNCH_PACKED(k_develop_rate, wide, n, planes, (hipStream_t)stream, image, slowness, planes, D, n, gains, n_gains, C, law.rmax_a1,
+                  law.rmin, law.q, law.a, law.surface);
     HIP_TRY(hipGetLastError());
     return LITHO_OK;
 }
@@ -382,7 +305,7 @@ int litho_develop_rate(const float* image, int volumes, int D, int n, const floa
 size_t litho_develop_work_bytes(int B, int D, int n, int max_iterations)
 {
     using namespace litho;
-    if (!volume_ok(B, D, n) || max_iterations < 1 || max_iterations > DEV_MAXIT) return 0;
+    if (!volume_ok(B, D, n) || max_iterations < 1 || max_iterations > VOL_MAXIT) return 0;
     return flag_bytes(max_iterations) + (size_t)B * D * n * n * sizeof(float);
 }
 
@@ -392,7 +315,7 @@ int litho_develop_time(const float* slowness, int B, int D, int n, double thickn
     using namespace litho;
     if (launches_host) *launches_host = 0;
     if (!slowness || !T || !work || !launches_host || !volume_ok(B, D, n)) return LITHO_E_ARG;
-    if (max_iterations < 1 || max_iterations > DEV_MAXIT || !finite_pos(thickness_nm) || !finite_pos(pixel_nm)) return LITHO_E_ARG;
+    if (max_iterations < 1 || max_iterations > VOL_MAXIT || !finite_pos(thickness_nm) || !finite_pos(pixel_nm)) return LITHO_E_ARG;
     const size_t vol_bytes = (size_t)B * D * n * n * sizeof(float), need = litho_develop_work_bytes(B, D, n, max_iterations);
     if (!aligned16(work) || overlap(T, vol_bytes, slowness, vol_bytes)) return LITHO_E_ARG;
     if (work_bytes < need) return LITHO_E_WORKSPACE;
@@ -407,41 +330,19 @@ int litho_develop_time(const float* slowness, int B, int D, int n, double thickn
     const size_t lds = (size_t)D * (DEV_TCELLS + DEV_SCELLS) * sizeof(float);
     if (lds > 64 * 1024) {                               // once per device: the worst case, D = 32
         static unsigned lds_done = 0;
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        const unsigned bit = 1u << (dev & 31);
-        if (!(__atomic_load_n(&lds_done, __ATOMIC_ACQUIRE) & bit)) {
-            HIP_TRY(hipFuncSetAttribute((const void*)k_develop_time, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)((size_t)DEV_DMAX * (DEV_TCELLS + DEV_SCELLS) * sizeof(float))));
-            __atomic_fetch_or(&lds_done, bit, __ATOMIC_RELEASE);
-        }
+        HIP_TRY(lds_opt_in(lds_done, (const void*)k_develop_time, (size_t)VOL_DMAX * (DEV_TCELLS + DEV_SCELLS) * sizeof(float)));
     }
-    HIP_TRY(hipMemsetAsync(flags, 0, flag_bytes(max_iterations), st));
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)T, 0x7f800000, cells, st));                    // +inf everywhere
-    const unsigned tiles = (unsigned)((n + DEV_TILE - 1) / DEV_TILE);
+    const unsigned tiles = (unsigned)((n + VOL_TILE - 1) / VOL_TILE);
     const dim3 grid(tiles, tiles, (unsigned)B);
-    int done = 0;
-    while (done < max_iterations) {
-        const int group = max_iterations - done < DEV_CHECK ? max_iterations - done : DEV_CHECK;
-        for (int j = 0; j < group; ++j) {
-            const int it = done + j;                     // launch `it` reads buf[it & 1] and writes the other
-            hipLaunchKernelGGL(k_develop_time, grid, dim3(256), lds, st, slowness, (const float*)buf[it & 1], buf[(it + 1) & 1], D, n,
-                               h, hz, wxy, wz, flags + it);
-        }
-        HIP_TRY(hipGetLastError());
-        int seen[DEV_CHECK] = {1, 1, 1, 1};
-        HIP_TRY(hipMemcpyAsync(seen, flags + done, (size_t)group * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (int j = 0; j < group; ++j) {
-            if (seen[j] == 0) {                          // this launch changed nothing: its output equals its input
-                *launches_host = done + j + 1;
-                return LITHO_OK;
-            }
-        }
-        done += group;
-    }
-    *launches_host = max_iterations;
-    return LITHO_E_NOCONV;
+    // launch `it` reads buf[it & 1] and writes the other
+    const int launches = iterate_until_unchanged(flags, max_iterations, st, [&](int it) {
+        hipLaunchKernelGGL(k_develop_time, grid, dim3(256), lds, st, slowness, (const float*)buf[it & 1], buf[(it + 1) & 1], D, n, h, hz,
+                           wxy, wz, flags + it);
+    });
+    if (launches < 0) return launches;
+    *launches_host = launches ? launches : max_iterations;
+    return launches ? LITHO_OK : LITHO_E_NOCONV;
 }
 
 int litho_developed_depth(const float* T, int B, int D, int n, double thickness_nm, double develop_time_s, float* depth, void* stream)
@@ -452,13 +353,7 @@ int litho_developed_depth(const float* T, int B, int D, int n, double thickness_
     const float thickness = (float)thickness_nm, hz = (float)(thickness_nm / D);
     if (!(hz > 0.f) || std::isinf(thickness)) return LITHO_E_ARG;
     const bool wide = (n & 3) == 0 && aligned16(T) && aligned16(depth);
-    const dim3 grid(plane_blocks(n, wide ? 4 : 1), (unsigned)B);
-    if (wide)
-        hipLaunchKernelGGL(k_developed_depth<4>, grid, dim3(256), 0, (hipStream_t)stream, T, depth, D, n, (float)develop_time_s, hz,
-                           thickness);
-    else
-        hipLaunchKernelGGL(k_developed_depth<1>, grid, dim3(256), 0, (hipStream_t)stream, T, depth, D, n, (float)develop_time_s, hz,
-                           thickness);
+    LAUNCH_PACKED(k_developed_depth, wide, n, B, (hipStream_t)stream, T, depth, D, n, (float)develop_time_s, hz, thickness);
     HIP_TRY(hipGetLastError());
     return LITHO_OK;
 }

@@ -13,7 +13,8 @@
 //   k_develop_scale     grad_s = lambda sigma, exactly 0 where the cell has no gradient
 //   k_develop_rate_vjp  the rate law of k_develop_rate / k_peb_rate backwards, double per cell, the gains summed inside
 // The pointwise kernels move four consecutive x per thread (16-byte accesses) when n is a multiple of 4 and the pointers are
-// 16-byte aligned, one otherwise.
+// 16-byte aligned, one otherwise.  The limits, the packs, the host predicates, the gains, the rate law (mack_slowness_dx, next to
+// the forward's mack_slowness) and the solver's host loop are resist_volume.hpp's, shared with develop.hip and peb.hip.
 //
 // Links.  Four fp32 per cell, (lx, ly, lz, sigma).  |l| is alpha on that axis; the sign carries the direction: positive when the
 // upwind cell is the lower-index neighbour (a tie of the two neighbours goes there), negative when it is the higher-index one.
@@ -36,63 +37,19 @@
 // written in that phase; halo cells are read-only: no race, no atomics.  Launches ping-pong lambda between two global buffers,
 // so no workgroup reads what another writes.  A cell "changed" when the new value's bit pattern differs from the old one (never
 // `!=`, which does not settle on a NaN); a thread that changed one stores 1 into the launch's own flag word with a plain store.
-// The host reads the flag words every DG_CHECK launches and stops at the first launch that changed nothing.  Every loop has a
+// The host reads the flag words every VOL_CHECK launches and stops at the first launch that changed nothing.  Every loop has a
 // trip count fixed by D; the launch count is capped by the caller.
 //
 // Determinism.  Each cell's final value is the fixed expression above on the final values of cells with strictly larger T.  By
 // induction from the sinks of the graph the bits depend on neither the tile schedule, nor the batch, nor the start value, nor
 // the launch at which the iteration stops.
-#include "engine_common.hpp"
-#include "../../include/litho_abbe.h"
-
-#include <cmath>
-#include <cstdint>
-#include <cstring>
+#include "resist_volume.hpp"
 
 namespace litho {
 
-static constexpr int DG_DMAX = 32, DG_GAINS = 64;
-static constexpr int DG_TILE = 16, DG_HALO = DG_TILE + 2, DG_INNER = 8, DG_CHECK = 4, DG_MAXIT = 65536;
-static constexpr int DG_HCELLS = DG_HALO * DG_HALO, DG_TCELLS = DG_TILE * DG_TILE;
+static constexpr int DG_HCELLS = VOL_HALO * VOL_HALO, DG_TCELLS = VOL_TILE * VOL_TILE;
 static constexpr size_t DG_PLANE_BYTES = (size_t)(3 * DG_HCELLS + DG_TCELLS) * sizeof(float);
-static_assert((size_t)DG_DMAX * DG_PLANE_BYTES <= 160 * 1024, "the tile of the deepest volume must fit a gfx950 workgroup's LDS");
-
-struct DgGains {
-    float g[DG_GAINS];
-};
-struct DgSurface {
-    double f[DG_DMAX];                                   // the surface-inhibition factor of plane d, from the host
-};
-
-template <int VEC>
-struct DgPack {
-    float v[VEC];
-};
-template <int VEC>
-__device__ __forceinline__ DgPack<VEC> dg_load(const float* p)
-{
-    DgPack<VEC> r;
-    if constexpr (VEC == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w;
-    } else {
-        r.v[0] = *p;
-    }
-    return r;
-}
-template <int VEC>
-__device__ __forceinline__ DgPack<VEC> dg_fill(float x)
-{
-    DgPack<VEC> r;
-    for (int v = 0; v < VEC; ++v) r.v[v] = x;
-    return r;
-}
-template <int VEC>
-__device__ __forceinline__ void dg_store(float* p, const DgPack<VEC>& r)
-{
-    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    else *p = r.v[0];
-}
+static_assert((size_t)VOL_DMAX * DG_PLANE_BYTES <= 160 * 1024, "the tile of the deepest volume must fit a gfx950 workgroup's LDS");
 
 // ---- 1. the links of one cell.  s, Ti: the cell's slowness and stored T; (xm, xp), (ym, yp), (zm, zp): the stored T of the two
 // neighbours per axis, +inf where there is none; top: plane 0, whose z axis is the resist top (a = 0 at hz / 2).  The branch and
@@ -163,11 +120,11 @@ __global__ __launch_bounds__(256) void k_develop_links(const float* __restrict__
     const int row = (int)(e / n), col = (int)(e % n);
     const size_t at = (size_t)p * plane_elems + e;
     const float inf = INFINITY;
-    const DgPack<VEC> s = dg_load<VEC>(slow + at), c = dg_load<VEC>(T + at);
-    const DgPack<VEC> ym = row > 0 ? dg_load<VEC>(T + at - n) : dg_fill<VEC>(inf);
-    const DgPack<VEC> yp = row + 1 < n ? dg_load<VEC>(T + at + n) : dg_fill<VEC>(inf);
-    const DgPack<VEC> zm = d > 0 ? dg_load<VEC>(T + at - plane_elems) : dg_fill<VEC>(inf);
-    const DgPack<VEC> zp = d + 1 < D ? dg_load<VEC>(T + at + plane_elems) : dg_fill<VEC>(inf);
+    const Pack<VEC> s = load_pack<VEC>(slow + at), c = load_pack<VEC>(T + at);
+    const Pack<VEC> ym = row > 0 ? load_pack<VEC>(T + at - n) : fill_pack<VEC>(inf);
+    const Pack<VEC> yp = row + 1 < n ? load_pack<VEC>(T + at + n) : fill_pack<VEC>(inf);
+    const Pack<VEC> zm = d > 0 ? load_pack<VEC>(T + at - plane_elems) : fill_pack<VEC>(inf);
+    const Pack<VEC> zp = d + 1 < D ? load_pack<VEC>(T + at + plane_elems) : fill_pack<VEC>(inf);
     const float left = col > 0 ? T[at - 1] : inf, right = col + VEC < n ? T[at + VEC] : inf;
     for (int v = 0; v < VEC; ++v) {
         const float xm = v > 0 ? c.v[v - 1] : left, xp = v + 1 < VEC ? c.v[v + 1] : right;
@@ -186,10 +143,10 @@ __device__ __forceinline__ bool gather_cell(float* lam, const float* lx, const f
     if (w < 0.f) acc = acc + (-w) * lam[-1];
     w = lx[1];
     if (w > 0.f) acc = acc + w * lam[1];
-    w = ly[-DG_HALO];
-    if (w < 0.f) acc = acc + (-w) * lam[-DG_HALO];
-    w = ly[DG_HALO];
-    if (w > 0.f) acc = acc + w * lam[DG_HALO];
+    w = ly[-VOL_HALO];
+    if (w < 0.f) acc = acc + (-w) * lam[-VOL_HALO];
+    w = ly[VOL_HALO];
+    if (w > 0.f) acc = acc + w * lam[VOL_HALO];
     if (d > 0) {
         w = lz[-DG_TCELLS];
         if (w < 0.f) acc = acc + (-w) * lam[-DG_HCELLS];
@@ -213,14 +170,14 @@ __global__ __launch_bounds__(256) void k_develop_time_vjp(const float* __restric
     float* ly = lx + D * DG_HCELLS;                      // [D][18][18]
     float* lz = ly + D * DG_HCELLS;                      // [D][16][16]  tile
     const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * DG_TILE, y0 = blockIdx.y * DG_TILE;
+    const int x0 = blockIdx.x * VOL_TILE, y0 = blockIdx.y * VOL_TILE;
     const size_t plane_elems = (size_t)n * n;
     const size_t vol = (size_t)blockIdx.z * D * plane_elems;
     // the tile: all three links and lambda; a tile cell outside the grid has no links and lambda 0
     for (int i = tid; i < D * DG_TCELLS; i += 256) {
-        const int d = i / DG_TCELLS, r = i - d * DG_TCELLS, ty = r / DG_TILE, tx = r - ty * DG_TILE;
+        const int d = i / DG_TCELLS, r = i - d * DG_TCELLS, ty = r / VOL_TILE, tx = r - ty * VOL_TILE;
         const int gy = y0 + ty, gx = x0 + tx;
-        const int q = d * DG_HCELLS + (ty + 1) * DG_HALO + tx + 1;
+        const int q = d * DG_HCELLS + (ty + 1) * VOL_HALO + tx + 1;
         float4 L = make_float4(0.f, 0.f, 0.f, 0.f);
         float l0 = 0.f;
         if (gy < n && gx < n) {
@@ -234,13 +191,13 @@ __global__ __launch_bounds__(256) void k_develop_time_vjp(const float* __restric
         lz[i] = L.z;
     }
     // the 64 edge cells of the halo per plane: lambda and the one link that can point into the tile
-    for (int i = tid; i < D * 4 * DG_TILE; i += 256) {
-        const int d = i / (4 * DG_TILE), r = i - d * (4 * DG_TILE), side = r / DG_TILE, k = r - side * DG_TILE;
+    for (int i = tid; i < D * 4 * VOL_TILE; i += 256) {
+        const int d = i / (4 * VOL_TILE), r = i - d * (4 * VOL_TILE), side = r / VOL_TILE, k = r - side * VOL_TILE;
         int hy, hx;                                      // position in the [18][18] plane
         if (side == 0) { hy = k + 1; hx = 0; }
-        else if (side == 1) { hy = k + 1; hx = DG_HALO - 1; }
+        else if (side == 1) { hy = k + 1; hx = VOL_HALO - 1; }
         else if (side == 2) { hy = 0; hx = k + 1; }
-        else { hy = DG_HALO - 1; hx = k + 1; }
+        else { hy = VOL_HALO - 1; hx = k + 1; }
         const int gy = y0 + hy - 1, gx = x0 + hx - 1;
         float l0 = 0.f, w = 0.f;
         if (gy >= 0 && gy < n && gx >= 0 && gx < n) {
@@ -248,20 +205,20 @@ __global__ __launch_bounds__(256) void k_develop_time_vjp(const float* __restric
             l0 = lin[cell];
             w = links[4 * cell + (side < 2 ? 0 : 1)];
         }
-        const int q = d * DG_HCELLS + hy * DG_HALO + hx;
+        const int q = d * DG_HCELLS + hy * VOL_HALO + hx;
         lam[q] = l0;
         if (side < 2) lx[q] = w;
         else ly[q] = w;
     }
     __syncthreads();
     // compute threads: 128, row = tid / 8, the columns of this phase's colour in that row
-    const int row = (tid >> 3) & (DG_TILE - 1), pair = tid & 7;
+    const int row = (tid >> 3) & (VOL_TILE - 1), pair = tid & 7;
     bool changed = false;
-    for (int round = 0; round < DG_INNER; ++round) {
+    for (int round = 0; round < VOL_INNER; ++round) {
         for (int colour = 0; colour < 2; ++colour) {
             const int col = 2 * pair + ((row + colour) & 1);
             if (tid < 128 && y0 + row < n && x0 + col < n) {
-                const int q = (row + 1) * DG_HALO + (col + 1), t = row * DG_TILE + col;
+                const int q = (row + 1) * VOL_HALO + (col + 1), t = row * VOL_TILE + col;
                 const float* gc = g + vol + (size_t)(y0 + row) * n + (x0 + col);     // the column's cotangent, from global memory
                 for (int d = D - 1; d >= 0; --d)
                     changed |= gather_cell(lam + d * DG_HCELLS + q, lx + d * DG_HCELLS + q, ly + d * DG_HCELLS + q,
@@ -274,10 +231,10 @@ __global__ __launch_bounds__(256) void k_develop_time_vjp(const float* __restric
         }
     }
     for (int i = tid; i < D * DG_TCELLS; i += 256) {
-        const int d = i / DG_TCELLS, r = i - d * DG_TCELLS, ty = r / DG_TILE, tx = r - ty * DG_TILE;
+        const int d = i / DG_TCELLS, r = i - d * DG_TCELLS, ty = r / VOL_TILE, tx = r - ty * VOL_TILE;
         const int gy = y0 + ty, gx = x0 + tx;
         if (gy < n && gx < n)
-            lout[vol + (size_t)d * plane_elems + (size_t)gy * n + gx] = lam[d * DG_HCELLS + (ty + 1) * DG_HALO + tx + 1];
+            lout[vol + (size_t)d * plane_elems + (size_t)gy * n + gx] = lam[d * DG_HCELLS + (ty + 1) * VOL_HALO + tx + 1];
     }
     if (changed) *flag = 1;
 }
@@ -291,22 +248,22 @@ __global__ __launch_bounds__(256) void k_develop_scale(const float* __restrict__
     const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
     if (e >= plane_elems) return;
     const size_t at = (size_t)blockIdx.y * plane_elems + e;
-    const DgPack<VEC> l = dg_load<VEC>(lambda + at);
-    DgPack<VEC> r;
+    const Pack<VEC> l = load_pack<VEC>(lambda + at);
+    Pack<VEC> r;
     for (int v = 0; v < VEC; ++v) {
         const float sigma = links[4 * (at + v) + 3];
         r.v[v] = sigma > 0.f ? l.v[v] * sigma : 0.f;
     }
-    dg_store<VEC>(out + at, r);
+    store_pack<VEC>(out + at, r);
 }
 
-// ---- 4. the rate law backwards: m = exp(-(kappa g) x), X = (1 - m)^q, r = (R X / (a + X) + rmin) f, s = 1 / r;
-// ds/dx = -s^2 f R a / (a + X)^2 q (1 - m)^(q - 1) (kappa g) m.  A wall (1 - m negative or NaN) contributes 0.
+// ---- 4. the rate law backwards: m = exp(-(kappa g) x), b = 1 - m, db/dx = (kappa g) m, ds/dx from mack_slowness_dx
+// (resist_volume.hpp), summed over the gains.  A wall (1 - m negative or NaN) contributes 0.
 template <int VEC>
 __global__ __launch_bounds__(256) void k_develop_rate_vjp(const float* __restrict__ x, const float* __restrict__ grad_s,
-                                                          float* __restrict__ grad_x, int planes, int D, int n, const DgGains gains,
+                                                          float* __restrict__ grad_x, int planes, int D, int n, const VolGains gains,
                                                           int n_gains, double kappa, double rmax_a1, double rmin, double q, double a,
-                                                          const DgSurface surface)
+                                                          const VolSurface surface)
 {
     const long long plane_elems = (long long)n * n;
     const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
@@ -314,41 +271,23 @@ __global__ __launch_bounds__(256) void k_develop_rate_vjp(const float* __restric
     const int p = blockIdx.y;
     const double f = surface.f[p % D];
     const size_t at = (size_t)p * plane_elems + e;
-    const DgPack<VEC> xv = dg_load<VEC>(x + at);
+    const Pack<VEC> xv = load_pack<VEC>(x + at);
     double acc[VEC];
     for (int v = 0; v < VEC; ++v) acc[v] = 0.0;
     for (int gi = 0; gi < n_gains; ++gi) {
         const double kg = kappa * (double)gains.g[gi];
-        const DgPack<VEC> gs = dg_load<VEC>(grad_s + ((size_t)gi * planes + p) * plane_elems + e);
+        const Pack<VEC> gs = load_pack<VEC>(grad_s + ((size_t)gi * planes + p) * plane_elems + e);
         for (int v = 0; v < VEC; ++v) {
             const double m = exp(-(kg * (double)xv.v[v]));
             const double b = 1.0 - m;
             if (!(b >= 0.0)) continue;                   // a wall
-            const double X = pow(b, q);
-            const double r = (rmax_a1 * X / (a + X) + rmin) * f;
-            const double s = 1.0 / r;
-            const double dX = q * pow(b, q - 1.0) * (kg * m);
-            acc[v] += (double)gs.v[v] * (-(s * s) * f * (rmax_a1 * a / ((a + X) * (a + X))) * dX);
+            acc[v] += (double)gs.v[v] * mack_slowness_dx(b, kg * m, rmax_a1, rmin, q, a, f);
         }
     }
-    DgPack<VEC> out;
+    Pack<VEC> out;
     for (int v = 0; v < VEC; ++v) out.v[v] = (float)acc[v];
-    dg_store<VEC>(grad_x + at, out);
+    store_pack<VEC>(grad_x + at, out);
 }
-
-static bool dg_aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static bool dg_overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + b_bytes && pb < pa + a_bytes;
-}
-static bool dg_finite_pos(double v) { return v > 0.0 && !std::isinf(v); }
-static unsigned dg_plane_blocks(int n, int vec) { return (unsigned)(((long long)n * n / vec + 255) / 256); }
-static bool dg_volume_ok(int B, int D, int n)
-{
-    return B >= 1 && D >= 1 && D <= DG_DMAX && n >= 1 && n <= 16384 && (long long)B * D <= 65535;
-}
-static size_t dg_flag_bytes(int max_iterations) { return ((size_t)max_iterations * sizeof(int) + 255) & ~(size_t)255; }
 
 }  // namespace litho
 
@@ -357,8 +296,8 @@ extern "C" {
 size_t litho_develop_vjp_work_bytes(int B, int D, int n, int max_iterations)
 {
     using namespace litho;
-    if (!dg_volume_ok(B, D, n) || max_iterations < 1 || max_iterations > DG_MAXIT) return 0;
-    return dg_flag_bytes(max_iterations) + 5 * (size_t)B * D * n * n * sizeof(float);     // flags, links (4), lambda (1)
+    if (!volume_ok(B, D, n) || max_iterations < 1 || max_iterations > VOL_MAXIT) return 0;
+    return flag_bytes(max_iterations) + 5 * (size_t)B * D * n * n * sizeof(float);     // flags, links (4), lambda (1)
 }
 
 int litho_develop_time_vjp(const float* slowness, const float* T, const float* grad_T, int B, int D, int n, double thickness_nm,
@@ -367,75 +306,47 @@ int litho_develop_time_vjp(const float* slowness, const float* T, const float* g
 {
     using namespace litho;
     if (launches_host) *launches_host = 0;
-    if (!slowness || !T || !grad_T || !grad_slowness || !work || !launches_host || !dg_volume_ok(B, D, n)) return LITHO_E_ARG;
-    if (max_iterations < 1 || max_iterations > DG_MAXIT || !dg_finite_pos(thickness_nm) || !dg_finite_pos(pixel_nm)) return LITHO_E_ARG;
+    if (!slowness || !T || !grad_T || !grad_slowness || !work || !launches_host || !volume_ok(B, D, n)) return LITHO_E_ARG;
+    if (max_iterations < 1 || max_iterations > VOL_MAXIT || !finite_pos(thickness_nm) || !finite_pos(pixel_nm)) return LITHO_E_ARG;
     const size_t cells = (size_t)B * D * n * n, vol_bytes = cells * sizeof(float);
     const size_t need = litho_develop_vjp_work_bytes(B, D, n, max_iterations);
-    if (!dg_aligned16(work)) return LITHO_E_ARG;
+    if (!aligned16(work)) return LITHO_E_ARG;
     const void* in[3] = {slowness, T, grad_T};
     for (int i = 0; i < 3; ++i)
-        if (dg_overlap(grad_slowness, vol_bytes, in[i], vol_bytes)) return LITHO_E_ARG;     // lambda lives in the output meanwhile
+        if (overlap(grad_slowness, vol_bytes, in[i], vol_bytes)) return LITHO_E_ARG;     // lambda lives in the output meanwhile
     if (work_bytes < need) return LITHO_E_WORKSPACE;
     for (int i = 0; i < 3; ++i)
-        if (dg_overlap(work, need, in[i], vol_bytes)) return LITHO_E_ARG;
-    if (dg_overlap(work, need, grad_slowness, vol_bytes)) return LITHO_E_ARG;
+        if (overlap(work, need, in[i], vol_bytes)) return LITHO_E_ARG;
+    if (overlap(work, need, grad_slowness, vol_bytes)) return LITHO_E_ARG;
     // the geometry as litho_develop_time rounds it
     const float hf = (float)pixel_nm, hzf = (float)(thickness_nm / D);
     const float wxy = 1.f / (hf * hf), wz = 1.f / (hzf * hzf);
     if (!(hf > 0.f) || !(hzf > 0.f) || std::isinf(wxy) || std::isinf(wz) || !(wxy > 0.f) || !(wz > 0.f)) return LITHO_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     int* flags = (int*)work;
-    float* links = (float*)((char*)work + dg_flag_bytes(max_iterations));
+    float* links = (float*)((char*)work + flag_bytes(max_iterations));
     float* buf[2] = {links + 4 * cells, grad_slowness};
     const size_t lds = (size_t)D * DG_PLANE_BYTES;
     if (lds > 64 * 1024) {                               // once per device: the worst case, D = 32
         static unsigned lds_done = 0;
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        const unsigned bit = 1u << (dev & 31);
-        if (!(__atomic_load_n(&lds_done, __ATOMIC_ACQUIRE) & bit)) {
-            HIP_TRY(hipFuncSetAttribute((const void*)k_develop_time_vjp, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)((size_t)DG_DMAX * DG_PLANE_BYTES)));
-            __atomic_fetch_or(&lds_done, bit, __ATOMIC_RELEASE);
-        }
+        HIP_TRY(lds_opt_in(lds_done, (const void*)k_develop_time_vjp, (size_t)VOL_DMAX * DG_PLANE_BYTES));
     }
-    HIP_TRY(hipMemsetAsync(flags, 0, dg_flag_bytes(max_iterations), st));
     HIP_TRY(hipMemsetAsync(buf[0], 0, vol_bytes, st));
-    const bool wide = (n & 3) == 0 && dg_aligned16(slowness) && dg_aligned16(T) && dg_aligned16(grad_slowness);
-    const dim3 pgrid(dg_plane_blocks(n, wide ? 4 : 1), (unsigned)(B * D));
-    if (wide)
-        hipLaunchKernelGGL(k_develop_links<4>, pgrid, dim3(256), 0, st, slowness, T, (float4*)links, D, n, (double)hf, (double)hzf);
-    else
-        hipLaunchKernelGGL(k_develop_links<1>, pgrid, dim3(256), 0, st, slowness, T, (float4*)links, D, n, (double)hf, (double)hzf);
+    const bool wide = (n & 3) == 0 && aligned16(slowness) && aligned16(T) && aligned16(grad_slowness);
+    LAUNCH_PACKED(k_develop_links, wide, n, B * D, st, slowness, T, (float4*)links, D, n, (double)hf, (double)hzf);
     HIP_TRY(hipGetLastError());
-    const unsigned tiles = (unsigned)((n + DG_TILE - 1) / DG_TILE);
+    const unsigned tiles = (unsigned)((n + VOL_TILE - 1) / VOL_TILE);
     const dim3 grid(tiles, tiles, (unsigned)B);
-    int done = 0, launches = 0;
-    while (done < max_iterations && !launches) {
-        const int group = max_iterations - done < DG_CHECK ? max_iterations - done : DG_CHECK;
-        for (int j = 0; j < group; ++j) {
-            const int it = done + j;                     // launch `it` reads buf[it & 1] and writes the other
-            hipLaunchKernelGGL(k_develop_time_vjp, grid, dim3(256), lds, st, (const float*)links, grad_T, (const float*)buf[it & 1],
-                               buf[(it + 1) & 1], D, n, flags + it);
-        }
-        HIP_TRY(hipGetLastError());
-        int seen[DG_CHECK] = {1, 1, 1, 1};
-        HIP_TRY(hipMemcpyAsync(seen, flags + done, (size_t)group * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        for (int j = 0; j < group && !launches; ++j)
-            if (seen[j] == 0) launches = done + j + 1;   // this launch changed nothing: its output equals its input
-        done += group;
-    }
-    if (!launches) {
-        *launches_host = max_iterations;
-        return LITHO_E_NOCONV;
-    }
-    *launches_host = launches;
+    // launch `it` reads buf[it & 1] and writes the other
+    const int launches = iterate_until_unchanged(flags, max_iterations, st, [&](int it) {
+        hipLaunchKernelGGL(k_develop_time_vjp, grid, dim3(256), lds, st, (const float*)links, grad_T, (const float*)buf[it & 1],
+                           buf[(it + 1) & 1], D, n, flags + it);
+    });
+    if (launches < 0) return launches;
+    *launches_host = launches ? launches : max_iterations;
+    if (!launches) return LITHO_E_NOCONV;
     // both buffers hold the fixed point: read the workspace's, write the output
-    if (wide)
-        hipLaunchKernelGGL(k_develop_scale<4>, pgrid, dim3(256), 0, st, (const float*)buf[0], (const float*)links, grad_slowness, n);
-    else
-        hipLaunchKernelGGL(k_develop_scale<1>, pgrid, dim3(256), 0, st, (const float*)buf[0], (const float*)links, grad_slowness, n);
+    LAUNCH_PACKED(k_develop_scale, wide, n, B * D, st, (const float*)buf[0], (const float*)links, grad_slowness, n);
     HIP_TRY(hipGetLastError());
     return LITHO_OK;
 }
@@ -445,35 +356,17 @@ int litho_develop_rate_vjp(const float* x, int volumes, int D, int n, const floa
                            const float* grad_slowness, float* grad_x, void* stream)
 {
     using namespace litho;
-    if (!x || !gains_host || !grad_slowness || !grad_x || n_gains < 1 || n_gains > DG_GAINS || !dg_volume_ok(volumes, D, n))
-        return LITHO_E_ARG;
-    if ((long long)volumes * n_gains * D > 65535) return LITHO_E_ARG;
-    if (!dg_finite_pos(kappa) || !dg_finite_pos(r_max) || !dg_finite_pos(r_min) || !(q > 1.0) || std::isinf(q) || !(m_th >= 0.0) ||
-        !(m_th < 1.0) || !(surface_rate > 0.0) || !(surface_rate <= 1.0) || !dg_finite_pos(surface_depth_nm) || !dg_finite_pos(thickness_nm))
+    VolGains gains;
+    MackLaw law;
+    if (!x || !grad_slowness || !grad_x || !volume_ok(volumes, D, n) || !make_gains(gains_host, n_gains, volumes, D, gains) ||
+        !finite_pos(kappa) || !make_mack(r_max, r_min, q, m_th, surface_rate, surface_depth_nm, thickness_nm, D, law))
         return LITHO_E_ARG;
     const size_t x_bytes = (size_t)volumes * D * n * n * sizeof(float);
-    if (dg_overlap(grad_x, x_bytes, x, x_bytes) || dg_overlap(grad_x, x_bytes, grad_slowness, x_bytes * n_gains)) return LITHO_E_ARG;
-    DgGains gains;
-    memset(&gains, 0, sizeof(gains));
-    for (int i = 0; i < n_gains; ++i) {
-        if (!(gains_host[i] == gains_host[i])) return LITHO_E_ARG;
-        gains.g[i] = gains_host[i];
-    }
-    const double a = (q + 1.0) / (q - 1.0) * std::pow(1.0 - m_th, q);
-    DgSurface surface;
-    for (int d = 0; d < DG_DMAX; ++d) {
-        const double z = thickness_nm * (d + 0.5) / D;
-        surface.f[d] = 1.0 - (1.0 - surface_rate) * std::exp(-z / surface_depth_nm);
-    }
+    if (overlap(grad_x, x_bytes, x, x_bytes) || overlap(grad_x, x_bytes, grad_slowness, x_bytes * n_gains)) return LITHO_E_ARG;
     const int planes = volumes * D;
-    const bool wide = (n & 3) == 0 && dg_aligned16(x) && dg_aligned16(grad_slowness) && dg_aligned16(grad_x);
-    const dim3 grid(dg_plane_blocks(n, wide ? 4 : 1), (unsigned)planes);
-    if (wide)
-        hipLaunchKernelGGL(k_develop_rate_vjp<4>, grid, dim3(256), 0, (hipStream_t)stream, x, grad_slowness, grad_x, planes, D, n, gains,
-                           n_gains, kappa, r_max * (a + 1.0), r_min, q, a, surface);
-    else
-        hipLaunchKernelGGL(k_develop_rate_vjp<1>, grid, dim3(256), 0, (hipStream_t)stream, x, grad_slowness, grad_x, planes, D, n, gains,
-                           n_gains, kappa, r_max * (a + 1.0), r_min, q, a, surface);
+    const bool wide = (n & 3) == 0 && aligned16(x) && aligned16(grad_slowness) && aligned16(grad_x);
+    LAUNCH_PACKED(k_develop_rate_vjp, wide, n, planes, (hipStream_t)stream, x, grad_slowness, grad_x, planes, D, n, gains, n_gains, kappa,
+                  law.rmax_a1, law.rmin, law.q, law.a, law.surface);
     HIP_TRY(hipGetLastError());
     return LITHO_OK;
 }

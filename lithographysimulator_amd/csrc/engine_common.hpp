@@ -12,6 +12,10 @@ void note_kernel(int pass, const char* fmt, int a0 = 0, int a1 = 0, int a2 = 0, 
 // Compute units of the CURRENT device (hipDeviceAttributeMultiprocessorCount, cached per device; 256 on an MI355X in
 // SPX mode, 32 per partition in CPX): the launch planners size their grids in whole rounds of it.
 int device_cus();
+// Opts `kernel` in to `bytes` of dynamic LDS (hipFuncAttributeMaxDynamicSharedMemorySize; launches above 64 KiB need it) once
+// per device instead of once per launch.  `done` is the call site's own static word for this kernel, zero-initialised: bit d is
+// set once the CURRENT device d has been served.
+hipError_t lds_opt_in(unsigned& done, const void* kernel, size_t bytes);
 }  // namespace litho
 
 #define HIP_TRY(expr)                                   \

@@ -875,14 +875,7 @@ int litho_postprocess_resist_diffused(const float* raw, int planes, int pn, doub
     const size_t lds = diff_lds_bytes(R);
     if (lds > 64 * 1024) {                           // once per device: the worst case, R = DIFF_RMAX
         static unsigned lds_done = 0;
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        const unsigned bit = 1u << (dev & 31);
-        if (!(__atomic_load_n(&lds_done, __ATOMIC_ACQUIRE) & bit)) {
-            HIP_TRY(hipFuncSetAttribute((const void*)k_postprocess_diffused, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)diff_lds_bytes(DIFF_RMAX)));
-            __atomic_fetch_or(&lds_done, bit, __ATOMIC_RELEASE);
-        }
+        HIP_TRY(lds_opt_in(lds_done, (const void*)k_postprocess_diffused, diff_lds_bytes(DIFF_RMAX)));
     }
     hipLaunchKernelGGL(k_postprocess_diffused, dim3((n_out + DIFF_TX - 1) / DIFF_TX, (n_out + DIFF_TY - 1) / DIFF_TY, planes),
                        dim3(256), lds, st, raw, pn, ns, pW, n_out, rs, taps, R, out, (float)gain, (float)threshold,

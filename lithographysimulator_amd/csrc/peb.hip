@@ -13,7 +13,9 @@
 //   k_peb_expose_vjp  gI = sum_g (C g) exp(-(C g) I) gh0[g] in double per cell
 // The arithmetic of a step is peb_step and nothing else: both bake kernels call it with the same inputs in the same order, so
 // the bits of a bake do not depend on how its steps are cut into launches.  expose and rate move four consecutive x per thread
-// (16-byte accesses) when n is a multiple of 4 and the pointers are 16-byte aligned, one otherwise.
+// (16-byte accesses) when n is a multiple of 4 and the pointers are 16-byte aligned, one otherwise.  The limits, the packs, the
+// host predicates, the gains and Mack's rate law are resist_volume.hpp's, shared with develop.hip and develop_grad.hip; the three
+// kernels that take one cell per thread (direct, taped, adjoint) get the cell and its six clamped neighbour offsets from peb_cell.
 //
 // k_peb_fused.  A workgroup owns a 16 x 16 lateral tile with all D planes.  It loads h and q of the tile and an s-cell lateral
 // halo into LDS, W = 16 + 2 s cells on a side; a cell beyond the grid is read from its mirror image (mirror_index, folding as
@@ -23,16 +25,11 @@
 // step and after s steps is the tile.  The amplification integral a is kept for the tile's own cells only, in LDS.  LDS:
 // D (4 W^2 + 256) floats.  Launches ping-pong h and q between the outputs and the caller's workspace; a is updated in place
 // by the one thread that owns the cell.  No workgroup reads what another writes in the same launch; no atomics.
-#include "engine_common.hpp"
-#include "../../include/litho_abbe.h"
-
-#include <cmath>
-#include <cstdint>
-#include <cstring>
+#include "resist_volume.hpp"
 
 namespace litho {
 
-static constexpr int PEB_DMAX = 32, PEB_GAINS = 64, PEB_TILE = 16, PEB_SMAX = 4, PEB_MAXSTEPS = 65536;
+static constexpr int PEB_SMAX = 4, PEB_MAXSTEPS = 65536;  // bake steps per launch, per bake
 static constexpr size_t PEB_LDS_MAX = 160 * 1024;         // what one workgroup can have on gfx950
 // The automatic choice of steps per launch takes the largest s <= PEB_SMAX whose LDS fits this budget, else the direct kernel.
 // It started at 64 KiB (two workgroups per CU of 160 KiB) and the first timing (scripts/peb_time.py, LABNOTES: 2048^2, S = 32)
@@ -41,12 +38,6 @@ static constexpr size_t PEB_LDS_MAX = 160 * 1024;         // what one workgroup 
 // index arithmetic and LDS traffic.  Until the fused kernel wins somewhere, the automatic choice is the direct kernel.
 static constexpr size_t PEB_LDS_BUDGET = 0;
 
-struct PebGains {
-    float g[PEB_GAINS];
-};
-struct PebSurface {
-    double f[PEB_DMAX];                                   // the surface-inhibition factor of plane d, from the host
-};
 // what one bake step needs, fp32 as the kernels use it; rides in the kernel arguments
 struct PebStep {
     float lxy_h, lz_h, lxy_q, lz_q;                       // lambda = D_s dt / spacing^2 per species and direction
@@ -57,42 +48,39 @@ struct PebNb {
     float w, e, s, n, u, d;
 };
 
-template <int VEC>
-struct Pack {
-    float v[VEC];
+// A thread's cell in the kernels that take one cell per thread (grid.x covers the n^2 cells of a plane, grid.y the B D planes):
+// its index in the batch and the offsets to its six neighbours.  A neighbour outside the grid is the cell's mirror image: the
+// cell itself, offset 0.
+struct PebCell {
+    size_t at;
+    long long w, e, s, n, u, d;
 };
-template <int VEC>
-__device__ __forceinline__ Pack<VEC> load_pack(const float* p)
+__device__ __forceinline__ bool peb_cell(int D, int n, PebCell& c)          // false: this thread has no cell
 {
-    Pack<VEC> r;
-    if constexpr (VEC == 4) {
-        const float4 q = *reinterpret_cast<const float4*>(p);
-        r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w;
-    } else {
-        r.v[0] = *p;
-    }
-    return r;
+    const long long plane_elems = (long long)n * n;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (e >= plane_elems) return false;
+    const int p = blockIdx.y, d = p % D, row = (int)(e / n), col = (int)(e - (long long)row * n);
+    c.at = (size_t)p * plane_elems + e;
+    c.w = col > 0 ? -1 : 0;
+    c.e = col + 1 < n ? 1 : 0;
+    c.s = row > 0 ? -(long long)n : 0;
+    c.n = row + 1 < n ? n : 0;
+    c.u = d > 0 ? -plane_elems : 0;
+    c.d = d + 1 < D ? plane_elems : 0;
+    return true;
 }
-template <int VEC>
-__device__ __forceinline__ void store_pack(float* p, const Pack<VEC>& r)
+// the six neighbours of the cell that `here` points at
+__device__ __forceinline__ PebNb peb_around(const float* here, const PebCell& c)
 {
-    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
-    else *p = r.v[0];
-}
-
-// index -1 - k <-> k and n + k <-> n - 1 - k, repeated as needed
-__host__ __device__ __forceinline__ int mirror_index(int i, int n)
-{
-    int m = i % (2 * n);
-    if (m < 0) m += 2 * n;
-    return m < n ? m : 2 * n - 1 - m;
+    return PebNb{here[c.w], here[c.e], here[c.s], here[c.n], here[c.u], here[c.d]};
 }
 
 // ---- 1. exposure: h0 = 1 - exp(-(C g) I), NaN where that is negative or NaN (litho_develop_rate's convention).  Double per
 // cell, rounded once.  grid.y: the F D planes of the image.
 template <int VEC>
 __global__ __launch_bounds__(256) void k_peb_expose(const float* __restrict__ image, float* __restrict__ out, int planes, int n,
-                                                    const PebGains gains, int n_gains, double C)
+                                                    const VolGains gains, int n_gains, double C)
 {
     const long long plane_elems = (long long)n * n;
     const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
@@ -139,20 +127,14 @@ __global__ __launch_bounds__(256) void k_peb_direct(const float* __restrict__ h_
                                                     float* __restrict__ h_out, float* __restrict__ q_out, float* __restrict__ a_io,
                                                     int D, int n, const PebStep P)
 {
-    const long long plane_elems = (long long)n * n;
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= plane_elems) return;
-    const int p = blockIdx.y, d = p % D, row = (int)(e / n), col = (int)(e - (long long)row * n);
-    const size_t at = (size_t)p * plane_elems + e;
-    // a neighbour outside the grid is the cell's mirror image: the cell itself
-    const long long w = col > 0 ? -1 : 0, ea = col + 1 < n ? 1 : 0, s = row > 0 ? -(long long)n : 0, nn = row + 1 < n ? n : 0;
-    const long long u = d > 0 ? -plane_elems : 0, dn = d + 1 < D ? plane_elems : 0;
-    auto around = [&](const float* c) -> PebNb { return PebNb{c[w], c[ea], c[s], c[nn], c[u], c[dn]}; };
+    PebCell c;
+    if (!peb_cell(D, n, c)) return;
+    const size_t at = c.at;
     const bool first = q_in == nullptr;
     const float h = h_in[at], q = first ? q0 : q_in[at];
     float a = first ? 0.f : a_io[at], h_new, q_new, hd, qd;
-    peb_step(P, h, q, [&] { return around(h_in + at); }, [&] { return first ? PebNb{q0, q0, q0, q0, q0, q0} : around(q_in + at); }, h_new,
-             q_new, a, hd, qd);
+    peb_step(P, h, q, [&] { return peb_around(h_in + at, c); },
+             [&] { return first ? PebNb{q0, q0, q0, q0, q0, q0} : peb_around(q_in + at, c); }, h_new, q_new, a, hd, qd);
     h_out[at] = h_new;
     q_out[at] = q_new;
     a_io[at] = a;
@@ -164,14 +146,14 @@ __global__ __launch_bounds__(256) void k_peb_fused(const float* __restrict__ h_i
                                                    int D, int n, int s, const PebStep P)
 {
     extern __shared__ __attribute__((aligned(16))) float peb_lds[];
-    const int W = PEB_TILE + 2 * s, WW = W * W, cells = D * WW;
+    const int W = VOL_TILE + 2 * s, WW = W * W, cells = D * WW;
     float* hc = peb_lds;                                  // [D][W][W]  the current copy of h, tile + halo
     float* hn = hc + cells;                               //            the next one
     float* qc = hn + cells;
     float* qn = qc + cells;
     float* al = qn + cells;                               // [D][16][16] a of the tile
     const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * PEB_TILE, y0 = blockIdx.y * PEB_TILE;
+    const int x0 = blockIdx.x * VOL_TILE, y0 = blockIdx.y * VOL_TILE;
     const size_t plane_elems = (size_t)n * n;
     const size_t vol = (size_t)blockIdx.z * D * plane_elems;
     const bool first = q_in == nullptr;
@@ -195,8 +177,8 @@ __global__ __launch_bounds__(256) void k_peb_fused(const float* __restrict__ h_i
             const int up = d > 0 ? -WW : 0, dn = d + 1 < D ? WW : 0;
             auto around = [&](const float* b) -> PebNb { return PebNb{b[c - 1], b[c + 1], b[c - W], b[c + W], b[c + up], b[c + dn]}; };
             const int ty = ly - s, tx = lx - s;
-            const bool mine = ty >= 0 && ty < PEB_TILE && tx >= 0 && tx < PEB_TILE;
-            const int ai = d * 256 + ty * PEB_TILE + tx;
+            const bool mine = ty >= 0 && ty < VOL_TILE && tx >= 0 && tx < VOL_TILE;
+            const int ai = d * 256 + ty * VOL_TILE + tx;
             float h_new, q_new, hd, qd, a = mine ? al[ai] : 0.f;          // a halo cell's a is not kept
             peb_step(P, hc[c], qc[c], [&] { return around(hc); }, [&] { return around(qc); }, h_new, q_new, a, hd, qd);
             hn[c] = h_new;
@@ -224,19 +206,14 @@ __global__ __launch_bounds__(256) void k_peb_taped(const float* __restrict__ h_i
                                                    float* __restrict__ h_out, float* __restrict__ q_out, float* __restrict__ hd_out,
                                                    float* __restrict__ qd_out, int D, int n, const PebStep P)
 {
-    const long long plane_elems = (long long)n * n;
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= plane_elems) return;
-    const int p = blockIdx.y, d = p % D, row = (int)(e / n), col = (int)(e - (long long)row * n);
-    const size_t at = (size_t)p * plane_elems + e;
-    const long long w = col > 0 ? -1 : 0, ea = col + 1 < n ? 1 : 0, s = row > 0 ? -(long long)n : 0, nn = row + 1 < n ? n : 0;
-    const long long u = d > 0 ? -plane_elems : 0, dn = d + 1 < D ? plane_elems : 0;
-    auto around = [&](const float* c) -> PebNb { return PebNb{c[w], c[ea], c[s], c[nn], c[u], c[dn]}; };
+    PebCell c;
+    if (!peb_cell(D, n, c)) return;
+    const size_t at = c.at;
     const bool first = q_in == nullptr;
     const float h = h_in[at], q = first ? q0 : q_in[at];
     float a = 0.f, h_new, q_new, hd, qd;
-    peb_step(P, h, q, [&] { return around(h_in + at); }, [&] { return first ? PebNb{q0, q0, q0, q0, q0, q0} : around(q_in + at); }, h_new,
-             q_new, a, hd, qd);
+    peb_step(P, h, q, [&] { return peb_around(h_in + at, c); },
+             [&] { return first ? PebNb{q0, q0, q0, q0, q0, q0} : peb_around(q_in + at, c); }, h_new, q_new, a, hd, qd);
     if (h_out) {
         h_out[at] = h_new;
         q_out[at] = q_new;
@@ -288,13 +265,10 @@ __global__ __launch_bounds__(256) void k_peb_adjoint(const float* __restrict__ h
                                                      const float* __restrict__ qd, float* __restrict__ hb_out, float* __restrict__ qb_out,
                                                      int D, int n, const PebStep P)
 {
-    const long long plane_elems = (long long)n * n;
-    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (e >= plane_elems) return;
-    const int p = blockIdx.y, d = p % D, row = (int)(e / n), col = (int)(e - (long long)row * n);
-    const size_t at = (size_t)p * plane_elems + e;
-    const long long off[7] = {0, col > 0 ? -1 : 0, col + 1 < n ? 1 : 0, row > 0 ? -(long long)n : 0, row + 1 < n ? n : 0,
-                              d > 0 ? -plane_elems : 0, d + 1 < D ? plane_elems : 0};
+    PebCell cell;
+    if (!peb_cell(D, n, cell)) return;
+    const size_t at = cell.at;
+    const long long off[7] = {0, cell.w, cell.e, cell.s, cell.n, cell.u, cell.d};
     auto uv = [&](int i) -> PebUV {
         const size_t c = (size_t)((long long)at + off[i]);
         const float hp = (hb_in ? hb_in[c] : 0.f) + P.half_dt * (abar ? abar[c] : 0.f);
@@ -309,7 +283,7 @@ __global__ __launch_bounds__(256) void k_peb_adjoint(const float* __restrict__ h
 // The exposure's VJP: gI = sum_g (C g) exp(-(C g) I) gh0[g], the gains in ascending order, double per cell, rounded once.
 template <int VEC>
 __global__ __launch_bounds__(256) void k_peb_expose_vjp(const float* __restrict__ image, const float* __restrict__ grad_acid,
-                                                        float* __restrict__ grad_image, int planes, int n, const PebGains gains,
+                                                        float* __restrict__ grad_image, int planes, int n, const VolGains gains,
                                                         int n_gains, double C)
 {
     const long long plane_elems = (long long)n * n;
@@ -329,12 +303,12 @@ __global__ __launch_bounds__(256) void k_peb_expose_vjp(const float* __restrict_
     store_pack<VEC>(grad_image + (size_t)p * plane_elems + e, out);
 }
 
-// ---- 3. rate: m = exp(-kAmp a), x = (1 - m)^q, r = (rmax (a_m + 1)) x / (a_m + x) + rmin, times the surface factor of the
-// plane; slowness = fp32(1 / r), NaN where 1 - m is negative or NaN (k_develop_rate's lines, restated).  grid.y: the B D planes.
+// ---- 3. rate: m = exp(-kAmp a), then mack_slowness of 1 - m with the surface factor of the plane (resist_volume.hpp, the
+// function k_develop_rate calls): NaN where 1 - m is negative or NaN.  grid.y: the B D planes.
 template <int VEC>
 __global__ __launch_bounds__(256) void k_peb_rate(const float* __restrict__ dose, float* __restrict__ slowness, float* __restrict__ inhibitor,
                                                   int D, int n, double k_amp, double rmax_a1, double rmin, double q, double a_m,
-                                                  const PebSurface surface)
+                                                  const VolSurface surface)
 {
     const long long plane_elems = (long long)n * n;
     const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
@@ -346,29 +320,17 @@ __global__ __launch_bounds__(256) void k_peb_rate(const float* __restrict__ dose
     Pack<VEC> s, mi;
     for (int v = 0; v < VEC; ++v) {
         const double m = exp(-(k_amp * (double)a.v[v]));
-        const double x = pow(1.0 - m, q);
-        const double r = (rmax_a1 * x / (a_m + x) + rmin) * f;
-        s.v[v] = (1.0 - m >= 0.0) ? (float)(1.0 / r) : __builtin_nanf("");
+        s.v[v] = mack_slowness(1.0 - m, rmax_a1, rmin, q, a_m, f);
         mi.v[v] = (float)m;
     }
     store_pack<VEC>(slowness + at, s);
     if (inhibitor) store_pack<VEC>(inhibitor + at, mi);
 }
 
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-static bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
-{
-    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
-    return pa < pb + b_bytes && pb < pa + a_bytes;
-}
-static bool finite_pos(double v) { return v > 0.0 && !std::isinf(v); }
-static bool finite_nonneg(double v) { return v >= 0.0 && !std::isinf(v); }
-static unsigned plane_blocks(int n, int vec) { return (unsigned)(((long long)n * n / vec + 255) / 256); }
-static bool volume_ok(int B, int D, int n) { return B >= 1 && D >= 1 && D <= PEB_DMAX && n >= 1 && n <= 16384 && (long long)B * D <= 65535; }
 static size_t lds_bytes(int D, int s)
 {
-    const size_t W = PEB_TILE + 2 * s;
-    return (size_t)D * (4 * W * W + PEB_TILE * PEB_TILE) * sizeof(float);
+    const size_t W = VOL_TILE + 2 * s;
+    return (size_t)D * (4 * W * W + VOL_TILE * VOL_TILE) * sizeof(float);
 }
 
 // lambda_xy = sigma^2 / (2 S pixel^2), lambda_z = (v sigma)^2 / (2 S hz^2): D_s dt / spacing^2 with sigma = sqrt(2 D_s bakeTime)
@@ -388,7 +350,7 @@ static bool stable(double sigma, double vscale, double pixel, double hz, int S)
 static int min_steps(double sigma_h, double sigma_q, double vscale, double thickness, int D, double pixel)
 {
     if (!finite_nonneg(sigma_h) || !finite_nonneg(sigma_q) || !finite_nonneg(vscale) || !finite_pos(thickness) || !finite_pos(pixel) ||
-        D < 1 || D > PEB_DMAX)
+        D < 1 || D > VOL_DMAX)
         return 0;
     const double hz = thickness / D;
     const double sigma = sigma_h > sigma_q ? sigma_h : sigma_q;       // both lambdas grow with sigma: the larger one decides
@@ -430,21 +392,14 @@ int litho_peb_expose(const float* image, int volumes, int D, int n, const float*
                      void* stream)
 {
     using namespace litho;
-    if (!image || !gains_host || !acid || n_gains < 1 || n_gains > PEB_GAINS || !volume_ok(volumes, D, n)) return LITHO_E_ARG;
-    if ((long long)volumes * n_gains * D > 65535 || !finite_pos(C)) return LITHO_E_ARG;
-    PebGains gains;
-    memset(&gains, 0, sizeof(gains));
-    for (int i = 0; i < n_gains; ++i) {
-        if (!(gains_host[i] == gains_host[i])) return LITHO_E_ARG;
-        gains.g[i] = gains_host[i];
-    }
+    VolGains gains;
+    if (!image || !acid || !volume_ok(volumes, D, n) || !make_gains(gains_host, n_gains, volumes, D, gains) || !finite_pos(C))
+        return LITHO_E_ARG;
     const size_t in_bytes = (size_t)volumes * D * n * n * sizeof(float);
     if (overlap(image, in_bytes, acid, in_bytes * n_gains)) return LITHO_E_ARG;
     const int planes = volumes * D;
     const bool wide = (n & 3) == 0 && aligned16(image) && aligned16(acid);
-    const dim3 grid(plane_blocks(n, wide ? 4 : 1), (unsigned)planes);
-    if (wide) hipLaunchKernelGGL(k_peb_expose<4>, grid, dim3(256), 0, (hipStream_t)stream, image, acid, planes, n, gains, n_gains, C);
-    else hipLaunchKernelGGL(k_peb_expose<1>, grid, dim3(256), 0, (hipStream_t)stream, image, acid, planes, n, gains, n_gains, C);
+    LAUNCH_PACKED(k_peb_expose, wide, n, planes, (hipStream_t)stream, image, acid, planes, n, gains, n_gains, C);
     HIP_TRY(hipGetLastError());
     return LITHO_OK;
 }
@@ -465,7 +420,7 @@ size_t litho_peb_work_bytes(int B, int D, int n)
 int litho_peb_steps_per_launch(int D)
 {
     using namespace litho;
-    if (D < 1 || D > PEB_DMAX) return 0;
+    if (D < 1 || D > VOL_DMAX) return 0;
     for (int s = PEB_SMAX; s >= 2; --s)
         if (lds_bytes(D, s) <= PEB_LDS_BUDGET) return s;
     return 1;
@@ -497,19 +452,13 @@ int litho_peb_bake(const float* acid_in, int B, int D, int n, double thickness_n
     hipStream_t st = (hipStream_t)stream;
     if (lds > 64 * 1024) {                                // once per device; the automatic choice never gets here
         static unsigned lds_done = 0;
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        const unsigned bit = 1u << (dev & 31);
-        if (!(__atomic_load_n(&lds_done, __ATOMIC_ACQUIRE) & bit)) {
-            HIP_TRY(hipFuncSetAttribute((const void*)k_peb_fused, hipFuncAttributeMaxDynamicSharedMemorySize, (int)PEB_LDS_MAX));
-            __atomic_fetch_or(&lds_done, bit, __ATOMIC_RELEASE);
-        }
+        HIP_TRY(lds_opt_in(lds_done, (const void*)k_peb_fused, PEB_LDS_MAX));
     }
     // launch k of L reads what launch k - 1 wrote; the last one writes the outputs, the ones before it alternate
     float* out_h[2] = {acid, (float*)work};
     float* out_q[2] = {quencher, (float*)work + (size_t)B * D * n * n};
     const int L = (steps + s - 1) / s;
-    const unsigned tiles = (unsigned)((n + PEB_TILE - 1) / PEB_TILE);
+    const unsigned tiles = (unsigned)((n + VOL_TILE - 1) / VOL_TILE);
     const float *src_h = acid_in, *src_q = nullptr;
     int left = steps;
     for (int k = 0; k < L; ++k) {
@@ -619,26 +568,15 @@ int litho_peb_expose_vjp(const float* image, int volumes, int D, int n, const fl
                          const float* grad_acid, float* grad_image, void* stream)
 {
     using namespace litho;
-    if (!image || !gains_host || !grad_acid || !grad_image || n_gains < 1 || n_gains > PEB_GAINS || !volume_ok(volumes, D, n))
+    VolGains gains;
+    if (!image || !grad_acid || !grad_image || !volume_ok(volumes, D, n) || !make_gains(gains_host, n_gains, volumes, D, gains) ||
+        !finite_pos(C))
         return LITHO_E_ARG;
-    if ((long long)volumes * n_gains * D > 65535 || !finite_pos(C)) return LITHO_E_ARG;
-    PebGains gains;
-    memset(&gains, 0, sizeof(gains));
-    for (int i = 0; i < n_gains; ++i) {
-        if (!(gains_host[i] == gains_host[i])) return LITHO_E_ARG;
-        gains.g[i] = gains_host[i];
-    }
     const size_t in_bytes = (size_t)volumes * D * n * n * sizeof(float);
     if (overlap(image, in_bytes, grad_image, in_bytes) || overlap(grad_acid, in_bytes * n_gains, grad_image, in_bytes)) return LITHO_E_ARG;
     const int planes = volumes * D;
     const bool wide = (n & 3) == 0 && aligned16(image) && aligned16(grad_acid) && aligned16(grad_image);
-    const dim3 grid(plane_blocks(n, wide ? 4 : 1), (unsigned)planes);
-    if (wide)
-        hipLaunchKernelGGL(k_peb_expose_vjp<4>, grid, dim3(256), 0, (hipStream_t)stream, image, grad_acid, grad_image, planes, n, gains,
-                           n_gains, C);
-    else
-        hipLaunchKernelGGL(k_peb_expose_vjp<1>, grid, dim3(256), 0, (hipStream_t)stream, image, grad_acid, grad_image, planes, n, gains,
-                           n_gains, C);
+    LAUNCH_PACKED(k_peb_expose_vjp, wide, n, planes, (hipStream_t)stream, image, grad_acid, grad_image, planes, n, gains, n_gains, C);
     HIP_TRY(hipGetLastError());
     return LITHO_OK;
 }
@@ -647,27 +585,16 @@ int litho_peb_rate(const float* acid_dose, int B, int D, int n, double k_amp, do
                    double surface_rate, double surface_depth_nm, double thickness_nm, float* slowness, float* inhibitor, void* stream)
 {
     using namespace litho;
-    if (!acid_dose || !slowness || !volume_ok(B, D, n)) return LITHO_E_ARG;
-    if (!finite_pos(k_amp) || !finite_pos(r_max) || !finite_pos(r_min) || !(q > 1.0) || std::isinf(q) || !(m_th >= 0.0) || !(m_th < 1.0) ||
-        !(surface_rate > 0.0) || !(surface_rate <= 1.0) || !finite_pos(surface_depth_nm) || !finite_pos(thickness_nm))
+    MackLaw law;
+    if (!acid_dose || !slowness || !volume_ok(B, D, n) || !finite_pos(k_amp) ||
+        !make_mack(r_max, r_min, q, m_th, surface_rate, surface_depth_nm, thickness_nm, D, law))
         return LITHO_E_ARG;
     const size_t bytes = (size_t)B * D * n * n * sizeof(float);
     if (overlap(acid_dose, bytes, slowness, bytes)) return LITHO_E_ARG;
     if (inhibitor && (overlap(acid_dose, bytes, inhibitor, bytes) || overlap(slowness, bytes, inhibitor, bytes))) return LITHO_E_ARG;
-    const double a_m = (q + 1.0) / (q - 1.0) * std::pow(1.0 - m_th, q);
-    PebSurface surface;
-    for (int d = 0; d < PEB_DMAX; ++d) {
-        const double z = thickness_nm * (d + 0.5) / D;
-        surface.f[d] = 1.0 - (1.0 - surface_rate) * std::exp(-z / surface_depth_nm);
-    }
     const bool wide = (n & 3) == 0 && aligned16(acid_dose) && aligned16(slowness) && aligned16(inhibitor);
-    const dim3 grid(plane_blocks(n, wide ? 4 : 1), (unsigned)(B * D));
-    if (wide)
-        hipLaunchKernelGGL(k_peb_rate<4>, grid, dim3(256), 0, (hipStream_t)stream, acid_dose, slowness, inhibitor, D, n, k_amp,
-                           r_max * (a_m + 1.0), r_min, q, a_m, surface);
-    else
-        hipLaunchKernelGGL(k_peb_rate<1>, grid, dim3(256), 0, (hipStream_t)stream, acid_dose, slowness, inhibitor, D, n, k_amp,
-                           r_max * (a_m + 1.0), r_min, q, a_m, surface);
+    LAUNCH_PACKED(k_peb_rate, wide, n, B * D, (hipStream_t)stream, acid_dose, slowness, inhibitor, D, n, k_amp, law.rmax_a1, law.rmin, law.q,
+                  law.a, law.surface);
     HIP_TRY(hipGetLastError());
     return LITHO_OK;
 }

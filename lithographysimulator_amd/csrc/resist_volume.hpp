@@ -1,0 +1,168 @@
+// resist_volume.hpp -- what the units of the resist chain share (peb.hip, develop.hip, develop_grad.hip): the limits of a volume
+// [B, D, n, n], the 16-byte packs of the pointwise kernels and their launch, the host predicates of the entry points, the gains,
+// Mack's rate law (host set-up, device forward and backward) and the host loop of the two tiled fixed-point solvers.
+//
+// The library is built without relocatable device code, so a translation unit cannot name another's __device__ symbols:
+// everything here is static or inline, and each unit that includes this header keeps its own copy.  The units are built with
+// -ffp-contract=off (Makefile): the device functions below are fixed sequences of single operations, and their lines are the
+// ones the float64 oracles of tests/ restate.
+#pragma once
+#include "engine_common.hpp"
+#include "../../include/litho_abbe.h"
+
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+
+namespace litho {
+
+static constexpr int VOL_DMAX = 32, VOL_GAINS = 64;                        // planes through the resist, gains per call
+static constexpr int VOL_TILE = 16, VOL_HALO = VOL_TILE + 2;               // a workgroup's lateral tile, and with its one-cell halo
+static constexpr int VOL_INNER = 8, VOL_CHECK = 4, VOL_MAXIT = 65536;      // solver rounds per launch, launches per host check, cap
+
+struct VolGains {
+    float g[VOL_GAINS];
+};
+struct VolSurface {
+    double f[VOL_DMAX];                                  // the surface-inhibition factor of plane d, from the host
+};
+
+// ---- packs: VEC consecutive x of a row, one 16-byte access when VEC = 4
+template <int VEC>
+struct Pack {
+    float v[VEC];
+};
+template <int VEC>
+__device__ __forceinline__ Pack<VEC> load_pack(const float* p)
+{
+    Pack<VEC> r;
+    if constexpr (VEC == 4) {
+        const float4 q = *reinterpret_cast<const float4*>(p);
+        r.v[0] = q.x; r.v[1] = q.y; r.v[2] = q.z; r.v[3] = q.w;
+    } else {
+        r.v[0] = *p;
+    }
+    return r;
+}
+template <int VEC>
+__device__ __forceinline__ Pack<VEC> fill_pack(float x)
+{
+    Pack<VEC> r;
+    for (int v = 0; v < VEC; ++v) r.v[v] = x;
+    return r;
+}
+template <int VEC>
+__device__ __forceinline__ void store_pack(float* p, const Pack<VEC>& r)
+{
+    if constexpr (VEC == 4) *reinterpret_cast<float4*>(p) = make_float4(r.v[0], r.v[1], r.v[2], r.v[3]);
+    else *p = r.v[0];
+}
+
+// index -1 - k <-> k and n + k <-> n - 1 - k, repeated as needed
+__host__ __device__ __forceinline__ int mirror_index(int i, int n)
+{
+    int m = i % (2 * n);
+    if (m < 0) m += 2 * n;
+    return m < n ? m : 2 * n - 1 - m;
+}
+
+// ---- host predicates of the entry points
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes)
+{
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + b_bytes && pb < pa + a_bytes;
+}
+static bool finite_pos(double v) { return v > 0.0 && !std::isinf(v); }
+static bool finite_nonneg(double v) { return v >= 0.0 && !std::isinf(v); }
+static unsigned plane_blocks(int n, int vec) { return (unsigned)(((long long)n * n / vec + 255) / 256); }
+static bool volume_ok(int B, int D, int n) { return B >= 1 && D >= 1 && D <= VOL_DMAX && n >= 1 && n <= 16384 && (long long)B * D <= 65535; }
+static size_t flag_bytes(int max_iterations) { return ((size_t)max_iterations * sizeof(int) + 255) & ~(size_t)255; }
+
+// The packed kernel k<4> when `wide` (n a multiple of 4 and every pointer 16-byte aligned: the caller's test), else its scalar
+// twin k<1>; grid.x covers the n^2 / VEC packs of a plane, grid.y the planes.
+#define LAUNCH_PACKED(k, wide, n, planes, st, ...)                                                                       \
+    do {                                                                                                                 \
+        if (wide) hipLaunchKernelGGL(k<4>, dim3(plane_blocks(n, 4), (unsigned)(planes)), dim3(256), 0, st, __VA_ARGS__); \
+        else hipLaunchKernelGGL(k<1>, dim3(plane_blocks(n, 1), (unsigned)(planes)), dim3(256), 0, st, __VA_ARGS__);      \
+    } while (0)
+
+// The gains of a call as its kernel takes them.  False when there are none, more than VOL_GAINS or a NaN among them, or when the
+// volumes x gains x D planes of the gained volume exceed what grid.y holds.
+static bool make_gains(const float* gains_host, int n_gains, int volumes, int D, VolGains& gains)
+{
+    if (!gains_host || n_gains < 1 || n_gains > VOL_GAINS || (long long)volumes * n_gains * D > 65535) return false;
+    memset(&gains, 0, sizeof(gains));
+    for (int i = 0; i < n_gains; ++i) {
+        if (!(gains_host[i] == gains_host[i])) return false;
+        gains.g[i] = gains_host[i];
+    }
+    return true;
+}
+
+// ---- Mack's rate law: with b = 1 - m the dissolved fraction, X = b^q, r = (rmax (a + 1) X / (a + X) + rmin) f, a = (q + 1) /
+// (q - 1) (1 - m_th)^q and f the surface-inhibition factor of the plane, 1 - (1 - r0) exp(-z / delta) at z = thickness (d + 1/2) / D.
+struct MackLaw {
+    double rmax_a1, rmin, q, a;                          // the kernels take these four as scalars
+    VolSurface surface;
+};
+// false when a parameter is outside its domain (litho_develop_rate's, include/litho_abbe.h)
+static bool make_mack(double r_max, double r_min, double q, double m_th, double surface_rate, double surface_depth_nm, double thickness_nm,
+                      int D, MackLaw& law)
+{
+    if (!finite_pos(r_max) || !finite_pos(r_min) || !(q > 1.0) || std::isinf(q) || !(m_th >= 0.0) || !(m_th < 1.0) ||
+        !(surface_rate > 0.0) || !(surface_rate <= 1.0) || !finite_pos(surface_depth_nm) || !finite_pos(thickness_nm))
+        return false;
+    law.a = (q + 1.0) / (q - 1.0) * std::pow(1.0 - m_th, q);
+    law.rmax_a1 = r_max * (law.a + 1.0);
+    law.rmin = r_min;
+    law.q = q;
+    for (int d = 0; d < VOL_DMAX; ++d) {
+        const double z = thickness_nm * (d + 0.5) / D;
+        law.surface.f[d] = 1.0 - (1.0 - surface_rate) * std::exp(-z / surface_depth_nm);
+    }
+    return true;
+}
+// slowness = fp32(1 / r), rounded once.  b < 0 (a negative dose-intensity product) or NaN: pow is finite there for an integer q,
+// so the NaN is written explicitly
+__device__ __forceinline__ float mack_slowness(double b, double rmax_a1, double rmin, double q, double a, double f)
+{
+    const double x = pow(b, q);
+    const double r = (rmax_a1 * x / (a + x) + rmin) * f;
+    return (b >= 0.0) ? (float)(1.0 / r) : __builtin_nanf("");
+}
+// ds/dx of s = 1 / r for b = b(x) with db/dx = db: -s^2 f R a / (a + X)^2 q b^(q - 1) db, R = rmax (a + 1).  For b >= 0 only (the
+// caller skips a wall).
+__device__ __forceinline__ double mack_slowness_dx(double b, double db, double rmax_a1, double rmin, double q, double a, double f)
+{
+    const double X = pow(b, q);
+    const double r = (rmax_a1 * X / (a + X) + rmin) * f;
+    const double s = 1.0 / r;
+    const double dX = q * pow(b, q - 1.0) * db;
+    return -(s * s) * f * (rmax_a1 * a / ((a + X) * (a + X))) * dX;
+}
+
+// ---- the host loop of the tiled solvers (k_develop_time, k_develop_time_vjp).  enqueue(it) puts launch it = 0, 1, ... on `st`;
+// launch `it` stores 1 into flags[it] when it changed a cell.  The flag words are zeroed up front; the launches go out in groups
+// of VOL_CHECK, each group followed by one copy-back of its flag words and one synchronise.  Returns the number of launches up
+// to and including the first one that changed nothing (its output equals its input), 0 when none of max_iterations did, or
+// LITHO_E_HIP.
+template <class F>
+static int iterate_until_unchanged(int* flags, int max_iterations, hipStream_t st, F enqueue)
+{
+    HIP_TRY(hipMemsetAsync(flags, 0, flag_bytes(max_iterations), st));
+    for (int done = 0; done < max_iterations;) {
+        const int group = max_iterations - done < VOL_CHECK ? max_iterations - done : VOL_CHECK;
+        for (int j = 0; j < group; ++j) enqueue(done + j);
+        HIP_TRY(hipGetLastError());
+        int seen[VOL_CHECK] = {1, 1, 1, 1};
+        HIP_TRY(hipMemcpyAsync(seen, flags + done, (size_t)group * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int j = 0; j < group; ++j)
+            if (seen[j] == 0) return done + j + 1;
+        done += group;
+    }
+    return 0;
+}
+
+}  // namespace litho

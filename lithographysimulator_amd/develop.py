@@ -102,6 +102,16 @@ def _positive(who, name, v):
     return v
 
 
+def _gains(who, doses, F, D):
+    """The doses of a call on F volumes of D planes as the C ABI takes them: (float array, count)."""
+    gains = [float(d) for d in doses]
+    if not 1 <= len(gains) <= 64:
+        raise ValueError(f"{who}: between 1 and 64 doses per call; got {len(gains)}")
+    if len(gains) * F * D > 65535:
+        raise ValueError(f"{who}: doses x volumes x planes exceeds 65535")
+    return (ctypes.c_float * len(gains))(*gains), len(gains)
+
+
 def latentDiffusion(image, thickness, pixelSize, diffusionLength=0.0, verticalDiffusionLength=0.0):
     """The intensity volume [D,n,n] or [B,D,n,n] convolved with a separable Gaussian (litho_latent_diffuse): standard deviation
     `diffusionLength` nm along x and y with zeros outside the grid -- the taps of resistContour(diffusionLength=) -- and
@@ -135,18 +145,13 @@ def developmentRate(image, resist, thickness, pixelSize, doses=(1.0,)):
         raise TypeError(f"{who}: resist must be a MackResist")
     v, F, D, n, _, dev = _volume(who, image)
     thickness, h = _positive(who, "thickness", thickness), _positive(who, "pixelSize", pixelSize)
-    gains = [float(d) for d in doses]
-    if not 1 <= len(gains) <= 64:
-        raise ValueError(f"{who}: between 1 and 64 doses per call; got {len(gains)}")
-    if len(gains) * F * D > 65535:
-        raise ValueError(f"{who}: doses x volumes x planes exceeds 65535")
+    g, count = _gains(who, doses, F, D)
     if resist.diffusionLength > 0.0 or resist.verticalDiffusionLength > 0.0:
         v = latentDiffusion(v, thickness, h, resist.diffusionLength, resist.verticalDiffusionLength)
-    out = torch.empty((len(gains) * F, D, n, n), dtype=torch.float32, device=dev)
-    g = (ctypes.c_float * len(gains))(*gains)
+    out = torch.empty((count * F, D, n, n), dtype=torch.float32, device=dev)
     delta = resist.surfaceDepth if resist.surfaceDepth is not None else thickness
     with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_develop_rate(nat.ptr(v), F, D, n, g, len(gains), resist.C, resist.rMax, resist.rMin, resist.q,
+        nat.check(nat.lib().litho_develop_rate(nat.ptr(v), F, D, n, g, count, resist.C, resist.rMax, resist.rMin, resist.q,
                                                resist.mTh, resist.surfaceRate, delta, thickness, nat.ptr(out), nat.stream_ptr(dev)),
                   "litho_develop_rate")
         v.record_stream(torch.cuda.current_stream(dev))
@@ -323,19 +328,15 @@ def developmentTimeGradient(slowness, T, gradT, thickness, pixelSize, maxIterati
     return (out, launches.value) if returnLaunches else out
 
 
-def _rate_vjp(who, x, gains, kappa, mack, thickness, gradSlowness):
+def _rate_vjp(who, x, doses, kappa, mack, thickness, gradSlowness):
     """litho_develop_rate_vjp on the volume x ([D,n,n] or [F,D,n,n]) with Mack's parameters of `mack`; shaped like x."""
     v, F, D, n, batched, dev = _volume(who, x)
-    if not 1 <= len(gains) <= 64:
-        raise ValueError(f"{who}: between 1 and 64 doses per call; got {len(gains)}")
-    if len(gains) * F * D > 65535:
-        raise ValueError(f"{who}: doses x volumes x planes exceeds 65535")
-    gs = _like(who, "gradSlowness", gradSlowness, (len(gains) * F, D, n, n), dev)
+    g, count = _gains(who, doses, F, D)
+    gs = _like(who, "gradSlowness", gradSlowness, (count * F, D, n, n), dev)
     out = torch.empty_like(v)
-    g = (ctypes.c_float * len(gains))(*gains)
     delta = mack.surfaceDepth if mack.surfaceDepth is not None else thickness
     with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_develop_rate_vjp(nat.ptr(v), F, D, n, g, len(gains), kappa, mack.rMax, mack.rMin, mack.q, mack.mTh,
+        nat.check(nat.lib().litho_develop_rate_vjp(nat.ptr(v), F, D, n, g, count, kappa, mack.rMax, mack.rMin, mack.q, mack.mTh,
                                                    mack.surfaceRate, delta, thickness, nat.ptr(gs), nat.ptr(out), nat.stream_ptr(dev)),
                   "litho_develop_rate_vjp")
         for t in (v, gs):
@@ -357,7 +358,7 @@ def developmentRateGradient(image, resist, thickness, pixelSize, doses, gradSlow
     thickness, h = _positive(who, "thickness", thickness), _positive(who, "pixelSize", pixelSize)
     diffuses = resist.diffusionLength > 0.0 or resist.verticalDiffusionLength > 0.0
     lat = latentDiffusion(v, thickness, h, resist.diffusionLength, resist.verticalDiffusionLength) if diffuses else v
-    out = _rate_vjp(who, lat, [float(d) for d in doses], resist.C, resist, thickness, gradSlowness)
+    out = _rate_vjp(who, lat, doses, resist.C, resist, thickness, gradSlowness)
     return latentDiffusion(out, thickness, h, resist.diffusionLength, resist.verticalDiffusionLength) if diffuses else out
 
 

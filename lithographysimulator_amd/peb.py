@@ -16,13 +16,12 @@ develop.py's gradients through development (`resistProfileGradient`, `ilt.develo
 
 NOT built: bleaching, a diffusivity that depends on the deprotection, gradients with respect to resist parameters other than
 the quencher loading."""
-import ctypes
 import math
 
 import torch
 
 from . import _native as nat
-from .develop import MackResist, _positive, _volume
+from .develop import MackResist, _gains, _positive, _volume
 
 MAX_STEPS = 65536
 
@@ -94,15 +93,10 @@ def exposeAcid(image, C, doses=(1.0,)):
     or NaN."""
     who = "exposeAcid"
     v, F, D, n, _, dev = _volume(who, image)
-    gains = [float(d) for d in doses]
-    if not 1 <= len(gains) <= 64:
-        raise ValueError(f"{who}: between 1 and 64 doses per call; got {len(gains)}")
-    if len(gains) * F * D > 65535:
-        raise ValueError(f"{who}: doses x volumes x planes exceeds 65535")
-    out = torch.empty((len(gains) * F, D, n, n), dtype=torch.float32, device=dev)
-    g = (ctypes.c_float * len(gains))(*gains)
+    g, count = _gains(who, doses, F, D)
+    out = torch.empty((count * F, D, n, n), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_peb_expose(nat.ptr(v), F, D, n, g, len(gains), _positive(who, "C", C), nat.ptr(out), nat.stream_ptr(dev)),
+        nat.check(nat.lib().litho_peb_expose(nat.ptr(v), F, D, n, g, count, _positive(who, "C", C), nat.ptr(out), nat.stream_ptr(dev)),
                   "litho_peb_expose")
         v.record_stream(torch.cuda.current_stream(dev))
     return out
@@ -244,20 +238,15 @@ def exposeAcidGradient(image, C, doses, gradAcid):
     shaped like `image` ([D,n,n] or [F,D,n,n]); gradAcid fp32 [len(doses) F, D, n, n], dose-major, as exposeAcid returns."""
     who = "exposeAcidGradient"
     v, F, D, n, batched, dev = _volume(who, image)
-    gains = [float(d) for d in doses]
-    if not 1 <= len(gains) <= 64:
-        raise ValueError(f"{who}: between 1 and 64 doses per call; got {len(gains)}")
-    if len(gains) * F * D > 65535:
-        raise ValueError(f"{who}: doses x volumes x planes exceeds 65535")
-    want = (len(gains) * F, D, n, n)
+    g, count = _gains(who, doses, F, D)
+    want = (count * F, D, n, n)
     if not isinstance(gradAcid, torch.Tensor) or gradAcid.dtype != torch.float32 or tuple(gradAcid.shape) != want or gradAcid.device != dev:
         raise ValueError(f"{who}: gradAcid must be a float32 tensor {want} on {dev}; got {getattr(gradAcid, 'dtype', type(gradAcid))} "
                          f"{tuple(getattr(gradAcid, 'shape', ()))} on {getattr(gradAcid, 'device', None)}")
     ga = gradAcid.detach().contiguous()
     out = torch.empty_like(v)
-    g = (ctypes.c_float * len(gains))(*gains)
     with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_peb_expose_vjp(nat.ptr(v), F, D, n, g, len(gains), _positive(who, "C", C), nat.ptr(ga), nat.ptr(out),
+        nat.check(nat.lib().litho_peb_expose_vjp(nat.ptr(v), F, D, n, g, count, _positive(who, "C", C), nat.ptr(ga), nat.ptr(out),
                                                  nat.stream_ptr(dev)), "litho_peb_expose_vjp")
         for t in (v, ga):
             t.record_stream(torch.cuda.current_stream(dev))

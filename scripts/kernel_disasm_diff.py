@@ -1,12 +1,13 @@
 """Compares the gfx950 machine code of two builds of liblitho_abbe.so kernel by kernel.
 
-    python scripts/kernel_disasm_diff.py OLD.so NEW.so [name-regex]
+    python scripts/kernel_disasm_diff.py OLD.so NEW.so [name-regex] [OLDTYPE=NEWTYPE ...]
 
 Extracts the device code object of each library, disassembles it (llvm-objdump -d) and compares the instruction
 streams of the kernels both builds have (addresses and encodings dropped, branch targets kept as offsets into the
 kernel).  Prints the kernels that differ, the ones only one build has, and a one-line summary; exit status 1 when a
 common kernel matching the regex differs.  Used to show that a change which adds kernels (weighted x-pass siblings)
-leaves the existing ones bit-identical."""
+leaves the existing ones bit-identical.  Kernels are paired by their full signature; OLDTYPE=NEWTYPE rewrites a type name in the
+old build's signatures first, for a change that renames the type of a kernel argument and nothing else about the kernel."""
 import os
 import re
 import subprocess
@@ -68,10 +69,14 @@ def kernels(cos):
 
 def main():
     old, new = sys.argv[1], sys.argv[2]
-    rx = re.compile(sys.argv[3] if len(sys.argv) > 3 else ".")
+    renames = [a.split("=", 1) for a in sys.argv[3:] if "=" in a]
+    rest = [a for a in sys.argv[3:] if "=" not in a]
+    rx = re.compile(rest[0] if rest else ".")
     with tempfile.TemporaryDirectory() as tmp:
         os.makedirs(os.path.join(tmp, "a")); os.makedirs(os.path.join(tmp, "b"))
         ka, kb = kernels(code_objects(old, os.path.join(tmp, "a"))), kernels(code_objects(new, os.path.join(tmp, "b")))
+    for old_type, new_type in renames:
+        ka = {re.sub(r"\b%s\b" % re.escape(old_type), new_type, n): v for n, v in ka.items()}
     common = sorted(n for n in ka if n in kb and rx.search(n))
     differ = [n for n in common if ka[n] != kb[n]]
     for n in differ:

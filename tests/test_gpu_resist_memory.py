@@ -29,9 +29,10 @@ Shapes (n, D, B), the smallest at which each mechanism exists:
   (17, 3, 2)    a one-cell second tile, halo traffic both ways
   (12, 14, 2)   the first D at which the adjoint's tile leaves 64 KiB of LDS
   (20, 29, 1)   n % 4 == 0 but no multiple of 16; the first D at which the forward solver's tile leaves 64 KiB
-LDS per plane of the tile, from the kernels' constants (test_the_shapes_sit_on_the_lds_thresholds asserts them):
-  k_develop_time      DEV_TILE 16, halo 18: (18 18 + 16 16) floats = 2320 B; 28 planes 64960 B <= 65536 < 67280 B = 29 planes
-  k_develop_time_vjp  DG_TILE 16, halo 18: (3 18 18 + 16 16) floats = 4912 B; 13 planes 63856 B <= 65536 < 68768 B = 14 planes
+LDS per plane of the tile, from the kernels' constants (test_the_shapes_sit_on_the_lds_thresholds asserts them; VOL_TILE 16 and
+VOL_HALO 18 of csrc/resist_volume.hpp are the tile of both solvers):
+  k_develop_time      VOL_TILE 16, halo 18: (18 18 + 16 16) floats = 2320 B; 28 planes 64960 B <= 65536 < 67280 B = 29 planes
+  k_develop_time_vjp  VOL_TILE 16, halo 18: (3 18 18 + 16 16) floats = 4912 B; 13 planes 63856 B <= 65536 < 68768 B = 14 planes
   k_peb_fused         s steps per launch: D (4 (16 + 2 s)^2 + 256) floats against the 160 KiB of a workgroup: at D = 29 not even
                       s = 2 fits (215296 B), at D = 14 s = 2 (103936 B) and s = 4 (143360 B) both leave 64 KiB and fit
 A change of the tile geometry shows there which shapes have to move.
