@@ -636,6 +636,65 @@ int litho_peb_bake_vjp(const float *acid_in, int B, int D, int n, double thickne
 int litho_peb_expose_vjp(const float *image, int volumes, int D, int n, const float *gains_host, int n_gains, double C,
                          const float *grad_acid, float *grad_image, void *stream);
 
+/* ---- Gradients with respect to the bake's parameters (csrc/peb.hip; checked against the float64 restatement
+ * tests/resist_param_oracle.py, itself pinned to central differences of tests/peb_oracle.py).  The six numbers of a bake step are
+ * theta = (lxy_h, lz_h, lxy_q, lz_q, beta, fl).  In the notation of the backward step above -- hp = hbar_k+1 + half_dt abar,
+ * qb = qbar_k+1, (u, v) its result, (hd, qd) the step's tape -- and with (h_k, q_k) the state at the START of step k, the backward
+ * step k contributes per cell
+ *   slot 0  lxy_h   u (((W + E) + (S + N)) - 4 x)  on x = h_k      slot 2  lxy_q   v (((W + E) + (S + N)) - 4 x)  on x = q_k
+ *   slot 1  lz_h    u ((U + Dn) - 2 x)             on x = h_k      slot 3  lz_q    v ((U + Dn) - 2 x)             on x = q_k
+ *   slot 4  beta    -(fl hp + qb) hd qd / (1 + beta (hd + qd))^2
+ *   slot 5  fl      hp (hd - R),  R = beta hd qd / (1 + beta (hd + qd)), or (hd < qd) ? hd : qd when beta = +inf
+ * and grad_step[b][slot] is the sum of these over the steps k = S-1 .. 0 and the cells of volume b: dl/dtheta with half_dt held
+ * fixed.  The neighbours follow the forward's face rule (the cell itself beyond a face).  The slots of a species that does not
+ * diffuse are exactly 0; at step 0 q_k is uniform, so its two terms are 0; slot 4 is exactly 0 for an instantaneous step, whose
+ * R = min(hd, qd) holds no beta.  Each term is formed in double from the fp32 operands (u, v, hp, qb, the tape and the state as
+ * the fp32 sweep has them) and the sums are kept in double.
+ *
+ * litho_peb_bake_vjp_params: the arguments and checks of litho_peb_bake_vjp, and grad_step, device double [B][6], 16-byte aligned
+ * and not NULL (LITHO_E_ARG), overlapping neither an input, nor an output, nor work (LITHO_E_ARG).  grad_acid_in and
+ * grad_quencher_in are written as litho_peb_bake_vjp writes them, bit for bit: the same forward launches, the same two functions
+ * in the backward step.  The tape of a segment keeps four volumes per step, (hd, qd) and the state after the step, which is the
+ * next step's (h_k, q_k) -- the forward's own bits, no recomputation.  work: litho_peb_vjp_params_work_bytes(B, D, n, steps, c) =
+ * (2 (ceil(S / c) - 1) + 4 c + 8) volumes of B D n n floats, rounded up to 16 bytes, then B D ceil(n n / 256) slots of six
+ * doubles, one per workgroup of a backward launch; 0 for a bad argument; 16-byte aligned, less is LITHO_E_WORKSPACE.  No atomics:
+ * a 256-thread workgroup adds its six terms in a fixed tree (within each wave of 64 the upper half onto the lower, 32, 16 .. 1,
+ * then the four waves in ascending order) and one thread adds the result into the workgroup's own slot, zeroed at the start of
+ * the call; the backward steps are successive launches on one stream, so a slot's additions come in the order k = S-1 .. 0
+ * whatever c is.  A last kernel adds the D ceil(n n / 256) slots of volume b, which lie planes ascending, then workgroups
+ * ascending: thread i of one workgroup takes the slots i, i + 256, .. in ascending order, then the same tree.  So grad_step has the
+ * same bits in two calls, for every c, and for a volume alone or inside a batch.  Asynchronous, no allocation, no host wait.
+ *
+ * litho_peb_param_chain: host only, no GPU call.  grad_param[5] = d/d(k_quench, k_loss, sigma_acid, sigma_quencher,
+ * vertical_scale) from grad_step[6] (host doubles) by the derivative of the step parameters' own formulas (section 2 of the bake)
+ * at a FIXED step count S, which is an integer the caller holds fixed:  d lxy / d sigma = 2 lxy / sigma = sigma / (S pixel^2),
+ * d lz / d sigma = 2 lz / sigma,  d lz / d vertical_scale = 2 lz / vertical_scale  (each 0 at a zero length or scale),
+ * d beta / d k_quench = dt (the result is 0 for k_quench = +inf),  d fl / d k_loss = -dt fl.  This is the analytic derivative in
+ * double, not the derivative of the fp32 rounding of the step parameters.  bake_time is a process setting and is not
+ * differentiated; the quencher loading's gradient stays the sum of grad_quencher_in over a volume.  LITHO_E_ARG: a NULL pointer,
+ * steps outside litho_peb_min_steps(...) .. 65536, k_quench negative or NaN, k_loss, bake_time or pixel outside their domains.
+ *
+ * litho_peb_expose_vjp_params: dl/dC of the exposure h0[g] = 1 - exp(-(C gain_g) I) for the cotangent grad_acid = dl/dh0:
+ * grad_C[g][v] = sum over the cells of volume v of grad_acid[g] (gain_g I) exp(-(C gain_g) I), device double [n_gains][volumes],
+ * 16-byte aligned, one number per gain and volume (the caller adds them).  Each term in double; a cell whose acid is NaN
+ * (1 - exp negative or NaN) contributes 0 whatever its cotangent holds.  The sums as above: a workgroup's fixed tree into its own
+ * slot, then the D ceil(n n / 256) slots of a gained volume, planes ascending, by one workgroup in a fixed order; no atomics,
+ * the same bits in two calls and for a volume alone or in a batch.  The arguments and checks of litho_peb_expose_vjp; work:
+ * litho_peb_expose_params_work_bytes(volumes, D, n, n_gains) = n_gains volumes D ceil(n n / 256) doubles (0 for a bad argument),
+ * 16-byte aligned, less is LITHO_E_WORKSPACE; grad_C and work overlap nothing (LITHO_E_ARG).  Asynchronous. */
+size_t litho_peb_expose_params_work_bytes(int volumes, int D, int n, int n_gains);
+int litho_peb_expose_vjp_params(const float *image, int volumes, int D, int n, const float *gains_host, int n_gains, double C,
+                                const float *grad_acid, double *grad_C, void *work, size_t work_bytes, void *stream);
+size_t litho_peb_vjp_params_work_bytes(int B, int D, int n, int steps, int checkpoint_every);
+int litho_peb_bake_vjp_params(const float *acid_in, int B, int D, int n, double thickness_nm, double pixel_nm, double quencher0,
+                              double k_quench, double k_loss, double sigma_acid_nm, double sigma_quencher_nm, double vertical_scale,
+                              double bake_time_s, int steps, int checkpoint_every, const float *grad_acid, const float *grad_quencher,
+                              const float *grad_acid_dose, float *grad_acid_in, float *grad_quencher_in, double *grad_step, void *work,
+                              size_t work_bytes, void *stream);
+int litho_peb_param_chain(double thickness_nm, double pixel_nm, double k_quench, double k_loss, double sigma_acid_nm,
+                          double sigma_quencher_nm, double vertical_scale, double bake_time_s, int D, int steps, const double *grad_step,
+                          double *grad_param);
+
 /* ---- Gradients through development (csrc/develop_grad.hip; checked against the float64 restatement
  * tests/develop_grad_oracle.py, itself pinned to central differences of tests/develop_oracle.py).  The arrival time T of
  * litho_develop_time is the fixed point T_i = G_i(T at i's neighbours, s_i) of the Godunov update of section 3 above.  For a
@@ -692,6 +751,40 @@ int litho_develop_time_vjp(const float *slowness, const float *T, const float *g
 int litho_develop_rate_vjp(const float *x, int volumes, int D, int n, const float *gains_host, int n_gains, double kappa, double r_max,
                            double r_min, double q, double m_th, double surface_rate, double surface_depth_nm, double thickness_nm,
                            const float *grad_slowness, float *grad_x, void *stream);
+
+/* ---- Gradients with respect to the rate law's parameters (csrc/develop_grad.hip; checked against tests/resist_param_oracle.py,
+ * itself pinned to central differences of the rate oracles).  For litho_develop_rate (kappa = C, the doses as gains) and
+ * litho_peb_rate (kappa = k_amp, one gain of 1) alike, in the notation of litho_develop_rate_vjp with b = 1 - m, X = b^q,
+ * R = r_max (a + 1), a = (q + 1) / (q - 1) (1 - m_th)^q:
+ *   slot 0  ds/dkappa = -s^2 f R a / (a + X)^2 q b^(q-1) (g x) m       (litho_develop_rate_vjp's line with db = (g x) m)
+ *   slot 1  ds/dR     = -s^2 f X / (a + X)                              at fixed a
+ *   slot 2  ds/dr_min = -s^2 f
+ *   slot 3  ds/dq     = -s^2 f R a / (a + X)^2 X ln b                   at fixed a; 0 at b = 0
+ *   slot 4  ds/da     = -s^2 f (R / (a + 1)) X (X - 1) / (a + X)^2      at fixed r_max, R following a
+ *   slot 5  ds/df     = -s / f
+ * litho_develop_rate_vjp_params: plane_sums[gained plane][slot] = the sum over the cells of the plane of grad_slowness times the
+ * slot's derivative, device double [n_gains volumes D][6], gain-major like grad_slowness, 16-byte aligned; every term in double, a
+ * wall (1 - m negative or NaN) contributes 0 whatever its cotangent holds.  Two kernels, no atomics: a 256-thread workgroup adds
+ * its terms in a fixed tree (as litho_peb_bake_vjp_params) into its own slot of work, and one workgroup per gained plane adds the
+ * plane's ceil(n n / 256) slots in a fixed order: the same bits in two calls and for a volume alone or in a batch.  The
+ * arguments and checks of litho_develop_rate_vjp without grad_x; work: litho_develop_rate_params_work_bytes(volumes, D, n,
+ * n_gains) = n_gains volumes D ceil(n n / 256) slots of six doubles (0 for a bad argument), 16-byte aligned, less is
+ * LITHO_E_WORKSPACE; plane_sums and work overlap nothing (LITHO_E_ARG).  Asynchronous, no allocation, no host wait.
+ *
+ * litho_develop_rate_param_chain: host only, no GPU call.  From plane_sums (HOST doubles [groups][D][6], a group = one gained
+ * volume) grad_param[group][7] = d/d(kappa, r_max, r_min, q, m_th, surface_rate, surface_depth), the planes added in ascending
+ * order:  kappa: slot 0;  r_max: (a + 1) slot 1;  r_min: slot 2;  q: slot 3 + slot 4 da/dq,  da/dq = a (1 / (q + 1) - 1 / (q - 1)
+ * + ln(1 - m_th));  m_th: slot 4 da/dm_th,  da/dm_th = -q a / (1 - m_th);  and with f_d = 1 - (1 - r0) exp(-z_d / delta),
+ * z_d = thickness (d + 1/2) / D:  surface_rate: sum_d slot 5 exp(-z_d / delta);  surface_depth: sum_d slot 5 (-(1 - r0)
+ * exp(-z_d / delta) z_d / delta^2).  LITHO_E_ARG: a NULL pointer, groups < 1, D outside 1..32, a parameter outside
+ * litho_develop_rate's domain.  NOT built: the gradients of a MackResist's own Gaussian diffusion lengths. */
+size_t litho_develop_rate_params_work_bytes(int volumes, int D, int n, int n_gains);
+int litho_develop_rate_vjp_params(const float *x, int volumes, int D, int n, const float *gains_host, int n_gains, double kappa,
+                                  double r_max, double r_min, double q, double m_th, double surface_rate, double surface_depth_nm,
+                                  double thickness_nm, const float *grad_slowness, double *plane_sums, void *work, size_t work_bytes,
+                                  void *stream);
+int litho_develop_rate_param_chain(double r_max, double r_min, double q, double m_th, double surface_rate, double surface_depth_nm,
+                                   double thickness_nm, int D, int groups, const double *plane_sums, double *grad_param);
 
 /* ---- Mask gradients of Hopkins imaging (csrc/socs_grad.hip; no reference counterpart, checked against tests/socs_grad_oracle.py).
  * With F[q][i] = exp(+2 pi i (i - c)(q - c) / N), c = pn / 2, q, i in [0, pn), the engine's chain at shift (0,0) is L(X) = F X F^T,

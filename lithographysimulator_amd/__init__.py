@@ -26,6 +26,10 @@ from .develop import (MackResist, ResistProfile, developedDepth, developmentRate
                       latentDiffusion, resistProfile, resistProfileGradient)
 from .peb import (BakeResult, ChemicallyAmplifiedResist, amplifiedRateGradient,        # noqa: F401
                   bakeGradient, exposeAcidGradient, postExposureBake, postExposureBakeGradient)
+from .calibrate import (bakeParameterChain, bakeParameterGradient, bakeStepGradient,  # noqa: F401
+                        calibrateResist, exposureParameterGradient, rateParameterChain,
+                        rateParameterGradient, resistArrivalTimes, resistParameter,
+                        resistParameterGradient, resistWith)
 from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
@@ -45,4 +49,6 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "MackResist", "ResistProfile", "latentDiffusion", "developmentRate", "developmentTime", "developedDepth", "resistProfile",
            "ChemicallyAmplifiedResist", "BakeResult", "postExposureBake",
            "bakeGradient", "exposeAcidGradient", "postExposureBakeGradient", "bakedResistModel",
-           "developmentTimeGradient", "developmentRateGradient", "resistProfileGradient", "amplifiedRateGradient", "developedResistModel"]
+           "developmentTimeGradient", "developmentRateGradient", "resistProfileGradient", "amplifiedRateGradient", "developedResistModel",
+           "bakeStepGradient", "bakeParameterChain", "bakeParameterGradient", "rateParameterChain", "rateParameterGradient",
+           "exposureParameterGradient", "resistParameterGradient", "calibrateResist", "resistArrivalTimes", "resistWith", "resistParameter"]

@@ -83,6 +83,21 @@ _SIGNATURES = {
                                    c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                    c_void_p]),
     "litho_peb_expose_vjp": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), c_int, c_double, c_void_p, c_void_p, c_void_p]),
+    "litho_peb_vjp_params_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "litho_peb_bake_vjp_params": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double,
+                                          c_double, c_double, c_double, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_size_t, c_void_p]),
+    "litho_peb_param_chain": (c_int, [c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_int, c_int,
+                                      POINTER(c_double), POINTER(c_double)]),
+    "litho_peb_expose_params_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "litho_peb_expose_vjp_params": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), c_int, c_double, c_void_p, c_void_p, c_void_p,
+                                            c_size_t, c_void_p]),
+    "litho_develop_rate_params_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "litho_develop_rate_vjp_params": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), c_int, c_double, c_double, c_double,
+                                              c_double, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_size_t,
+                                              c_void_p]),
+    "litho_develop_rate_param_chain": (c_int, [c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_int, c_int,
+                                               POINTER(c_double), POINTER(c_double)]),
     "litho_peb_rate": (c_int,[c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_double,
                                c_double, c_void_p, c_void_p, c_void_p]),
     "litho_develop_vjp_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -12,6 +12,7 @@
 //   k_develop_time_vjp  the tiled gather iteration for lambda (below)
 //   k_develop_scale     grad_s = lambda sigma, exactly 0 where the cell has no gradient
 //   k_develop_rate_vjp  the rate law of k_develop_rate / k_peb_rate backwards, double per cell, the gains summed inside
+// and behind litho_develop_rate_vjp_params k_develop_rate_params, the rate law's six parameter sums per gained plane (section 5).
 // The pointwise kernels move four consecutive x per thread (16-byte accesses) when n is a multiple of 4 and the pointers are
 // 16-byte aligned, one otherwise.  The limits, the packs, the host predicates, the gains, the rate law (mack_slowness_dx, next to
 // the forward's mack_slowness) and the solver's host loop are resist_volume.hpp's, shared with develop.hip and peb.hip.
@@ -289,6 +290,39 @@ __global__ __launch_bounds__(256) void k_develop_rate_vjp(const float* __restric
     store_pack<VEC>(grad_x + at, out);
 }
 
+// ---- 5. the rate law's parameter sums (litho_develop_rate_vjp_params): per cell of a gained plane the six products of the
+// cotangent with ds/dkappa (mack_slowness_dx with db/dkappa = g x m) and with mack_slowness_dparams' five, in double; a wall
+// contributes 0.  A workgroup adds its terms in vol_block_sum's fixed tree and writes them to its own slot
+// partials[gained plane][workgroup][6]; k_vol_total adds the slots of a gained plane.  grid.y: the n_gains x planes gained planes.
+__global__ __launch_bounds__(256) void k_develop_rate_params(const float* __restrict__ x, const float* __restrict__ grad_s,
+                                                             double* __restrict__ partials, int planes, int D, int n,
+                                                             const VolGains gains, double kappa, double rmax_a1, double rmin, double q,
+                                                             double a, const VolSurface surface)
+{
+    __shared__ double lds[4][6];
+    double t[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    const long long plane_elems = (long long)n * n;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int gp = blockIdx.y, gi = gp / planes, p = gp - gi * planes;
+    if (e < plane_elems) {
+        const double f = surface.f[p % D], g = (double)gains.g[gi], kg = kappa * g;
+        const double xv = x[(size_t)p * plane_elems + e], gs = grad_s[(size_t)gp * plane_elems + e];
+        const double m = exp(-(kg * xv));
+        const double b = 1.0 - m;
+        if (b >= 0.0) {                                  // else a wall
+            double d[5];
+            mack_slowness_dparams(b, rmax_a1, rmin, q, a, f, d);
+            t[0] = gs * mack_slowness_dx(b, (g * xv) * m, rmax_a1, rmin, q, a, f);
+            for (int j = 0; j < 5; ++j) t[1 + j] = gs * d[j];
+        }
+    }
+    vol_block_sum<6>(t, lds);
+    if (threadIdx.x == 0) {
+        double* slot = partials + ((size_t)gp * gridDim.x + blockIdx.x) * 6;
+        for (int j = 0; j < 6; ++j) slot[j] = t[j];
+    }
+}
+
 }  // namespace litho
 
 extern "C" {
@@ -368,6 +402,72 @@ int litho_develop_rate_vjp(const float* x, int volumes, int D, int n, const floa
     LAUNCH_PACKED(k_develop_rate_vjp, wide, n, planes, (hipStream_t)stream, x, grad_slowness, grad_x, planes, D, n, gains, n_gains, kappa,
                   law.rmax_a1, law.rmin, law.q, law.a, law.surface);
     HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+size_t litho_develop_rate_params_work_bytes(int volumes, int D, int n, int n_gains)
+{
+    using namespace litho;
+    if (!volume_ok(volumes, D, n) || n_gains < 1 || n_gains > VOL_GAINS || (long long)volumes * n_gains * D > 65535) return 0;
+    return (size_t)n_gains * volumes * D * plane_blocks(n, 1) * 6 * sizeof(double);
+}
+
+int litho_develop_rate_vjp_params(const float* x, int volumes, int D, int n, const float* gains_host, int n_gains, double kappa, double r_max,
+                                  double r_min, double q, double m_th, double surface_rate, double surface_depth_nm, double thickness_nm,
+                                  const float* grad_slowness, double* plane_sums, void* work, size_t work_bytes, void* stream)
+{
+    using namespace litho;
+    VolGains gains;
+    MackLaw law;
+    if (!x || !grad_slowness || !plane_sums || !work || !volume_ok(volumes, D, n) || !make_gains(gains_host, n_gains, volumes, D, gains) ||
+        !finite_pos(kappa) || !make_mack(r_max, r_min, q, m_th, surface_rate, surface_depth_nm, thickness_nm, D, law))
+        return LITHO_E_ARG;
+    if (!aligned16(work) || !aligned16(plane_sums)) return LITHO_E_ARG;
+    const size_t need = litho_develop_rate_params_work_bytes(volumes, D, n, n_gains);
+    if (work_bytes < need) return LITHO_E_WORKSPACE;
+    const int planes = volumes * D;
+    const size_t x_bytes = (size_t)planes * n * n * sizeof(float), out_bytes = (size_t)n_gains * planes * 6 * sizeof(double);
+    if (overlap(plane_sums, out_bytes, x, x_bytes) || overlap(plane_sums, out_bytes, grad_slowness, x_bytes * n_gains) ||
+        overlap(plane_sums, out_bytes, work, need) || overlap(work, need, x, x_bytes) || overlap(work, need, grad_slowness, x_bytes * n_gains))
+        return LITHO_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned blocks = plane_blocks(n, 1);
+    hipLaunchKernelGGL(k_develop_rate_params, dim3(blocks, (unsigned)(n_gains * planes)), dim3(256), 0, st, x, grad_slowness, (double*)work,
+                       planes, D, n, gains, kappa, law.rmax_a1, law.rmin, law.q, law.a, law.surface);
+    hipLaunchKernelGGL(k_vol_total<6>, dim3((unsigned)(n_gains * planes)), dim3(256), 0, st, (const double*)work, (long long)blocks, plane_sums);
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+int litho_develop_rate_param_chain(double r_max, double r_min, double q, double m_th, double surface_rate, double surface_depth_nm,
+                                   double thickness_nm, int D, int groups, const double* plane_sums, double* grad_param)
+{
+    using namespace litho;
+    MackLaw law;
+    if (!plane_sums || !grad_param || groups < 1 || D < 1 || D > VOL_DMAX ||
+        !make_mack(r_max, r_min, q, m_th, surface_rate, surface_depth_nm, thickness_nm, D, law))
+        return LITHO_E_ARG;
+    const double a = law.a;
+    const double da_dq = a * (1.0 / (q + 1.0) - 1.0 / (q - 1.0) + std::log(1.0 - m_th)), da_dm = -q * a / (1.0 - m_th);
+    for (int g = 0; g < groups; ++g) {
+        double sum[4] = {0.0, 0.0, 0.0, 0.0}, s_a = 0.0, s_r0 = 0.0, s_delta = 0.0;       // kappa, R, rmin, q at fixed a
+        for (int d = 0; d < D; ++d) {                    // the planes in ascending order
+            const double* t = plane_sums + ((size_t)g * D + d) * 6;
+            for (int j = 0; j < 4; ++j) sum[j] += t[j];
+            s_a += t[4];
+            const double z = thickness_nm * (d + 0.5) / D, ez = std::exp(-z / surface_depth_nm);
+            s_r0 += t[5] * ez;                           // f = 1 - (1 - r0) exp(-z / delta)
+            s_delta += t[5] * (-(1.0 - surface_rate) * ez * z / (surface_depth_nm * surface_depth_nm));
+        }
+        double* out = grad_param + (size_t)g * 7;
+        out[0] = sum[0];
+        out[1] = sum[1] * (a + 1.0);                     // R = rmax (a + 1); the a slot already follows R through a
+        out[2] = sum[2];
+        out[3] = sum[3] + s_a * da_dq;
+        out[4] = s_a * da_dm;
+        out[5] = s_r0;
+        out[6] = s_delta;
+    }
     return LITHO_OK;
 }
 

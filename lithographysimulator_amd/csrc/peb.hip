@@ -11,6 +11,10 @@
 //   k_peb_taped       one bake step per launch through peb_step, without a, storing the step's (hd, qd) when a tape is given
 //   k_peb_adjoint     one backward step per launch: a thread per cell gathers (u, v) at the cell and its six neighbours
 //   k_peb_expose_vjp  gI = sum_g (C g) exp(-(C g) I) gh0[g] in double per cell
+// and behind litho_peb_bake_vjp_params and litho_peb_expose_vjp_params, the sums for the resist's parameters (section 2c):
+//   k_peb_adjoint_params  k_peb_adjoint plus the six step-parameter terms of the cell, added per workgroup into its own slot
+//   k_peb_expose_params   gh0 (g I) exp(-(C g) I) per cell, added per workgroup into its own slot
+//   k_vol_total           (resist_volume.hpp) the slots of a volume added in a fixed order
 // The arithmetic of a step is peb_step and nothing else: both bake kernels call it with the same inputs in the same order, so
 // the bits of a bake do not depend on how its steps are cut into launches.  expose and rate move four consecutive x per thread
 // (16-byte accesses) when n is a multiple of 4 and the pointers are 16-byte aligned, one otherwise.  The limits, the packs, the
@@ -280,6 +284,64 @@ __global__ __launch_bounds__(256) void k_peb_adjoint(const float* __restrict__ h
     qb_out[at] = qb;
 }
 
+// ---- 2c. the step-parameter sums of the backward sweep (litho_peb_bake_vjp_params; include/litho_abbe.h's "Gradients with respect
+// to the bake's parameters").  The workgroup's fixed-order sum and the closing kernel are resist_volume.hpp's (vol_block_sum,
+// k_vol_total).
+// k_peb_adjoint with the step's six parameter terms: the same two functions give (hbar_k, qbar_k), so their bits are
+// k_peb_adjoint's.  h, q: the state at the start of the step (q == nullptr: the first step, q uniform, its Laplacians 0).  The
+// terms are formed in double from the fp32 operands; thread 0 adds the workgroup's six sums into the workgroup's own slot
+// partials[blockIdx.y][blockIdx.x][6] -- the backward steps are successive launches on one stream, so a slot's additions come in
+// the order k = S-1 .. 0.  A thread without a cell contributes zeros and still takes part in the sum.
+__global__ __launch_bounds__(256) void k_peb_adjoint_params(const float* __restrict__ hb_in, const float* __restrict__ qb_in,
+                                                            const float* __restrict__ abar, const float* __restrict__ h,
+                                                            const float* __restrict__ q, const float* __restrict__ hd,
+                                                            const float* __restrict__ qd, float* __restrict__ hb_out,
+                                                            float* __restrict__ qb_out, double* __restrict__ partials, int D, int n,
+                                                            const PebStep P)
+{
+    __shared__ double lds[4][6];
+    double t[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    PebCell cell;
+    if (peb_cell(D, n, cell)) {
+        const size_t at = cell.at;
+        const long long off[7] = {0, cell.w, cell.e, cell.s, cell.n, cell.u, cell.d};
+        auto uv = [&](int i) -> PebUV {
+            const size_t c = (size_t)((long long)at + off[i]);
+            const float hp = (hb_in ? hb_in[c] : 0.f) + P.half_dt * (abar ? abar[c] : 0.f);
+            return peb_react_adjoint(P, hp, qb_in ? qb_in[c] : 0.f, hd[c], qd[c]);
+        };
+        float hb, qb;
+        peb_step_adjoint(P, uv, P.half_dt * (abar ? abar[at] : 0.f), hb, qb);
+        hb_out[at] = hb;
+        qb_out[at] = qb;
+        const PebUV c = uv(0);
+        const double hp = (hb_in ? hb_in[at] : 0.f) + P.half_dt * (abar ? abar[at] : 0.f);   // the fp32 hp of uv(0), widened
+        const double qbk = qb_in ? qb_in[at] : 0.f, hdc = hd[at], qdc = qd[at], fl = P.fl;
+        auto laplacians = [&](const float* x, double w, int j) {
+            const PebNb b = peb_around(x + at, cell);
+            const double x0 = x[at];
+            t[j] = w * ((((double)b.w + (double)b.e) + ((double)b.s + (double)b.n)) - 4.0 * x0);
+            t[j + 1] = w * (((double)b.u + (double)b.d) - 2.0 * x0);
+        };
+        if (P.diffuse_h) laplacians(h, (double)c.u, 0);
+        if (P.diffuse_q && q) laplacians(q, (double)c.v, 2);
+        double R;
+        if (P.instant) {
+            R = (hdc < qdc) ? hdc : qdc;                  // the forward's own comparison; no beta in it
+        } else {
+            const double beta = P.beta, Dn = 1.0 + beta * (hdc + qdc);
+            R = beta * hdc * qdc / Dn;
+            t[4] = -(fl * hp + qbk) * (hdc * qdc) / (Dn * Dn);
+        }
+        t[5] = hp * (hdc - R);
+    }
+    vol_block_sum<6>(t, lds);
+    if (threadIdx.x == 0) {
+        double* slot = partials + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 6;
+        for (int j = 0; j < 6; ++j) slot[j] = slot[j] + t[j];
+    }
+}
+
 // The exposure's VJP: gI = sum_g (C g) exp(-(C g) I) gh0[g], the gains in ascending order, double per cell, rounded once.
 template <int VEC>
 __global__ __launch_bounds__(256) void k_peb_expose_vjp(const float* __restrict__ image, const float* __restrict__ grad_acid,
@@ -301,6 +363,26 @@ __global__ __launch_bounds__(256) void k_peb_expose_vjp(const float* __restrict_
     Pack<VEC> out;
     for (int v = 0; v < VEC; ++v) out.v[v] = (float)sum[v];
     store_pack<VEC>(grad_image + (size_t)p * plane_elems + e, out);
+}
+
+// The exposure's parameter sum (litho_peb_expose_vjp_params): per cell of a gained plane gh0 (g I) exp(-(C g) I), the derivative of
+// h0 with respect to C times its cotangent, in double; a cell whose acid is NaN (1 - exp negative or NaN) contributes 0.  The
+// workgroup's sum goes to its own slot partials[gained plane][workgroup]; grid.y: the n_gains x planes gained planes.
+__global__ __launch_bounds__(256) void k_peb_expose_params(const float* __restrict__ image, const float* __restrict__ grad_acid,
+                                                           double* __restrict__ partials, int planes, int n, const VolGains gains, double C)
+{
+    __shared__ double lds[4][1];
+    double t[1] = {0.0};
+    const long long plane_elems = (long long)n * n;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int gp = blockIdx.y, gi = gp / planes, p = gp - gi * planes;
+    if (e < plane_elems) {
+        const double g = (double)gains.g[gi], Cg = C * g, I = image[(size_t)p * plane_elems + e];
+        const double ex = exp(-(Cg * I));
+        if (1.0 - ex >= 0.0) t[0] = (double)grad_acid[(size_t)gp * plane_elems + e] * ((g * I) * ex);
+    }
+    vol_block_sum<1>(t, lds);
+    if (threadIdx.x == 0) partials[(size_t)gp * gridDim.x + blockIdx.x] = t[0];
 }
 
 // ---- 3. rate: m = exp(-kAmp a), then mack_slowness of 1 - m with the surface factor of the plane (resist_volume.hpp, the
@@ -383,6 +465,137 @@ static PebStep step_of(double thickness_nm, double pixel_nm, double k_quench, do
 // the workspace of litho_peb_bake_vjp in volumes: the checkpoints (h, q) at c, 2 c, ... < S, one segment's tape (hd, qd) of c steps,
 // the ping-pong of the re-run's (h, q) and the ping-pong of (hbar, qbar)
 static size_t vjp_volumes(int steps, int c) { return 2 * (size_t)((steps + c - 1) / c - 1) + 2 * (size_t)c + 8; }
+// the workspace of litho_peb_bake_vjp_params: its tape keeps four volumes per step -- (hd, qd) and the state (h, q) after the
+// step, which is the next step's state at its start -- and behind the volumes, on a 16-byte boundary, one slot of six doubles per
+// workgroup of a backward launch
+static size_t vjp_params_volumes(int steps, int c) { return 2 * (size_t)((steps + c - 1) / c - 1) + 4 * (size_t)c + 8; }
+static size_t vjp_params_slots(int B, int D, int n) { return (size_t)B * D * plane_blocks(n, 1); }
+static size_t vjp_params_tape_bytes(int B, int D, int n, int steps, int c)
+{
+    return (vjp_params_volumes(steps, c) * ((size_t)B * D * n * n * sizeof(float)) + 15) & ~(size_t)15;
+}
+
+// litho_peb_bake_vjp (grad_step == nullptr) and litho_peb_bake_vjp_params behind one set of checks and one sweep.  The forward
+// launches and the arithmetic of the backward steps are the same in both, so grad_acid_in and grad_quencher_in have the same bits.
+static int bake_vjp_run(const float* acid_in, int B, int D, int n, double thickness_nm, double pixel_nm, double quencher0, double k_quench,
+                        double k_loss, double sigma_acid_nm, double sigma_quencher_nm, double vertical_scale, double bake_time_s, int steps,
+                        int checkpoint_every, const float* grad_acid, const float* grad_quencher, const float* grad_acid_dose,
+                        float* grad_acid_in, float* grad_quencher_in, double* grad_step, bool params, void* work, size_t work_bytes,
+                        void* stream)
+{
+    if (!acid_in || !grad_acid_in || !work || (params && !grad_step) || !volume_ok(B, D, n)) return LITHO_E_ARG;
+    if (!grad_acid && !grad_quencher && !grad_acid_dose) return LITHO_E_ARG;
+    if (!finite_nonneg(quencher0) || !(k_quench >= 0.0) || !finite_nonneg(k_loss) || !finite_pos(bake_time_s)) return LITHO_E_ARG;
+    const int least = min_steps(sigma_acid_nm, sigma_quencher_nm, vertical_scale, thickness_nm, D, pixel_nm);
+    if (least == 0 || steps < least || steps > PEB_MAXSTEPS) return LITHO_E_ARG;
+    const int c = checkpoint_every;
+    if (c < 1 || c > steps) return LITHO_E_ARG;
+    const size_t V = (size_t)B * D * n * n, vol_bytes = V * sizeof(float);
+    const size_t slots = params ? vjp_params_slots(B, D, n) : 0, tape_bytes = params ? vjp_params_tape_bytes(B, D, n, steps, c) : 0;
+    const size_t need = params ? tape_bytes + slots * 6 * sizeof(double) : vjp_volumes(steps, c) * vol_bytes;
+    const size_t step_bytes = (size_t)B * 6 * sizeof(double);
+    if (!aligned16(work) || (params && !aligned16(grad_step))) return LITHO_E_ARG;
+    if (work_bytes < need) return LITHO_E_WORKSPACE;
+    // the outputs may overlap neither an input, nor the workspace, nor each other; the inputs are only read
+    const void* ins[4] = {acid_in, grad_acid, grad_quencher, grad_acid_dose};
+    const void* outs[2] = {grad_acid_in, grad_quencher_in};
+    for (int o = 0; o < 2; ++o) {
+        if (!outs[o]) continue;
+        for (int i = 0; i < 4; ++i)
+            if (ins[i] && overlap(outs[o], vol_bytes, ins[i], vol_bytes)) return LITHO_E_ARG;
+        if (overlap(outs[o], vol_bytes, work, need)) return LITHO_E_ARG;
+        if (params && overlap(outs[o], vol_bytes, grad_step, step_bytes)) return LITHO_E_ARG;
+    }
+    if (grad_quencher_in && overlap(grad_acid_in, vol_bytes, grad_quencher_in, vol_bytes)) return LITHO_E_ARG;
+    for (int i = 0; i < 4; ++i) {
+        if (ins[i] && overlap(ins[i], vol_bytes, work, need)) return LITHO_E_ARG;
+        if (params && ins[i] && overlap(ins[i], vol_bytes, grad_step, step_bytes)) return LITHO_E_ARG;
+    }
+    if (params && overlap(grad_step, step_bytes, work, need)) return LITHO_E_ARG;
+    const PebStep P = step_of(thickness_nm, pixel_nm, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps);
+    const float q0 = (float)quencher0;
+    if (std::isinf(q0) || std::isinf(P.half_dt)) return LITHO_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int nc = (steps + c - 1) / c;                   // segments; checkpoint j = (h, q) at step j c, j = 1 .. nc - 1, kept in work
+    const size_t per = params ? 4 : 2;                    // tape volumes per step
+    float* base = (float*)work;
+    auto ck_h = [&](int j) { return base + (size_t)(2 * (j - 1)) * V; };
+    auto ck_q = [&](int j) { return base + (size_t)(2 * (j - 1) + 1) * V; };
+    float* tape = base + (size_t)(2 * (nc - 1)) * V;      // step i of the segment: hd at tape + per i V, qd one volume on; with
+                                                          // params the state after the step in the two volumes behind them
+    float* state = tape + (per * c) * V;                  // (h, q) x 2
+    float* bar = state + 4 * V;                           // (hbar, qbar) x 2
+    double* partials = params ? (double*)((char*)work + tape_bytes) : nullptr;
+    if (params) HIP_TRY(hipMemsetAsync(partials, 0, slots * 6 * sizeof(double), st));
+    const dim3 grid(plane_blocks(n, 1), (unsigned)(B * D)), block(256);
+    // the forward sweep to the last checkpoint: step k writes checkpoint (k + 1) / c when k + 1 is a multiple of c
+    const float *src_h = acid_in, *src_q = nullptr;
+    for (int k = 0; k < (nc - 1) * c; ++k) {
+        const bool keep = (k + 1) % c == 0;
+        float* to_h = keep ? ck_h((k + 1) / c) : state + (size_t)(2 * (k & 1)) * V;
+        float* to_q = keep ? ck_q((k + 1) / c) : to_h + V;
+        hipLaunchKernelGGL(k_peb_taped, grid, block, 0, st, src_h, src_q, q0, to_h, to_q, (float*)nullptr, (float*)nullptr, D, n, P);
+        src_h = to_h;
+        src_q = to_q;
+    }
+    // the segments last to first: the taped steps from the checkpoint, then their backward steps
+    const float *hb = grad_acid, *qb = grad_quencher;
+    int flip = 0;
+    for (int j = nc - 1; j >= 0; --j) {
+        const int k0 = j * c, k1 = (k0 + c < steps) ? k0 + c : steps;
+        const float *seg_h = j ? ck_h(j) : acid_in, *seg_q = j ? ck_q(j) : nullptr;
+        src_h = seg_h;
+        src_q = seg_q;
+        for (int k = k0; k < k1; ++k) {
+            const bool last = k + 1 == k1;                // its new state is the next checkpoint, or of no use
+            float* t = tape + (per * (k - k0)) * V;
+            float* to_h = last ? nullptr : (params ? t + 2 * V : state + (size_t)(2 * ((k - k0) & 1)) * V);
+            float* to_q = last ? nullptr : to_h + V;
+            hipLaunchKernelGGL(k_peb_taped, grid, block, 0, st, src_h, src_q, q0, to_h, to_q, t, t + V, D, n, P);
+            src_h = to_h;
+            src_q = to_q;
+        }
+        for (int k = k1 - 1; k >= k0; --k) {
+            float* to_h = k == 0 ? grad_acid_in : bar + (size_t)(2 * flip) * V;
+            float* to_q = (k == 0 && grad_quencher_in) ? grad_quencher_in : bar + (size_t)(2 * flip + 1) * V;
+            const float* t = tape + (per * (k - k0)) * V;
+            if (params) {
+                const float* at_h = k == k0 ? seg_h : t - 2 * V;           // the state at the start of step k
+                const float* at_q = k == k0 ? seg_q : t - V;
+                hipLaunchKernelGGL(k_peb_adjoint_params, grid, block, 0, st, hb, qb, grad_acid_dose, at_h, at_q, t, t + V, to_h, to_q,
+                                   partials, D, n, P);
+            } else {
+                hipLaunchKernelGGL(k_peb_adjoint, grid, block, 0, st, hb, qb, grad_acid_dose, t, t + V, to_h, to_q, D, n, P);
+            }
+            hb = to_h;
+            qb = to_q;
+            flip ^= 1;
+        }
+    }
+    if (params)
+        hipLaunchKernelGGL(k_vol_total<6>, dim3((unsigned)B), block, 0, st, (const double*)partials,
+                           (long long)D * (long long)plane_blocks(n, 1), grad_step);
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+// d(step parameters) / d(physical parameters) of step_of's formulas at a fixed step count, in double: lxy = sigma^2 / (2 S pixel^2),
+// lz = (v sigma)^2 / (2 S hz^2), beta = k_quench dt, fl = exp(-k_loss dt).  Written so that a zero length or scale gives 0, not 0 / 0.
+static void param_chain(double thickness_nm, double pixel_nm, double k_quench, double k_loss, double sigma_acid_nm, double sigma_quencher_nm,
+                        double vertical_scale, double bake_time_s, int D, int steps, const double* g, double* out)
+{
+    const double hz = thickness_nm / D, dt = bake_time_s / steps, S = steps;
+    const double dxy_h = sigma_acid_nm / (S * (pixel_nm * pixel_nm)), dxy_q = sigma_quencher_nm / (S * (pixel_nm * pixel_nm));
+    const double vv = vertical_scale * vertical_scale / (S * (hz * hz));
+    const double dz_h = vv * sigma_acid_nm, dz_q = vv * sigma_quencher_nm;
+    const double dv_h = vertical_scale * sigma_acid_nm * sigma_acid_nm / (S * (hz * hz));
+    const double dv_q = vertical_scale * sigma_quencher_nm * sigma_quencher_nm / (S * (hz * hz));
+    out[0] = std::isinf(k_quench) ? 0.0 : g[4] * dt;
+    out[1] = g[5] * (-dt * std::exp(-k_loss * dt));
+    out[2] = g[0] * dxy_h + g[1] * dz_h;
+    out[3] = g[2] * dxy_q + g[3] * dz_q;
+    out[4] = g[1] * dv_h + g[3] * dv_q;
+}
 
 }  // namespace litho
 
@@ -490,77 +703,40 @@ int litho_peb_bake_vjp(const float* acid_in, int B, int D, int n, double thickne
                        float* grad_acid_in, float* grad_quencher_in, void* work, size_t work_bytes, void* stream)
 {
     using namespace litho;
-    if (!acid_in || !grad_acid_in || !work || !volume_ok(B, D, n)) return LITHO_E_ARG;
-    if (!grad_acid && !grad_quencher && !grad_acid_dose) return LITHO_E_ARG;
-    if (!finite_nonneg(quencher0) || !(k_quench >= 0.0) || !finite_nonneg(k_loss) || !finite_pos(bake_time_s)) return LITHO_E_ARG;
+    return bake_vjp_run(acid_in, B, D, n, thickness_nm, pixel_nm, quencher0, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale,
+                        bake_time_s, steps, checkpoint_every, grad_acid, grad_quencher, grad_acid_dose, grad_acid_in, grad_quencher_in,
+                        nullptr, false, work, work_bytes, stream);
+}
+
+size_t litho_peb_vjp_params_work_bytes(int B, int D, int n, int steps, int checkpoint_every)
+{
+    using namespace litho;
+    if (!volume_ok(B, D, n) || steps < 1 || steps > PEB_MAXSTEPS || checkpoint_every < 1 || checkpoint_every > steps) return 0;
+    return vjp_params_tape_bytes(B, D, n, steps, checkpoint_every) + vjp_params_slots(B, D, n) * 6 * sizeof(double);
+}
+
+int litho_peb_bake_vjp_params(const float* acid_in, int B, int D, int n, double thickness_nm, double pixel_nm, double quencher0,
+                              double k_quench, double k_loss, double sigma_acid_nm, double sigma_quencher_nm, double vertical_scale,
+                              double bake_time_s, int steps, int checkpoint_every, const float* grad_acid, const float* grad_quencher,
+                              const float* grad_acid_dose, float* grad_acid_in, float* grad_quencher_in, double* grad_step, void* work,
+                              size_t work_bytes, void* stream)
+{
+    using namespace litho;
+    return bake_vjp_run(acid_in, B, D, n, thickness_nm, pixel_nm, quencher0, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale,
+                        bake_time_s, steps, checkpoint_every, grad_acid, grad_quencher, grad_acid_dose, grad_acid_in, grad_quencher_in,
+                        grad_step, true, work, work_bytes, stream);
+}
+
+int litho_peb_param_chain(double thickness_nm, double pixel_nm, double k_quench, double k_loss, double sigma_acid_nm,
+                          double sigma_quencher_nm, double vertical_scale, double bake_time_s, int D, int steps, const double* grad_step,
+                          double* grad_param)
+{
+    using namespace litho;
+    if (!grad_step || !grad_param || !(k_quench >= 0.0) || !finite_nonneg(k_loss) || !finite_pos(bake_time_s) || !finite_pos(pixel_nm)) return LITHO_E_ARG;
     const int least = min_steps(sigma_acid_nm, sigma_quencher_nm, vertical_scale, thickness_nm, D, pixel_nm);
     if (least == 0 || steps < least || steps > PEB_MAXSTEPS) return LITHO_E_ARG;
-    const int c = checkpoint_every;
-    if (c < 1 || c > steps) return LITHO_E_ARG;
-    const size_t V = (size_t)B * D * n * n, vol_bytes = V * sizeof(float), need = vjp_volumes(steps, c) * vol_bytes;
-    if (!aligned16(work)) return LITHO_E_ARG;
-    if (work_bytes < need) return LITHO_E_WORKSPACE;
-    // the outputs may overlap neither an input, nor the workspace, nor each other; the inputs are only read
-    const void* ins[4] = {acid_in, grad_acid, grad_quencher, grad_acid_dose};
-    const void* outs[2] = {grad_acid_in, grad_quencher_in};
-    for (int o = 0; o < 2; ++o) {
-        if (!outs[o]) continue;
-        for (int i = 0; i < 4; ++i)
-            if (ins[i] && overlap(outs[o], vol_bytes, ins[i], vol_bytes)) return LITHO_E_ARG;
-        if (overlap(outs[o], vol_bytes, work, need)) return LITHO_E_ARG;
-    }
-    if (grad_quencher_in && overlap(grad_acid_in, vol_bytes, grad_quencher_in, vol_bytes)) return LITHO_E_ARG;
-    for (int i = 0; i < 4; ++i)
-        if (ins[i] && overlap(ins[i], vol_bytes, work, need)) return LITHO_E_ARG;
-    const PebStep P = step_of(thickness_nm, pixel_nm, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps);
-    const float q0 = (float)quencher0;
-    if (std::isinf(q0) || std::isinf(P.half_dt)) return LITHO_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const int nc = (steps + c - 1) / c;                   // segments; checkpoint j = (h, q) at step j c, j = 1 .. nc - 1, kept in work
-    float* base = (float*)work;
-    auto ck_h = [&](int j) { return base + (size_t)(2 * (j - 1)) * V; };
-    auto ck_q = [&](int j) { return base + (size_t)(2 * (j - 1) + 1) * V; };
-    float* tape = base + (size_t)(2 * (nc - 1)) * V;      // step i of the segment: hd at tape + 2 i V, qd one volume on
-    float* state = tape + (size_t)(2 * c) * V;            // (h, q) x 2
-    float* bar = state + 4 * V;                           // (hbar, qbar) x 2
-    const dim3 grid(plane_blocks(n, 1), (unsigned)(B * D)), block(256);
-    // the forward sweep to the last checkpoint: step k writes checkpoint (k + 1) / c when k + 1 is a multiple of c
-    const float *src_h = acid_in, *src_q = nullptr;
-    for (int k = 0; k < (nc - 1) * c; ++k) {
-        const bool keep = (k + 1) % c == 0;
-        float* to_h = keep ? ck_h((k + 1) / c) : state + (size_t)(2 * (k & 1)) * V;
-        float* to_q = keep ? ck_q((k + 1) / c) : to_h + V;
-        hipLaunchKernelGGL(k_peb_taped, grid, block, 0, st, src_h, src_q, q0, to_h, to_q, (float*)nullptr, (float*)nullptr, D, n, P);
-        src_h = to_h;
-        src_q = to_q;
-    }
-    // the segments last to first: the taped steps from the checkpoint, then their backward steps
-    const float *hb = grad_acid, *qb = grad_quencher;
-    int flip = 0;
-    for (int j = nc - 1; j >= 0; --j) {
-        const int k0 = j * c, k1 = (k0 + c < steps) ? k0 + c : steps;
-        src_h = j ? ck_h(j) : acid_in;
-        src_q = j ? ck_q(j) : nullptr;
-        for (int k = k0; k < k1; ++k) {
-            const bool last = k + 1 == k1;                // its new state is the next checkpoint, or of no use
-            float* to_h = last ? nullptr : state + (size_t)(2 * ((k - k0) & 1)) * V;
-            float* to_q = last ? nullptr : to_h + V;
-            float* t = tape + (size_t)(2 * (k - k0)) * V;
-            hipLaunchKernelGGL(k_peb_taped, grid, block, 0, st, src_h, src_q, q0, to_h, to_q, t, t + V, D, n, P);
-            src_h = to_h;
-            src_q = to_q;
-        }
-        for (int k = k1 - 1; k >= k0; --k) {
-            float* to_h = k == 0 ? grad_acid_in : bar + (size_t)(2 * flip) * V;
-            float* to_q = (k == 0 && grad_quencher_in) ? grad_quencher_in : bar + (size_t)(2 * flip + 1) * V;
-            const float* t = tape + (size_t)(2 * (k - k0)) * V;
-            hipLaunchKernelGGL(k_peb_adjoint, grid, block, 0, st, hb, qb, grad_acid_dose, t, t + V, to_h, to_q, D, n, P);
-            hb = to_h;
-            qb = to_q;
-            flip ^= 1;
-        }
-    }
-    HIP_TRY(hipGetLastError());
+    param_chain(thickness_nm, pixel_nm, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps, grad_step,
+                grad_param);
     return LITHO_OK;
 }
 
@@ -577,6 +753,39 @@ int litho_peb_expose_vjp(const float* image, int volumes, int D, int n, const fl
     const int planes = volumes * D;
     const bool wide = (n & 3) == 0 && aligned16(image) && aligned16(grad_acid) && aligned16(grad_image);
     LAUNCH_PACKED(k_peb_expose_vjp, wide, n, planes, (hipStream_t)stream, image, grad_acid, grad_image, planes, n, gains, n_gains, C);
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+size_t litho_peb_expose_params_work_bytes(int volumes, int D, int n, int n_gains)
+{
+    using namespace litho;
+    if (!volume_ok(volumes, D, n) || n_gains < 1 || n_gains > VOL_GAINS || (long long)volumes * n_gains * D > 65535) return 0;
+    return (size_t)n_gains * volumes * D * plane_blocks(n, 1) * sizeof(double);
+}
+
+int litho_peb_expose_vjp_params(const float* image, int volumes, int D, int n, const float* gains_host, int n_gains, double C,
+                                const float* grad_acid, double* grad_C, void* work, size_t work_bytes, void* stream)
+{
+    using namespace litho;
+    VolGains gains;
+    if (!image || !grad_acid || !grad_C || !work || !volume_ok(volumes, D, n) || !make_gains(gains_host, n_gains, volumes, D, gains) ||
+        !finite_pos(C))
+        return LITHO_E_ARG;
+    if (!aligned16(work) || !aligned16(grad_C)) return LITHO_E_ARG;
+    const size_t need = litho_peb_expose_params_work_bytes(volumes, D, n, n_gains);
+    if (work_bytes < need) return LITHO_E_WORKSPACE;
+    const size_t in_bytes = (size_t)volumes * D * n * n * sizeof(float), out_bytes = (size_t)n_gains * volumes * sizeof(double);
+    if (overlap(grad_C, out_bytes, image, in_bytes) || overlap(grad_C, out_bytes, grad_acid, in_bytes * n_gains) ||
+        overlap(grad_C, out_bytes, work, need) || overlap(work, need, image, in_bytes) || overlap(work, need, grad_acid, in_bytes * n_gains))
+        return LITHO_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int planes = volumes * D;
+    const unsigned blocks = plane_blocks(n, 1);
+    hipLaunchKernelGGL(k_peb_expose_params, dim3(blocks, (unsigned)(n_gains * planes)), dim3(256), 0, st, image, grad_acid, (double*)work,
+                       planes, n, gains, C);
+    hipLaunchKernelGGL(k_vol_total<1>, dim3((unsigned)(n_gains * volumes)), dim3(256), 0, st, (const double*)work,
+                       (long long)D * (long long)blocks, grad_C);
     HIP_TRY(hipGetLastError());
     return LITHO_OK;
 }

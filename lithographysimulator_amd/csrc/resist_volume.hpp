@@ -142,6 +142,56 @@ __device__ __forceinline__ double mack_slowness_dx(double b, double db, double r
     return -(s * s) * f * (rmax_a1 * a / ((a + X) * (a + X))) * dX;
 }
 
+// The derivatives of s = 1 / r with respect to the rate law's own numbers, for b >= 0 (the caller skips a wall), R = rmax (a + 1):
+//   d[0] ds/dR     = -s^2 f X / (a + X)                        at fixed a
+//   d[1] ds/drmin  = -s^2 f
+//   d[2] ds/dq     = -s^2 f R a / (a + X)^2 X ln b             at fixed a; 0 at b = 0
+//   d[3] ds/da     = -s^2 f (R / (a + 1)) X (X - 1) / (a + X)^2  at fixed rmax = R / (a + 1), R following a
+//   d[4] ds/df     = -s / f
+__device__ __forceinline__ void mack_slowness_dparams(double b, double rmax_a1, double rmin, double q, double a, double f, double (&d)[5])
+{
+    const double X = pow(b, q), aX = a + X;
+    const double r = (rmax_a1 * X / aX + rmin) * f;
+    const double s = 1.0 / r, ssf = (s * s) * f;
+    d[0] = -ssf * (X / aX);
+    d[1] = -ssf;
+    d[2] = (b > 0.0) ? -ssf * (rmax_a1 * a / (aX * aX)) * (X * log(b)) : 0.0;
+    d[3] = -ssf * (rmax_a1 / (a + 1.0)) * (X * (X - 1.0) / (aX * aX));
+    d[4] = -(s / f);
+}
+
+// ---- sums without atomics (the parameter reductions of peb.hip and develop_grad.hip).  vol_block_sum: the N doubles of each
+// thread of a 256-thread workgroup added in one fixed tree -- within a wave of 64 by shuffles from the upper half onto the lower
+// (32, 16, .. 1), then the four waves in ascending order through LDS by thread 0, whose t[] holds the sums on return.  Every
+// thread of the workgroup must call it.
+template <int N>
+__device__ __forceinline__ void vol_block_sum(double (&t)[N], double (*lds)[N])
+{
+    for (int j = 0; j < N; ++j)
+        for (int off = 32; off >= 1; off >>= 1) t[j] = t[j] + __shfl_down(t[j], off, 64);
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+        for (int j = 0; j < N; ++j) lds[wave][j] = t[j];
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int j = 0; j < N; ++j) t[j] = ((lds[0][j] + lds[1][j]) + lds[2][j]) + lds[3][j];
+}
+// out[g][N] = the sum of the `count` consecutive slots [N] of group g = blockIdx.x: thread i adds the slots i, i + 256, ... in
+// ascending order, then the tree of vol_block_sum.  The order is fixed by `count` alone.
+template <int N>
+__global__ __launch_bounds__(256) void k_vol_total(const double* __restrict__ partials, long long count, double* __restrict__ out)
+{
+    __shared__ double lds[4][N];
+    double t[N];
+    for (int j = 0; j < N; ++j) t[j] = 0.0;
+    const double* mine = partials + (size_t)blockIdx.x * (size_t)count * N;
+    for (long long i = threadIdx.x; i < count; i += 256)
+        for (int j = 0; j < N; ++j) t[j] = t[j] + mine[i * N + j];
+    vol_block_sum<N>(t, lds);
+    if (threadIdx.x == 0)
+        for (int j = 0; j < N; ++j) out[(size_t)blockIdx.x * N + j] = t[j];
+}
+
 // ---- the host loop of the tiled solvers (k_develop_time, k_develop_time_vjp).  enqueue(it) puts launch it = 0, 1, ... on `st`;
 // launch `it` stores 1 into flags[it] when it changed a cell.  The flag words are zeroed up front; the launches go out in groups
 // of VOL_CHECK, each group followed by one copy-back of its flag words and one synchronise.  Returns the number of launches up

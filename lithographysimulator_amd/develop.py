@@ -22,7 +22,8 @@ either kind of resist; `ilt.developedResistModel` hands that to `optimizeMask`. 
 where the two neighbours of an axis tie, the gradient is a valid but one-sided subgradient (the tie goes to the lower index).
 
 NOT built: bleaching (Dill A, B: the intensity is taken as given), development of anything but one layer, the gradient of
-`developedDepth`, gradients with respect to the resist's parameters, a fused or coarser-grained backward solver."""
+`developedDepth`, the gradients of a MackResist's own Gaussian diffusion lengths (the other resist parameters: calibrate.py), a
+fused or coarser-grained backward solver."""
 import ctypes
 import math
 

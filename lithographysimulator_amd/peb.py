@@ -14,8 +14,10 @@ scheme, for a loss on the acid, the quencher, the acid dose or the inhibitor aft
 forward sweep, then one backward step per launch); `ilt.bakedResistModel` hands them to `optimizeMask`.  `amplifiedRateGradient` is amplifiedRate backwards, the link from
 develop.py's gradients through development (`resistProfileGradient`, `ilt.developedResistModel`) to the bake's.
 
-NOT built: bleaching, a diffusivity that depends on the deprotection, gradients with respect to resist parameters other than
-the quencher loading."""
+Gradients with respect to the resist's own parameters (kQuench, kLoss, the diffusion lengths, verticalScale, kAmp, C) and the
+calibration loop built on them are in calibrate.py.
+
+NOT built: bleaching, a diffusivity that depends on the deprotection."""
 import math
 
 import torch
