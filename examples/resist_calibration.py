@@ -1,13 +1,14 @@
 """Calibrating a chemically amplified resist to CDs measured through dose and focus, on one MI355X.
 
     python examples/resist_calibration.py [--n 32] [--depths 4] [--pixel 10] [--thickness 80] [--time 20] [--iterations 40]
-                                          [--off 1.2] [--parameters kAmp acidDiffusionLength]
+                                          [--off 1.2] [--parameters kAmp acidDiffusionLength] [--method descent|lm]
 
 A synthetic experiment.  The intensity is a line/space grating with a standing wave through the depth at two focus settings (the
 second with less contrast), exposed at three doses.  A KNOWN resist prints it; the widths of the developed space at every dose,
 focus and depth are the "measured" CDs.  The fit then starts from the same resist with the chosen parameters multiplied by
 `--off` and runs calibrateResist: steepest descent with backtracking on the mean of (T / developTime - 1)^2 at the measured edges,
 the gradient coming from resistParameterGradient's chain (development front -> rate law -> bake -> exposure, all in HIP).
+`--method lm` takes Levenberg-Marquardt steps instead, on the Jacobian of the edge residuals from the forward mode (tangent.py).
 
 It prints the measured CDs, the loss and the parameters before and after, the accepted steps, and the CDs the fitted resist
 prints next to the measured ones."""
@@ -41,6 +42,7 @@ def main():
     ap.add_argument("--iterations", type=int, default=40)
     ap.add_argument("--off", type=float, default=1.2, help="the factor on every fitted parameter at the start")
     ap.add_argument("--parameters", nargs="+", default=["kAmp", "acidDiffusionLength"])
+    ap.add_argument("--method", choices=("descent", "lm"), default="descent")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     n, D, F, doses = a.n, a.depths, 2, (0.8, 1.0, 1.25)
@@ -62,11 +64,11 @@ def main():
             print(f"   dose {dose:4.2f} focus {fi}: " + " ".join(f"{cds[di, fi, d, 0]:7.2f}" for d in range(D)))
     start = L.resistWith(truth, **{k: a.off * L.resistParameter(truth, k) for k in a.parameters})
     fitted, history = L.calibrateResist(image, start, a.thickness, a.pixel, a.time, measurements, parameters=a.parameters, doses=doses,
-                                        focalPlanes=F, iterations=a.iterations, steps=steps)
+                                        focalPlanes=F, iterations=a.iterations, steps=steps, method=a.method)
     accepted = [h for h in history if h["accepted"]]
     print(f"-- {len(history)} evaluations, {len(accepted)} accepted")
     for h in accepted:
-        print(f"   loss {h['loss']:.4e}  step {h['step']:.4f}  " + "  ".join(f"{k} {v:.5g}" for k, v in h["parameters"].items()))
+        print(f"   loss {h['loss']:.4e}  step {h['step']:.4f}  " + (f"damping {h['damping']:.0e}  " if "damping" in h else "") + "  ".join(f"{k} {v:.5g}" for k, v in h["parameters"].items()))
     print(f"-- loss {history[0]['loss']:.4e} -> {accepted[-1]['loss']:.4e}")
     for k in a.parameters:
         print(f"   {k}: start {L.resistParameter(start, k):.5g}, fitted {L.resistParameter(fitted, k):.5g}, known {L.resistParameter(truth, k):.5g}")

@@ -786,6 +786,83 @@ int litho_develop_rate_vjp_params(const float *x, int volumes, int D, int n, con
 int litho_develop_rate_param_chain(double r_max, double r_min, double q, double m_th, double surface_rate, double surface_depth_nm,
                                    double thickness_nm, int D, int groups, const double *plane_sums, double *grad_param);
 
+/* ---- Forward mode (tangents) of the resist chain (csrc/peb.hip, csrc/develop_grad.hip; checked against the float64 restatement
+ * tests/resist_tangent_oracle.py, itself pinned to central differences of the forward oracles and to the adjoint oracles by
+ * <g, J v> = <J^T g, v>).  Each call is the tangent-linear twin of one adjoint call above and carries P directions,
+ * 1 <= P <= LITHO_TANGENT_MAX; direction-major volumes are fp32 [P, B, D, n, n] and P B D <= 65535.  A direction alone has the
+ * bits of that direction inside a batch of P, a volume alone the bits of that volume inside a batch of B, two calls the same
+ * bits.  No atomics, no allocation.  The checks are those of the adjoint twin: LITHO_E_ARG before any GPU call, LITHO_E_WORKSPACE
+ * for too little workspace; an output overlaps no input, no other output and no workspace (LITHO_E_ARG).
+ *
+ * litho_peb_expose_jvp: the tangent of litho_peb_expose for the directions (dC_p, dI_p), dC HOST doubles [P], dimage device fp32
+ * [P, volumes, D, n, n] or NULL = 0:
+ *   dacid[p][gain][cell] = exp(-(C g) I) ((g I) dC_p + (C g) dI_p),
+ * in double per cell, rounded once; exactly 0 where the acid is NaN (1 - exp negative or NaN), whatever dimage holds there.
+ * dacid fp32 [P, n_gains volumes, D, n, n], gain-major inside a direction like litho_peb_expose's acid.
+ *
+ * litho_peb_bake_jvp: the S bake steps of litho_peb_bake with their tangent, one step per launch, a thread per cell with the primal
+ * and all P tangents.  The primal goes through the forward's own step function: acid, quencher, acid_dose (each fp32 [B,D,n,n] or
+ * NULL = not written) are litho_peb_bake's bits.  Per direction p: dacid_in device fp32 [P,B,D,n,n] or NULL = 0 (dh_0), dquencher0
+ * HOST doubles [P] (the uniform dq_0, the direction of the quencher loading) and dstep HOST doubles [P][6] = d(lxy_h, lz_h, lxy_q,
+ * lz_q, beta, fl), the three rounded to fp32 once; half_dt is fixed (bake_time_s is a process setting).  With Lxy(x) = ((W + E) +
+ * (S + N)) - 4 x and Lz(x) = (U + Dn) - 2 x under the forward's mirror rule, (h, q) the state at the start of the step, (hd, qd)
+ * the step's species after diffusion and R its neutralisation, one tangent step in fp32, every line a fixed sequence of single
+ * operations, added left to right:
+ *   dhd = dh + lxy_h Lxy(dh) + lz_h Lz(dh) + dlxy_h Lxy(h) + dlz_h Lz(h)        (dhd = dh when the acid does not diffuse; dqd likewise)
+ *   finite beta:    dR = (R_h dhd + R_q dqd) + (hd qd / (Dn Dn)) dbeta,   Dn = 1 + beta (hd + qd),
+ *                   R_h = beta qd (1 + beta qd) / (Dn Dn),  R_q = beta hd (1 + beta hd) / (Dn Dn)   (the adjoint's expressions)
+ *   instantaneous:  dR = hd < qd ? dhd : dqd                                     (the forward's own comparison)
+ *   dh' = (dhd - dR) fl + (hd - R) dfl,      dq' = dqd - dR,      da' = da + half_dt (dh + dh').
+ * Outputs dacid, dquencher, dacid_dose fp32 [P,B,D,n,n] = (dh_S, dq_S, da_S); a direction of zeros comes back exactly 0.  work:
+ * litho_peb_jvp_work_bytes(B, D, n, P) = (5 + 2 P) volumes (the ping-pong of the primal pair with its a, and the second side of
+ * the P tangent pairs, whose first side is the outputs; 0 for a bad argument), 16-byte aligned; nothing scales with the step count.
+ * The other arguments and their domain are litho_peb_bake's.
+ *
+ * litho_peb_param_tangent: host only.  dstep[6] from dparam[5] = d(kQuench, kLoss, acidDiffusionLength, quencherDiffusionLength,
+ * verticalScale): the transpose of litho_peb_param_chain at the same fixed step count, analytic in double; 0 for a zero length or
+ * scale and for kQuench = +inf.
+ *
+ * litho_develop_rate_jvp: the tangent of litho_develop_rate (kappa = C) and litho_peb_rate (kappa = k_amp, one gain of 1):
+ *   dslowness[p][gain][cell] = ds/dx (kappa g) m dx_p  +  sum_j d_j dphi[p][plane d][j],   j = 0 .. 5 in this order,
+ * ds/dx litho_develop_rate_vjp's line and d_j the six slot derivatives of litho_develop_rate_vjp_params.  dx device fp32
+ * [P, volumes, D, n, n] or NULL = 0; dphi device doubles [P][D][6], 16-byte aligned (slot 5, the surface factor, differs per plane).
+ * Double per cell, rounded once; a wall (1 - m negative or NaN) gives exactly 0.  dslowness fp32 [P, n_gains volumes, D, n, n].
+ *
+ * litho_develop_rate_param_tangent: host only.  dphi[D][6] from dparam[7] = d(kappa, r_max, r_min, q, m_th, surface_rate,
+ * surface_depth): the transpose of litho_develop_rate_param_chain.
+ *
+ * litho_develop_time_jvp: the tangent of the Godunov fixed point of litho_develop_time.  With the links (alpha on the three axes,
+ * sigma) of litho_develop_time_vjp, computed once per volume and shared by the P directions,
+ *   dT_i = sigma_i ds_i (+) |l_x| dT_up(x) (+) |l_y| dT_up(y) (+) |l_z| dT_up(z)     in this order,
+ * each term one fp32 multiplication and one addition, the upwind neighbour of an axis the one the link's sign names, a zero link
+ * adding nothing; where sigma_i = 0 (a wall, or T = +inf) dT_i = 0 exactly whatever ds_i holds.  A cell gathers along its own links
+ * from cells with strictly smaller T, so by induction from the sources of the graph the bits depend on neither the schedule, nor
+ * the batch, nor P, nor the launch at which the iteration stops.  The tiling, colours, rounds per launch, bitwise fixed point and
+ * launch cap (LITHO_E_NOCONV) are litho_develop_time_vjp's; a column is swept down and then up.  dslowness, dT fp32 [P,B,D,n,n].
+ * work: litho_develop_jvp_work_bytes(B, D, n, P, max_iterations) = the flag words, the links (4 volumes) and one side of the
+ * ping-pong (P volumes), 16-byte aligned.  Waits for the device while it iterates, like its twin. */
+#define LITHO_TANGENT_MAX 16
+int litho_peb_expose_jvp(const float *image, int volumes, int D, int n, const float *gains_host, int n_gains, double C, int P,
+                         const double *dC_host, const float *dimage, float *dacid, void *stream);
+size_t litho_peb_jvp_work_bytes(int B, int D, int n, int P);
+int litho_peb_bake_jvp(const float *acid_in, int B, int D, int n, double thickness_nm, double pixel_nm, double quencher0,
+                       double k_quench, double k_loss, double sigma_acid_nm, double sigma_quencher_nm, double vertical_scale,
+                       double bake_time_s, int steps, int P, const float *dacid_in, const double *dquencher0_host,
+                       const double *dstep_host, float *acid, float *quencher, float *acid_dose, float *dacid, float *dquencher,
+                       float *dacid_dose, void *work, size_t work_bytes, void *stream);
+int litho_peb_param_tangent(double thickness_nm, double pixel_nm, double k_quench, double k_loss, double sigma_acid_nm,
+                            double sigma_quencher_nm, double vertical_scale, double bake_time_s, int D, int steps,
+                            const double *dparam, double *dstep);
+int litho_develop_rate_jvp(const float *x, int volumes, int D, int n, const float *gains_host, int n_gains, double kappa, double r_max,
+                           double r_min, double q, double m_th, double surface_rate, double surface_depth_nm, double thickness_nm,
+                           int P, const float *dx, const double *dphi, float *dslowness, void *stream);
+int litho_develop_rate_param_tangent(double r_max, double r_min, double q, double m_th, double surface_rate, double surface_depth_nm,
+                                     double thickness_nm, int D, const double *dparam, double *dphi);
+size_t litho_develop_jvp_work_bytes(int B, int D, int n, int P, int max_iterations);
+int litho_develop_time_jvp(const float *slowness, const float *T, const float *dslowness, int B, int D, int n, int P,
+                           double thickness_nm, double pixel_nm, int max_iterations, float *dT, void *work, size_t work_bytes,
+                           int *launches_host, void *stream);
+
 /* ---- Mask gradients of Hopkins imaging (csrc/socs_grad.hip; no reference counterpart, checked against tests/socs_grad_oracle.py).
  * With F[q][i] = exp(+2 pi i (i - c)(q - c) / N), c = pn / 2, q, i in [0, pn), the engine's chain at shift (0,0) is L(X) = F X F^T,
  * the coherent fields are E_k = L(phi_k . M) and I = sum_k |E_k|^2.  For a real loss l with G = dl/dI,

@@ -30,6 +30,9 @@ from .calibrate import (bakeParameterChain, bakeParameterGradient, bakeStepGradi
                         calibrateResist, exposureParameterGradient, rateParameterChain,
                         rateParameterGradient, resistArrivalTimes, resistParameter,
                         resistParameterGradient, resistWith)
+from .tangent import (amplifiedRateTangent, bakeParameterTangent, bakeTangent,         # noqa: F401
+                      calibrationJacobian, developmentRateTangent, developmentTimeTangent,
+                      exposeAcidTangent, rateParameterTangent, resistProfileTangent)
 from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
@@ -51,4 +54,6 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "bakeGradient", "exposeAcidGradient", "postExposureBakeGradient", "bakedResistModel",
            "developmentTimeGradient", "developmentRateGradient", "resistProfileGradient", "amplifiedRateGradient", "developedResistModel",
            "bakeStepGradient", "bakeParameterChain", "bakeParameterGradient", "rateParameterChain", "rateParameterGradient",
-           "exposureParameterGradient", "resistParameterGradient", "calibrateResist", "resistArrivalTimes", "resistWith", "resistParameter"]
+           "exposureParameterGradient", "resistParameterGradient", "calibrateResist", "resistArrivalTimes", "resistWith", "resistParameter",
+           "exposeAcidTangent", "bakeTangent", "bakeParameterTangent", "developmentRateTangent", "amplifiedRateTangent",
+           "rateParameterTangent", "developmentTimeTangent", "resistProfileTangent", "calibrationJacobian"]

@@ -98,6 +98,21 @@ _SIGNATURES = {
                                               c_void_p]),
     "litho_develop_rate_param_chain": (c_int, [c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_int, c_int,
                                                POINTER(c_double), POINTER(c_double)]),
+    "litho_peb_expose_jvp": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), c_int, c_double, c_int, POINTER(c_double), c_void_p,
+                                     c_void_p, c_void_p]),
+    "litho_peb_jvp_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "litho_peb_bake_jvp": (c_int, [c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_double,
+                                   c_double, c_double, c_int, c_int, c_void_p, POINTER(c_double), POINTER(c_double), c_void_p, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "litho_peb_param_tangent": (c_int, [c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_int, c_int,
+                                        POINTER(c_double), POINTER(c_double)]),
+    "litho_develop_rate_jvp": (c_int, [c_void_p, c_int, c_int, c_int, POINTER(c_float), c_int, c_double, c_double, c_double, c_double,
+                                       c_double, c_double, c_double, c_double, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "litho_develop_rate_param_tangent": (c_int, [c_double, c_double, c_double, c_double, c_double, c_double, c_double, c_int,
+                                                 POINTER(c_double), POINTER(c_double)]),
+    "litho_develop_jvp_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "litho_develop_time_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_double, c_double, c_int, c_void_p,
+                                       c_void_p, c_size_t, POINTER(c_int), c_void_p]),
     "litho_peb_rate": (c_int,[c_void_p, c_int, c_int, c_int, c_double, c_double, c_double, c_double, c_double, c_double, c_double,
                                c_double, c_void_p, c_void_p, c_void_p]),
     "litho_develop_vjp_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),

@@ -19,7 +19,7 @@ The bake's step count is an integer that the caller holds fixed: the derivative 
 the step parameters' formulas at that count, the analytic one, not that of their rounding to fp32.
 
 NOT built: the gradients of a MackResist's own Gaussian diffusion lengths, of bakeTime (a process setting) and of
-`developedDepth`; bleaching; second-order (Gauss-Newton) calibration."""
+`developedDepth`; bleaching.  calibrateResist(method="lm") is the Levenberg-Marquardt step on tangent.py's Jacobian."""
 import ctypes
 import math
 
@@ -329,23 +329,67 @@ def _edge_points(who, measurements, nd, F, D, n, pixel, dev):
     return ix, torch.tensor(wts, dtype=torch.float32, device=dev)
 
 
-def _edge_loss(T, developTime, ix, w):
-    """(loss, dl/dT): the mean over the edge points of (min(T~, 2 t) / t - 1)^2, T~ the bilinear sample of T with +inf read as
-    2 t + 1 (ResistProfile.clampedT, what the CDs were measured on).  No gradient goes to a cell that was never reached."""
-    t = float(developTime)
+def _edge_residuals(T, t, ix, w):
+    """(residuals [P], live [P, 4]): min(T~, 2 t) / t - 1 per edge point, and which of its four cells take a derivative."""
     reached = ~torch.isposinf(T)
     near = torch.where(reached, T, torch.full_like(T, 2.0 * t + 1.0))[ix[0], ix[1], ix[2], ix[3]]      # [P, 4]
     sample = (near * w).sum(dim=1)
     res = torch.clamp(sample, max=2.0 * t) / t - 1.0
-    loss = float((res.double() ** 2).mean())
     live = (sample < 2.0 * t)[:, None] & reached[ix[0], ix[1], ix[2], ix[3]]
+    return res, live
+
+
+def _edge_loss(T, developTime, ix, w):
+    """(loss, dl/dT): the mean over the edge points of (min(T~, 2 t) / t - 1)^2, T~ the bilinear sample of T with +inf read as
+    2 t + 1 (ResistProfile.clampedT, what the CDs were measured on).  No gradient goes to a cell that was never reached."""
+    t = float(developTime)
+    res, live = _edge_residuals(T, t, ix, w)
+    loss = float((res.double() ** 2).mean())
     coef = (2.0 / (res.numel() * t)) * res[:, None] * w * live
     grad = torch.zeros_like(T).index_put_(tuple(i.reshape(-1) for i in ix), coef.reshape(-1).to(T.dtype), accumulate=True)
     return loss, grad
 
 
+def _levenberg_marquardt(who, run, measurements, t, names, start, lo, hi, logs, iterations, dev):
+    """calibrateResist's method="lm": (best values or None, history).  run(values) is the forward chain at those values."""
+    import numpy as np
+
+    from .tangent import _jacobian
+    to_z = lambda k, v: math.log(v) if logs[k] else v                             # noqa: E731
+    from_z = lambda k, z: math.exp(z) if logs[k] else z                           # noqa: E731
+    values, best, best_values, points, history, mu, moved = dict(start), None, None, None, [], 1e-3, 0.0
+    A = g = None
+    for it in range(iterations + 1):
+        f = run(values)
+        if points is None:
+            points = _edge_points(who, measurements, len(f.doses), f.F, f.D, f.n, f.pixel, dev)
+        loss = _edge_loss(f.T, t, *points)[0]
+        accepted = math.isfinite(loss) and (best is None or loss < best)
+        history.append(dict(loss=loss, parameters=dict(values), step=moved, accepted=accepted, damping=mu))
+        if accepted:
+            best, best_values = loss, dict(values)
+            r, J = _jacobian(who, f, t, points, names, logs)
+            J, r = J.numpy(), r.numpy()
+            A, g = J.T @ J, J.T @ r
+            if it:
+                mu = max(mu / 10.0, 1e-12)
+        else:
+            mu *= 10.0
+        if it == iterations or best is None or mu > 1e12 or not np.isfinite(A).all() or not np.any(g != 0.0):
+            break
+        diag = np.diag(A)
+        move = diag > 0.0                                                         # a parameter whose column is zero does not move
+        delta = np.zeros(len(names))
+        delta[move] = np.linalg.solve((A + mu * np.diag(diag))[np.ix_(move, move)], -g[move])
+        moved = float(np.abs(delta).max())
+        for i, k in enumerate(names):
+            z = min(max(to_z(k, best_values[k]) + delta[i], to_z(k, lo[k])), to_z(k, hi[k]))        # clipped in z: exp cannot overflow
+            values[k] = min(max(from_z(k, z), lo[k]), hi[k])
+    return best_values, history
+
+
 def calibrateResist(image, resist, stack_or_thickness, pixelSize, developTime, measurements, parameters=None, bounds=None, doses=(1.0,),
-                    focalPlanes=1, iterations=20, steps=None, step=0.1, maxIterations=1024):
+                    focalPlanes=1, iterations=20, steps=None, step=0.1, maxIterations=1024, method="descent"):
     """Fit resist parameters to measured CDs through dose and focus by steepest descent with backtracking, the resist-side twin of
     fitAberrations.  Returns (resist, history): the resist with the lowest loss and one record per evaluated iterate,
     dict(loss, parameters, step, accepted).
@@ -367,9 +411,19 @@ def calibrateResist(image, resist, stack_or_thickness, pixelSize, developTime, m
     the value given.  The bake's step count is one integer for the
     whole fit: `steps`, or max(8, minSteps at the upper bounds of the diffusion lengths and of verticalScale).
 
+    method="lm": Levenberg-Marquardt on the same coordinates z, bounds and step count, with the Jacobian J of the residuals from
+    the forward mode (tangent.py: one forward run and one tangent sweep per accepted iterate, no tape).  delta solves
+    (J^T J + mu diag(J^T J)) delta = -J^T r in float64 on the host, a parameter whose column is zero does not move, and
+    z <- clip(z + delta).  mu starts at 1e-3 and is divided by 10 on an accepted iterate (floor 1e-12); on a rejected one it is
+    multiplied by 10 and the loop returns to the best iterate.  It stops after `iterations`, on J^T r = 0, or when mu exceeds
+    1e12.  Each record also carries `damping`, the mu the iterate was computed with; `step` is max |delta| of that move.  Any
+    other `method` raises ValueError.
+
     Raises ValueError for kQuench of a resist with instantaneous neutralisation, for a parameter the resist class does not have,
     and for surfaceRate or surfaceDepth with the surface factor switched off."""
     who = "calibrateResist"
+    if method not in ("descent", "lm"):
+        raise ValueError(f"{who}: method must be 'descent' or 'lm'; got {method!r}")
     car = isinstance(resist, ChemicallyAmplifiedResist)
     if not car and not isinstance(resist, MackResist):
         raise TypeError(f"{who}: resist must be a MackResist or a ChemicallyAmplifiedResist")
@@ -406,6 +460,13 @@ def calibrateResist(image, resist, stack_or_thickness, pixelSize, developTime, m
         steps = max(8, top.minSteps(thickness, image.shape[0] // int(focalPlanes), float(pixelSize)))
     dev = nat.require_gpu(image.device)
     doses = tuple(doses)
+    if method == "lm":
+        run = lambda values: _forward(who, image, _replace(resist, values), thickness, pixelSize, doses, focalPlanes, maxIterations,   # noqa: E731
+                                      steps if car else None)
+        best_values, history = _levenberg_marquardt(who, run, measurements, t, names, start, lo, hi, logs, iterations, dev)
+        if best_values is None:
+            raise RuntimeError(f"{who}: the loss at the starting point is not finite")
+        return _replace(resist, best_values), history
     values, best, best_values, points, history, direction, first_step = dict(start), None, None, None, [], None, step
     for it in range(iterations + 1):
         trial = _replace(resist, values)

@@ -323,6 +323,153 @@ __global__ __launch_bounds__(256) void k_develop_rate_params(const float* __rest
     }
 }
 
+// ---- 6. forward mode (litho_develop_rate_jvp, litho_develop_time_jvp; include/litho_abbe.h's "Forward mode (tangents) of the
+// resist chain").
+//
+// The rate law's tangent: ds = ds/dx (kappa g) m dx_p + sum_j d_j dphi[p][plane][j], j = 0 .. 5 in this order, d_0 the line of
+// k_develop_rate_params' slot 0 and d_1 .. d_5 mack_slowness_dparams'; double per cell, rounded once; a wall gives exactly 0.
+// grid.y: the planes of x; the directions and the gains in loops inside.  dx == nullptr: dx = 0.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_develop_rate_jvp(const float* __restrict__ x, const float* __restrict__ dx,
+                                                          const double* __restrict__ dphi, float* __restrict__ out, int planes, int D,
+                                                          int n, const VolGains gains, int n_gains, int P, double kappa, double rmax_a1,
+                                                          double rmin, double q, double a, const VolSurface surface)
+{
+    const long long plane_elems = (long long)n * n;
+    const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
+    if (e >= plane_elems) return;
+    const int p = blockIdx.y, d = p % D;
+    const double f = surface.f[d];
+    const Pack<VEC> xv = load_pack<VEC>(x + (size_t)p * plane_elems + e);
+    for (int gi = 0; gi < n_gains; ++gi) {
+        const double g = (double)gains.g[gi], kg = kappa * g;
+        double m[VEC], b[VEC], dj[VEC][6];
+        for (int v = 0; v < VEC; ++v) {
+            m[v] = exp(-(kg * (double)xv.v[v]));
+            b[v] = 1.0 - m[v];
+            if (!(b[v] >= 0.0)) continue;                // a wall
+            double five[5];
+            mack_slowness_dparams(b[v], rmax_a1, rmin, q, a, f, five);
+            dj[v][0] = mack_slowness_dx(b[v], (g * (double)xv.v[v]) * m[v], rmax_a1, rmin, q, a, f);
+            for (int j = 0; j < 5; ++j) dj[v][1 + j] = five[j];
+        }
+        for (int k = 0; k < P; ++k) {
+            const Pack<VEC> dxv = dx ? load_pack<VEC>(dx + ((size_t)k * planes + p) * plane_elems + e) : fill_pack<VEC>(0.f);
+            const double* phi = dphi + ((size_t)k * D + d) * 6;
+            Pack<VEC> r;
+            for (int v = 0; v < VEC; ++v) {
+                if (!(b[v] >= 0.0)) {
+                    r.v[v] = 0.f;
+                    continue;
+                }
+                double acc = mack_slowness_dx(b[v], (kg * m[v]) * (double)dxv.v[v], rmax_a1, rmin, q, a, f);
+                for (int j = 0; j < 6; ++j) acc = acc + dj[v][j] * phi[j];
+                r.v[v] = (float)acc;
+            }
+            store_pack<VEC>(out + (((size_t)k * n_gains + gi) * planes + p) * plane_elems + e, r);
+        }
+    }
+}
+
+// The front's tangent, the transpose of k_develop_time_vjp on the same tiling: a cell gathers along its OWN links from its upwind
+// cells, so only tau needs the one-cell halo in LDS and the links of the tile alone are kept: tau [D][18][18] and lx, ly, lz
+// [D][16][16], D (324 + 768) floats = 4368 D bytes, 136.5 KiB at D = 32.  The source sigma ds of a cell is read from global memory
+// by the thread that owns the column (as the adjoint reads its cotangent).  grid.z: the P B volumes, direction-major; the links
+// belong to volume blockIdx.z % B.  A column is swept down and then up: the tangent flows the way the front ran.
+static constexpr size_t DT_PLANE_BYTES = (size_t)(DG_HCELLS + 3 * DG_TCELLS) * sizeof(float);
+static_assert((size_t)VOL_DMAX * DT_PLANE_BYTES <= 160 * 1024, "the tile of the deepest volume must fit a gfx950 workgroup's LDS");
+
+// One cell: tau points at it in the [18][18] planes, (lx, ly, lz) are its own links; true when its bits changed.
+__device__ __forceinline__ bool tangent_cell(float* tau, float lx, float ly, float lz, float src, int d, int D)
+{
+    float acc = src;
+    if (lx > 0.f) acc = acc + lx * tau[-1];
+    else if (lx < 0.f) acc = acc + (-lx) * tau[1];
+    if (ly > 0.f) acc = acc + ly * tau[-VOL_HALO];
+    else if (ly < 0.f) acc = acc + (-ly) * tau[VOL_HALO];
+    if (lz > 0.f && d > 0) acc = acc + lz * tau[-DG_HCELLS];
+    else if (lz < 0.f && d + 1 < D) acc = acc + (-lz) * tau[DG_HCELLS];
+    const bool changed = bits_of(acc) != bits_of(*tau);
+    *tau = acc;
+    return changed;
+}
+
+__global__ __launch_bounds__(256) void k_develop_time_jvp(const float* __restrict__ links, const float* __restrict__ ds,
+                                                          const float* __restrict__ tin, float* __restrict__ tout, int B, int D, int n,
+                                                          int* __restrict__ flag)
+{
+    extern __shared__ __attribute__((aligned(16))) float dt_lds[];
+    float* tau = dt_lds;                                 // [D][18][18]  tile + halo
+    float* lx = tau + D * DG_HCELLS;                     // [D][16][16]  tile
+    float* ly = lx + D * DG_TCELLS;
+    float* lz = ly + D * DG_TCELLS;
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * VOL_TILE, y0 = blockIdx.y * VOL_TILE;
+    const size_t plane_elems = (size_t)n * n;
+    const size_t vol = (size_t)blockIdx.z * D * plane_elems;                 // in the direction-major tangent volumes
+    const size_t lvol = (size_t)(blockIdx.z % B) * D * plane_elems;          // in the links
+    // the tile: its links and tau; a tile cell outside the grid has no links and tau 0
+    for (int i = tid; i < D * DG_TCELLS; i += 256) {
+        const int d = i / DG_TCELLS, r = i - d * DG_TCELLS, ty = r / VOL_TILE, tx = r - ty * VOL_TILE;
+        const int gy = y0 + ty, gx = x0 + tx;
+        float4 L = make_float4(0.f, 0.f, 0.f, 0.f);
+        float t0 = 0.f;
+        if (gy < n && gx < n) {
+            const size_t cell = (size_t)d * plane_elems + (size_t)gy * n + gx;
+            L = *reinterpret_cast<const float4*>(links + 4 * (lvol + cell));
+            t0 = tin[vol + cell];
+        }
+        tau[d * DG_HCELLS + (ty + 1) * VOL_HALO + tx + 1] = t0;
+        lx[i] = L.x;
+        ly[i] = L.y;
+        lz[i] = L.z;
+    }
+    // the 64 edge cells of the halo per plane: tau alone
+    for (int i = tid; i < D * 4 * VOL_TILE; i += 256) {
+        const int d = i / (4 * VOL_TILE), r = i - d * (4 * VOL_TILE), side = r / VOL_TILE, k = r - side * VOL_TILE;
+        int hy, hx;                                      // position in the [18][18] plane
+        if (side == 0) { hy = k + 1; hx = 0; }
+        else if (side == 1) { hy = k + 1; hx = VOL_HALO - 1; }
+        else if (side == 2) { hy = 0; hx = k + 1; }
+        else { hy = VOL_HALO - 1; hx = k + 1; }
+        const int gy = y0 + hy - 1, gx = x0 + hx - 1;
+        float t0 = 0.f;
+        if (gy >= 0 && gy < n && gx >= 0 && gx < n) t0 = tin[vol + (size_t)d * plane_elems + (size_t)gy * n + gx];
+        tau[d * DG_HCELLS + hy * VOL_HALO + hx] = t0;
+    }
+    __syncthreads();
+    // compute threads: 128, row = tid / 8, the columns of this phase's colour in that row
+    const int row = (tid >> 3) & (VOL_TILE - 1), pair = tid & 7;
+    bool changed = false;
+    for (int round = 0; round < VOL_INNER; ++round) {
+        for (int colour = 0; colour < 2; ++colour) {
+            const int col = 2 * pair + ((row + colour) & 1);
+            if (tid < 128 && y0 + row < n && x0 + col < n) {
+                const int q = (row + 1) * VOL_HALO + (col + 1), t = row * VOL_TILE + col;
+                const size_t column = (size_t)(y0 + row) * n + (x0 + col);
+                const float* sc = ds + vol + column;                         // the column's ds and sigma, from global memory
+                const float* gc = links + 4 * (lvol + column) + 3;
+                auto cell = [&](int d) {
+                    const float sigma = gc[4 * d * plane_elems];
+                    const float src = sigma > 0.f ? sigma * sc[d * plane_elems] : 0.f;
+                    const int l = d * DG_TCELLS + t;
+                    return tangent_cell(tau + d * DG_HCELLS + q, lx[l], ly[l], lz[l], src, d, D);
+                };
+                for (int d = 0; d < D; ++d) changed |= cell(d);
+                for (int d = D - 2; d >= 0; --d) changed |= cell(d);
+            }
+            __syncthreads();
+        }
+    }
+    for (int i = tid; i < D * DG_TCELLS; i += 256) {
+        const int d = i / DG_TCELLS, r = i - d * DG_TCELLS, ty = r / VOL_TILE, tx = r - ty * VOL_TILE;
+        const int gy = y0 + ty, gx = x0 + tx;
+        if (gy < n && gx < n)
+            tout[vol + (size_t)d * plane_elems + (size_t)gy * n + gx] = tau[d * DG_HCELLS + (ty + 1) * VOL_HALO + tx + 1];
+    }
+    if (changed) *flag = 1;
+}
+
 }  // namespace litho
 
 extern "C" {
@@ -468,6 +615,111 @@ int litho_develop_rate_param_chain(double r_max, double r_min, double q, double 
         out[5] = s_r0;
         out[6] = s_delta;
     }
+    return LITHO_OK;
+}
+
+int litho_develop_rate_jvp(const float* x, int volumes, int D, int n, const float* gains_host, int n_gains, double kappa, double r_max,
+                           double r_min, double q, double m_th, double surface_rate, double surface_depth_nm, double thickness_nm, int P,
+                           const float* dx, const double* dphi, float* dslowness, void* stream)
+{
+    using namespace litho;
+    VolGains gains;
+    MackLaw law;
+    if (!x || !dphi || !dslowness || P < 1 || P > LITHO_TANGENT_MAX || !volume_ok(volumes, D, n) ||
+        !make_gains(gains_host, n_gains, volumes, D, gains) || (long long)P * n_gains * volumes * D > 65535 || !finite_pos(kappa) ||
+        !make_mack(r_max, r_min, q, m_th, surface_rate, surface_depth_nm, thickness_nm, D, law))
+        return LITHO_E_ARG;
+    if (!aligned16(dphi)) return LITHO_E_ARG;
+    const size_t x_bytes = (size_t)volumes * D * n * n * sizeof(float), out_bytes = x_bytes * n_gains * P;
+    const size_t phi_bytes = (size_t)P * D * 6 * sizeof(double);
+    if (overlap(dslowness, out_bytes, x, x_bytes) || overlap(dslowness, out_bytes, dphi, phi_bytes) ||
+        (dx && overlap(dslowness, out_bytes, dx, x_bytes * P)))
+        return LITHO_E_ARG;
+    const int planes = volumes * D;
+    const bool wide = (n & 3) == 0 && aligned16(x) && aligned16(dx) && aligned16(dslowness);
+    LAUNCH_PACKED(k_develop_rate_jvp, wide, n, planes, (hipStream_t)stream, x, dx, dphi, dslowness, planes, D, n, gains, n_gains, P, kappa,
+                  law.rmax_a1, law.rmin, law.q, law.a, law.surface);
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+int litho_develop_rate_param_tangent(double r_max, double r_min, double q, double m_th, double surface_rate, double surface_depth_nm,
+                                     double thickness_nm, int D, const double* dparam, double* dphi)
+{
+    using namespace litho;
+    MackLaw law;
+    if (!dparam || !dphi || D < 1 || D > VOL_DMAX || !make_mack(r_max, r_min, q, m_th, surface_rate, surface_depth_nm, thickness_nm, D, law))
+        return LITHO_E_ARG;
+    const double a = law.a;
+    const double da_dq = a * (1.0 / (q + 1.0) - 1.0 / (q - 1.0) + std::log(1.0 - m_th)), da_dm = -q * a / (1.0 - m_th);
+    for (int d = 0; d < D; ++d) {
+        const double z = thickness_nm * (d + 0.5) / D, ez = std::exp(-z / surface_depth_nm);
+        double* out = dphi + (size_t)d * 6;
+        out[0] = dparam[0];
+        out[1] = (a + 1.0) * dparam[1];
+        out[2] = dparam[2];
+        out[3] = dparam[3];
+        out[4] = da_dq * dparam[3] + da_dm * dparam[4];
+        out[5] = ez * dparam[5] + (-(1.0 - surface_rate) * ez * z / (surface_depth_nm * surface_depth_nm)) * dparam[6];
+    }
+    return LITHO_OK;
+}
+
+size_t litho_develop_jvp_work_bytes(int B, int D, int n, int P, int max_iterations)
+{
+    using namespace litho;
+    if (!volume_ok(B, D, n) || P < 1 || P > LITHO_TANGENT_MAX || (long long)P * B * D > 65535 || max_iterations < 1 ||
+        max_iterations > VOL_MAXIT)
+        return 0;
+    return flag_bytes(max_iterations) + (4 + (size_t)P) * B * D * n * n * sizeof(float);     // flags, links (4), tau (P)
+}
+
+int litho_develop_time_jvp(const float* slowness, const float* T, const float* dslowness, int B, int D, int n, int P, double thickness_nm,
+                           double pixel_nm, int max_iterations, float* dT, void* work, size_t work_bytes, int* launches_host, void* stream)
+{
+    using namespace litho;
+    if (launches_host) *launches_host = 0;
+    if (!slowness || !T || !dslowness || !dT || !work || !launches_host || !volume_ok(B, D, n)) return LITHO_E_ARG;
+    if (P < 1 || P > LITHO_TANGENT_MAX || (long long)P * B * D > 65535) return LITHO_E_ARG;
+    if (max_iterations < 1 || max_iterations > VOL_MAXIT || !finite_pos(thickness_nm) || !finite_pos(pixel_nm)) return LITHO_E_ARG;
+    const size_t cells = (size_t)B * D * n * n, vol_bytes = cells * sizeof(float), tan_bytes = vol_bytes * P;
+    const size_t need = litho_develop_jvp_work_bytes(B, D, n, P, max_iterations);
+    if (!aligned16(work)) return LITHO_E_ARG;
+    const void* in[3] = {slowness, T, dslowness};
+    const size_t in_bytes[3] = {vol_bytes, vol_bytes, tan_bytes};
+    for (int i = 0; i < 3; ++i)
+        if (overlap(dT, tan_bytes, in[i], in_bytes[i])) return LITHO_E_ARG;
+    if (work_bytes < need) return LITHO_E_WORKSPACE;
+    for (int i = 0; i < 3; ++i)
+        if (overlap(work, need, in[i], in_bytes[i])) return LITHO_E_ARG;
+    if (overlap(work, need, dT, tan_bytes)) return LITHO_E_ARG;
+    // the geometry as litho_develop_time rounds it
+    const float hf = (float)pixel_nm, hzf = (float)(thickness_nm / D);
+    const float wxy = 1.f / (hf * hf), wz = 1.f / (hzf * hzf);
+    if (!(hf > 0.f) || !(hzf > 0.f) || std::isinf(wxy) || std::isinf(wz) || !(wxy > 0.f) || !(wz > 0.f)) return LITHO_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    int* flags = (int*)work;
+    float* links = (float*)((char*)work + flag_bytes(max_iterations));
+    float* buf[2] = {links + 4 * cells, dT};
+    const size_t lds = (size_t)D * DT_PLANE_BYTES;
+    if (lds > 64 * 1024) {                               // once per device: the worst case, D = 32
+        static unsigned lds_done = 0;
+        HIP_TRY(lds_opt_in(lds_done, (const void*)k_develop_time_jvp, (size_t)VOL_DMAX * DT_PLANE_BYTES));
+    }
+    HIP_TRY(hipMemsetAsync(buf[0], 0, tan_bytes, st));
+    const bool wide = (n & 3) == 0 && aligned16(slowness) && aligned16(T);
+    LAUNCH_PACKED(k_develop_links, wide, n, B * D, st, slowness, T, (float4*)links, D, n, (double)hf, (double)hzf);
+    HIP_TRY(hipGetLastError());
+    const unsigned tiles = (unsigned)((n + VOL_TILE - 1) / VOL_TILE);
+    const dim3 grid(tiles, tiles, (unsigned)(P * B));
+    // launch `it` reads buf[it & 1] and writes the other; the one that changed nothing leaves the fixed point in both
+    const int launches = iterate_until_unchanged(flags, max_iterations, st, [&](int it) {
+        hipLaunchKernelGGL(k_develop_time_jvp, grid, dim3(256), lds, st, (const float*)links, dslowness, (const float*)buf[it & 1],
+                           buf[(it + 1) & 1], B, D, n, flags + it);
+    });
+    if (launches < 0) return launches;
+    *launches_host = launches ? launches : max_iterations;
+    if (!launches) return LITHO_E_NOCONV;
     return LITHO_OK;
 }
 

@@ -385,6 +385,123 @@ __global__ __launch_bounds__(256) void k_peb_expose_params(const float* __restri
     if (threadIdx.x == 0) partials[(size_t)gp * gridDim.x + blockIdx.x] = t[0];
 }
 
+// ---- 2d. forward mode (litho_peb_expose_jvp, litho_peb_bake_jvp; include/litho_abbe.h's "Forward mode (tangents) of the resist
+// chain").  P directions ride in one launch: the kernel arguments carry their host numbers, the volumes are direction-major.
+static constexpr int TAN_MAX = LITHO_TANGENT_MAX;
+struct TanScalars {
+    double v[TAN_MAX];                                    // dC per direction
+};
+struct PebTanStep {
+    float d[TAN_MAX][6];                                  // d(lxy_h, lz_h, lxy_q, lz_q, beta, fl) per direction, rounded once
+    float dq0[TAN_MAX];                                   // the uniform dq_0 per direction
+};
+
+// The exposure's tangent: dh0 = exp(-(C g) I) ((g I) dC_p + (C g) dI_p) in double per cell, rounded once; exactly 0 where the acid
+// is NaN.  grid.y: the planes of the image; the directions and the gains in loops inside.  dimage == nullptr: dI = 0.
+template <int VEC>
+__global__ __launch_bounds__(256) void k_peb_expose_jvp(const float* __restrict__ image, const float* __restrict__ dimage,
+                                                        float* __restrict__ out, int planes, int n, const VolGains gains, int n_gains,
+                                                        double C, int P, const TanScalars dC)
+{
+    const long long plane_elems = (long long)n * n;
+    const long long e = ((long long)blockIdx.x * 256 + threadIdx.x) * VEC;
+    if (e >= plane_elems) return;
+    const int p = blockIdx.y;
+    const Pack<VEC> I = load_pack<VEC>(image + (size_t)p * plane_elems + e);
+    for (int k = 0; k < P; ++k) {
+        const Pack<VEC> dI = dimage ? load_pack<VEC>(dimage + ((size_t)k * planes + p) * plane_elems + e) : fill_pack<VEC>(0.f);
+        for (int gi = 0; gi < n_gains; ++gi) {
+            const double g = (double)gains.g[gi], Cg = C * g;
+            Pack<VEC> r;
+            for (int v = 0; v < VEC; ++v) {
+                const double Iv = (double)I.v[v], ex = exp(-(Cg * Iv));
+                const double t = ex * ((g * Iv) * dC.v[k] + Cg * (double)dI.v[v]);
+                r.v[v] = (1.0 - ex >= 0.0) ? (float)t : 0.f;
+            }
+            store_pack<VEC>(out + (((size_t)k * n_gains + gi) * planes + p) * plane_elems + e, r);
+        }
+    }
+}
+
+// One bake step with its P tangents: grid as k_peb_direct, a thread per cell.  The primal goes through peb_step with
+// k_peb_direct's operands, so (h, q, a) are its bits; the cell's seven-point loads, its two Laplacians per species and R_h, R_q,
+// Dn of the reaction are formed once and reused by every direction.  q_in == nullptr: the first step, q = q0, dq = dq0[p], a = da
+// = 0, and dh = 0 when dh_in is nullptr too.  Tangent volumes are [P][V], V the cells of the batch.
+__global__ __launch_bounds__(256) void k_peb_jvp(const float* __restrict__ h_in, const float* __restrict__ q_in, float q0,
+                                                 float* __restrict__ h_out, float* __restrict__ q_out, float* __restrict__ a_io,
+                                                 const float* __restrict__ dh_in, const float* __restrict__ dq_in,
+                                                 float* __restrict__ dh_out, float* __restrict__ dq_out, float* __restrict__ da_io,
+                                                 size_t V, int D, int n, int P, const PebStep S, const PebTanStep T)
+{
+    PebCell c;
+    if (!peb_cell(D, n, c)) return;
+    const size_t at = c.at;
+    const bool first = q_in == nullptr;
+    const float h = h_in[at], q = first ? q0 : q_in[at];
+    const PebNb zero = PebNb{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    const PebNb bh = S.diffuse_h ? peb_around(h_in + at, c) : zero;
+    const PebNb bq = S.diffuse_q ? (first ? PebNb{q0, q0, q0, q0, q0, q0} : peb_around(q_in + at, c)) : zero;
+    float a = first ? 0.f : a_io[at], h_new, q_new, hd, qd;
+    peb_step(S, h, q, [&] { return bh; }, [&] { return bq; }, h_new, q_new, a, hd, qd);
+    h_out[at] = h_new;
+    q_out[at] = q_new;
+    a_io[at] = a;
+    // what every direction shares
+    const float lxy_of_h = ((bh.w + bh.e) + (bh.s + bh.n)) - 4.f * h, lz_of_h = (bh.u + bh.d) - 2.f * h;
+    const float lxy_of_q = ((bq.w + bq.e) + (bq.s + bq.n)) - 4.f * q, lz_of_q = (bq.u + bq.d) - 2.f * q;
+    float Rh, Rq, Rb = 0.f, R;
+    if (S.instant) {
+        Rh = (hd < qd) ? 1.f : 0.f;
+        Rq = 1.f - Rh;
+        R = (hd < qd) ? hd : qd;
+    } else {
+        const float Dn = 1.f + S.beta * (hd + qd), DD = Dn * Dn;
+        Rh = S.beta * qd * (1.f + S.beta * qd) / DD;
+        Rq = S.beta * hd * (1.f + S.beta * hd) / DD;
+        Rb = hd * qd / DD;
+        R = S.beta * hd * qd / Dn;
+    }
+    const float hR = hd - R;
+    for (int p = 0; p < P; ++p) {
+        const size_t tp = (size_t)p * V + at;
+        const float dh = dh_in ? dh_in[tp] : 0.f, dq = first ? T.dq0[p] : dq_in[tp];
+        float dhd = dh, dqd = dq;
+        if (S.diffuse_h) {
+            const PebNb b = dh_in ? peb_around(dh_in + tp, c) : zero;
+            dhd = dh + S.lxy_h * (((b.w + b.e) + (b.s + b.n)) - 4.f * dh) + S.lz_h * ((b.u + b.d) - 2.f * dh) + T.d[p][0] * lxy_of_h +
+                  T.d[p][1] * lz_of_h;
+        }
+        if (S.diffuse_q) {
+            const PebNb b = first ? PebNb{dq, dq, dq, dq, dq, dq} : peb_around(dq_in + tp, c);
+            dqd = dq + S.lxy_q * (((b.w + b.e) + (b.s + b.n)) - 4.f * dq) + S.lz_q * ((b.u + b.d) - 2.f * dq) + T.d[p][2] * lxy_of_q +
+                  T.d[p][3] * lz_of_q;
+        }
+        const float dR = S.instant ? ((hd < qd) ? dhd : dqd) : (Rh * dhd + Rq * dqd) + Rb * T.d[p][4];
+        const float dh_new = (dhd - dR) * S.fl + hR * T.d[p][5];
+        dh_out[tp] = dh_new;
+        dq_out[tp] = dqd - dR;
+        da_io[tp] = (first ? 0.f : da_io[tp]) + S.half_dt * (dh + dh_new);
+    }
+}
+
+// the transpose of param_chain: dstep[6] from dparam[5]
+static void param_tangent(double thickness_nm, double pixel_nm, double k_quench, double k_loss, double sigma_acid_nm, double sigma_quencher_nm,
+                          double vertical_scale, double bake_time_s, int D, int steps, const double* dp, double* out)
+{
+    const double hz = thickness_nm / D, dt = bake_time_s / steps, S = steps;
+    const double dxy_h = sigma_acid_nm / (S * (pixel_nm * pixel_nm)), dxy_q = sigma_quencher_nm / (S * (pixel_nm * pixel_nm));
+    const double vv = vertical_scale * vertical_scale / (S * (hz * hz));
+    const double dz_h = vv * sigma_acid_nm, dz_q = vv * sigma_quencher_nm;
+    const double dv_h = vertical_scale * sigma_acid_nm * sigma_acid_nm / (S * (hz * hz));
+    const double dv_q = vertical_scale * sigma_quencher_nm * sigma_quencher_nm / (S * (hz * hz));
+    out[0] = dxy_h * dp[2];
+    out[1] = dz_h * dp[2] + dv_h * dp[4];
+    out[2] = dxy_q * dp[3];
+    out[3] = dz_q * dp[3] + dv_q * dp[4];
+    out[4] = std::isinf(k_quench) ? 0.0 : dt * dp[0];
+    out[5] = (-dt * std::exp(-k_loss * dt)) * dp[1];
+}
+
 // ---- 3. rate: m = exp(-kAmp a), then mack_slowness of 1 - m with the surface factor of the plane (resist_volume.hpp, the
 // function k_develop_rate calls): NaN where 1 - m is negative or NaN.  grid.y: the B D planes.
 template <int VEC>
@@ -787,6 +904,112 @@ int litho_peb_expose_vjp_params(const float* image, int volumes, int D, int n, c
     hipLaunchKernelGGL(k_vol_total<1>, dim3((unsigned)(n_gains * volumes)), dim3(256), 0, st, (const double*)work,
                        (long long)D * (long long)blocks, grad_C);
     HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+int litho_peb_expose_jvp(const float* image, int volumes, int D, int n, const float* gains_host, int n_gains, double C, int P,
+                         const double* dC_host, const float* dimage, float* dacid, void* stream)
+{
+    using namespace litho;
+    VolGains gains;
+    if (!image || !dacid || !dC_host || P < 1 || P > TAN_MAX || !volume_ok(volumes, D, n) ||
+        !make_gains(gains_host, n_gains, volumes, D, gains) || !finite_pos(C) || (long long)P * n_gains * volumes * D > 65535)
+        return LITHO_E_ARG;
+    TanScalars dC;
+    memset(&dC, 0, sizeof(dC));
+    for (int p = 0; p < P; ++p) {
+        if (!std::isfinite(dC_host[p])) return LITHO_E_ARG;
+        dC.v[p] = dC_host[p];
+    }
+    const size_t in_bytes = (size_t)volumes * D * n * n * sizeof(float), out_bytes = in_bytes * n_gains * P;
+    if (overlap(image, in_bytes, dacid, out_bytes) || (dimage && overlap(dimage, in_bytes * P, dacid, out_bytes))) return LITHO_E_ARG;
+    const int planes = volumes * D;
+    const bool wide = (n & 3) == 0 && aligned16(image) && aligned16(dimage) && aligned16(dacid);
+    LAUNCH_PACKED(k_peb_expose_jvp, wide, n, planes, (hipStream_t)stream, image, dimage, dacid, planes, n, gains, n_gains, C, P, dC);
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+size_t litho_peb_jvp_work_bytes(int B, int D, int n, int P)
+{
+    using namespace litho;
+    if (!volume_ok(B, D, n) || P < 1 || P > TAN_MAX || (long long)P * B * D > 65535) return 0;
+    return (5 + 2 * (size_t)P) * ((size_t)B * D * n * n * sizeof(float));
+}
+
+int litho_peb_bake_jvp(const float* acid_in, int B, int D, int n, double thickness_nm, double pixel_nm, double quencher0, double k_quench,
+                       double k_loss, double sigma_acid_nm, double sigma_quencher_nm, double vertical_scale, double bake_time_s, int steps,
+                       int P, const float* dacid_in, const double* dquencher0_host, const double* dstep_host, float* acid, float* quencher,
+                       float* acid_dose, float* dacid, float* dquencher, float* dacid_dose, void* work, size_t work_bytes, void* stream)
+{
+    using namespace litho;
+    if (!acid_in || !dquencher0_host || !dstep_host || !dacid || !dquencher || !dacid_dose || !work || !volume_ok(B, D, n)) return LITHO_E_ARG;
+    if (P < 1 || P > TAN_MAX || (long long)P * B * D > 65535) return LITHO_E_ARG;
+    if (!finite_nonneg(quencher0) || !(k_quench >= 0.0) || !finite_nonneg(k_loss) || !finite_pos(bake_time_s)) return LITHO_E_ARG;
+    const int least = min_steps(sigma_acid_nm, sigma_quencher_nm, vertical_scale, thickness_nm, D, pixel_nm);
+    if (least == 0 || steps < least || steps > PEB_MAXSTEPS) return LITHO_E_ARG;
+    PebTanStep T;
+    memset(&T, 0, sizeof(T));
+    for (int p = 0; p < P; ++p) {
+        if (!std::isfinite(dquencher0_host[p])) return LITHO_E_ARG;
+        T.dq0[p] = (float)dquencher0_host[p];
+        for (int j = 0; j < 6; ++j) {
+            if (!std::isfinite(dstep_host[p * 6 + j])) return LITHO_E_ARG;
+            T.d[p][j] = (float)dstep_host[p * 6 + j];
+        }
+    }
+    const size_t V = (size_t)B * D * n * n, vol_bytes = V * sizeof(float), need = (5 + 2 * (size_t)P) * vol_bytes;
+    if (!aligned16(work)) return LITHO_E_ARG;
+    if (work_bytes < need) return LITHO_E_WORKSPACE;
+    // the outputs overlap no input, no other output and not the workspace; the inputs are only read
+    const void* bufs[9] = {acid, quencher, acid_dose, dacid, dquencher, dacid_dose, acid_in, dacid_in, work};
+    const size_t size[9] = {vol_bytes, vol_bytes, vol_bytes, P * vol_bytes, P * vol_bytes, P * vol_bytes, vol_bytes, P * vol_bytes, need};
+    for (int i = 0; i < 6; ++i) {
+        if (!bufs[i]) continue;
+        for (int j = i + 1; j < 9; ++j)
+            if (bufs[j] && overlap(bufs[i], size[i], bufs[j], size[j])) return LITHO_E_ARG;
+    }
+    for (int j = 6; j < 8; ++j)
+        if (bufs[j] && overlap(bufs[j], size[j], work, need)) return LITHO_E_ARG;
+    const PebStep S = step_of(thickness_nm, pixel_nm, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps);
+    const float q0 = (float)quencher0;
+    if (std::isinf(q0) || std::isinf(S.half_dt)) return LITHO_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    // the primal pair ping-pongs between two sides of the workspace, a lives in its fifth volume; the last step writes the
+    // outputs that were asked for.  The tangent pairs ping-pong between the outputs and the workspace, the last step to the
+    // outputs; da is updated in place in its output.
+    float* base = (float*)work;
+    float* ph[2] = {base, base + 2 * V};
+    float* pa = acid_dose ? acid_dose : base + 4 * V;
+    float* th[2] = {dacid, base + 5 * V};
+    float* tq[2] = {dquencher, base + (5 + (size_t)P) * V};
+    const dim3 grid(plane_blocks(n, 1), (unsigned)(B * D)), block(256);
+    const float *src_h = acid_in, *src_q = nullptr, *src_dh = dacid_in, *src_dq = nullptr;
+    for (int k = 0; k < steps; ++k) {
+        const int to = (steps - 1 - k) & 1;
+        const bool last = k + 1 == steps;
+        float* to_h = (last && acid) ? acid : ph[k & 1];
+        float* to_q = (last && quencher) ? quencher : ph[k & 1] + V;
+        hipLaunchKernelGGL(k_peb_jvp, grid, block, 0, st, src_h, src_q, q0, to_h, to_q, pa, src_dh, src_dq, th[to], tq[to], dacid_dose, V, D,
+                           n, P, S, T);
+        src_h = to_h;
+        src_q = to_q;
+        src_dh = th[to];
+        src_dq = tq[to];
+    }
+    HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+int litho_peb_param_tangent(double thickness_nm, double pixel_nm, double k_quench, double k_loss, double sigma_acid_nm,
+                            double sigma_quencher_nm, double vertical_scale, double bake_time_s, int D, int steps, const double* dparam,
+                            double* dstep)
+{
+    using namespace litho;
+    if (!dparam || !dstep || !(k_quench >= 0.0) || !finite_nonneg(k_loss) || !finite_pos(bake_time_s) || !finite_pos(pixel_nm)) return LITHO_E_ARG;
+    const int least = min_steps(sigma_acid_nm, sigma_quencher_nm, vertical_scale, thickness_nm, D, pixel_nm);
+    if (least == 0 || steps < least || steps > PEB_MAXSTEPS) return LITHO_E_ARG;
+    param_tangent(thickness_nm, pixel_nm, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps, dparam, dstep);
     return LITHO_OK;
 }
 
