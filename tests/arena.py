@@ -19,13 +19,15 @@ never equals itself as a float.  Works on CPU tensors as well (tests/test_arena_
 import torch
 
 POISON = 0xFF
-POISON_WORD = -1                                                               # 0xFFFFFFFF as int32
+POISON_WORD = -1                                                               # all-ones as int16, int32 or int64
+_BITS = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}       # the integer view of an element, by its width
 ROLES = ("in", "out", "work")
 
 
 class Buf:
     """One buffer of the call: `role` "in" (must not change), "out" (must be written completely) or "work" (scratch: its
-    contents are nobody's business, its borders are); `mod` = the start offset in bytes modulo 16."""
+    contents are nobody's business, its borders are); `mod` = the start offset in bytes modulo 16, a multiple of the element
+    size (an 8-byte element starts at 0 or 8)."""
 
     def __init__(self, name, role, dtype, shape, mod=0):
         assert role in ROLES and mod in (0, 4, 8, 12), (name, role, mod)
@@ -33,25 +35,33 @@ class Buf:
         count = 1
         for v in self.shape:
             count *= v
-        self.nbytes = count * torch.empty((), dtype=dtype).element_size()
-        assert self.nbytes > 0, name
+        self.itemsize = torch.empty((), dtype=dtype).element_size()
+        self.nbytes = count * self.itemsize
+        assert self.nbytes > 0 and mod % min(self.itemsize, 16) == 0, (name, self.nbytes, dtype, mod)
         self.start = self.end = None
 
 
 def words(t):
-    """The bit patterns of a tensor as a flat int32 tensor (fp32, int32, complex64) or uint8 tensor (uint8)."""
+    """The bit patterns of a tensor, element by element, as a flat integer tensor of the element's width: uint8 (1 byte), int16
+    (int16), int32 (fp32, int32; complex64 as its real parts) or int64 (fp64, int64; complex128 as its real parts)."""
     t = t.contiguous()
     if t.is_complex():
         t = torch.view_as_real(t)
     t = t.reshape(-1)
-    return t if t.dtype == torch.uint8 else t.view(torch.int32)
+    bits = _BITS[t.element_size()]
+    return t if t.dtype == bits else t.view(bits)
+
+
+def poison_of(w):
+    """The poison pattern as an element of words()' dtype: 0xFF for bytes, -1 (all-ones) for the signed widths."""
+    return POISON if w.dtype == torch.uint8 else POISON_WORD
 
 
 def differing(a, b):
-    """Byte offsets of the 4-byte words (bytes, for uint8) in which a and b differ as bit patterns; a shape mismatch is an error."""
+    """Byte offsets of the elements (of a's own width) in which a and b differ as bit patterns; a shape mismatch is an error."""
     wa, wb = words(a), words(b.to(a.device))
     assert wa.shape == wb.shape and wa.dtype == wb.dtype, (tuple(a.shape), tuple(b.shape))
-    step = 1 if wa.dtype == torch.uint8 else 4
+    step = wa.element_size()
     return [step * i for i in (wa != wb).nonzero().flatten().cpu().tolist()]
 
 
@@ -68,7 +78,7 @@ class Report:
     def __str__(self):
         def some(items):
             return f"{len(items)}: {items[:8]}{' ...' if len(items) > 8 else ''}"
-        return f"guard bytes changed {some(self.guards)}; input bytes changed {some(self.inputs)}; output words never written {some(self.unwritten)}"
+        return f"guard bytes changed {some(self.guards)}; input bytes changed {some(self.inputs)}; output elements never written {some(self.unwritten)}"
 
 
 class Arena:
@@ -152,7 +162,7 @@ class Arena:
             if b.role != "out":
                 continue
             got, want = words(self[b.name]), words(reference[b.name].to(cur.device))
-            assert got.shape == want.shape and got.dtype == torch.int32, (b.name, tuple(got.shape), tuple(want.shape))
-            left = (got == POISON_WORD) & (want != POISON_WORD)
-            unwritten += [(b.name, 4 * i) for i in left.nonzero().flatten().cpu().tolist()]
+            assert got.shape == want.shape and got.dtype == want.dtype, (b.name, tuple(got.shape), tuple(want.shape), got.dtype, want.dtype)
+            left = (got == poison_of(got)) & (want != poison_of(got))
+            unwritten += [(b.name, got.element_size() * i) for i in left.nonzero().flatten().cpu().tolist()]
         return Report(guards, inputs, unwritten)

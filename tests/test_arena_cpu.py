@@ -110,6 +110,57 @@ def test_a_workspace_of_exact_size(nbytes):
     assert a.report(want).guards == [("work", nbytes)]
 
 
+WIDTHS = {"int16 of odd length": (torch.int16, (7, 7), 4), "int64": (torch.int64, (9,), 8), "float64": (torch.float64, (5, 4), 8)}
+
+
+@pytest.mark.parametrize("kind", list(WIDTHS))
+def test_elements_of_two_and_eight_bytes(kind):
+    """The dtypes of the geometry family: int16 [pn, pn] with odd pn (98 bytes: no multiple of 4), int64 counts, float64 edges.
+    A flipped guard byte, a changed input and an unwritten element are each reported at their byte offset, the last element of
+    the odd-length buffer included; the poison is all-ones at every width."""
+    dtype, shape, mod = WIDTHS[kind]
+    size = torch.empty((), dtype=dtype).element_size()
+    count = int(torch.tensor(shape).prod())
+    a = Arena([Buf("x", "in", dtype, shape, mod), Buf("y", "out", dtype, shape, mod), Buf("tail", "out", torch.int16, (3,), 4)], 64)
+    assert a.ptr("x") % 16 == mod and a.ptr("y") % 16 == mod and a.bufs["y"].nbytes == count * size and a.bufs["tail"].nbytes == 6
+    assert (count * size) % 4 == (2 if dtype == torch.int16 else 0)
+    x = (torch.arange(count, dtype=torch.float64).reshape(shape) * 3.0 + 1.0).to(dtype)
+    a.fill("x", x)
+    a.seal()
+    assert words(a["y"]).dtype == {2: torch.int16, 8: torch.int64}[size] and bool((words(a["y"]) == -1).all())
+    assert bool(torch.isnan(a["y"]).all()) if dtype.is_floating_point else bool((a["y"] == -1).all())
+    want = {"y": x + x, "tail": torch.tensor([1, 0, 1], dtype=torch.int16)}
+    assert a.report(want).unwritten == [("y", size * i) for i in range(count)] + [("tail", 2 * i) for i in range(3)]
+    a["y"].copy_(want["y"])
+    a["tail"].copy_(want["tail"])
+    assert a.report(want).clean and differing(a["y"], want["y"]) == [] and differing(a["tail"], want["tail"]) == []
+    y = a.bufs["y"]
+    a.bytes[y.end] = 0                                                         # the first byte behind y: for int16 [7, 7] at byte 98
+    a.bytes[y.start - 3] ^= 0x01                                               # in front of it
+    a.bytes[a.bufs["x"].start + size * (count - 1) + size - 1] ^= 0x80        # the last byte of the last input element
+    a["y"].view(-1).view({2: torch.int16, 8: torch.int64}[size])[count - 1] = -1     # the last element left as poison
+    a["tail"][2] = -1                                                          # and the odd one behind a 4-byte boundary
+    rep = a.report(want)
+    assert rep.guards == [("y", -3), ("y", y.nbytes)] and rep.inputs == [("x", size * count - 1)], str(rep)
+    assert rep.unwritten == [("y", size * (count - 1)), ("tail", 4)] and not rep.clean, str(rep)
+    assert differing(a["y"], want["y"]) == [size * (count - 1)] and differing(a["tail"], want["tail"]) == [4]
+    # half of an 8-byte element still poison is a written element (its bits differ from the reference, which differing() reports)
+    if size == 8:
+        a["y"].view(-1).view(torch.int32)[0] = -1
+        assert a.report(want).unwritten == [("y", size * (count - 1)), ("tail", 4)] and differing(a["y"], want["y"])[0] == 0
+    # where the reference itself is all-ones, an equal element is no finding
+    want["tail"][2] = -1
+    assert a.report(want).unwritten == [("y", size * (count - 1))]
+
+
+def test_an_eight_byte_element_starts_at_0_or_8():
+    with pytest.raises(AssertionError):
+        Buf("e", "in", torch.float64, (4,), 4)
+    with pytest.raises(AssertionError):
+        Buf("c", "out", torch.int64, (4,), 12)
+    assert Buf("g", "out", torch.int16, (3,), 12).nbytes == 6
+
+
 def test_nothing_launched_leaves_everything_poison():
     a, x = make(mod_w=8)
     assert a.ptr("work") % 16 == 8
