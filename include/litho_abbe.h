@@ -230,7 +230,8 @@ typedef struct litho_abbe_dry_part {
     int64_t source_points;
     int64_t t_item_bytes;       /* one T item of the run's geometry */
     litho_abbe_region plan, twtab, twtab2, slab_region, slab_used, ic_used, chat_used, gam_used, T_region, T_used, recon_T_used,
-                      embed_M, embed_P, embed_O;     /* (bytes 0 = not used by this part) */
+                      embed_M, embed_P, embed_O;     /* (bytes 0 = not used by this part; twtab2 is also filled, in front of the
+                                                      * planning read-back, when a run at the call's own size COULD take the coarse grid) */
 } litho_abbe_dry_part;
 typedef struct litho_abbe_dry_run {
     int32_t size;               /* sizeof(litho_abbe_dry_run) as the caller compiled it */
@@ -239,6 +240,10 @@ typedef struct litho_abbe_dry_run {
     int64_t workspace_bytes;    /* litho_abbe_workspace_bytes(pn, N) */
     litho_abbe_region list_a, list_b, split_counts;   /* the two lists of a split source list; the block counts (head of T, dead before the loops) */
     litho_abbe_dry_part part[2];   /* [0] the whole list, or the non-wrapping part of a split; [1] the wrapping part */
+    litho_abbe_region plan_scratch;   /* the planning launch's partial extrema: 64 bytes per block, ceil(pn / 8) * planes box blocks +
+                                       * ceil(S / 1024) extent blocks (1 .. 256; a counted call: S = its capacity), at the head of
+                                       * the T region of the call's OWN size -- dead before the loops; for an embedded run that lies
+                                       * inside the padded layout's slab region, whichever slabs the plan uses */
 } litho_abbe_dry_run;
 int litho_abbe_plan_dry_run(int pn, int N, int planes, const int32_t *plan_words, const int32_t *split_words,
                             const litho_abbe_options *options, int cus, size_t workspace_bytes, litho_abbe_dry_run *result);

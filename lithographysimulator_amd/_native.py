@@ -317,7 +317,7 @@ class DryRun(ctypes.Structure):
     """litho_abbe_dry_run (include/litho_abbe.h)."""
     _fields_ = ([(n, ctypes.c_int32) for n in ("size", "status", "run_size", "nowrap", "split", "reserved")]
                 + [("workspace_bytes", ctypes.c_int64), ("list_a", Region), ("list_b", Region), ("split_counts", Region),
-                   ("part", DryPart * 2)])
+                   ("part", DryPart * 2), ("plan_scratch", Region)])
 
 
 def plan_dry_run(pn, N, planes, plan_words, split_words=None, options=None, cus=256, workspace_bytes=0):

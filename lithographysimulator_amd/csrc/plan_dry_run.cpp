@@ -13,7 +13,7 @@ litho_abbe_region reg(const Region& r) { return reg(r.off, r.bytes); }
 
 // one run of the source-point loop (accumulate_planned) at grid size `pr` inside the layout `l`, whose T region is `t_bytes` long
 int fill_part(litho_abbe_dry_part& d, const WsLayout& l, size_t t_bytes, const Knobs& kn, const int pl[PLAN_WORDS], int pr, int N,
-              int planes, int64_t S, int cus)
+              int planes, int64_t S, int cus, bool tw2_ready = false)
 {
     RunPlan rp;
     const int rc = plan_run(rp, t_bytes, kn, pl, pr, N, planes, S, cus, true);
@@ -31,7 +31,9 @@ int fill_part(litho_abbe_dry_part& d, const WsLayout& l, size_t t_bytes, const K
     const size_t slab_plane = (size_t)run.g.nt * 4 * pr * sizeof(float);
     d.plan = reg(l.plan);
     d.twtab = reg(l.twtab);
-    d.twtab2 = rp.coarse ? reg(l.twtab2) : reg(l.twtab2.off, 0);
+    // (tw2_ready: abbe_accumulate fills the coarse grid's table in front of the planning read-back whenever a run at the call's
+    // own size COULD take that path, whether or not the plan then does)
+    d.twtab2 = (rp.coarse || tw2_ready) ? reg(l.twtab2) : reg(l.twtab2.off, 0);
     d.slab_region = reg(l.slab);
     d.slab_used = reg(l.slab.off, (size_t)run.PC * run.G * slab_plane);          // zero_slabs: PC planes x G slabs (stride G)
     d.T_region = reg(l.T.off, t_bytes);
@@ -101,6 +103,13 @@ extern "C" int litho_abbe_plan_dry_run(int pn, int N, int planes, const int32_t*
     result->run_size = pe;
     const bool nowrap = list_nowrap(pl, pn);
     result->nowrap = nowrap ? 1 : 0;
+    {   // gather_plan (abbe_engine.hip): one 16-int slot per block of the planning launch, at the head of the own-size T region
+        const int64_t nb_box = (int64_t)((pn + 7) / 8) * planes;
+        int64_t nb_ext = (S + 1023) / 1024;
+        nb_ext = nb_ext < 1 ? 1 : (nb_ext > 256 ? 256 : nb_ext);
+        result->plan_scratch = reg(own.T.off, (size_t)(nb_box + nb_ext) * 16 * sizeof(int32_t));
+    }
+    const bool tw2_ready = pe == pn && kn.coarse && coarse_eligible(pn, N);
     if (S <= 0 || pl[1] < pl[0]) { result->status = LITHO_OK; return LITHO_OK; }      // nothing to add
     if (split_wanted(kn, nowrap, false, S)) {
         const SplitLayout sl = split_layout(pn, pe, N, S);
@@ -121,13 +130,13 @@ extern "C" int litho_abbe_plan_dry_run(int pn, int N, int planes, const int32_t*
                 for (int i = 0; i < 4; ++i) plp[4 + i] = split_words[2 + 4 * part + i];
                 plp[8] = (int)n;
                 if (part == 0 && pe != pn) rc = fill_embedded(result->part[0], kn, plp, pn, pe, N, planes, n, sl.t_end_pad, cus);
-                else rc = fill_part(result->part[part], own, sl.t_bytes_own, kn, plp, pn, N, planes, n, cus);
+                else rc = fill_part(result->part[part], own, sl.t_bytes_own, kn, plp, pn, N, planes, n, cus, tw2_ready);
                 if (rc) { result->status = rc; return LITHO_OK; }
             }
             return LITHO_OK;
         }
     }
-    if (pe == pn || !nowrap || kn.force_general) rc = fill_part(result->part[0], own, own.T.bytes, kn, pl, pn, N, planes, S, cus);
+    if (pe == pn || !nowrap || kn.force_general) rc = fill_part(result->part[0], own, own.T.bytes, kn, pl, pn, N, planes, S, cus, tw2_ready);
     else rc = fill_embedded(result->part[0], kn, pl, pn, pe, N, planes, S, 0, cus);
     result->status = rc;
     return LITHO_OK;

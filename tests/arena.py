@@ -15,18 +15,23 @@ After the call `report(reference)` lists, as (buffer name, byte offset from the 
 changed (a negative offset lies in front of the buffer, one >= its size behind it; a byte between two buffers goes to the nearer
 one), every input byte that changed, and every 4-byte word of an output that still holds the poison pattern where the reference
 result does not.  All comparisons are of bit patterns, through uint8 or int32 views: a result may hold NaN (walls) and a NaN
-never equals itself as a float.  Works on CPU tensors as well (tests/test_arena_cpu.py)."""
+never equals itself as a float.  A buffer that is accumulated into has the role "inout": filled, sealed and guarded, but left
+to the caller to compare (sealed(name) is what it held).  For a workspace whose call declares WHICH bytes it may use,
+touched_outside(name, ranges) lists the bytes outside those ranges that no longer hold the poison.  Every comparison runs on the
+arena's own device, in runs of at most CHUNK bytes.  Works on CPU tensors as well (tests/test_arena_cpu.py)."""
 import torch
 
 POISON = 0xFF
 POISON_WORD = -1                                                               # all-ones as int16, int32 or int64
 _BITS = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}       # the integer view of an element, by its width
-ROLES = ("in", "out", "work")
+ROLES = ("in", "out", "work", "inout")
+CHUNK = 1 << 28                                                                # bytes compared at a time: a workspace may be 5 GiB
 
 
 class Buf:
-    """One buffer of the call: `role` "in" (must not change), "out" (must be written completely) or "work" (scratch: its
-    contents are nobody's business, its borders are); `mod` = the start offset in bytes modulo 16, a multiple of the element
+    """One buffer of the call: `role` "in" (must not change), "out" (must be written completely), "work" (scratch: its
+    contents are nobody's business, its borders are) or "inout" (accumulated into: filled, sealed and guarded like an input, but
+    exempt from the input-unchanged and the never-written scans -- the caller compares its values); `mod` = the start offset in bytes modulo 16, a multiple of the element
     size (an 8-byte element starts at 0 or 8)."""
 
     def __init__(self, name, role, dtype, shape, mod=0):
@@ -97,14 +102,16 @@ class Arena:
         shift = -raw.data_ptr() % 256
         self.bytes = raw[shift:shift + self.size]
         assert self.bytes.data_ptr() % 256 == 0 and shift % 16 == 0
-        outside = torch.ones(self.size, dtype=torch.bool)
-        inside_in = torch.zeros(self.size, dtype=torch.bool)
         for b in bufs:
-            outside[b.start:b.end] = False
-            if b.role == "in":
-                inside_in[b.start:b.end] = True
             assert self[b.name].data_ptr() % 16 == b.mod, (b.name, self[b.name].data_ptr() % 16, b.mod)
-        self._guard_mask, self._input_mask = outside.to(device), inside_in.to(device)
+        # the guards, as (start, end) byte runs of the arena between its buffers; no mask is built: the comparisons below run run
+        # by run and buffer by buffer on the arena's own device (a workspace of 5 GiB would need as much again per mask, and
+        # a mask built on the CPU would have to be copied there)
+        self._gaps, at = [], 0
+        for b in bufs:
+            self._gaps.append((at, b.start))
+            at = b.end
+        self._gaps.append((at, self.size))
         self._sealed = None
 
     def __getitem__(self, name):
@@ -132,7 +139,7 @@ class Arena:
 
     def seal(self):
         """Remember the arena as it is now, inputs in place: what report() compares the inputs with."""
-        self._sealed = self.bytes.clone()
+        self._sealed = {b.name: self.bytes[b.start:b.end].clone() for b in self.bufs.values() if b.role in ("in", "inout")}
 
     def _locate(self, positions):
         """(name, offset) per arena byte position: inside a buffer that buffer, outside the nearer one."""
@@ -146,17 +153,47 @@ class Arena:
             out.append((best[1].name, p - best[1].start))
         return out
 
+    def _where(self, lo, hi, other=None):
+        """Arena byte positions in [lo, hi) that differ from the poison -- or from `other`, a tensor of hi - lo bytes."""
+        out = []
+        for a in range(lo, hi, CHUNK):
+            b = min(hi, a + CHUNK)
+            bad = self.bytes[a:b] != (POISON if other is None else other[a - lo:b - lo])
+            if bool(bad.any()):
+                out += [a + i for i in bad.nonzero().flatten().cpu().tolist()]
+        return out
+
+    def sealed(self, name):
+        """The buffer as seal() found it ("in" and "inout" buffers), in its own dtype and shape."""
+        b = self.bufs[name]
+        return self._sealed[name].view(b.dtype).view(b.shape)
+
+    def touched_outside(self, name, ranges):
+        """For a "work" buffer and `ranges` = [(offset, bytes), ...] relative to its start: the byte offsets of the buffer that lie
+        outside every range and no longer hold the poison, in ascending order."""
+        b = self.bufs[name]
+        assert b.role == "work", (name, b.role)
+        out, at = [], 0
+        for off, n in sorted((int(o), int(n)) for o, n in ranges if n > 0):
+            assert 0 <= off and off + n <= b.nbytes, (name, off, n, b.nbytes)
+            if off > at:
+                out += self._where(b.start + at, b.start + off)
+            at = max(at, off + n)
+        if at < b.nbytes:
+            out += self._where(b.start + at, b.end)
+        return [p - b.start for p in out]
+
     def still_poison(self, name):
         """True when every byte of the buffer is still 0xFF: nothing was launched on it."""
         b = self.bufs[name]
-        return bool((self.bytes[b.start:b.end] == POISON).all())
+        return not self._where(b.start, b.end)
 
     def report(self, reference):
         """`reference`: {output name: the tensor the output is expected to equal}; every "out" buffer needs one."""
         assert self._sealed is not None, "seal() the arena after the inputs are in"
         cur = self.bytes
-        guards = self._locate(((cur != POISON) & self._guard_mask).nonzero().flatten().cpu().tolist())
-        inputs = self._locate(((cur != self._sealed) & self._input_mask).nonzero().flatten().cpu().tolist())
+        guards = self._locate([p for lo, hi in self._gaps for p in self._where(lo, hi)])
+        inputs = self._locate([p for b in self.bufs.values() if b.role == "in" for p in self._where(b.start, b.end, self._sealed[b.name])])
         unwritten = []
         for b in self.bufs.values():
             if b.role != "out":

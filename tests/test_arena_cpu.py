@@ -167,3 +167,82 @@ def test_nothing_launched_leaves_everything_poison():
     assert a.still_poison("y") and a.still_poison("work") and a.report({"y": 2.0 * x}).unwritten[0] == ("y", 0)
     a["work"][3] = 0
     assert not a.still_poison("work")
+
+
+# ---- a workspace whose call declares which bytes it may use -----------------------------------------------------------------------
+RANGES = [(256, 512), (1024, 256)]                                             # [256, 768) and [1024, 1280) of a 2000-byte workspace
+
+
+def declared(work_bytes=2000):
+    a, x = make(work_bytes=work_bytes)
+    w = a["work"]
+    for off, n in RANGES:                                                      # a correct call: writes inside its ranges only
+        w[off:off + n] = 0x11
+    return a, x
+
+
+def test_touched_outside_a_clean_case():
+    a, x = declared()
+    assert a.touched_outside("work", RANGES) == [] and a.touched_outside("work", list(reversed(RANGES))) == []
+    assert a.touched_outside("work", RANGES + [(0, 0)]) == []                 # an absent region (0 bytes) declares nothing
+    assert a.touched_outside("work", [RANGES[0]]) == list(range(1024, 1280))   # the harness can fail: a range withheld
+    assert a.touched_outside("work", [(256, 511), RANGES[1]]) == [767]         # ... or shortened by one byte
+
+
+@pytest.mark.parametrize("where, at", [("just before a range", 255), ("just after a range", 768), ("between two ranges", 900),
+                                       ("just before the second range", 1023), ("just after the last range", 1280),
+                                       ("the first byte", 0), ("the last byte", 1999)])
+def test_touched_outside_one_planted_byte(where, at):
+    a, x = declared()
+    a["work"][at] = 0
+    assert a.touched_outside("work", RANGES) == [at], where
+    a["work"][at] = POISON                                                     # the poison value itself written there: not seen, by design
+    assert a.touched_outside("work", RANGES) == []
+
+
+def test_touched_outside_overlapping_ranges_and_a_whole_buffer():
+    a, x = declared()
+    a["work"][700:1100] = 0x22
+    assert a.touched_outside("work", [(256, 512), (600, 500), (1024, 256)]) == []
+    assert a.touched_outside("work", [(0, 2000)]) == [] and a.touched_outside("work", []) == list(range(256, 1280))
+    with pytest.raises(AssertionError):
+        a.touched_outside("work", [(1900, 101)])                               # a range that leaves the buffer
+    with pytest.raises(AssertionError):
+        a.touched_outside("x", RANGES)                                         # only a workspace has declared ranges
+
+
+def test_an_accumulated_buffer_is_guarded_and_sealed_but_left_to_the_caller():
+    """Role "inout": the prefill is kept by seal(), a change of the buffer is neither "input changed" nor "never written" --
+    whether it was written at all is for the caller to see by comparing values -- and its guards are watched like any other."""
+    a = Arena([Buf("x", "in", torch.float32, (4,)), Buf("acc", "inout", torch.float32, (3, 3), 8), Buf("w", "work", torch.uint8, (64,))], 64)
+    pre = torch.arange(9, dtype=torch.float32).reshape(3, 3) * 0.5 + 1.0
+    a.fill("x", torch.ones(4))
+    a.fill("acc", pre)
+    a.seal()
+    assert a.ptr("acc") % 16 == 8 and a.leading_guard("acc") >= 64 and a.trailing_guard("acc") >= 64
+    assert a.report({}).clean and torch.equal(a.sealed("acc"), pre) and torch.equal(a.sealed("x"), torch.ones(4))
+    a["acc"].add_(2.0)                                                         # the call accumulates: no finding
+    a["acc"].view(torch.int32)[1, 1] = -1                                      # even an element that IS the poison pattern is the caller's
+    rep = a.report({})
+    assert rep.clean, str(rep)
+    assert torch.equal(a.sealed("acc"), pre) and differing(a["acc"], pre + 2.0) == [16]
+    b = a.bufs["acc"]
+    a.bytes[b.end] = 0
+    a.bytes[b.start - 1] = 0
+    a["x"][2] = 5.0
+    rep = a.report({})
+    assert rep.guards == [("acc", -1), ("acc", b.nbytes)] and [n for n, _ in rep.inputs] == ["x"] * len(rep.inputs) and rep.inputs
+    assert all(8 <= off < 12 for _, off in rep.inputs) and not rep.unwritten
+
+
+def test_comparisons_in_chunks(monkeypatch):
+    """The scans walk the arena CHUNK bytes at a time: findings on both sides of a chunk border, reported once each."""
+    import arena
+    monkeypatch.setattr(arena, "CHUNK", 100)
+    a, x = declared()
+    for at in (99, 100, 199, 900, 1999):
+        a["work"][at] = 3
+    assert a.touched_outside("work", RANGES) == [99, 100, 199, 900, 1999]
+    assert not a.still_poison("work") and a.still_poison("y")
+    a.bytes[a.size - 1] = 0
+    assert a.report({"y": 2.0 * x}).guards == [("work", a.size - 1 - a.bufs["work"].start)]
