@@ -193,6 +193,20 @@ def check(rc, what):
                      "16..16384)")
 
 
+def call(dev, name, *args, keep=(), noconv=None):
+    """The guarded call of a resist-chain entry point: `name`(*args, the current stream of `dev`) in the device's context, its return
+    code through `check` (LITHO_E_NOCONV as RuntimeError(noconv) where `noconv` is given), then record_stream on the tensors of
+    `keep` that are not None."""
+    with torch.cuda.device(dev):
+        rc = getattr(lib(), name)(*args, stream_ptr(dev))
+        if noconv is not None and rc == E_NOCONV:
+            raise RuntimeError(noconv)
+        check(rc, name)
+        for t in keep:
+            if t is not None:
+                t.record_stream(torch.cuda.current_stream(dev))
+
+
 def require_gpu(device):
     if not isinstance(device, torch.device):
         device = torch.device(device)

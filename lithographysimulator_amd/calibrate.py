@@ -26,9 +26,10 @@ import math
 import torch
 
 from . import _native as nat
-from .develop import MackResist, _development_time, _gains, _like, _positive, _volume, developmentRate, developmentTimeGradient, latentDiffusion
+from .develop import (MackResist, _development_time, _gains, _like, _positive, _surface_depth, _volume, developmentRate, developmentTimeGradient,
+                      latentDiffusion)
 from .film import FilmStack
-from .peb import (ChemicallyAmplifiedResist, _cotangent, _steps, amplifiedRate, amplifiedRateGradient, bakeAcid, exposeAcid)
+from .peb import ChemicallyAmplifiedResist, _bake_vjp, _steps, amplifiedRate, amplifiedRateGradient, bakeAcid, exposeAcid
 
 STEP_SLOTS = ("lxy_h", "lz_h", "lxy_q", "lz_q", "beta", "fl")
 BAKE_PARAMETERS = ("kQuench", "kLoss", "acidDiffusionLength", "quencherDiffusionLength", "verticalScale")
@@ -43,34 +44,24 @@ def bakeStepGradient(acid, resist, thickness, pixelSize, gradAcid=None, gradQuen
     each volume, in double, in a fixed order: the bits depend on neither `checkpointEvery`, nor the other volumes of the batch,
     nor the call.  The slots of a species that does not diffuse are exactly 0, and so is beta's for instantaneous
     neutralisation.  The workspace keeps four volumes per taped step: (2 (ceil(steps / c) - 1) + 4 c + 8) volumes."""
-    who = "bakeStepGradient"
-    if not isinstance(resist, ChemicallyAmplifiedResist):
-        raise TypeError(f"{who}: resist must be a ChemicallyAmplifiedResist")
-    v, B, D, n, batched, dev = _volume(who, acid, "acid")
-    thickness, h = _positive(who, "thickness", thickness), _positive(who, "pixelSize", pixelSize)
-    S = _steps(who, resist, thickness, D, h, steps)
-    c = math.isqrt(S - 1) + 1 if checkpointEvery is None else int(checkpointEvery)    # ceil(sqrt(S))
-    if not 1 <= c <= S:
-        raise ValueError(f"{who}: checkpointEvery must be 1 ... steps ({S}); got {checkpointEvery}")
-    gh, gq, ga = (_cotangent(who, name, g, v, batched) for name, g in (("gradAcid", gradAcid), ("gradQuencher", gradQuencher),
-                                                                        ("gradAcidDose", gradAcidDose)))
-    if gh is None and gq is None and ga is None:
-        raise ValueError(f"{who}: give at least one of gradAcid, gradQuencher, gradAcidDose")
-    lib = nat.lib()
-    out_h, out_q = torch.empty_like(v), torch.empty_like(v)
-    out_s = torch.empty((B, 6), dtype=torch.float64, device=dev)
-    nbytes = int(lib.litho_peb_vjp_params_work_bytes(B, D, n, S, c))
-    work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    opt = lambda t: nat.ptr(t) if t is not None else None                       # noqa: E731
-    with torch.cuda.device(dev):
-        nat.check(lib.litho_peb_bake_vjp_params(nat.ptr(v), B, D, n, thickness, h, resist.quencher, resist.kQuench, resist.kLoss,
-                                                resist.acidDiffusionLength, resist.quencherDiffusionLength, resist.verticalScale,
-                                                resist.bakeTime, S, c, opt(gh), opt(gq), opt(ga), nat.ptr(out_h), nat.ptr(out_q),
-                                                nat.ptr(out_s), nat.ptr(work), nbytes, nat.stream_ptr(dev)), "litho_peb_bake_vjp_params")
-        for t in (v, gh, gq, ga, work):
-            if t is not None:
-                t.record_stream(torch.cuda.current_stream(dev))
-    return (out_h, out_q, out_s) if batched else (out_h[0], out_q[0], out_s[0])
+    return _bake_vjp("bakeStepGradient", True, acid, resist, thickness, pixelSize, gradAcid, gradQuencher, gradAcidDose, steps, checkpointEvery)
+
+
+def _bake_rows(who, what, rows, n_in, n_out, entry, resist, thickness, pixelSize, D, steps):
+    """`rows` [..., n_in] -> float64 [..., n_out] on the host, row by row through the host entry `entry` of the bake's step
+    parameters (litho_peb_param_chain or its transpose litho_peb_param_tangent) at the fixed step count."""
+    t = torch.as_tensor(rows).detach().to(device="cpu", dtype=torch.float64)
+    if t.shape[-1:] != (n_in,):
+        raise ValueError(f"{who}: {what} must be [..., {n_in}]; got {tuple(t.shape)}")
+    flat = t.reshape(-1, n_in)
+    out = torch.empty((flat.shape[0], n_out), dtype=torch.float64)
+    src, dst = (ctypes.c_double * n_in)(), (ctypes.c_double * n_out)()
+    for i in range(flat.shape[0]):
+        src[:] = flat[i].tolist()
+        nat.check(getattr(nat.lib(), entry)(float(thickness), float(pixelSize), resist.kQuench, resist.kLoss, resist.acidDiffusionLength,
+                                            resist.quencherDiffusionLength, resist.verticalScale, resist.bakeTime, int(D), int(steps), src, dst), entry)
+        out[i] = torch.tensor(list(dst), dtype=torch.float64)
+    return out.reshape(t.shape[:-1] + (n_out,))
 
 
 def bakeParameterChain(gradStep, resist, thickness, pixelSize, D, steps):
@@ -78,20 +69,7 @@ def bakeParameterChain(gradStep, resist, thickness, pixelSize, D, steps):
     quencherDiffusionLength, verticalScale) at the fixed step count `steps` (litho_peb_param_chain, host arithmetic in double):
     the analytic derivative of lambda_xy = sigma^2 / (2 S pixel^2), lambda_z = (v sigma)^2 / (2 S hz^2), beta = kQuench dt and
     fl = exp(-kLoss dt), not the derivative of their rounding to fp32.  kQuench's is 0 for instantaneous neutralisation."""
-    who = "bakeParameterChain"
-    g = torch.as_tensor(gradStep).detach().to(device="cpu", dtype=torch.float64)
-    if g.shape[-1:] != (6,):
-        raise ValueError(f"{who}: gradStep must be [..., 6]; got {tuple(g.shape)}")
-    flat = g.reshape(-1, 6)
-    out = torch.empty((flat.shape[0], 5), dtype=torch.float64)
-    src, dst = (ctypes.c_double * 6)(), (ctypes.c_double * 5)()
-    for i in range(flat.shape[0]):
-        src[:] = flat[i].tolist()
-        nat.check(nat.lib().litho_peb_param_chain(float(thickness), float(pixelSize), resist.kQuench, resist.kLoss, resist.acidDiffusionLength,
-                                                  resist.quencherDiffusionLength, resist.verticalScale, resist.bakeTime, int(D), int(steps),
-                                                  src, dst), "litho_peb_param_chain")
-        out[i] = torch.tensor(list(dst), dtype=torch.float64)
-    return out.reshape(g.shape[:-1] + (5,))
+    return _bake_rows("bakeParameterChain", "gradStep", gradStep, 6, 5, "litho_peb_param_chain", resist, thickness, pixelSize, D, steps)
 
 
 def bakeParameterGradient(acid, resist, thickness, pixelSize, gradAcid=None, gradQuencher=None, gradAcidDose=None, steps=None, checkpointEvery=None):
@@ -118,16 +96,10 @@ def _rate_sums(who, x, doses, kappa, mack, thickness, gradSlowness):
     g, count = _gains(who, doses, F, D)
     gs = _like(who, "gradSlowness", gradSlowness, (count * F, D, n, n), dev)
     out = torch.empty((count * F, D, 6), dtype=torch.float64, device=dev)
-    lib = nat.lib()
-    nbytes = int(lib.litho_develop_rate_params_work_bytes(F, D, n, count))
+    nbytes = int(nat.lib().litho_develop_rate_params_work_bytes(F, D, n, count))
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    delta = mack.surfaceDepth if mack.surfaceDepth is not None else thickness
-    with torch.cuda.device(dev):
-        nat.check(lib.litho_develop_rate_vjp_params(nat.ptr(v), F, D, n, g, count, kappa, mack.rMax, mack.rMin, mack.q, mack.mTh,
-                                                    mack.surfaceRate, delta, thickness, nat.ptr(gs), nat.ptr(out), nat.ptr(work), nbytes,
-                                                    nat.stream_ptr(dev)), "litho_develop_rate_vjp_params")
-        for t in (v, gs, work):
-            t.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_develop_rate_vjp_params", nat.ptr(v), F, D, n, g, count, kappa, mack.rMax, mack.rMin, mack.q, mack.mTh, mack.surfaceRate,
+             _surface_depth(mack, thickness), thickness, nat.ptr(gs), nat.ptr(out), nat.ptr(work), nbytes, keep=(v, gs, work))
     return out
 
 
@@ -139,11 +111,10 @@ def rateParameterChain(planeSums, mack, thickness):
         raise ValueError(f"rateParameterChain: planeSums must be [G, D, 6]; got {tuple(s.shape)}")
     G, D = int(s.shape[0]), int(s.shape[1])
     thickness = float(thickness)
-    delta = mack.surfaceDepth if mack.surfaceDepth is not None else thickness
     src = (ctypes.c_double * (G * D * 6))(*s.reshape(-1).tolist())
     dst = (ctypes.c_double * (G * 7))()
-    nat.check(nat.lib().litho_develop_rate_param_chain(mack.rMax, mack.rMin, mack.q, mack.mTh, mack.surfaceRate, delta, thickness, D, G, src,
-                                                       dst), "litho_develop_rate_param_chain")
+    nat.check(nat.lib().litho_develop_rate_param_chain(mack.rMax, mack.rMin, mack.q, mack.mTh, mack.surfaceRate, _surface_depth(mack, thickness),
+                                                       thickness, D, G, src, dst), "litho_develop_rate_param_chain")
     return torch.tensor(list(dst), dtype=torch.float64).reshape(G, 7)
 
 
@@ -183,14 +154,10 @@ def exposureParameterGradient(image, C, doses, gradAcid):
     g, count = _gains(who, doses, F, D)
     ga = _like(who, "gradAcid", gradAcid, (count * F, D, n, n), dev)
     out = torch.empty(count * F, dtype=torch.float64, device=dev)
-    lib = nat.lib()
-    nbytes = int(lib.litho_peb_expose_params_work_bytes(F, D, n, count))
+    nbytes = int(nat.lib().litho_peb_expose_params_work_bytes(F, D, n, count))
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(lib.litho_peb_expose_vjp_params(nat.ptr(v), F, D, n, g, count, _positive(who, "C", C), nat.ptr(ga), nat.ptr(out),
-                                                  nat.ptr(work), nbytes, nat.stream_ptr(dev)), "litho_peb_expose_vjp_params")
-        for t in (v, ga, work):
-            t.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_peb_expose_vjp_params", nat.ptr(v), F, D, n, g, count, _positive(who, "C", C), nat.ptr(ga), nat.ptr(out), nat.ptr(work),
+             nbytes, keep=(v, ga, work))
     return out.cpu()
 
 

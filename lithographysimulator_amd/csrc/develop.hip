@@ -253,12 +253,12 @@ int litho_latent_diffuse(const float* image, int B, int D, int n, double sigma_x
     int Rxy = 0, Rz = 0;
     if (!make_taps(sigma_xy_px, txy, Rxy) || !make_taps(sigma_z_px, tz, Rz)) return LITHO_E_ARG;
     const size_t bytes = (size_t)B * D * n * n * sizeof(float);
-    if (overlap(image, bytes, out, bytes)) return LITHO_E_ARG;
+    if (!writes_clear({{out, bytes}}, {{image, bytes}})) return LITHO_E_ARG;
     const int passes = (Rxy ? 2 : 0) + (Rz ? 1 : 0);
     if (passes >= 2) {
         if (!work) return LITHO_E_ARG;
         if (work_bytes < bytes) return LITHO_E_WORKSPACE;
-        if (overlap(work, bytes, image, bytes) || overlap(work, bytes, out, bytes)) return LITHO_E_ARG;   // a pass would read what it writes
+        if (!writes_clear({{work, bytes}, {out, bytes}}, {{image, bytes}})) return LITHO_E_ARG;   // a pass would read what it writes
     }
     hipStream_t st = (hipStream_t)stream;
     if (passes == 0) {                                   // the identity, bit for bit
@@ -317,12 +317,11 @@ int litho_develop_time(const float* slowness, int B, int D, int n, double thickn
     if (!slowness || !T || !work || !launches_host || !volume_ok(B, D, n)) return LITHO_E_ARG;
     if (max_iterations < 1 || max_iterations > VOL_MAXIT || !finite_pos(thickness_nm) || !finite_pos(pixel_nm)) return LITHO_E_ARG;
     const size_t vol_bytes = (size_t)B * D * n * n * sizeof(float), need = litho_develop_work_bytes(B, D, n, max_iterations);
-    if (!aligned16(work) || overlap(T, vol_bytes, slowness, vol_bytes)) return LITHO_E_ARG;
+    if (!aligned16(work) || !writes_clear({{T, vol_bytes}}, {{slowness, vol_bytes}})) return LITHO_E_ARG;
     if (work_bytes < need) return LITHO_E_WORKSPACE;
-    if (overlap(work, need, T, vol_bytes) || overlap(work, need, slowness, vol_bytes)) return LITHO_E_ARG;   // the second T buffer lives there
-    const float h = (float)pixel_nm, hz = (float)(thickness_nm / D);
-    const float wxy = 1.f / (h * h), wz = 1.f / (hz * hz);
-    if (!(h > 0.f) || !(hz > 0.f) || std::isinf(wxy) || std::isinf(wz) || !(wxy > 0.f) || !(wz > 0.f)) return LITHO_E_ARG;
+    if (!writes_clear({{work, need}, {T, vol_bytes}}, {{slowness, vol_bytes}})) return LITHO_E_ARG;   // the second T buffer lives there
+    FrontGeometry geo;
+    if (!front_geometry(pixel_nm, thickness_nm, D, geo)) return LITHO_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     int* flags = (int*)work;
     float* buf[2] = {T, (float*)((char*)work + flag_bytes(max_iterations))};
@@ -337,8 +336,8 @@ int litho_develop_time(const float* slowness, int B, int D, int n, double thickn
     const dim3 grid(tiles, tiles, (unsigned)B);
     // launch `it` reads buf[it & 1] and writes the other
     const int launches = iterate_until_unchanged(flags, max_iterations, st, [&](int it) {
-        hipLaunchKernelGGL(k_develop_time, grid, dim3(256), lds, st, slowness, (const float*)buf[it & 1], buf[(it + 1) & 1], D, n, h, hz,
-                           wxy, wz, flags + it);
+        hipLaunchKernelGGL(k_develop_time, grid, dim3(256), lds, st, slowness, (const float*)buf[it & 1], buf[(it + 1) & 1], D, n, geo.h, geo.hz,
+                           geo.wxy, geo.wz, flags + it);
     });
     if (launches < 0) return launches;
     *launches_host = launches ? launches : max_iterations;

@@ -12,10 +12,13 @@
 //   k_develop_time_vjp  the tiled gather iteration for lambda (below)
 //   k_develop_scale     grad_s = lambda sigma, exactly 0 where the cell has no gradient
 //   k_develop_rate_vjp  the rate law of k_develop_rate / k_peb_rate backwards, double per cell, the gains summed inside
-// and behind litho_develop_rate_vjp_params k_develop_rate_params, the rate law's six parameter sums per gained plane (section 5).
+// and behind litho_develop_rate_vjp_params k_develop_rate_params, the rate law's six parameter sums per gained plane (section 5);
+// behind litho_develop_rate_jvp and litho_develop_time_jvp k_develop_rate_jvp and k_develop_time_jvp, forward mode (section 6).  The
+// three rate kernels share rate_cell and rate_derivatives, the two solver entries front_derivative (section 7), the two host
+// chains of the rate law rate_chain (section 8).
 // The pointwise kernels move four consecutive x per thread (16-byte accesses) when n is a multiple of 4 and the pointers are
 // 16-byte aligned, one otherwise.  The limits, the packs, the host predicates, the gains, the rate law (mack_slowness_dx, next to
-// the forward's mack_slowness) and the solver's host loop are resist_volume.hpp's, shared with develop.hip and peb.hip.
+// the forward's mack_slowness), the solvers' geometry and host loop are resist_volume.hpp's, shared with develop.hip and peb.hip.
 //
 // Links.  Four fp32 per cell, (lx, ly, lz, sigma).  |l| is alpha on that axis; the sign carries the direction: positive when the
 // upwind cell is the lower-index neighbour (a tie of the two neighbours goes there), negative when it is the higher-index one.
@@ -258,8 +261,26 @@ __global__ __launch_bounds__(256) void k_develop_scale(const float* __restrict__
     store_pack<VEC>(out + at, r);
 }
 
-// ---- 4. the rate law backwards: m = exp(-(kappa g) x), b = 1 - m, db/dx = (kappa g) m, ds/dx from mack_slowness_dx
-// (resist_volume.hpp), summed over the gains.  A wall (1 - m negative or NaN) contributes 0.
+// ---- 4. the rate law backwards.  A cell of the rate law under the gain g: m = exp(-(kappa g) x) and b = 1 - m, the dissolved
+// fraction; a wall where b is negative or NaN.
+struct RateCell { double m, b; bool wall; };
+__device__ __forceinline__ RateCell rate_cell(double kg, double x)
+{
+    const double m = exp(-(kg * x)), b = 1.0 - m;
+    return RateCell{m, b, !(b >= 0.0)};
+}
+// The six derivatives of the slowness of a cell that is no wall: d[0] = ds/dkappa (mack_slowness_dx with db/dkappa = (g x) m) and
+// d[1 .. 5] = mack_slowness_dparams' five (resist_volume.hpp), what the parameter sums and the tangent both take.
+__device__ __forceinline__ void rate_derivatives(const RateCell& c, double g, double x, double rmax_a1, double rmin, double q, double a, double f,
+                                                 double (&d)[6])
+{
+    double five[5];
+    mack_slowness_dparams(c.b, rmax_a1, rmin, q, a, f, five);
+    d[0] = mack_slowness_dx(c.b, (g * x) * c.m, rmax_a1, rmin, q, a, f);
+    for (int j = 0; j < 5; ++j) d[1 + j] = five[j];
+}
+
+// k_develop_rate_vjp: db/dx = (kappa g) m, ds/dx from mack_slowness_dx, summed over the gains.  A wall contributes 0.
 template <int VEC>
 __global__ __launch_bounds__(256) void k_develop_rate_vjp(const float* __restrict__ x, const float* __restrict__ grad_s,
                                                           float* __restrict__ grad_x, int planes, int D, int n, const VolGains gains,
@@ -279,10 +300,9 @@ __global__ __launch_bounds__(256) void k_develop_rate_vjp(const float* __restric
         const double kg = kappa * (double)gains.g[gi];
         const Pack<VEC> gs = load_pack<VEC>(grad_s + ((size_t)gi * planes + p) * plane_elems + e);
         for (int v = 0; v < VEC; ++v) {
-            const double m = exp(-(kg * (double)xv.v[v]));
-            const double b = 1.0 - m;
-            if (!(b >= 0.0)) continue;                   // a wall
-            acc[v] += (double)gs.v[v] * mack_slowness_dx(b, kg * m, rmax_a1, rmin, q, a, f);
+            const RateCell c = rate_cell(kg, (double)xv.v[v]);
+            if (c.wall) continue;
+            acc[v] += (double)gs.v[v] * mack_slowness_dx(c.b, kg * c.m, rmax_a1, rmin, q, a, f);
         }
     }
     Pack<VEC> out;
@@ -291,8 +311,7 @@ __global__ __launch_bounds__(256) void k_develop_rate_vjp(const float* __restric
 }
 
 // ---- 5. the rate law's parameter sums (litho_develop_rate_vjp_params): per cell of a gained plane the six products of the
-// cotangent with ds/dkappa (mack_slowness_dx with db/dkappa = g x m) and with mack_slowness_dparams' five, in double; a wall
-// contributes 0.  A workgroup adds its terms in vol_block_sum's fixed tree and writes them to its own slot
+// cotangent with rate_derivatives' six, in double; a wall contributes 0.  A workgroup adds its terms in vol_block_sum's fixed tree and writes them to its own slot
 // partials[gained plane][workgroup][6]; k_vol_total adds the slots of a gained plane.  grid.y: the n_gains x planes gained planes.
 __global__ __launch_bounds__(256) void k_develop_rate_params(const float* __restrict__ x, const float* __restrict__ grad_s,
                                                              double* __restrict__ partials, int planes, int D, int n,
@@ -307,13 +326,11 @@ __global__ __launch_bounds__(256) void k_develop_rate_params(const float* __rest
     if (e < plane_elems) {
         const double f = surface.f[p % D], g = (double)gains.g[gi], kg = kappa * g;
         const double xv = x[(size_t)p * plane_elems + e], gs = grad_s[(size_t)gp * plane_elems + e];
-        const double m = exp(-(kg * xv));
-        const double b = 1.0 - m;
-        if (b >= 0.0) {                                  // else a wall
-            double d[5];
-            mack_slowness_dparams(b, rmax_a1, rmin, q, a, f, d);
-            t[0] = gs * mack_slowness_dx(b, (g * xv) * m, rmax_a1, rmin, q, a, f);
-            for (int j = 0; j < 5; ++j) t[1 + j] = gs * d[j];
+        const RateCell c = rate_cell(kg, xv);
+        if (!c.wall) {
+            double d[6];
+            rate_derivatives(c, g, xv, rmax_a1, rmin, q, a, f, d);
+            for (int j = 0; j < 6; ++j) t[j] = gs * d[j];
         }
     }
     vol_block_sum<6>(t, lds);
@@ -327,7 +344,7 @@ __global__ __launch_bounds__(256) void k_develop_rate_params(const float* __rest
 // resist chain").
 //
 // The rate law's tangent: ds = ds/dx (kappa g) m dx_p + sum_j d_j dphi[p][plane][j], j = 0 .. 5 in this order, d_0 the line of
-// k_develop_rate_params' slot 0 and d_1 .. d_5 mack_slowness_dparams'; double per cell, rounded once; a wall gives exactly 0.
+// rate_derivatives' d[0] and d_1 .. d_5 its other five; double per cell, rounded once; a wall gives exactly 0.
 // grid.y: the planes of x; the directions and the gains in loops inside.  dx == nullptr: dx = 0.
 template <int VEC>
 __global__ __launch_bounds__(256) void k_develop_rate_jvp(const float* __restrict__ x, const float* __restrict__ dx,
@@ -343,26 +360,22 @@ __global__ __launch_bounds__(256) void k_develop_rate_jvp(const float* __restric
     const Pack<VEC> xv = load_pack<VEC>(x + (size_t)p * plane_elems + e);
     for (int gi = 0; gi < n_gains; ++gi) {
         const double g = (double)gains.g[gi], kg = kappa * g;
-        double m[VEC], b[VEC], dj[VEC][6];
+        RateCell c[VEC];
+        double dj[VEC][6];
         for (int v = 0; v < VEC; ++v) {
-            m[v] = exp(-(kg * (double)xv.v[v]));
-            b[v] = 1.0 - m[v];
-            if (!(b[v] >= 0.0)) continue;                // a wall
-            double five[5];
-            mack_slowness_dparams(b[v], rmax_a1, rmin, q, a, f, five);
-            dj[v][0] = mack_slowness_dx(b[v], (g * (double)xv.v[v]) * m[v], rmax_a1, rmin, q, a, f);
-            for (int j = 0; j < 5; ++j) dj[v][1 + j] = five[j];
+            c[v] = rate_cell(kg, (double)xv.v[v]);
+            if (!c[v].wall) rate_derivatives(c[v], g, (double)xv.v[v], rmax_a1, rmin, q, a, f, dj[v]);
         }
         for (int k = 0; k < P; ++k) {
             const Pack<VEC> dxv = dx ? load_pack<VEC>(dx + ((size_t)k * planes + p) * plane_elems + e) : fill_pack<VEC>(0.f);
             const double* phi = dphi + ((size_t)k * D + d) * 6;
             Pack<VEC> r;
             for (int v = 0; v < VEC; ++v) {
-                if (!(b[v] >= 0.0)) {
+                if (c[v].wall) {
                     r.v[v] = 0.f;
                     continue;
                 }
-                double acc = mack_slowness_dx(b[v], (kg * m[v]) * (double)dxv.v[v], rmax_a1, rmin, q, a, f);
+                double acc = mack_slowness_dx(c[v].b, (kg * c[v].m) * (double)dxv.v[v], rmax_a1, rmin, q, a, f);
                 for (int j = 0; j < 6; ++j) acc = acc + dj[v][j] * phi[j];
                 r.v[v] = (float)acc;
             }
@@ -470,6 +483,73 @@ __global__ __launch_bounds__(256) void k_develop_time_jvp(const float* __restric
     if (changed) *flag = 1;
 }
 
+// ---- 7. what litho_develop_time_vjp (P = 1) and litho_develop_time_jvp share: the checks in their order (the output over an
+// input is reported before the workspace's size), the workspace (flags | links | one buffer of P volumes), the LDS opt-in of
+// `kernel` (lds_done: the caller's once-per-device word, one per kernel), the links, the iteration of launch(...) on a grid P B
+// deep and the launch count.  `source`: the cotangent, or the P directions of the slowness; `out`: P volumes, the second buffer of
+// the ping-pong.  scale: k_develop_scale from the workspace's buffer into `out` closes the call.
+template <class Launch>
+static int front_derivative(const float* slowness, const float* T, const float* source, int B, int D, int n, int P, double thickness_nm,
+                            double pixel_nm, int max_iterations, float* out, void* work, size_t work_bytes, int* launches_host, void* stream,
+                            bool wide, const void* kernel, unsigned& lds_done, size_t lds_plane_bytes, bool scale, Launch launch)
+{
+    if (launches_host) *launches_host = 0;
+    if (!slowness || !T || !source || !out || !work || !launches_host || !volume_ok(B, D, n)) return LITHO_E_ARG;
+    if (P < 1 || P > LITHO_TANGENT_MAX || (long long)P * B * D > 65535) return LITHO_E_ARG;
+    if (max_iterations < 1 || max_iterations > VOL_MAXIT || !finite_pos(thickness_nm) || !finite_pos(pixel_nm)) return LITHO_E_ARG;
+    const size_t cells = (size_t)B * D * n * n, vol_bytes = cells * sizeof(float), tan_bytes = vol_bytes * P;
+    const size_t need = flag_bytes(max_iterations) + 4 * vol_bytes + tan_bytes;
+    if (!aligned16(work)) return LITHO_E_ARG;
+    if (!writes_clear({{out, tan_bytes}}, {{slowness, vol_bytes}, {T, vol_bytes}, {source, tan_bytes}})) return LITHO_E_ARG;
+    if (work_bytes < need) return LITHO_E_WORKSPACE;
+    if (!writes_clear({{work, need}, {out, tan_bytes}}, {{slowness, vol_bytes}, {T, vol_bytes}, {source, tan_bytes}})) return LITHO_E_ARG;
+    FrontGeometry geo;
+    if (!front_geometry(pixel_nm, thickness_nm, D, geo)) return LITHO_E_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    int* flags = (int*)work;
+    float* links = (float*)((char*)work + flag_bytes(max_iterations));
+    float* buf[2] = {links + 4 * cells, out};
+    const size_t lds = (size_t)D * lds_plane_bytes;
+    if (lds > 64 * 1024) HIP_TRY(lds_opt_in(lds_done, kernel, (size_t)VOL_DMAX * lds_plane_bytes));     // once per device: the worst case, D = 32
+    HIP_TRY(hipMemsetAsync(buf[0], 0, tan_bytes, st));
+    LAUNCH_PACKED(k_develop_links, wide, n, B * D, st, slowness, T, (float4*)links, D, n, (double)geo.h, (double)geo.hz);
+    HIP_TRY(hipGetLastError());
+    const unsigned tiles = (unsigned)((n + VOL_TILE - 1) / VOL_TILE);
+    const dim3 grid(tiles, tiles, (unsigned)(P * B));
+    // launch `it` reads buf[it & 1] and writes the other
+    const int launches = iterate_until_unchanged(flags, max_iterations, st, [&](int it) {
+        launch(grid, lds, st, (const float*)links, (const float*)buf[it & 1], buf[(it + 1) & 1], flags + it);
+    });
+    if (launches < 0) return launches;
+    *launches_host = launches ? launches : max_iterations;
+    if (!launches) return LITHO_E_NOCONV;
+    if (scale) {                                         // both buffers hold the fixed point: read the workspace's, write the output
+        LAUNCH_PACKED(k_develop_scale, wide, n, B * D, st, (const float*)buf[0], (const float*)links, out, n);
+        HIP_TRY(hipGetLastError());
+    }
+    return LITHO_OK;
+}
+
+// ---- 8. the coefficients of the chain from the rate law's seven physical numbers to the kernels' six slots, whose two products
+// are litho_develop_rate_param_chain and _param_tangent: a and its two derivatives, and per plane ez = df_d/dr0 and ddelta =
+// df_d/d delta of f_d = 1 - (1 - r0) exp(-z_d / delta).  False when D or a parameter is outside its domain (make_mack's).
+struct RateChain { double a, da_dq, da_dm, ez[VOL_DMAX], ddelta[VOL_DMAX]; };
+static bool rate_chain(double r_max, double r_min, double q, double m_th, double surface_rate, double surface_depth_nm, double thickness_nm, int D,
+                       RateChain& c)
+{
+    MackLaw law;
+    if (D < 1 || D > VOL_DMAX || !make_mack(r_max, r_min, q, m_th, surface_rate, surface_depth_nm, thickness_nm, D, law)) return false;
+    c.a = law.a;
+    c.da_dq = c.a * (1.0 / (q + 1.0) - 1.0 / (q - 1.0) + std::log(1.0 - m_th));
+    c.da_dm = -q * c.a / (1.0 - m_th);
+    for (int d = 0; d < D; ++d) {
+        const double z = thickness_nm * (d + 0.5) / D, ez = std::exp(-z / surface_depth_nm);
+        c.ez[d] = ez;
+        c.ddelta[d] = -(1.0 - surface_rate) * ez * z / (surface_depth_nm * surface_depth_nm);
+    }
+    return true;
+}
+
 }  // namespace litho
 
 extern "C" {
@@ -486,50 +566,13 @@ int litho_develop_time_vjp(const float* slowness, const float* T, const float* g
                            int* launches_host, void* stream)
 {
     using namespace litho;
-    if (launches_host) *launches_host = 0;
-    if (!slowness || !T || !grad_T || !grad_slowness || !work || !launches_host || !volume_ok(B, D, n)) return LITHO_E_ARG;
-    if (max_iterations < 1 || max_iterations > VOL_MAXIT || !finite_pos(thickness_nm) || !finite_pos(pixel_nm)) return LITHO_E_ARG;
-    const size_t cells = (size_t)B * D * n * n, vol_bytes = cells * sizeof(float);
-    const size_t need = litho_develop_vjp_work_bytes(B, D, n, max_iterations);
-    if (!aligned16(work)) return LITHO_E_ARG;
-    const void* in[3] = {slowness, T, grad_T};
-    for (int i = 0; i < 3; ++i)
-        if (overlap(grad_slowness, vol_bytes, in[i], vol_bytes)) return LITHO_E_ARG;     // lambda lives in the output meanwhile
-    if (work_bytes < need) return LITHO_E_WORKSPACE;
-    for (int i = 0; i < 3; ++i)
-        if (overlap(work, need, in[i], vol_bytes)) return LITHO_E_ARG;
-    if (overlap(work, need, grad_slowness, vol_bytes)) return LITHO_E_ARG;
-    // the geometry as litho_develop_time rounds it
-    const float hf = (float)pixel_nm, hzf = (float)(thickness_nm / D);
-    const float wxy = 1.f / (hf * hf), wz = 1.f / (hzf * hzf);
-    if (!(hf > 0.f) || !(hzf > 0.f) || std::isinf(wxy) || std::isinf(wz) || !(wxy > 0.f) || !(wz > 0.f)) return LITHO_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    int* flags = (int*)work;
-    float* links = (float*)((char*)work + flag_bytes(max_iterations));
-    float* buf[2] = {links + 4 * cells, grad_slowness};
-    const size_t lds = (size_t)D * DG_PLANE_BYTES;
-    if (lds > 64 * 1024) {                               // once per device: the worst case, D = 32
-        static unsigned lds_done = 0;
-        HIP_TRY(lds_opt_in(lds_done, (const void*)k_develop_time_vjp, (size_t)VOL_DMAX * DG_PLANE_BYTES));
-    }
-    HIP_TRY(hipMemsetAsync(buf[0], 0, vol_bytes, st));
+    static unsigned lds_done = 0;
     const bool wide = (n & 3) == 0 && aligned16(slowness) && aligned16(T) && aligned16(grad_slowness);
-    LAUNCH_PACKED(k_develop_links, wide, n, B * D, st, slowness, T, (float4*)links, D, n, (double)hf, (double)hzf);
-    HIP_TRY(hipGetLastError());
-    const unsigned tiles = (unsigned)((n + VOL_TILE - 1) / VOL_TILE);
-    const dim3 grid(tiles, tiles, (unsigned)B);
-    // launch `it` reads buf[it & 1] and writes the other
-    const int launches = iterate_until_unchanged(flags, max_iterations, st, [&](int it) {
-        hipLaunchKernelGGL(k_develop_time_vjp, grid, dim3(256), lds, st, (const float*)links, grad_T, (const float*)buf[it & 1],
-                           buf[(it + 1) & 1], D, n, flags + it);
-    });
-    if (launches < 0) return launches;
-    *launches_host = launches ? launches : max_iterations;
-    if (!launches) return LITHO_E_NOCONV;
-    // both buffers hold the fixed point: read the workspace's, write the output
-    LAUNCH_PACKED(k_develop_scale, wide, n, B * D, st, (const float*)buf[0], (const float*)links, grad_slowness, n);
-    HIP_TRY(hipGetLastError());
-    return LITHO_OK;
+    return front_derivative(slowness, T, grad_T, B, D, n, 1, thickness_nm, pixel_nm, max_iterations, grad_slowness, work, work_bytes,
+                            launches_host, stream, wide, (const void*)k_develop_time_vjp, lds_done, DG_PLANE_BYTES, true,
+                            [&](dim3 grid, size_t lds, hipStream_t st, const float* links, const float* in, float* out, int* flag) {
+                                hipLaunchKernelGGL(k_develop_time_vjp, grid, dim3(256), lds, st, links, grad_T, in, out, D, n, flag);
+                            });
 }
 
 int litho_develop_rate_vjp(const float* x, int volumes, int D, int n, const float* gains_host, int n_gains, double kappa, double r_max,
@@ -543,7 +586,7 @@ int litho_develop_rate_vjp(const float* x, int volumes, int D, int n, const floa
         !finite_pos(kappa) || !make_mack(r_max, r_min, q, m_th, surface_rate, surface_depth_nm, thickness_nm, D, law))
         return LITHO_E_ARG;
     const size_t x_bytes = (size_t)volumes * D * n * n * sizeof(float);
-    if (overlap(grad_x, x_bytes, x, x_bytes) || overlap(grad_x, x_bytes, grad_slowness, x_bytes * n_gains)) return LITHO_E_ARG;
+    if (!writes_clear({{grad_x, x_bytes}}, {{x, x_bytes}, {grad_slowness, x_bytes * n_gains}})) return LITHO_E_ARG;
     const int planes = volumes * D;
     const bool wide = (n & 3) == 0 && aligned16(x) && aligned16(grad_slowness) && aligned16(grad_x);
     LAUNCH_PACKED(k_develop_rate_vjp, wide, n, planes, (hipStream_t)stream, x, grad_slowness, grad_x, planes, D, n, gains, n_gains, kappa,
@@ -574,9 +617,7 @@ int litho_develop_rate_vjp_params(const float* x, int volumes, int D, int n, con
     if (work_bytes < need) return LITHO_E_WORKSPACE;
     const int planes = volumes * D;
     const size_t x_bytes = (size_t)planes * n * n * sizeof(float), out_bytes = (size_t)n_gains * planes * 6 * sizeof(double);
-    if (overlap(plane_sums, out_bytes, x, x_bytes) || overlap(plane_sums, out_bytes, grad_slowness, x_bytes * n_gains) ||
-        overlap(plane_sums, out_bytes, work, need) || overlap(work, need, x, x_bytes) || overlap(work, need, grad_slowness, x_bytes * n_gains))
-        return LITHO_E_ARG;
+    if (!writes_clear({{plane_sums, out_bytes}, {work, need}}, {{x, x_bytes}, {grad_slowness, x_bytes * n_gains}})) return LITHO_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     const unsigned blocks = plane_blocks(n, 1);
     hipLaunchKernelGGL(k_develop_rate_params, dim3(blocks, (unsigned)(n_gains * planes)), dim3(256), 0, st, x, grad_slowness, (double*)work,
@@ -590,28 +631,25 @@ int litho_develop_rate_param_chain(double r_max, double r_min, double q, double 
                                    double thickness_nm, int D, int groups, const double* plane_sums, double* grad_param)
 {
     using namespace litho;
-    MackLaw law;
-    if (!plane_sums || !grad_param || groups < 1 || D < 1 || D > VOL_DMAX ||
-        !make_mack(r_max, r_min, q, m_th, surface_rate, surface_depth_nm, thickness_nm, D, law))
+    RateChain c;
+    if (!plane_sums || !grad_param || groups < 1 || !rate_chain(r_max, r_min, q, m_th, surface_rate, surface_depth_nm, thickness_nm, D, c))
         return LITHO_E_ARG;
-    const double a = law.a;
-    const double da_dq = a * (1.0 / (q + 1.0) - 1.0 / (q - 1.0) + std::log(1.0 - m_th)), da_dm = -q * a / (1.0 - m_th);
+    const double a = c.a;
     for (int g = 0; g < groups; ++g) {
         double sum[4] = {0.0, 0.0, 0.0, 0.0}, s_a = 0.0, s_r0 = 0.0, s_delta = 0.0;       // kappa, R, rmin, q at fixed a
         for (int d = 0; d < D; ++d) {                    // the planes in ascending order
             const double* t = plane_sums + ((size_t)g * D + d) * 6;
             for (int j = 0; j < 4; ++j) sum[j] += t[j];
             s_a += t[4];
-            const double z = thickness_nm * (d + 0.5) / D, ez = std::exp(-z / surface_depth_nm);
-            s_r0 += t[5] * ez;                           // f = 1 - (1 - r0) exp(-z / delta)
-            s_delta += t[5] * (-(1.0 - surface_rate) * ez * z / (surface_depth_nm * surface_depth_nm));
+            s_r0 += t[5] * c.ez[d];                      // f = 1 - (1 - r0) exp(-z / delta)
+            s_delta += t[5] * c.ddelta[d];
         }
         double* out = grad_param + (size_t)g * 7;
         out[0] = sum[0];
         out[1] = sum[1] * (a + 1.0);                     // R = rmax (a + 1); the a slot already follows R through a
         out[2] = sum[2];
-        out[3] = sum[3] + s_a * da_dq;
-        out[4] = s_a * da_dm;
+        out[3] = sum[3] + s_a * c.da_dq;
+        out[4] = s_a * c.da_dm;
         out[5] = s_r0;
         out[6] = s_delta;
     }
@@ -632,9 +670,7 @@ int litho_develop_rate_jvp(const float* x, int volumes, int D, int n, const floa
     if (!aligned16(dphi)) return LITHO_E_ARG;
     const size_t x_bytes = (size_t)volumes * D * n * n * sizeof(float), out_bytes = x_bytes * n_gains * P;
     const size_t phi_bytes = (size_t)P * D * 6 * sizeof(double);
-    if (overlap(dslowness, out_bytes, x, x_bytes) || overlap(dslowness, out_bytes, dphi, phi_bytes) ||
-        (dx && overlap(dslowness, out_bytes, dx, x_bytes * P)))
-        return LITHO_E_ARG;
+    if (!writes_clear({{dslowness, out_bytes}}, {{x, x_bytes}, {dphi, phi_bytes}, {dx, x_bytes * P}})) return LITHO_E_ARG;
     const int planes = volumes * D;
     const bool wide = (n & 3) == 0 && aligned16(x) && aligned16(dx) && aligned16(dslowness);
     LAUNCH_PACKED(k_develop_rate_jvp, wide, n, planes, (hipStream_t)stream, x, dx, dphi, dslowness, planes, D, n, gains, n_gains, P, kappa,
@@ -647,20 +683,16 @@ int litho_develop_rate_param_tangent(double r_max, double r_min, double q, doubl
                                      double thickness_nm, int D, const double* dparam, double* dphi)
 {
     using namespace litho;
-    MackLaw law;
-    if (!dparam || !dphi || D < 1 || D > VOL_DMAX || !make_mack(r_max, r_min, q, m_th, surface_rate, surface_depth_nm, thickness_nm, D, law))
-        return LITHO_E_ARG;
-    const double a = law.a;
-    const double da_dq = a * (1.0 / (q + 1.0) - 1.0 / (q - 1.0) + std::log(1.0 - m_th)), da_dm = -q * a / (1.0 - m_th);
+    RateChain c;
+    if (!dparam || !dphi || !rate_chain(r_max, r_min, q, m_th, surface_rate, surface_depth_nm, thickness_nm, D, c)) return LITHO_E_ARG;
     for (int d = 0; d < D; ++d) {
-        const double z = thickness_nm * (d + 0.5) / D, ez = std::exp(-z / surface_depth_nm);
         double* out = dphi + (size_t)d * 6;
         out[0] = dparam[0];
-        out[1] = (a + 1.0) * dparam[1];
+        out[1] = (c.a + 1.0) * dparam[1];
         out[2] = dparam[2];
         out[3] = dparam[3];
-        out[4] = da_dq * dparam[3] + da_dm * dparam[4];
-        out[5] = ez * dparam[5] + (-(1.0 - surface_rate) * ez * z / (surface_depth_nm * surface_depth_nm)) * dparam[6];
+        out[4] = c.da_dq * dparam[3] + c.da_dm * dparam[4];
+        out[5] = c.ez[d] * dparam[5] + c.ddelta[d] * dparam[6];
     }
     return LITHO_OK;
 }
@@ -678,49 +710,13 @@ int litho_develop_time_jvp(const float* slowness, const float* T, const float* d
                            double pixel_nm, int max_iterations, float* dT, void* work, size_t work_bytes, int* launches_host, void* stream)
 {
     using namespace litho;
-    if (launches_host) *launches_host = 0;
-    if (!slowness || !T || !dslowness || !dT || !work || !launches_host || !volume_ok(B, D, n)) return LITHO_E_ARG;
-    if (P < 1 || P > LITHO_TANGENT_MAX || (long long)P * B * D > 65535) return LITHO_E_ARG;
-    if (max_iterations < 1 || max_iterations > VOL_MAXIT || !finite_pos(thickness_nm) || !finite_pos(pixel_nm)) return LITHO_E_ARG;
-    const size_t cells = (size_t)B * D * n * n, vol_bytes = cells * sizeof(float), tan_bytes = vol_bytes * P;
-    const size_t need = litho_develop_jvp_work_bytes(B, D, n, P, max_iterations);
-    if (!aligned16(work)) return LITHO_E_ARG;
-    const void* in[3] = {slowness, T, dslowness};
-    const size_t in_bytes[3] = {vol_bytes, vol_bytes, tan_bytes};
-    for (int i = 0; i < 3; ++i)
-        if (overlap(dT, tan_bytes, in[i], in_bytes[i])) return LITHO_E_ARG;
-    if (work_bytes < need) return LITHO_E_WORKSPACE;
-    for (int i = 0; i < 3; ++i)
-        if (overlap(work, need, in[i], in_bytes[i])) return LITHO_E_ARG;
-    if (overlap(work, need, dT, tan_bytes)) return LITHO_E_ARG;
-    // the geometry as litho_develop_time rounds it
-    const float hf = (float)pixel_nm, hzf = (float)(thickness_nm / D);
-    const float wxy = 1.f / (hf * hf), wz = 1.f / (hzf * hzf);
-    if (!(hf > 0.f) || !(hzf > 0.f) || std::isinf(wxy) || std::isinf(wz) || !(wxy > 0.f) || !(wz > 0.f)) return LITHO_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    int* flags = (int*)work;
-    float* links = (float*)((char*)work + flag_bytes(max_iterations));
-    float* buf[2] = {links + 4 * cells, dT};
-    const size_t lds = (size_t)D * DT_PLANE_BYTES;
-    if (lds > 64 * 1024) {                               // once per device: the worst case, D = 32
-        static unsigned lds_done = 0;
-        HIP_TRY(lds_opt_in(lds_done, (const void*)k_develop_time_jvp, (size_t)VOL_DMAX * DT_PLANE_BYTES));
-    }
-    HIP_TRY(hipMemsetAsync(buf[0], 0, tan_bytes, st));
+    static unsigned lds_done = 0;
     const bool wide = (n & 3) == 0 && aligned16(slowness) && aligned16(T);
-    LAUNCH_PACKED(k_develop_links, wide, n, B * D, st, slowness, T, (float4*)links, D, n, (double)hf, (double)hzf);
-    HIP_TRY(hipGetLastError());
-    const unsigned tiles = (unsigned)((n + VOL_TILE - 1) / VOL_TILE);
-    const dim3 grid(tiles, tiles, (unsigned)(P * B));
-    // launch `it` reads buf[it & 1] and writes the other; the one that changed nothing leaves the fixed point in both
-    const int launches = iterate_until_unchanged(flags, max_iterations, st, [&](int it) {
-        hipLaunchKernelGGL(k_develop_time_jvp, grid, dim3(256), lds, st, (const float*)links, dslowness, (const float*)buf[it & 1],
-                           buf[(it + 1) & 1], B, D, n, flags + it);
-    });
-    if (launches < 0) return launches;
-    *launches_host = launches ? launches : max_iterations;
-    if (!launches) return LITHO_E_NOCONV;
-    return LITHO_OK;
+    return front_derivative(slowness, T, dslowness, B, D, n, P, thickness_nm, pixel_nm, max_iterations, dT, work, work_bytes, launches_host,
+                            stream, wide, (const void*)k_develop_time_jvp, lds_done, DT_PLANE_BYTES, false,
+                            [&](dim3 grid, size_t lds, hipStream_t st, const float* links, const float* in, float* out, int* flag) {
+                                hipLaunchKernelGGL(k_develop_time_jvp, grid, dim3(256), lds, st, links, dslowness, in, out, B, D, n, flag);
+                            });
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 // (no reference counterpart; the definitions are in include/litho_abbe.h, the checker is their float64 restatement
 // tests/peb_oracle.py).  Built with -ffp-contract=off (Makefile): every fp32 result is a fixed sequence of single operations.
 //
-// Volumes are fp32 [B, D, n, n], D <= 32 planes through the resist, x fastest.  Four kernels:
+// Volumes are fp32 [B, D, n, n], D <= 32 planes through the resist, x fastest.  The forward kernels:
 //   k_peb_expose   acid h0 = 1 - exp(-(C g) I) in double per cell, the gains in a loop inside
 //   k_peb_direct   one bake step per launch: a thread per cell, the six neighbours of both species from global memory
 //   k_peb_fused    s >= 2 bake steps per launch (temporal blocking, below)
@@ -15,11 +15,17 @@
 //   k_peb_adjoint_params  k_peb_adjoint plus the six step-parameter terms of the cell, added per workgroup into its own slot
 //   k_peb_expose_params   gh0 (g I) exp(-(C g) I) per cell, added per workgroup into its own slot
 //   k_vol_total           (resist_volume.hpp) the slots of a volume added in a fixed order
-// The arithmetic of a step is peb_step and nothing else: both bake kernels call it with the same inputs in the same order, so
-// the bits of a bake do not depend on how its steps are cut into launches.  expose and rate move four consecutive x per thread
-// (16-byte accesses) when n is a multiple of 4 and the pointers are 16-byte aligned, one otherwise.  The limits, the packs, the
-// host predicates, the gains and Mack's rate law are resist_volume.hpp's, shared with develop.hip and develop_grad.hip; the three
-// kernels that take one cell per thread (direct, taped, adjoint) get the cell and its six clamped neighbour offsets from peb_cell.
+// and behind litho_peb_expose_jvp and litho_peb_bake_jvp, forward mode (section 2d): k_peb_expose_jvp, and k_peb_jvp, one bake step
+// with its P tangents.  Each piece of arithmetic exists once: peb_laplacians and peb_diffuse (the diffusion line of the step, of
+// its transpose and of its tangent), peb_step (every forward kernel calls it with the same inputs in the same order, so the bits
+// of a bake depend neither on how its steps are cut into launches nor on the entry that runs them), peb_react_partials (the
+// reaction's derivatives, adjoint and tangent), peb_start (the opening of k_peb_taped and k_peb_jvp) and peb_step_adjoint (one
+// backward cell, both adjoint kernels); the kernels that take one cell per thread get it and its six clamped neighbour offsets
+// from peb_cell.  On the host PebBake and bake_checked are the one description and the one set of checks of the five entries that
+// take a bake, and step_jacobian the coefficients whose two products are param_chain and param_tangent.  expose and rate move
+// four consecutive x per thread (16-byte accesses) when n is a multiple of 4 and the pointers are 16-byte aligned, one otherwise.
+// The limits, the packs, the host predicates (the aliasing rule writes_clear among them), the gains and Mack's rate law are
+// resist_volume.hpp's, shared with develop.hip and develop_grad.hip.
 //
 // k_peb_fused.  A workgroup owns a 16 x 16 lateral tile with all D planes.  It loads h and q of the tile and an s-cell lateral
 // halo into LDS, W = 16 + 2 s cells on a side; a cell beyond the grid is read from its mirror image (mirror_index, folding as
@@ -102,28 +108,50 @@ __global__ __launch_bounds__(256) void k_peb_expose(const float* __restrict__ im
     }
 }
 
-// ---- 2. one bake step of one cell.  h, q: the cell at the start of the step; nb_h(), nb_q(): its six neighbours at the start
-// of the step, fetched only for a species that diffuses.  Diffusion (Jacobi, no flux), neutralisation, acid loss, and the
-// trapezoid of the amplification integral, in this order; every line is include/litho_abbe.h's.  hd, qd: the two species after
-// the diffusion line, what the reaction saw -- the tape of the backward sweep (k_peb_taped), a dead store elsewhere.
+// ---- 2. one bake step of one cell.  The two Laplacians of a value x with the neighbours b, lateral and vertical, in T = float,
+// or in double from the widened fp32 operands (the parameter terms of k_peb_adjoint_params); and the diffusion update of one
+// value with them: the forward's line, its transpose on (u, v) and its tangent.
+template <class T>
+struct PebLap { T xy, z; };
+template <class T>
+__device__ __forceinline__ PebLap<T> peb_laplacians(const PebNb& b, T x)
+{
+    return PebLap<T>{(((T)b.w + (T)b.e) + ((T)b.s + (T)b.n)) - (T)4 * x, ((T)b.u + (T)b.d) - (T)2 * x};
+}
+__device__ __forceinline__ float peb_diffuse(float x, const PebNb& b, float lxy, float lz)
+{
+    const PebLap<float> L = peb_laplacians(b, x);
+    return x + lxy * L.xy + lz * L.z;
+}
+// h, q: the cell at the start of the step; nb_h(), nb_q(): its six neighbours at the start of the step, fetched only for a
+// species that diffuses.  Diffusion (Jacobi, no flux), neutralisation, acid loss, and the trapezoid of the amplification
+// integral, in this order; every line is include/litho_abbe.h's.  hd, qd: the two species after the diffusion line, what the
+// reaction saw -- the tape of the backward sweep (k_peb_taped), a dead store elsewhere.
 template <class FH, class FQ>
 __device__ __forceinline__ void peb_step(const PebStep& P, float h, float q, FH nb_h, FQ nb_q, float& h_new, float& q_new, float& a,
                                          float& hd, float& qd)
 {
-    hd = h;
-    qd = q;
-    if (P.diffuse_h) {
-        const PebNb b = nb_h();
-        hd = h + P.lxy_h * (((b.w + b.e) + (b.s + b.n)) - 4.f * h) + P.lz_h * ((b.u + b.d) - 2.f * h);
-    }
-    if (P.diffuse_q) {
-        const PebNb b = nb_q();
-        qd = q + P.lxy_q * (((b.w + b.e) + (b.s + b.n)) - 4.f * q) + P.lz_q * ((b.u + b.d) - 2.f * q);
-    }
+    hd = P.diffuse_h ? peb_diffuse(h, nb_h(), P.lxy_h, P.lz_h) : h;
+    qd = P.diffuse_q ? peb_diffuse(q, nb_q(), P.lxy_q, P.lz_q) : q;
     const float R = P.instant ? ((hd < qd) ? hd : qd) : P.beta * hd * qd / (1.f + P.beta * (hd + qd));
     h_new = (hd - R) * P.fl;
     q_new = qd - R;
     a = a + P.half_dt * (h + h_new);
+}
+// The start of a forward step of one cell in k_peb_taped and k_peb_jvp (k_peb_direct keeps its own lines: its machine code is the
+// measured one): the cell, whether this is the first step (q_in == nullptr: q = q0 everywhere), h and q at the start of the step
+// and the six neighbours of each species that diffuses -- zeros for one that does not, which nothing reads.
+struct PebStart { PebCell c; bool first; float h, q; PebNb bh, bq; };
+__device__ __forceinline__ bool peb_start(const PebStep& P, const float* h_in, const float* q_in, float q0, int D, int n, PebStart& s)
+{
+    if (!peb_cell(D, n, s.c)) return false;              // this thread has no cell
+    const PebNb zero = PebNb{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    s.first = q_in == nullptr;
+    s.h = h_in[s.c.at];
+    s.q = s.first ? q0 : q_in[s.c.at];
+    s.bh = P.diffuse_h ? peb_around(h_in + s.c.at, s.c) : zero;
+    s.bq = P.diffuse_q ? (s.first ? PebNb{q0, q0, q0, q0, q0, q0} : peb_around(q_in + s.c.at, s.c)) : zero;
+    return true;
 }
 
 // grid.x covers the n^2 cells of a plane, grid.y the B D planes.  q_in == nullptr: the first step, q = q0 everywhere and a = 0.
@@ -210,14 +238,11 @@ __global__ __launch_bounds__(256) void k_peb_taped(const float* __restrict__ h_i
                                                    float* __restrict__ h_out, float* __restrict__ q_out, float* __restrict__ hd_out,
                                                    float* __restrict__ qd_out, int D, int n, const PebStep P)
 {
-    PebCell c;
-    if (!peb_cell(D, n, c)) return;
-    const size_t at = c.at;
-    const bool first = q_in == nullptr;
-    const float h = h_in[at], q = first ? q0 : q_in[at];
+    PebStart s;
+    if (!peb_start(P, h_in, q_in, q0, D, n, s)) return;
+    const size_t at = s.c.at;
     float a = 0.f, h_new, q_new, hd, qd;
-    peb_step(P, h, q, [&] { return peb_around(h_in + at, c); },
-             [&] { return first ? PebNb{q0, q0, q0, q0, q0, q0} : peb_around(q_in + at, c); }, h_new, q_new, a, hd, qd);
+    peb_step(P, s.h, s.q, [&] { return s.bh; }, [&] { return s.bq; }, h_new, q_new, a, hd, qd);
     if (h_out) {
         h_out[at] = h_new;
         q_out[at] = q_new;
@@ -228,42 +253,53 @@ __global__ __launch_bounds__(256) void k_peb_taped(const float* __restrict__ h_i
     }
 }
 
+// The reaction's partials at the (hd, qd) the reaction saw, fp32: R itself, Rh = dR/dhd, Rq = dR/dqd and Rb = dR/dbeta.  With
+// instantaneous neutralisation R = min(hd, qd) and the partials take the forward's own comparison; no beta in it.
+struct PebReact { float Rh, Rq, Rb, R; };
+__device__ __forceinline__ PebReact peb_react_partials(const PebStep& P, float hd, float qd)
+{
+    if (P.instant) return (hd < qd) ? PebReact{1.f, 0.f, 0.f, hd} : PebReact{0.f, 1.f, 0.f, qd};
+    const float Dn = 1.f + P.beta * (hd + qd), DD = Dn * Dn;
+    return PebReact{P.beta * qd * (1.f + P.beta * qd) / DD, P.beta * hd * (1.f + P.beta * hd) / DD, hd * qd / DD, P.beta * hd * qd / Dn};
+}
 // The pointwise half of the backward step: (u, v) of one cell from hp = hbar + half_dt abar, qbar and the step's (hd, qd).
 struct PebUV {
     float u, v;
 };
 __device__ __forceinline__ PebUV peb_react_adjoint(const PebStep& P, float hp, float qb, float hd, float qd)
 {
-    float Rh, Rq;
-    if (P.instant) {
-        Rh = (hd < qd) ? 1.f : 0.f;                      // the forward's own comparison
-        Rq = 1.f - Rh;
-    } else {
-        const float Dn = 1.f + P.beta * (hd + qd), DD = Dn * Dn;
-        Rh = P.beta * qd * (1.f + P.beta * qd) / DD;
-        Rq = P.beta * hd * (1.f + P.beta * hd) / DD;
-    }
+    const PebReact r = peb_react_partials(P, hd, qd);
     const float fhp = P.fl * hp;
-    return PebUV{fhp * (1.f - Rh) - qb * Rh, qb * (1.f - Rq) - fhp * Rq};
+    return PebUV{fhp * (1.f - r.Rh) - qb * r.Rh, qb * (1.f - r.Rq) - fhp * r.Rq};
 }
-// One backward step of one cell.  uv(i): (u, v) at the cell (i = 0) and at its neighbours W, E, S, N, U, Dn (i = 1 .. 6, the cell
-// itself beyond a face), asked for only when a species diffuses; ha = half_dt abar at the cell.  A_s is symmetric, so the
+// One backward step of one cell: (hb, qb) = (hbar, qbar) before the step, and with them the cell's own fp32 hp and (u, v), which
+// the parameter terms take.  hb_in, qb_in, abar: the cotangents after the step, nullptr = zero; hd, qd: the step's tape.  (u, v)
+// at the six neighbours (the cell itself beyond a face) are asked for only when a species diffuses.  A_s is symmetric, so the
 // transposed stencil is the forward's line on u and v: a gather.
-template <class F>
-__device__ __forceinline__ void peb_step_adjoint(const PebStep& P, F uv, float ha, float& hb, float& qb)
+struct PebBack { float hb, qb, hp; PebUV c; };
+__device__ __forceinline__ PebBack peb_step_adjoint(const PebStep& P, const PebCell& cell, const float* hb_in, const float* qb_in,
+                                                    const float* abar, const float* hd, const float* qd)
 {
-    const PebUV c = uv(0);
-    float hu = c.u, qv = c.v;
+    auto hp_at = [&](size_t c) { return (hb_in ? hb_in[c] : 0.f) + P.half_dt * (abar ? abar[c] : 0.f); };
+    auto uv = [&](long long off) -> PebUV {
+        const size_t c = (size_t)((long long)cell.at + off);
+        return peb_react_adjoint(P, hp_at(c), qb_in ? qb_in[c] : 0.f, hd[c], qd[c]);
+    };
+    PebBack r;
+    r.hp = hp_at(cell.at);
+    r.c = uv(0);
+    float hu = r.c.u, qv = r.c.v;
     if (P.diffuse_h || P.diffuse_q) {
-        const PebUV w = uv(1), e = uv(2), s = uv(3), n = uv(4), up = uv(5), dn = uv(6);
-        if (P.diffuse_h) hu = c.u + P.lxy_h * (((w.u + e.u) + (s.u + n.u)) - 4.f * c.u) + P.lz_h * ((up.u + dn.u) - 2.f * c.u);
-        if (P.diffuse_q) qv = c.v + P.lxy_q * (((w.v + e.v) + (s.v + n.v)) - 4.f * c.v) + P.lz_q * ((up.v + dn.v) - 2.f * c.v);
+        const PebUV w = uv(cell.w), e = uv(cell.e), s = uv(cell.s), n = uv(cell.n), up = uv(cell.u), dn = uv(cell.d);
+        if (P.diffuse_h) hu = peb_diffuse(r.c.u, PebNb{w.u, e.u, s.u, n.u, up.u, dn.u}, P.lxy_h, P.lz_h);
+        if (P.diffuse_q) qv = peb_diffuse(r.c.v, PebNb{w.v, e.v, s.v, n.v, up.v, dn.v}, P.lxy_q, P.lz_q);
     }
-    hb = hu + ha;
-    qb = qv;
+    r.hb = hu + P.half_dt * (abar ? abar[cell.at] : 0.f);
+    r.qb = qv;
+    return r;
 }
 
-// grid as k_peb_direct.  hb_in, qb_in, abar: the cotangents after the step, nullptr = zero; hd, qd: the step's tape.
+// grid as k_peb_direct.
 __global__ __launch_bounds__(256) void k_peb_adjoint(const float* __restrict__ hb_in, const float* __restrict__ qb_in,
                                                      const float* __restrict__ abar, const float* __restrict__ hd,
                                                      const float* __restrict__ qd, float* __restrict__ hb_out, float* __restrict__ qb_out,
@@ -271,25 +307,17 @@ __global__ __launch_bounds__(256) void k_peb_adjoint(const float* __restrict__ h
 {
     PebCell cell;
     if (!peb_cell(D, n, cell)) return;
-    const size_t at = cell.at;
-    const long long off[7] = {0, cell.w, cell.e, cell.s, cell.n, cell.u, cell.d};
-    auto uv = [&](int i) -> PebUV {
-        const size_t c = (size_t)((long long)at + off[i]);
-        const float hp = (hb_in ? hb_in[c] : 0.f) + P.half_dt * (abar ? abar[c] : 0.f);
-        return peb_react_adjoint(P, hp, qb_in ? qb_in[c] : 0.f, hd[c], qd[c]);
-    };
-    float hb, qb;
-    peb_step_adjoint(P, uv, P.half_dt * (abar ? abar[at] : 0.f), hb, qb);
-    hb_out[at] = hb;
-    qb_out[at] = qb;
+    const PebBack r = peb_step_adjoint(P, cell, hb_in, qb_in, abar, hd, qd);
+    hb_out[cell.at] = r.hb;
+    qb_out[cell.at] = r.qb;
 }
 
 // ---- 2c. the step-parameter sums of the backward sweep (litho_peb_bake_vjp_params; include/litho_abbe.h's "Gradients with respect
 // to the bake's parameters").  The workgroup's fixed-order sum and the closing kernel are resist_volume.hpp's (vol_block_sum,
 // k_vol_total).
-// k_peb_adjoint with the step's six parameter terms: the same two functions give (hbar_k, qbar_k), so their bits are
-// k_peb_adjoint's.  h, q: the state at the start of the step (q == nullptr: the first step, q uniform, its Laplacians 0).  The
-// terms are formed in double from the fp32 operands; thread 0 adds the workgroup's six sums into the workgroup's own slot
+// k_peb_adjoint with the step's six parameter terms: the same function gives (hbar_k, qbar_k), so their bits are k_peb_adjoint's.
+// h, q: the state at the start of the step (q == nullptr: the first step, q uniform, its Laplacians 0).  The terms are formed in
+// double from the fp32 operands; thread 0 adds the workgroup's six sums into the workgroup's own slot
 // partials[blockIdx.y][blockIdx.x][6] -- the backward steps are successive launches on one stream, so a slot's additions come in
 // the order k = S-1 .. 0.  A thread without a cell contributes zeros and still takes part in the sum.
 __global__ __launch_bounds__(256) void k_peb_adjoint_params(const float* __restrict__ hb_in, const float* __restrict__ qb_in,
@@ -304,27 +332,17 @@ __global__ __launch_bounds__(256) void k_peb_adjoint_params(const float* __restr
     PebCell cell;
     if (peb_cell(D, n, cell)) {
         const size_t at = cell.at;
-        const long long off[7] = {0, cell.w, cell.e, cell.s, cell.n, cell.u, cell.d};
-        auto uv = [&](int i) -> PebUV {
-            const size_t c = (size_t)((long long)at + off[i]);
-            const float hp = (hb_in ? hb_in[c] : 0.f) + P.half_dt * (abar ? abar[c] : 0.f);
-            return peb_react_adjoint(P, hp, qb_in ? qb_in[c] : 0.f, hd[c], qd[c]);
-        };
-        float hb, qb;
-        peb_step_adjoint(P, uv, P.half_dt * (abar ? abar[at] : 0.f), hb, qb);
-        hb_out[at] = hb;
-        qb_out[at] = qb;
-        const PebUV c = uv(0);
-        const double hp = (hb_in ? hb_in[at] : 0.f) + P.half_dt * (abar ? abar[at] : 0.f);   // the fp32 hp of uv(0), widened
-        const double qbk = qb_in ? qb_in[at] : 0.f, hdc = hd[at], qdc = qd[at], fl = P.fl;
+        const PebBack r = peb_step_adjoint(P, cell, hb_in, qb_in, abar, hd, qd);
+        hb_out[at] = r.hb;
+        qb_out[at] = r.qb;
+        const double hp = r.hp, qbk = qb_in ? qb_in[at] : 0.f, hdc = hd[at], qdc = qd[at], fl = P.fl;
         auto laplacians = [&](const float* x, double w, int j) {
-            const PebNb b = peb_around(x + at, cell);
-            const double x0 = x[at];
-            t[j] = w * ((((double)b.w + (double)b.e) + ((double)b.s + (double)b.n)) - 4.0 * x0);
-            t[j + 1] = w * (((double)b.u + (double)b.d) - 2.0 * x0);
+            const PebLap<double> L = peb_laplacians(peb_around(x + at, cell), (double)x[at]);
+            t[j] = w * L.xy;
+            t[j + 1] = w * L.z;
         };
-        if (P.diffuse_h) laplacians(h, (double)c.u, 0);
-        if (P.diffuse_q && q) laplacians(q, (double)c.v, 2);
+        if (P.diffuse_h) laplacians(h, (double)r.c.u, 0);
+        if (P.diffuse_q && q) laplacians(q, (double)r.c.v, 2);
         double R;
         if (P.instant) {
             R = (hdc < qdc) ? hdc : qdc;                  // the forward's own comparison; no beta in it
@@ -433,73 +451,36 @@ __global__ __launch_bounds__(256) void k_peb_jvp(const float* __restrict__ h_in,
                                                  float* __restrict__ dh_out, float* __restrict__ dq_out, float* __restrict__ da_io,
                                                  size_t V, int D, int n, int P, const PebStep S, const PebTanStep T)
 {
-    PebCell c;
-    if (!peb_cell(D, n, c)) return;
+    PebStart s;
+    if (!peb_start(S, h_in, q_in, q0, D, n, s)) return;
+    const PebCell& c = s.c;
     const size_t at = c.at;
-    const bool first = q_in == nullptr;
-    const float h = h_in[at], q = first ? q0 : q_in[at];
-    const PebNb zero = PebNb{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    const PebNb bh = S.diffuse_h ? peb_around(h_in + at, c) : zero;
-    const PebNb bq = S.diffuse_q ? (first ? PebNb{q0, q0, q0, q0, q0, q0} : peb_around(q_in + at, c)) : zero;
+    const bool first = s.first;
     float a = first ? 0.f : a_io[at], h_new, q_new, hd, qd;
-    peb_step(S, h, q, [&] { return bh; }, [&] { return bq; }, h_new, q_new, a, hd, qd);
+    peb_step(S, s.h, s.q, [&] { return s.bh; }, [&] { return s.bq; }, h_new, q_new, a, hd, qd);
     h_out[at] = h_new;
     q_out[at] = q_new;
     a_io[at] = a;
     // what every direction shares
-    const float lxy_of_h = ((bh.w + bh.e) + (bh.s + bh.n)) - 4.f * h, lz_of_h = (bh.u + bh.d) - 2.f * h;
-    const float lxy_of_q = ((bq.w + bq.e) + (bq.s + bq.n)) - 4.f * q, lz_of_q = (bq.u + bq.d) - 2.f * q;
-    float Rh, Rq, Rb = 0.f, R;
-    if (S.instant) {
-        Rh = (hd < qd) ? 1.f : 0.f;
-        Rq = 1.f - Rh;
-        R = (hd < qd) ? hd : qd;
-    } else {
-        const float Dn = 1.f + S.beta * (hd + qd), DD = Dn * Dn;
-        Rh = S.beta * qd * (1.f + S.beta * qd) / DD;
-        Rq = S.beta * hd * (1.f + S.beta * hd) / DD;
-        Rb = hd * qd / DD;
-        R = S.beta * hd * qd / Dn;
-    }
-    const float hR = hd - R;
+    const PebLap<float> lap_h = peb_laplacians(s.bh, s.h), lap_q = peb_laplacians(s.bq, s.q);
+    const PebReact r = peb_react_partials(S, hd, qd);
+    const float hR = hd - r.R;
+    const PebNb zero = PebNb{0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int p = 0; p < P; ++p) {
         const size_t tp = (size_t)p * V + at;
         const float dh = dh_in ? dh_in[tp] : 0.f, dq = first ? T.dq0[p] : dq_in[tp];
         float dhd = dh, dqd = dq;
-        if (S.diffuse_h) {
-            const PebNb b = dh_in ? peb_around(dh_in + tp, c) : zero;
-            dhd = dh + S.lxy_h * (((b.w + b.e) + (b.s + b.n)) - 4.f * dh) + S.lz_h * ((b.u + b.d) - 2.f * dh) + T.d[p][0] * lxy_of_h +
-                  T.d[p][1] * lz_of_h;
-        }
-        if (S.diffuse_q) {
-            const PebNb b = first ? PebNb{dq, dq, dq, dq, dq, dq} : peb_around(dq_in + tp, c);
-            dqd = dq + S.lxy_q * (((b.w + b.e) + (b.s + b.n)) - 4.f * dq) + S.lz_q * ((b.u + b.d) - 2.f * dq) + T.d[p][2] * lxy_of_q +
-                  T.d[p][3] * lz_of_q;
-        }
-        const float dR = S.instant ? ((hd < qd) ? dhd : dqd) : (Rh * dhd + Rq * dqd) + Rb * T.d[p][4];
+        if (S.diffuse_h)
+            dhd = peb_diffuse(dh, dh_in ? peb_around(dh_in + tp, c) : zero, S.lxy_h, S.lz_h) + T.d[p][0] * lap_h.xy + T.d[p][1] * lap_h.z;
+        if (S.diffuse_q)
+            dqd = peb_diffuse(dq, first ? PebNb{dq, dq, dq, dq, dq, dq} : peb_around(dq_in + tp, c), S.lxy_q, S.lz_q) + T.d[p][2] * lap_q.xy +
+                  T.d[p][3] * lap_q.z;
+        const float dR = S.instant ? ((hd < qd) ? dhd : dqd) : (r.Rh * dhd + r.Rq * dqd) + r.Rb * T.d[p][4];
         const float dh_new = (dhd - dR) * S.fl + hR * T.d[p][5];
         dh_out[tp] = dh_new;
         dq_out[tp] = dqd - dR;
         da_io[tp] = (first ? 0.f : da_io[tp]) + S.half_dt * (dh + dh_new);
     }
-}
-
-// the transpose of param_chain: dstep[6] from dparam[5]
-static void param_tangent(double thickness_nm, double pixel_nm, double k_quench, double k_loss, double sigma_acid_nm, double sigma_quencher_nm,
-                          double vertical_scale, double bake_time_s, int D, int steps, const double* dp, double* out)
-{
-    const double hz = thickness_nm / D, dt = bake_time_s / steps, S = steps;
-    const double dxy_h = sigma_acid_nm / (S * (pixel_nm * pixel_nm)), dxy_q = sigma_quencher_nm / (S * (pixel_nm * pixel_nm));
-    const double vv = vertical_scale * vertical_scale / (S * (hz * hz));
-    const double dz_h = vv * sigma_acid_nm, dz_q = vv * sigma_quencher_nm;
-    const double dv_h = vertical_scale * sigma_acid_nm * sigma_acid_nm / (S * (hz * hz));
-    const double dv_q = vertical_scale * sigma_quencher_nm * sigma_quencher_nm / (S * (hz * hz));
-    out[0] = dxy_h * dp[2];
-    out[1] = dz_h * dp[2] + dv_h * dp[4];
-    out[2] = dxy_q * dp[3];
-    out[3] = dz_q * dp[3] + dv_q * dp[4];
-    out[4] = std::isinf(k_quench) ? 0.0 : dt * dp[0];
-    out[5] = (-dt * std::exp(-k_loss * dt)) * dp[1];
 }
 
 // ---- 3. rate: m = exp(-kAmp a), then mack_slowness of 1 - m with the surface factor of the plane (resist_volume.hpp, the
@@ -561,24 +542,42 @@ static int min_steps(double sigma_h, double sigma_q, double vscale, double thick
     return S <= PEB_MAXSTEPS ? S : 0;
 }
 
+// The bake's physical description as the entry points take it; quencher0 where the entry has one.
+struct PebBake {
+    double thickness_nm, pixel_nm, quencher0, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s;
+    int D, steps;
+};
 // the step's parameters as the kernels take them: formed in double, rounded to fp32 once
-static PebStep step_of(double thickness_nm, double pixel_nm, double k_quench, double k_loss, double sigma_acid_nm, double sigma_quencher_nm,
-                       double vertical_scale, double bake_time_s, int D, int steps)
+static PebStep step_of(const PebBake& b)
 {
-    const double hz = thickness_nm / D, dt = bake_time_s / steps;
+    const double hz = b.thickness_nm / b.D, dt = b.bake_time_s / b.steps;
     double lxy_h, lz_h, lxy_q, lz_q;
-    lambdas(sigma_acid_nm, vertical_scale, pixel_nm, hz, steps, lxy_h, lz_h);
-    lambdas(sigma_quencher_nm, vertical_scale, pixel_nm, hz, steps, lxy_q, lz_q);
+    lambdas(b.sigma_acid_nm, b.vertical_scale, b.pixel_nm, hz, b.steps, lxy_h, lz_h);
+    lambdas(b.sigma_quencher_nm, b.vertical_scale, b.pixel_nm, hz, b.steps, lxy_q, lz_q);
     PebStep P;
     P.lxy_h = (float)lxy_h; P.lz_h = (float)lz_h; P.lxy_q = (float)lxy_q; P.lz_q = (float)lz_q;
-    P.beta = (float)(k_quench * dt);
-    P.fl = (float)std::exp(-k_loss * dt);
+    P.beta = (float)(b.k_quench * dt);
+    P.fl = (float)std::exp(-b.k_loss * dt);
     P.half_dt = (float)(0.5 * dt);
-    P.diffuse_h = sigma_acid_nm > 0.0;
-    P.diffuse_q = sigma_quencher_nm > 0.0;
+    P.diffuse_h = b.sigma_acid_nm > 0.0;
+    P.diffuse_q = b.sigma_quencher_nm > 0.0;
     P.instant = std::isinf(P.beta);                       // kQuench = +inf, or kQuench dt beyond fp32
     return P;
 }
+// The domains of a bake's description: false is LITHO_E_ARG.  with_q0: the entry takes the quencher loading.  Yields what the
+// kernels run with; fits: q0 and dt / 2 lie inside fp32's range, which the entries report last, after workspace and aliasing.
+struct PebRun { PebStep P; float q0; bool fits; };
+static bool bake_checked(const PebBake& b, bool with_q0, PebRun& r)
+{
+    if ((with_q0 && !finite_nonneg(b.quencher0)) || !(b.k_quench >= 0.0) || !finite_nonneg(b.k_loss) || !finite_pos(b.bake_time_s)) return false;
+    const int least = min_steps(b.sigma_acid_nm, b.sigma_quencher_nm, b.vertical_scale, b.thickness_nm, b.D, b.pixel_nm);
+    if (least == 0 || b.steps < least || b.steps > PEB_MAXSTEPS) return false;
+    r.P = step_of(b);
+    r.q0 = with_q0 ? (float)b.quencher0 : 0.f;
+    r.fits = !std::isinf(r.q0) && !std::isinf(r.P.half_dt);
+    return true;
+}
+static bool vjp_shape_ok(int B, int D, int n, int steps, int c) { return volume_ok(B, D, n) && steps >= 1 && steps <= PEB_MAXSTEPS && c >= 1 && c <= steps; }
 // the workspace of litho_peb_bake_vjp in volumes: the checkpoints (h, q) at c, 2 c, ... < S, one segment's tape (hd, qd) of c steps,
 // the ping-pong of the re-run's (h, q) and the ping-pong of (hbar, qbar)
 static size_t vjp_volumes(int steps, int c) { return 2 * (size_t)((steps + c - 1) / c - 1) + 2 * (size_t)c + 8; }
@@ -594,44 +593,25 @@ static size_t vjp_params_tape_bytes(int B, int D, int n, int steps, int c)
 
 // litho_peb_bake_vjp (grad_step == nullptr) and litho_peb_bake_vjp_params behind one set of checks and one sweep.  The forward
 // launches and the arithmetic of the backward steps are the same in both, so grad_acid_in and grad_quencher_in have the same bits.
-static int bake_vjp_run(const float* acid_in, int B, int D, int n, double thickness_nm, double pixel_nm, double quencher0, double k_quench,
-                        double k_loss, double sigma_acid_nm, double sigma_quencher_nm, double vertical_scale, double bake_time_s, int steps,
-                        int checkpoint_every, const float* grad_acid, const float* grad_quencher, const float* grad_acid_dose,
-                        float* grad_acid_in, float* grad_quencher_in, double* grad_step, bool params, void* work, size_t work_bytes,
-                        void* stream)
+static int bake_vjp_run(const float* acid_in, int B, int n, const PebBake& bake, int checkpoint_every, const float* grad_acid,
+                        const float* grad_quencher, const float* grad_acid_dose, float* grad_acid_in, float* grad_quencher_in, double* grad_step,
+                        bool params, void* work, size_t work_bytes, void* stream)
 {
+    const int D = bake.D, steps = bake.steps, c = checkpoint_every;
+    PebRun run;
     if (!acid_in || !grad_acid_in || !work || (params && !grad_step) || !volume_ok(B, D, n)) return LITHO_E_ARG;
     if (!grad_acid && !grad_quencher && !grad_acid_dose) return LITHO_E_ARG;
-    if (!finite_nonneg(quencher0) || !(k_quench >= 0.0) || !finite_nonneg(k_loss) || !finite_pos(bake_time_s)) return LITHO_E_ARG;
-    const int least = min_steps(sigma_acid_nm, sigma_quencher_nm, vertical_scale, thickness_nm, D, pixel_nm);
-    if (least == 0 || steps < least || steps > PEB_MAXSTEPS) return LITHO_E_ARG;
-    const int c = checkpoint_every;
-    if (c < 1 || c > steps) return LITHO_E_ARG;
+    if (!bake_checked(bake, true, run) || c < 1 || c > steps) return LITHO_E_ARG;
     const size_t V = (size_t)B * D * n * n, vol_bytes = V * sizeof(float);
     const size_t slots = params ? vjp_params_slots(B, D, n) : 0, tape_bytes = params ? vjp_params_tape_bytes(B, D, n, steps, c) : 0;
     const size_t need = params ? tape_bytes + slots * 6 * sizeof(double) : vjp_volumes(steps, c) * vol_bytes;
     const size_t step_bytes = (size_t)B * 6 * sizeof(double);
     if (!aligned16(work) || (params && !aligned16(grad_step))) return LITHO_E_ARG;
     if (work_bytes < need) return LITHO_E_WORKSPACE;
-    // the outputs may overlap neither an input, nor the workspace, nor each other; the inputs are only read
-    const void* ins[4] = {acid_in, grad_acid, grad_quencher, grad_acid_dose};
-    const void* outs[2] = {grad_acid_in, grad_quencher_in};
-    for (int o = 0; o < 2; ++o) {
-        if (!outs[o]) continue;
-        for (int i = 0; i < 4; ++i)
-            if (ins[i] && overlap(outs[o], vol_bytes, ins[i], vol_bytes)) return LITHO_E_ARG;
-        if (overlap(outs[o], vol_bytes, work, need)) return LITHO_E_ARG;
-        if (params && overlap(outs[o], vol_bytes, grad_step, step_bytes)) return LITHO_E_ARG;
-    }
-    if (grad_quencher_in && overlap(grad_acid_in, vol_bytes, grad_quencher_in, vol_bytes)) return LITHO_E_ARG;
-    for (int i = 0; i < 4; ++i) {
-        if (ins[i] && overlap(ins[i], vol_bytes, work, need)) return LITHO_E_ARG;
-        if (params && ins[i] && overlap(ins[i], vol_bytes, grad_step, step_bytes)) return LITHO_E_ARG;
-    }
-    if (params && overlap(grad_step, step_bytes, work, need)) return LITHO_E_ARG;
-    const PebStep P = step_of(thickness_nm, pixel_nm, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps);
-    const float q0 = (float)quencher0;
-    if (std::isinf(q0) || std::isinf(P.half_dt)) return LITHO_E_ARG;
+    if (!writes_clear({{grad_acid_in, vol_bytes}, {grad_quencher_in, vol_bytes}, {work, need}, {grad_step, step_bytes}},
+                      {{acid_in, vol_bytes}, {grad_acid, vol_bytes}, {grad_quencher, vol_bytes}, {grad_acid_dose, vol_bytes}}))
+        return LITHO_E_ARG;
+    if (!run.fits) return LITHO_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int nc = (steps + c - 1) / c;                   // segments; checkpoint j = (h, q) at step j c, j = 1 .. nc - 1, kept in work
     const size_t per = params ? 4 : 2;                    // tape volumes per step
@@ -651,7 +631,8 @@ static int bake_vjp_run(const float* acid_in, int B, int D, int n, double thickn
         const bool keep = (k + 1) % c == 0;
         float* to_h = keep ? ck_h((k + 1) / c) : state + (size_t)(2 * (k & 1)) * V;
         float* to_q = keep ? ck_q((k + 1) / c) : to_h + V;
-        hipLaunchKernelGGL(k_peb_taped, grid, block, 0, st, src_h, src_q, q0, to_h, to_q, (float*)nullptr, (float*)nullptr, D, n, P);
+        hipLaunchKernelGGL(k_peb_taped, grid, block, 0, st, src_h, src_q, run.q0, to_h, to_q, (float*)nullptr, (float*)nullptr, D, n,
+                           run.P);
         src_h = to_h;
         src_q = to_q;
     }
@@ -668,7 +649,7 @@ static int bake_vjp_run(const float* acid_in, int B, int D, int n, double thickn
             float* t = tape + (per * (k - k0)) * V;
             float* to_h = last ? nullptr : (params ? t + 2 * V : state + (size_t)(2 * ((k - k0) & 1)) * V);
             float* to_q = last ? nullptr : to_h + V;
-            hipLaunchKernelGGL(k_peb_taped, grid, block, 0, st, src_h, src_q, q0, to_h, to_q, t, t + V, D, n, P);
+            hipLaunchKernelGGL(k_peb_taped, grid, block, 0, st, src_h, src_q, run.q0, to_h, to_q, t, t + V, D, n, run.P);
             src_h = to_h;
             src_q = to_q;
         }
@@ -680,9 +661,9 @@ static int bake_vjp_run(const float* acid_in, int B, int D, int n, double thickn
                 const float* at_h = k == k0 ? seg_h : t - 2 * V;           // the state at the start of step k
                 const float* at_q = k == k0 ? seg_q : t - V;
                 hipLaunchKernelGGL(k_peb_adjoint_params, grid, block, 0, st, hb, qb, grad_acid_dose, at_h, at_q, t, t + V, to_h, to_q,
-                                   partials, D, n, P);
+                                   partials, D, n, run.P);
             } else {
-                hipLaunchKernelGGL(k_peb_adjoint, grid, block, 0, st, hb, qb, grad_acid_dose, t, t + V, to_h, to_q, D, n, P);
+                hipLaunchKernelGGL(k_peb_adjoint, grid, block, 0, st, hb, qb, grad_acid_dose, t, t + V, to_h, to_q, D, n, run.P);
             }
             hb = to_h;
             qb = to_q;
@@ -698,20 +679,31 @@ static int bake_vjp_run(const float* acid_in, int B, int D, int n, double thickn
 
 // d(step parameters) / d(physical parameters) of step_of's formulas at a fixed step count, in double: lxy = sigma^2 / (2 S pixel^2),
 // lz = (v sigma)^2 / (2 S hz^2), beta = k_quench dt, fl = exp(-k_loss dt).  Written so that a zero length or scale gives 0, not 0 / 0.
-static void param_chain(double thickness_nm, double pixel_nm, double k_quench, double k_loss, double sigma_acid_nm, double sigma_quencher_nm,
-                        double vertical_scale, double bake_time_s, int D, int steps, const double* g, double* out)
+// param_chain (physical gradient [5] from step gradient [6]) and param_tangent (its transpose) are the Jacobian's two products.
+struct PebJacobian { double dxy_h, dz_h, dv_h, dxy_q, dz_q, dv_q, dt, dfl; bool instant; };
+static PebJacobian step_jacobian(const PebBake& b)
 {
-    const double hz = thickness_nm / D, dt = bake_time_s / steps, S = steps;
-    const double dxy_h = sigma_acid_nm / (S * (pixel_nm * pixel_nm)), dxy_q = sigma_quencher_nm / (S * (pixel_nm * pixel_nm));
-    const double vv = vertical_scale * vertical_scale / (S * (hz * hz));
-    const double dz_h = vv * sigma_acid_nm, dz_q = vv * sigma_quencher_nm;
-    const double dv_h = vertical_scale * sigma_acid_nm * sigma_acid_nm / (S * (hz * hz));
-    const double dv_q = vertical_scale * sigma_quencher_nm * sigma_quencher_nm / (S * (hz * hz));
-    out[0] = std::isinf(k_quench) ? 0.0 : g[4] * dt;
-    out[1] = g[5] * (-dt * std::exp(-k_loss * dt));
-    out[2] = g[0] * dxy_h + g[1] * dz_h;
-    out[3] = g[2] * dxy_q + g[3] * dz_q;
-    out[4] = g[1] * dv_h + g[3] * dv_q;
+    const double hz = b.thickness_nm / b.D, S = b.steps, dt = b.bake_time_s / b.steps, sh = b.sigma_acid_nm, sq = b.sigma_quencher_nm;
+    const double pp = S * (b.pixel_nm * b.pixel_nm), zz = S * (hz * hz), vs = b.vertical_scale, vv = vs * vs / zz;
+    return PebJacobian{sh / pp, vv * sh, vs * sh * sh / zz, sq / pp, vv * sq, vs * sq * sq / zz, dt, -dt * std::exp(-b.k_loss * dt),
+                       std::isinf(b.k_quench)};
+}
+static void param_chain(const PebJacobian& J, const double* g, double* out)
+{
+    out[0] = J.instant ? 0.0 : g[4] * J.dt;
+    out[1] = g[5] * J.dfl;
+    out[2] = g[0] * J.dxy_h + g[1] * J.dz_h;
+    out[3] = g[2] * J.dxy_q + g[3] * J.dz_q;
+    out[4] = g[1] * J.dv_h + g[3] * J.dv_q;
+}
+static void param_tangent(const PebJacobian& J, const double* dp, double* out)
+{
+    out[0] = J.dxy_h * dp[2];
+    out[1] = J.dz_h * dp[2] + J.dv_h * dp[4];
+    out[2] = J.dxy_q * dp[3];
+    out[3] = J.dz_q * dp[3] + J.dv_q * dp[4];
+    out[4] = J.instant ? 0.0 : J.dt * dp[0];
+    out[5] = J.dfl * dp[1];
 }
 
 }  // namespace litho
@@ -726,7 +718,7 @@ int litho_peb_expose(const float* image, int volumes, int D, int n, const float*
     if (!image || !acid || !volume_ok(volumes, D, n) || !make_gains(gains_host, n_gains, volumes, D, gains) || !finite_pos(C))
         return LITHO_E_ARG;
     const size_t in_bytes = (size_t)volumes * D * n * n * sizeof(float);
-    if (overlap(image, in_bytes, acid, in_bytes * n_gains)) return LITHO_E_ARG;
+    if (!writes_clear({{acid, in_bytes * n_gains}}, {{image, in_bytes}})) return LITHO_E_ARG;
     const int planes = volumes * D;
     const bool wide = (n & 3) == 0 && aligned16(image) && aligned16(acid);
     LAUNCH_PACKED(k_peb_expose, wide, n, planes, (hipStream_t)stream, image, acid, planes, n, gains, n_gains, C);
@@ -761,24 +753,18 @@ int litho_peb_bake(const float* acid_in, int B, int D, int n, double thickness_n
                    int steps_per_launch, float* acid, float* quencher, float* acid_dose, void* work, size_t work_bytes, void* stream)
 {
     using namespace litho;
-    if (!acid_in || !acid || !quencher || !acid_dose || !work || !volume_ok(B, D, n)) return LITHO_E_ARG;
-    if (!finite_nonneg(quencher0) || !(k_quench >= 0.0) || !finite_nonneg(k_loss) || !finite_pos(bake_time_s)) return LITHO_E_ARG;
-    const int least = min_steps(sigma_acid_nm, sigma_quencher_nm, vertical_scale, thickness_nm, D, pixel_nm);
-    if (least == 0 || steps < least || steps > PEB_MAXSTEPS) return LITHO_E_ARG;
+    const PebBake bake = {thickness_nm, pixel_nm, quencher0, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps};
+    PebRun run;
+    if (!acid_in || !acid || !quencher || !acid_dose || !work || !volume_ok(B, D, n) || !bake_checked(bake, true, run)) return LITHO_E_ARG;
     if (steps_per_launch < 0 || steps_per_launch > PEB_SMAX) return LITHO_E_ARG;
     const int s = steps_per_launch ? steps_per_launch : litho_peb_steps_per_launch(D);
     const size_t lds = s >= 2 ? lds_bytes(D, s) : 0;
     if (lds > PEB_LDS_MAX) return LITHO_E_ARG;
     const size_t vol_bytes = (size_t)B * D * n * n * sizeof(float), need = 2 * vol_bytes;
-    const void* bufs[5] = {acid_in, acid, quencher, acid_dose, work};
     if (!aligned16(work)) return LITHO_E_ARG;
     if (work_bytes < need) return LITHO_E_WORKSPACE;
-    for (int i = 0; i < 5; ++i)
-        for (int j = i + 1; j < 5; ++j)
-            if (overlap(bufs[i], i == 4 ? need : vol_bytes, bufs[j], j == 4 ? need : vol_bytes)) return LITHO_E_ARG;
-    const PebStep P = step_of(thickness_nm, pixel_nm, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps);
-    const float q0 = (float)quencher0;
-    if (std::isinf(q0) || std::isinf(P.half_dt)) return LITHO_E_ARG;
+    if (!writes_clear({{acid, vol_bytes}, {quencher, vol_bytes}, {acid_dose, vol_bytes}, {work, need}}, {{acid_in, vol_bytes}})) return LITHO_E_ARG;
+    if (!run.fits) return LITHO_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     if (lds > 64 * 1024) {                                // once per device; the automatic choice never gets here
         static unsigned lds_done = 0;
@@ -794,11 +780,11 @@ int litho_peb_bake(const float* acid_in, int B, int D, int n, double thickness_n
     for (int k = 0; k < L; ++k) {
         const int now = left < s ? left : s, to = (L - 1 - k) & 1;
         if (now == 1)
-            hipLaunchKernelGGL(k_peb_direct, dim3(plane_blocks(n, 1), (unsigned)(B * D)), dim3(256), 0, st, src_h, src_q, q0, out_h[to],
-                               out_q[to], acid_dose, D, n, P);
+            hipLaunchKernelGGL(k_peb_direct, dim3(plane_blocks(n, 1), (unsigned)(B * D)), dim3(256), 0, st, src_h, src_q, run.q0,
+                               out_h[to], out_q[to], acid_dose, D, n, run.P);
         else
-            hipLaunchKernelGGL(k_peb_fused, dim3(tiles, tiles, (unsigned)B), dim3(256), lds_bytes(D, now), st, src_h, src_q, q0, out_h[to],
-                               out_q[to], acid_dose, D, n, now, P);
+            hipLaunchKernelGGL(k_peb_fused, dim3(tiles, tiles, (unsigned)B), dim3(256), lds_bytes(D, now), st, src_h, src_q, run.q0,
+                               out_h[to], out_q[to], acid_dose, D, n, now, run.P);
         src_h = out_h[to];
         src_q = out_q[to];
         left -= now;
@@ -810,7 +796,7 @@ int litho_peb_bake(const float* acid_in, int B, int D, int n, double thickness_n
 size_t litho_peb_vjp_work_bytes(int B, int D, int n, int steps, int checkpoint_every)
 {
     using namespace litho;
-    if (!volume_ok(B, D, n) || steps < 1 || steps > PEB_MAXSTEPS || checkpoint_every < 1 || checkpoint_every > steps) return 0;
+    if (!vjp_shape_ok(B, D, n, steps, checkpoint_every)) return 0;
     return vjp_volumes(steps, checkpoint_every) * ((size_t)B * D * n * n * sizeof(float));
 }
 
@@ -820,15 +806,15 @@ int litho_peb_bake_vjp(const float* acid_in, int B, int D, int n, double thickne
                        float* grad_acid_in, float* grad_quencher_in, void* work, size_t work_bytes, void* stream)
 {
     using namespace litho;
-    return bake_vjp_run(acid_in, B, D, n, thickness_nm, pixel_nm, quencher0, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale,
-                        bake_time_s, steps, checkpoint_every, grad_acid, grad_quencher, grad_acid_dose, grad_acid_in, grad_quencher_in,
-                        nullptr, false, work, work_bytes, stream);
+    const PebBake bake = {thickness_nm, pixel_nm, quencher0, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps};
+    return bake_vjp_run(acid_in, B, n, bake, checkpoint_every, grad_acid, grad_quencher, grad_acid_dose, grad_acid_in, grad_quencher_in, nullptr,
+                        false, work, work_bytes, stream);
 }
 
 size_t litho_peb_vjp_params_work_bytes(int B, int D, int n, int steps, int checkpoint_every)
 {
     using namespace litho;
-    if (!volume_ok(B, D, n) || steps < 1 || steps > PEB_MAXSTEPS || checkpoint_every < 1 || checkpoint_every > steps) return 0;
+    if (!vjp_shape_ok(B, D, n, steps, checkpoint_every)) return 0;
     return vjp_params_tape_bytes(B, D, n, steps, checkpoint_every) + vjp_params_slots(B, D, n) * 6 * sizeof(double);
 }
 
@@ -839,9 +825,9 @@ int litho_peb_bake_vjp_params(const float* acid_in, int B, int D, int n, double 
                               size_t work_bytes, void* stream)
 {
     using namespace litho;
-    return bake_vjp_run(acid_in, B, D, n, thickness_nm, pixel_nm, quencher0, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale,
-                        bake_time_s, steps, checkpoint_every, grad_acid, grad_quencher, grad_acid_dose, grad_acid_in, grad_quencher_in,
-                        grad_step, true, work, work_bytes, stream);
+    const PebBake bake = {thickness_nm, pixel_nm, quencher0, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps};
+    return bake_vjp_run(acid_in, B, n, bake, checkpoint_every, grad_acid, grad_quencher, grad_acid_dose, grad_acid_in, grad_quencher_in, grad_step,
+                        true, work, work_bytes, stream);
 }
 
 int litho_peb_param_chain(double thickness_nm, double pixel_nm, double k_quench, double k_loss, double sigma_acid_nm,
@@ -849,11 +835,10 @@ int litho_peb_param_chain(double thickness_nm, double pixel_nm, double k_quench,
                           double* grad_param)
 {
     using namespace litho;
-    if (!grad_step || !grad_param || !(k_quench >= 0.0) || !finite_nonneg(k_loss) || !finite_pos(bake_time_s) || !finite_pos(pixel_nm)) return LITHO_E_ARG;
-    const int least = min_steps(sigma_acid_nm, sigma_quencher_nm, vertical_scale, thickness_nm, D, pixel_nm);
-    if (least == 0 || steps < least || steps > PEB_MAXSTEPS) return LITHO_E_ARG;
-    param_chain(thickness_nm, pixel_nm, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps, grad_step,
-                grad_param);
+    const PebBake bake = {thickness_nm, pixel_nm, 0.0, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps};
+    PebRun run;                                           // not looked at: no kernel runs
+    if (!grad_step || !grad_param || !finite_pos(pixel_nm) || !bake_checked(bake, false, run)) return LITHO_E_ARG;
+    param_chain(step_jacobian(bake), grad_step, grad_param);
     return LITHO_OK;
 }
 
@@ -866,7 +851,7 @@ int litho_peb_expose_vjp(const float* image, int volumes, int D, int n, const fl
         !finite_pos(C))
         return LITHO_E_ARG;
     const size_t in_bytes = (size_t)volumes * D * n * n * sizeof(float);
-    if (overlap(image, in_bytes, grad_image, in_bytes) || overlap(grad_acid, in_bytes * n_gains, grad_image, in_bytes)) return LITHO_E_ARG;
+    if (!writes_clear({{grad_image, in_bytes}}, {{image, in_bytes}, {grad_acid, in_bytes * n_gains}})) return LITHO_E_ARG;
     const int planes = volumes * D;
     const bool wide = (n & 3) == 0 && aligned16(image) && aligned16(grad_acid) && aligned16(grad_image);
     LAUNCH_PACKED(k_peb_expose_vjp, wide, n, planes, (hipStream_t)stream, image, grad_acid, grad_image, planes, n, gains, n_gains, C);
@@ -893,9 +878,7 @@ int litho_peb_expose_vjp_params(const float* image, int volumes, int D, int n, c
     const size_t need = litho_peb_expose_params_work_bytes(volumes, D, n, n_gains);
     if (work_bytes < need) return LITHO_E_WORKSPACE;
     const size_t in_bytes = (size_t)volumes * D * n * n * sizeof(float), out_bytes = (size_t)n_gains * volumes * sizeof(double);
-    if (overlap(grad_C, out_bytes, image, in_bytes) || overlap(grad_C, out_bytes, grad_acid, in_bytes * n_gains) ||
-        overlap(grad_C, out_bytes, work, need) || overlap(work, need, image, in_bytes) || overlap(work, need, grad_acid, in_bytes * n_gains))
-        return LITHO_E_ARG;
+    if (!writes_clear({{grad_C, out_bytes}, {work, need}}, {{image, in_bytes}, {grad_acid, in_bytes * n_gains}})) return LITHO_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     const int planes = volumes * D;
     const unsigned blocks = plane_blocks(n, 1);
@@ -922,7 +905,7 @@ int litho_peb_expose_jvp(const float* image, int volumes, int D, int n, const fl
         dC.v[p] = dC_host[p];
     }
     const size_t in_bytes = (size_t)volumes * D * n * n * sizeof(float), out_bytes = in_bytes * n_gains * P;
-    if (overlap(image, in_bytes, dacid, out_bytes) || (dimage && overlap(dimage, in_bytes * P, dacid, out_bytes))) return LITHO_E_ARG;
+    if (!writes_clear({{dacid, out_bytes}}, {{image, in_bytes}, {dimage, in_bytes * P}})) return LITHO_E_ARG;
     const int planes = volumes * D;
     const bool wide = (n & 3) == 0 && aligned16(image) && aligned16(dimage) && aligned16(dacid);
     LAUNCH_PACKED(k_peb_expose_jvp, wide, n, planes, (hipStream_t)stream, image, dimage, dacid, planes, n, gains, n_gains, C, P, dC);
@@ -943,11 +926,10 @@ int litho_peb_bake_jvp(const float* acid_in, int B, int D, int n, double thickne
                        float* acid_dose, float* dacid, float* dquencher, float* dacid_dose, void* work, size_t work_bytes, void* stream)
 {
     using namespace litho;
+    const PebBake bake = {thickness_nm, pixel_nm, quencher0, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps};
+    PebRun run;
     if (!acid_in || !dquencher0_host || !dstep_host || !dacid || !dquencher || !dacid_dose || !work || !volume_ok(B, D, n)) return LITHO_E_ARG;
-    if (P < 1 || P > TAN_MAX || (long long)P * B * D > 65535) return LITHO_E_ARG;
-    if (!finite_nonneg(quencher0) || !(k_quench >= 0.0) || !finite_nonneg(k_loss) || !finite_pos(bake_time_s)) return LITHO_E_ARG;
-    const int least = min_steps(sigma_acid_nm, sigma_quencher_nm, vertical_scale, thickness_nm, D, pixel_nm);
-    if (least == 0 || steps < least || steps > PEB_MAXSTEPS) return LITHO_E_ARG;
+    if (P < 1 || P > TAN_MAX || (long long)P * B * D > 65535 || !bake_checked(bake, true, run)) return LITHO_E_ARG;
     PebTanStep T;
     memset(&T, 0, sizeof(T));
     for (int p = 0; p < P; ++p) {
@@ -961,19 +943,12 @@ int litho_peb_bake_jvp(const float* acid_in, int B, int D, int n, double thickne
     const size_t V = (size_t)B * D * n * n, vol_bytes = V * sizeof(float), need = (5 + 2 * (size_t)P) * vol_bytes;
     if (!aligned16(work)) return LITHO_E_ARG;
     if (work_bytes < need) return LITHO_E_WORKSPACE;
-    // the outputs overlap no input, no other output and not the workspace; the inputs are only read
-    const void* bufs[9] = {acid, quencher, acid_dose, dacid, dquencher, dacid_dose, acid_in, dacid_in, work};
-    const size_t size[9] = {vol_bytes, vol_bytes, vol_bytes, P * vol_bytes, P * vol_bytes, P * vol_bytes, vol_bytes, P * vol_bytes, need};
-    for (int i = 0; i < 6; ++i) {
-        if (!bufs[i]) continue;
-        for (int j = i + 1; j < 9; ++j)
-            if (bufs[j] && overlap(bufs[i], size[i], bufs[j], size[j])) return LITHO_E_ARG;
-    }
-    for (int j = 6; j < 8; ++j)
-        if (bufs[j] && overlap(bufs[j], size[j], work, need)) return LITHO_E_ARG;
-    const PebStep S = step_of(thickness_nm, pixel_nm, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps);
-    const float q0 = (float)quencher0;
-    if (std::isinf(q0) || std::isinf(S.half_dt)) return LITHO_E_ARG;
+    const size_t tan_bytes = P * vol_bytes;
+    if (!writes_clear({{acid, vol_bytes}, {quencher, vol_bytes}, {acid_dose, vol_bytes}, {dacid, tan_bytes}, {dquencher, tan_bytes},
+                       {dacid_dose, tan_bytes}, {work, need}},
+                      {{acid_in, vol_bytes}, {dacid_in, tan_bytes}}))
+        return LITHO_E_ARG;
+    if (!run.fits) return LITHO_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     // the primal pair ping-pongs between two sides of the workspace, a lives in its fifth volume; the last step writes the
     // outputs that were asked for.  The tangent pairs ping-pong between the outputs and the workspace, the last step to the
@@ -990,8 +965,8 @@ int litho_peb_bake_jvp(const float* acid_in, int B, int D, int n, double thickne
         const bool last = k + 1 == steps;
         float* to_h = (last && acid) ? acid : ph[k & 1];
         float* to_q = (last && quencher) ? quencher : ph[k & 1] + V;
-        hipLaunchKernelGGL(k_peb_jvp, grid, block, 0, st, src_h, src_q, q0, to_h, to_q, pa, src_dh, src_dq, th[to], tq[to], dacid_dose, V, D,
-                           n, P, S, T);
+        hipLaunchKernelGGL(k_peb_jvp, grid, block, 0, st, src_h, src_q, run.q0, to_h, to_q, pa, src_dh, src_dq, th[to], tq[to], dacid_dose,
+                           V, D, n, P, run.P, T);
         src_h = to_h;
         src_q = to_q;
         src_dh = th[to];
@@ -1006,10 +981,10 @@ int litho_peb_param_tangent(double thickness_nm, double pixel_nm, double k_quenc
                             double* dstep)
 {
     using namespace litho;
-    if (!dparam || !dstep || !(k_quench >= 0.0) || !finite_nonneg(k_loss) || !finite_pos(bake_time_s) || !finite_pos(pixel_nm)) return LITHO_E_ARG;
-    const int least = min_steps(sigma_acid_nm, sigma_quencher_nm, vertical_scale, thickness_nm, D, pixel_nm);
-    if (least == 0 || steps < least || steps > PEB_MAXSTEPS) return LITHO_E_ARG;
-    param_tangent(thickness_nm, pixel_nm, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps, dparam, dstep);
+    const PebBake bake = {thickness_nm, pixel_nm, 0.0, k_quench, k_loss, sigma_acid_nm, sigma_quencher_nm, vertical_scale, bake_time_s, D, steps};
+    PebRun run;                                           // not looked at: no kernel runs
+    if (!dparam || !dstep || !finite_pos(pixel_nm) || !bake_checked(bake, false, run)) return LITHO_E_ARG;
+    param_tangent(step_jacobian(bake), dparam, dstep);
     return LITHO_OK;
 }
 
@@ -1022,8 +997,7 @@ int litho_peb_rate(const float* acid_dose, int B, int D, int n, double k_amp, do
         !make_mack(r_max, r_min, q, m_th, surface_rate, surface_depth_nm, thickness_nm, D, law))
         return LITHO_E_ARG;
     const size_t bytes = (size_t)B * D * n * n * sizeof(float);
-    if (overlap(acid_dose, bytes, slowness, bytes)) return LITHO_E_ARG;
-    if (inhibitor && (overlap(acid_dose, bytes, inhibitor, bytes) || overlap(slowness, bytes, inhibitor, bytes))) return LITHO_E_ARG;
+    if (!writes_clear({{slowness, bytes}, {inhibitor, bytes}}, {{acid_dose, bytes}})) return LITHO_E_ARG;
     const bool wide = (n & 3) == 0 && aligned16(acid_dose) && aligned16(slowness) && aligned16(inhibitor);
     LAUNCH_PACKED(k_peb_rate, wide, n, B * D, (hipStream_t)stream, acid_dose, slowness, inhibitor, D, n, k_amp, law.rmax_a1, law.rmin, law.q,
                   law.a, law.surface);

@@ -1,6 +1,7 @@
 // resist_volume.hpp -- what the units of the resist chain share (peb.hip, develop.hip, develop_grad.hip): the limits of a volume
 // [B, D, n, n], the 16-byte packs of the pointwise kernels and their launch, the host predicates of the entry points, the gains,
-// Mack's rate law (host set-up, device forward and backward) and the host loop of the two tiled fixed-point solvers.
+// Mack's rate law (host set-up, device forward and backward), the entry points' aliasing rule (Span, writes_clear), and the
+// geometry and the host loop of the tiled fixed-point solvers.
 //
 // The library is built without relocatable device code, so a translation unit cannot name another's __device__ symbols:
 // everything here is static or inline, and each unit that includes this header keeps its own copy.  The units are built with
@@ -13,6 +14,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <initializer_list>
 
 namespace litho {
 
@@ -72,6 +74,21 @@ static bool overlap(const void* a, size_t a_bytes, const void* b, size_t b_bytes
 {
     const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
     return pa < pb + b_bytes && pb < pa + a_bytes;
+}
+// The aliasing rule of every entry point: what a call writes (outputs, workspace, sum outputs) overlaps nothing else the call
+// touches; what it only reads may alias.  True when no span of `writes` overlaps another of them or one of `reads`; a null span is
+// an optional buffer that was not given.
+struct Span { const void* p; size_t bytes; };
+static bool writes_clear(std::initializer_list<Span> writes, std::initializer_list<Span> reads)
+{
+    for (const Span* w = writes.begin(); w != writes.end(); ++w) {
+        if (!w->p) continue;
+        for (const Span* o = w + 1; o != writes.end(); ++o)
+            if (o->p && overlap(w->p, w->bytes, o->p, o->bytes)) return false;
+        for (const Span& r : reads)
+            if (r.p && overlap(w->p, w->bytes, r.p, r.bytes)) return false;
+    }
+    return true;
 }
 static bool finite_pos(double v) { return v > 0.0 && !std::isinf(v); }
 static bool finite_nonneg(double v) { return v >= 0.0 && !std::isinf(v); }
@@ -190,6 +207,16 @@ __global__ __launch_bounds__(256) void k_vol_total(const double* __restrict__ pa
     vol_block_sum<N>(t, lds);
     if (threadIdx.x == 0)
         for (int j = 0; j < N; ++j) out[(size_t)blockIdx.x * N + j] = t[j];
+}
+
+// ---- the geometry of the front solvers (litho_develop_time and its two derivatives) as they round it: the fp32 spacings and the
+// weights 1 / spacing^2.  False when one of them leaves fp32's range.
+struct FrontGeometry { float h, hz, wxy, wz; };
+static bool front_geometry(double pixel_nm, double thickness_nm, int D, FrontGeometry& g)
+{
+    g.h = (float)pixel_nm; g.hz = (float)(thickness_nm / D);
+    g.wxy = 1.f / (g.h * g.h); g.wz = 1.f / (g.hz * g.hz);
+    return g.h > 0.f && g.hz > 0.f && !std::isinf(g.wxy) && !std::isinf(g.wz) && g.wxy > 0.f && g.wz > 0.f;
 }
 
 // ---- the host loop of the tiled solvers (k_develop_time, k_develop_time_vjp).  enqueue(it) puts launch it = 0, 1, ... on `st`;

@@ -113,6 +113,11 @@ def _gains(who, doses, F, D):
     return (ctypes.c_float * len(gains))(*gains), len(gains)
 
 
+def _surface_depth(mack, thickness):
+    """The depth of the surface-inhibition factor as the C ABI takes it: the layer's thickness where the factor is switched off."""
+    return mack.surfaceDepth if mack.surfaceDepth is not None else thickness
+
+
 def latentDiffusion(image, thickness, pixelSize, diffusionLength=0.0, verticalDiffusionLength=0.0):
     """The intensity volume [D,n,n] or [B,D,n,n] convolved with a separable Gaussian (litho_latent_diffuse): standard deviation
     `diffusionLength` nm along x and y with zeros outside the grid -- the taps of resistContour(diffusionLength=) -- and
@@ -128,11 +133,8 @@ def latentDiffusion(image, thickness, pixelSize, diffusionLength=0.0, verticalDi
     out = torch.empty_like(v)
     passes = (2 if sxy > 0 else 0) + (1 if sz > 0 else 0)
     work = torch.empty_like(v) if passes >= 2 else None
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_latent_diffuse(nat.ptr(v), B, D, n, sxy, sz, nat.ptr(out), nat.ptr(work) if work is not None else None,
-                                                 work.numel() * 4 if work is not None else 0, nat.stream_ptr(dev)), "litho_latent_diffuse")
-        if work is not None:
-            work.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_latent_diffuse", nat.ptr(v), B, D, n, sxy, sz, nat.ptr(out), nat.ptr(work) if work is not None else None,
+             work.numel() * 4 if work is not None else 0, keep=(work,))
     return out if batched else out[0]
 
 
@@ -150,12 +152,8 @@ def developmentRate(image, resist, thickness, pixelSize, doses=(1.0,)):
     if resist.diffusionLength > 0.0 or resist.verticalDiffusionLength > 0.0:
         v = latentDiffusion(v, thickness, h, resist.diffusionLength, resist.verticalDiffusionLength)
     out = torch.empty((count * F, D, n, n), dtype=torch.float32, device=dev)
-    delta = resist.surfaceDepth if resist.surfaceDepth is not None else thickness
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_develop_rate(nat.ptr(v), F, D, n, g, count, resist.C, resist.rMax, resist.rMin, resist.q,
-                                               resist.mTh, resist.surfaceRate, delta, thickness, nat.ptr(out), nat.stream_ptr(dev)),
-                  "litho_develop_rate")
-        v.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_develop_rate", nat.ptr(v), F, D, n, g, count, resist.C, resist.rMax, resist.rMin, resist.q, resist.mTh,
+             resist.surfaceRate, _surface_depth(resist, thickness), thickness, nat.ptr(out), keep=(v,))
     return out
 
 
@@ -170,9 +168,7 @@ def _development_time(slowness, thickness, pixelSize, maxIterations):
     nbytes = int(nat.lib().litho_develop_work_bytes(B, D, n, maxIterations))
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     launches = ctypes.c_int(0)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_develop_time(nat.ptr(s), B, D, n, thickness, h, maxIterations, nat.ptr(T), nat.ptr(work), nbytes,
-                                               ctypes.byref(launches), nat.stream_ptr(dev)), "litho_develop_time")
+    nat.call(dev, "litho_develop_time", nat.ptr(s), B, D, n, thickness, h, maxIterations, nat.ptr(T), nat.ptr(work), nbytes, ctypes.byref(launches))
     return (T if batched else T[0]), launches.value
 
 
@@ -198,10 +194,7 @@ def developedDepth(T, thickness, developTime):
     if not (t >= 0.0 and math.isfinite(t)):
         raise ValueError(f"{who}: developTime must be finite and >= 0; got {developTime}")
     out = torch.empty((B, n, n), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_developed_depth(nat.ptr(v), B, D, n, thickness, t, nat.ptr(out), nat.stream_ptr(dev)),
-                  "litho_developed_depth")
-        v.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_developed_depth", nat.ptr(v), B, D, n, thickness, t, nat.ptr(out), keep=(v,))
     return out if batched else out[0]
 
 
@@ -316,15 +309,10 @@ def developmentTimeGradient(slowness, T, gradT, thickness, pixelSize, maxIterati
     nbytes = int(nat.lib().litho_develop_vjp_work_bytes(B, D, n, maxIterations))
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     launches = ctypes.c_int(0)
-    with torch.cuda.device(dev):
-        rc = nat.lib().litho_develop_time_vjp(nat.ptr(s), nat.ptr(Tv), nat.ptr(g), B, D, n, thickness, h, maxIterations, nat.ptr(out),
-                                              nat.ptr(work), nbytes, ctypes.byref(launches), nat.stream_ptr(dev))
-        if rc == nat.E_NOCONV:
-            raise RuntimeError(f"{who}: the adjoint iteration did not reach its fixed point within the launch cap (maxIterations = "
-                               f"{maxIterations}); the gradient is not a result")
-        nat.check(rc, "litho_develop_time_vjp")
-        for t in (s, Tv, g, work):
-            t.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_develop_time_vjp", nat.ptr(s), nat.ptr(Tv), nat.ptr(g), B, D, n, thickness, h, maxIterations, nat.ptr(out), nat.ptr(work),
+             nbytes, ctypes.byref(launches), keep=(s, Tv, g, work),
+             noconv=f"{who}: the adjoint iteration did not reach its fixed point within the launch cap (maxIterations = {maxIterations}); "
+                    "the gradient is not a result")
     out = out if batched else out[0]
     return (out, launches.value) if returnLaunches else out
 
@@ -335,13 +323,8 @@ def _rate_vjp(who, x, doses, kappa, mack, thickness, gradSlowness):
     g, count = _gains(who, doses, F, D)
     gs = _like(who, "gradSlowness", gradSlowness, (count * F, D, n, n), dev)
     out = torch.empty_like(v)
-    delta = mack.surfaceDepth if mack.surfaceDepth is not None else thickness
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_develop_rate_vjp(nat.ptr(v), F, D, n, g, count, kappa, mack.rMax, mack.rMin, mack.q, mack.mTh,
-                                                   mack.surfaceRate, delta, thickness, nat.ptr(gs), nat.ptr(out), nat.stream_ptr(dev)),
-                  "litho_develop_rate_vjp")
-        for t in (v, gs):
-            t.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_develop_rate_vjp", nat.ptr(v), F, D, n, g, count, kappa, mack.rMax, mack.rMin, mack.q, mack.mTh, mack.surfaceRate,
+             _surface_depth(mack, thickness), thickness, nat.ptr(gs), nat.ptr(out), keep=(v, gs))
     return out if batched else out[0]
 
 

@@ -23,7 +23,7 @@ import math
 import torch
 
 from . import _native as nat
-from .develop import MackResist, _gains, _positive, _volume
+from .develop import MackResist, _gains, _positive, _surface_depth, _volume
 
 MAX_STEPS = 65536
 
@@ -81,6 +81,12 @@ class BakeResult:
         self.acid, self.quencher, self.acidDose, self.inhibitor, self.slowness, self.steps = acid, quencher, acidDose, inhibitor, slowness, steps
 
 
+def _bake_scalars(resist):
+    """The bake's physical numbers in the order every litho_peb_bake* entry takes them between the pixel size and the step count."""
+    return (resist.quencher, resist.kQuench, resist.kLoss, resist.acidDiffusionLength, resist.quencherDiffusionLength, resist.verticalScale,
+            resist.bakeTime)
+
+
 def _steps(who, resist, thickness, D, pixel, steps):
     least = resist.minSteps(thickness, D, pixel)
     S = max(least, 8) if steps is None else int(steps)
@@ -97,10 +103,7 @@ def exposeAcid(image, C, doses=(1.0,)):
     v, F, D, n, _, dev = _volume(who, image)
     g, count = _gains(who, doses, F, D)
     out = torch.empty((count * F, D, n, n), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_peb_expose(nat.ptr(v), F, D, n, g, count, _positive(who, "C", C), nat.ptr(out), nat.stream_ptr(dev)),
-                  "litho_peb_expose")
-        v.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_peb_expose", nat.ptr(v), F, D, n, g, count, _positive(who, "C", C), nat.ptr(out), keep=(v,))
     return out
 
 
@@ -117,17 +120,11 @@ def bakeAcid(acid, resist, thickness, pixelSize, steps=None, stepsPerLaunch=0):
     spl = int(stepsPerLaunch)
     if not 0 <= spl <= 4:
         raise ValueError(f"{who}: stepsPerLaunch must be 0 (automatic) ... 4; got {stepsPerLaunch}")
-    lib = nat.lib()
     out_h, out_q, out_a = (torch.empty_like(v) for _ in range(3))
-    nbytes = int(lib.litho_peb_work_bytes(B, D, n))
+    nbytes = int(nat.lib().litho_peb_work_bytes(B, D, n))
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(lib.litho_peb_bake(nat.ptr(v), B, D, n, thickness, h, resist.quencher, resist.kQuench, resist.kLoss,
-                                     resist.acidDiffusionLength, resist.quencherDiffusionLength, resist.verticalScale, resist.bakeTime, S, spl,
-                                     nat.ptr(out_h), nat.ptr(out_q), nat.ptr(out_a), nat.ptr(work), nbytes, nat.stream_ptr(dev)),
-                  "litho_peb_bake")
-        for t in (v, work):
-            t.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_peb_bake", nat.ptr(v), B, D, n, thickness, h, *_bake_scalars(resist), S, spl, nat.ptr(out_h), nat.ptr(out_q),
+             nat.ptr(out_a), nat.ptr(work), nbytes, keep=(v, work))
     if not batched:
         out_h, out_q, out_a = out_h[0], out_q[0], out_a[0]
     return out_h, out_q, out_a, S
@@ -143,11 +140,8 @@ def amplifiedRate(acidDose, resist, thickness):
     v, B, D, n, batched, dev = _volume(who, acidDose, "acidDose")
     thickness, mack = _positive(who, "thickness", thickness), resist.mack
     slow, m = torch.empty_like(v), torch.empty_like(v)
-    delta = mack.surfaceDepth if mack.surfaceDepth is not None else thickness
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_peb_rate(nat.ptr(v), B, D, n, resist.kAmp, mack.rMax, mack.rMin, mack.q, mack.mTh, mack.surfaceRate, delta,
-                                           thickness, nat.ptr(slow), nat.ptr(m), nat.stream_ptr(dev)), "litho_peb_rate")
-        v.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_peb_rate", nat.ptr(v), B, D, n, resist.kAmp, mack.rMax, mack.rMin, mack.q, mack.mTh, mack.surfaceRate,
+             _surface_depth(mack, thickness), thickness, nat.ptr(slow), nat.ptr(m), keep=(v,))
     return (m, slow) if batched else (m[0], slow[0])
 
 
@@ -206,7 +200,12 @@ def bakeGradient(acid, resist, thickness, pixelSize, gradAcid=None, gradQuencher
     steps; None: ceil(sqrt(steps))), re-running each segment once: the result does not depend on it, bit for bit, only the
     workspace does, (2 (ceil(steps / c) - 1) + 2 c + 8) volumes.  With instantaneous neutralisation the loss is differentiable
     only where acid and quencher do not tie; a tie takes the forward's branch."""
-    who = "bakeGradient"
+    return _bake_vjp("bakeGradient", False, acid, resist, thickness, pixelSize, gradAcid, gradQuencher, gradAcidDose, steps, checkpointEvery)
+
+
+def _bake_vjp(who, withStep, acid, resist, thickness, pixelSize, gradAcid, gradQuencher, gradAcidDose, steps, checkpointEvery):
+    """bakeGradient (litho_peb_bake_vjp) and, withStep, calibrate.bakeStepGradient (litho_peb_bake_vjp_params: one more output,
+    float64 [B, 6], and its own workspace size) behind one set of checks."""
     if not isinstance(resist, ChemicallyAmplifiedResist):
         raise TypeError(f"{who}: resist must be a ChemicallyAmplifiedResist")
     v, B, D, n, batched, dev = _volume(who, acid, "acid")
@@ -219,20 +218,14 @@ def bakeGradient(acid, resist, thickness, pixelSize, gradAcid=None, gradQuencher
                                                                         ("gradAcidDose", gradAcidDose)))
     if gh is None and gq is None and ga is None:
         raise ValueError(f"{who}: give at least one of gradAcid, gradQuencher, gradAcidDose")
-    lib = nat.lib()
-    out_h, out_q = torch.empty_like(v), torch.empty_like(v)
-    nbytes = int(lib.litho_peb_vjp_work_bytes(B, D, n, S, c))
+    entry, sizer = ("litho_peb_bake_vjp_params", "litho_peb_vjp_params_work_bytes") if withStep else ("litho_peb_bake_vjp", "litho_peb_vjp_work_bytes")
+    outs = [torch.empty_like(v), torch.empty_like(v)] + ([torch.empty((B, 6), dtype=torch.float64, device=dev)] if withStep else [])
+    nbytes = int(getattr(nat.lib(), sizer)(B, D, n, S, c))
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     opt = lambda t: nat.ptr(t) if t is not None else None                       # noqa: E731
-    with torch.cuda.device(dev):
-        nat.check(lib.litho_peb_bake_vjp(nat.ptr(v), B, D, n, thickness, h, resist.quencher, resist.kQuench, resist.kLoss,
-                                         resist.acidDiffusionLength, resist.quencherDiffusionLength, resist.verticalScale, resist.bakeTime, S, c,
-                                         opt(gh), opt(gq), opt(ga), nat.ptr(out_h), nat.ptr(out_q), nat.ptr(work), nbytes,
-                                         nat.stream_ptr(dev)), "litho_peb_bake_vjp")
-        for t in (v, gh, gq, ga, work):
-            if t is not None:
-                t.record_stream(torch.cuda.current_stream(dev))
-    return (out_h, out_q) if batched else (out_h[0], out_q[0])
+    nat.call(dev, entry, nat.ptr(v), B, D, n, thickness, h, *_bake_scalars(resist), S, c, opt(gh), opt(gq), opt(ga), *(nat.ptr(t) for t in outs),
+             nat.ptr(work), nbytes, keep=(v, gh, gq, ga, work))
+    return tuple(outs) if batched else tuple(t[0] for t in outs)
 
 
 def exposeAcidGradient(image, C, doses, gradAcid):
@@ -247,11 +240,7 @@ def exposeAcidGradient(image, C, doses, gradAcid):
                          f"{tuple(getattr(gradAcid, 'shape', ()))} on {getattr(gradAcid, 'device', None)}")
     ga = gradAcid.detach().contiguous()
     out = torch.empty_like(v)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_peb_expose_vjp(nat.ptr(v), F, D, n, g, count, _positive(who, "C", C), nat.ptr(ga), nat.ptr(out),
-                                                 nat.stream_ptr(dev)), "litho_peb_expose_vjp")
-        for t in (v, ga):
-            t.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_peb_expose_vjp", nat.ptr(v), F, D, n, g, count, _positive(who, "C", C), nat.ptr(ga), nat.ptr(out), keep=(v, ga))
     return out if batched else out[0]
 
 

@@ -22,9 +22,9 @@ import ctypes
 import torch
 
 from . import _native as nat
-from .calibrate import _BAKED, _MACK, BAKE_PARAMETERS, _edge_points, _edge_residuals, _forward
-from .develop import MackResist, _gains, _like, _positive, _volume, latentDiffusion
-from .peb import ChemicallyAmplifiedResist, _steps
+from .calibrate import _BAKED, _MACK, BAKE_PARAMETERS, _bake_rows, _edge_points, _edge_residuals, _forward
+from .develop import MackResist, _gains, _like, _positive, _surface_depth, _volume, latentDiffusion
+from .peb import ChemicallyAmplifiedResist, _bake_scalars, _steps
 
 MAX_DIRECTIONS = 16
 RATE_PARAMETERS = ("kappa",) + _MACK
@@ -66,13 +66,8 @@ def exposeAcidTangent(image, C, doses, dC, dImage=None):
     dc = _doubles(who, "dC", dC, (P,))
     dI = _directions(who, "dImage", dImage, P, v.shape if batched else v.shape[1:], dev)
     out = torch.empty((P, count * F, D, n, n), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_peb_expose_jvp(nat.ptr(v), F, D, n, g, count, _positive(who, "C", C), P, dc,
-                                                 nat.ptr(dI) if dI is not None else None, nat.ptr(out), nat.stream_ptr(dev)),
-                  "litho_peb_expose_jvp")
-        for t in (v, dI):
-            if t is not None:
-                t.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_peb_expose_jvp", nat.ptr(v), F, D, n, g, count, _positive(who, "C", C), P, dc, nat.ptr(dI) if dI is not None else None,
+             nat.ptr(out), keep=(v, dI))
     return out
 
 
@@ -80,20 +75,7 @@ def bakeParameterTangent(dParam, resist, thickness, pixelSize, D, steps):
     """dParam [..., 5] = d(kQuench, kLoss, acidDiffusionLength, quencherDiffusionLength, verticalScale) -> float64 [..., 6] on the
     host = d(lxy_h, lz_h, lxy_q, lz_q, beta, fl) at the fixed step count `steps` (litho_peb_param_tangent): the transpose of
     bakeParameterChain.  0 for a zero length or scale and for instantaneous neutralisation."""
-    who = "bakeParameterTangent"
-    d = torch.as_tensor(dParam).detach().to(device="cpu", dtype=torch.float64)
-    if d.shape[-1:] != (5,):
-        raise ValueError(f"{who}: dParam must be [..., 5]; got {tuple(d.shape)}")
-    flat = d.reshape(-1, 5)
-    out = torch.empty((flat.shape[0], 6), dtype=torch.float64)
-    src, dst = (ctypes.c_double * 5)(), (ctypes.c_double * 6)()
-    for i in range(flat.shape[0]):
-        src[:] = flat[i].tolist()
-        nat.check(nat.lib().litho_peb_param_tangent(float(thickness), float(pixelSize), resist.kQuench, resist.kLoss, resist.acidDiffusionLength,
-                                                    resist.quencherDiffusionLength, resist.verticalScale, resist.bakeTime, int(D), int(steps),
-                                                    src, dst), "litho_peb_param_tangent")
-        out[i] = torch.tensor(list(dst), dtype=torch.float64)
-    return out.reshape(d.shape[:-1] + (6,))
+    return _bake_rows("bakeParameterTangent", "dParam", dParam, 5, 6, "litho_peb_param_tangent", resist, thickness, pixelSize, D, steps)
 
 
 def bakeTangent(acid, resist, thickness, pixelSize, dAcid=None, dQuencher=None, dStep=None, steps=None, returnPrimal=False):
@@ -117,20 +99,13 @@ def bakeTangent(acid, resist, thickness, pixelSize, dAcid=None, dQuencher=None, 
     dh = _directions(who, "dAcid", dAcid, P, v.shape if batched else v.shape[1:], dev)
     dq = _doubles(who, "dQuencher", dQuencher if dQuencher is not None else [0.0] * P, (P,))
     ds = _doubles(who, "dStep", dStep if dStep is not None else [[0.0] * 6] * P, (P, 6))
-    lib = nat.lib()
     prim = [torch.empty_like(v) for _ in range(3)] if returnPrimal else [None] * 3
     out = [torch.empty((P,) + tuple(v.shape), dtype=torch.float32, device=dev) for _ in range(3)]
-    nbytes = int(lib.litho_peb_jvp_work_bytes(B, D, n, P))
+    nbytes = int(nat.lib().litho_peb_jvp_work_bytes(B, D, n, P))
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     opt = lambda t: nat.ptr(t) if t is not None else None                       # noqa: E731
-    with torch.cuda.device(dev):
-        nat.check(lib.litho_peb_bake_jvp(nat.ptr(v), B, D, n, thickness, h, resist.quencher, resist.kQuench, resist.kLoss,
-                                         resist.acidDiffusionLength, resist.quencherDiffusionLength, resist.verticalScale, resist.bakeTime, S,
-                                         P, opt(dh), dq, ds, opt(prim[0]), opt(prim[1]), opt(prim[2]), nat.ptr(out[0]), nat.ptr(out[1]),
-                                         nat.ptr(out[2]), nat.ptr(work), nbytes, nat.stream_ptr(dev)), "litho_peb_bake_jvp")
-        for t in (v, dh, work):
-            if t is not None:
-                t.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_peb_bake_jvp", nat.ptr(v), B, D, n, thickness, h, *_bake_scalars(resist), S, P, opt(dh), dq, ds, opt(prim[0]),
+             opt(prim[1]), opt(prim[2]), nat.ptr(out[0]), nat.ptr(out[1]), nat.ptr(out[2]), nat.ptr(work), nbytes, keep=(v, dh, work))
     if not batched:
         out, prim = [t[:, 0] for t in out], [t[0] if t is not None else None for t in prim]
     return tuple(out) + (tuple(prim) if returnPrimal else ())
@@ -145,7 +120,7 @@ def rateParameterTangent(dParam, mack, thickness, D):
     if d.dim() != 2 or d.shape[1] != 7:
         raise ValueError(f"{who}: dParam must be [P, 7]; got {tuple(d.shape)}")
     thickness, D = float(thickness), int(D)
-    delta = mack.surfaceDepth if mack.surfaceDepth is not None else thickness
+    delta = _surface_depth(mack, thickness)
     out = torch.empty((d.shape[0], D, 6), dtype=torch.float64)
     src, dst = (ctypes.c_double * 7)(), (ctypes.c_double * (max(D, 1) * 6))()
     for i in range(d.shape[0]):
@@ -170,14 +145,8 @@ def _rate_jvp(who, x, doses, kappa, mack, thickness, dX, dPhi):
         raise ValueError(f"{who}: dPhi must be finite numbers [P, D, 6] = {(P, D, 6)}; got {tuple(phi.shape)}")
     phi = phi.contiguous().to(dev)
     out = torch.empty((P, count * F, D, n, n), dtype=torch.float32, device=dev)
-    delta = mack.surfaceDepth if mack.surfaceDepth is not None else thickness
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().litho_develop_rate_jvp(nat.ptr(v), F, D, n, g, count, kappa, mack.rMax, mack.rMin, mack.q, mack.mTh,
-                                                   mack.surfaceRate, delta, thickness, P, nat.ptr(dx) if dx is not None else None,
-                                                   nat.ptr(phi), nat.ptr(out), nat.stream_ptr(dev)), "litho_develop_rate_jvp")
-        for t in (v, dx, phi):
-            if t is not None:
-                t.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_develop_rate_jvp", nat.ptr(v), F, D, n, g, count, kappa, mack.rMax, mack.rMin, mack.q, mack.mTh, mack.surfaceRate,
+             _surface_depth(mack, thickness), thickness, P, nat.ptr(dx) if dx is not None else None, nat.ptr(phi), nat.ptr(out), keep=(v, dx, phi))
     return out
 
 
@@ -224,15 +193,10 @@ def developmentTimeTangent(slowness, T, dSlowness, thickness, pixelSize, maxIter
     nbytes = int(nat.lib().litho_develop_jvp_work_bytes(B, D, n, P, maxIterations))
     work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     launches = ctypes.c_int(0)
-    with torch.cuda.device(dev):
-        rc = nat.lib().litho_develop_time_jvp(nat.ptr(s), nat.ptr(Tv), nat.ptr(ds), B, D, n, P, thickness, h, maxIterations, nat.ptr(out),
-                                              nat.ptr(work), nbytes, ctypes.byref(launches), nat.stream_ptr(dev))
-        if rc == nat.E_NOCONV:
-            raise RuntimeError(f"{who}: the tangent iteration did not reach its fixed point within the launch cap (maxIterations = "
-                               f"{maxIterations}); the tangent is not a result")
-        nat.check(rc, "litho_develop_time_jvp")
-        for t in (s, Tv, ds, work):
-            t.record_stream(torch.cuda.current_stream(dev))
+    nat.call(dev, "litho_develop_time_jvp", nat.ptr(s), nat.ptr(Tv), nat.ptr(ds), B, D, n, P, thickness, h, maxIterations, nat.ptr(out),
+             nat.ptr(work), nbytes, ctypes.byref(launches), keep=(s, Tv, ds, work),
+             noconv=f"{who}: the tangent iteration did not reach its fixed point within the launch cap (maxIterations = {maxIterations}); "
+                    "the tangent is not a result")
     out = out if batched else out[:, 0]
     return (out, launches.value) if returnLaunches else out
 

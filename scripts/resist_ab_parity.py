@@ -1,12 +1,12 @@
-"""Bit equality of the resist chain (csrc/peb.hip, csrc/develop.hip, csrc/develop_grad.hip, develop.py, peb.py) between two
-checkouts:
+"""Bit equality of the resist chain (csrc/peb.hip, csrc/develop.hip, csrc/develop_grad.hip, develop.py, peb.py, calibrate.py,
+tangent.py) between two checkouts:
 
     python scripts/resist_ab_parity.py ROOT_A ROOT_B [--timeout 300]
 
 Runs the same seeded workload in one fresh child process per root, each under its own `timeout` and with its root first on
 sys.path, so the Python of the two trees is compared as well as their libraries (LITHO_ABBE_LIB is dropped from the children's
 environment, and a child asserts that its package and its library come from its root).  Every output is saved as its raw bits
-(fp32 viewed as uint32, so NaN cells compare) and compared with numpy.array_equal: nothing in these kernels reorders a sum, so
+(fp32 viewed as uint32 and float64 as uint64, so NaN cells compare) and compared with numpy.array_equal: nothing in these kernels reorders a sum, so
 there is no tolerance, and a differing bit is a bug to find.  Stops at the first child that fails; exit status 1 on any
 difference.
 
@@ -16,7 +16,11 @@ negative and a NaN cell (the rate law's explicit NaN), slowness volumes the four
 runs with q integer and not, m_th 0 and > 0; the bake with stepsPerLaunch 0, 2 and 4 wherever the fused kernel's LDS fits
 160 KiB, kQuench finite and infinite, and each species not diffusing; the bake adjoint with checkpointEvery 1, the default and
 steps; both solvers keep their launch counts.  Every pointwise entry (and the development adjoint, whose link and scale
-kernels are packed) runs once more through the raw C ABI with every buffer one float past a 16-byte boundary: the scalar twins."""
+kernels are packed) runs once more through the raw C ABI with every buffer one float past a 16-byte boundary: the scalar twins.
+The entries added since ride on the same shapes and variants: the three parameter gradients (the bake's at checkpointEvery 1, the
+default and steps), the four forward-mode entries with P = 1 and P = 3 directions (the bake's with and without dacid_in and with
+the primal outputs; the three packed ones once more shifted), and the four host chains, whose float64 outputs compare as raw
+64-bit words."""
 import argparse
 import ctypes
 import math
@@ -44,7 +48,9 @@ def child(root, path):
     import torch
     import lithographysimulator_amd as L
     from lithographysimulator_amd import _native as nat
+    from lithographysimulator_amd import calibrate as cal
     from lithographysimulator_amd import peb
+    from lithographysimulator_amd import tangent as tan
     package = os.path.join(os.path.abspath(root), "lithographysimulator_amd")
     assert os.path.dirname(os.path.abspath(L.__file__)) == package, L.__file__
     assert os.path.abspath(nat.LIB_PATH) == os.path.join(package, "lib", "liblitho_abbe.so"), nat.LIB_PATH
@@ -54,7 +60,7 @@ def child(root, path):
     def keep(name, t):
         a = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
         assert name not in res and a.size, name                                      # no vacuous equality
-        res[name] = a.view(np.uint32) if a.dtype == np.float32 else a
+        res[name] = a.view(np.uint32) if a.dtype == np.float32 else a.view(np.uint64) if a.dtype == np.float64 else a
 
     def put(a):
         return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
@@ -184,6 +190,69 @@ def child(root, path):
                     keep(f"{tag}/peb_bake_vjp/{name}/checkpoint{c}/grad_acid_in", gh)
                     keep(f"{tag}/peb_bake_vjp/{name}/checkpoint{c}/grad_quencher_in", gq)
             keep(f"{tag}/peb_bake_vjp/dose only/grad_acid_in", peb.bakeGradient(acid, resists["finite"], THICK, H, gradAcidDose=cot[2], steps=STEPS)[0])
+
+            # the parameter gradients: litho_peb_expose_vjp_params, litho_peb_bake_vjp_params, litho_develop_rate_vjp_params and the
+            # two host chains litho_peb_param_chain, litho_develop_rate_param_chain
+            keep(f"{tag}/peb_expose_vjp_params", cal.exposureParameterGradient(V, 0.9, DOSES, ga))
+            for name, r in resists.items():
+                for c in (1, None, STEPS):
+                    gh, gq, gstep = cal.bakeStepGradient(acid, r, THICK, H, cot[0], cot[1], cot[2], steps=STEPS, checkpointEvery=c)
+                    keep(f"{tag}/peb_bake_vjp_params/{name}/checkpoint{c}/grad_acid_in", gh)
+                    keep(f"{tag}/peb_bake_vjp_params/{name}/checkpoint{c}/grad_quencher_in", gq)
+                    keep(f"{tag}/peb_bake_vjp_params/{name}/checkpoint{c}/grad_step", gstep)
+                keep(f"{tag}/peb_param_chain/{name}", cal.bakeParameterChain(gstep, r, THICK, H, D, STEPS))
+            for q, m_th in LAWS:
+                r, law = mack(q, m_th), f"q{q}-mth{m_th}"
+                g = gs.clone()
+                g[torch.isnan(L.developmentRate(V, r, THICK, H, DOSES))] = float("nan")
+                sums = cal._rate_sums("parity", V, DOSES, r.C, r, THICK, g)
+                keep(f"{tag}/develop_rate_vjp_params/{law}", sums)
+                keep(f"{tag}/develop_rate_param_chain/{law}", cal.rateParameterChain(sums, r, THICK))
+
+            # forward mode: litho_peb_expose_jvp, litho_peb_bake_jvp, litho_develop_rate_jvp, litho_develop_time_jvp and the two host
+            # chains litho_peb_param_tangent, litho_develop_rate_param_tangent; P = 1 and P = 3
+            for P in (1, 3):
+                dC = rng.uniform(-1.0, 1.0, P)
+                dI, dh = uniform(P, *vol), uniform(P, *vol)
+                keep(f"{tag}/peb_expose_jvp/P{P}", tan.exposeAcidTangent(V, 0.9, DOSES, dC, dI))
+                keep(f"{tag}/peb_expose_jvp/P{P}/no dImage", tan.exposeAcidTangent(V, 0.9, DOSES, dC))
+                out, dCc = shifted((P,) + gained), (ctypes.c_double * P)(*dC)
+                nat.check(lib.litho_peb_expose_jvp(nat.ptr(shifted(V)), B, D, n, g3, nd, 0.9, P, dCc, nat.ptr(shifted(dI)), nat.ptr(out), st),
+                          "litho_peb_expose_jvp")
+                keep(f"{tag}/peb_expose_jvp/P{P}/shifted", out)
+                dq, dpar = rng.uniform(-1.0, 1.0, P), rng.uniform(-1.0, 1.0, (P, 5))
+                for name, r in resists.items():
+                    dstep = tan.bakeParameterTangent(dpar, r, THICK, H, D, STEPS)
+                    keep(f"{tag}/peb_param_tangent/{name}/P{P}", dstep)
+                    outs = tan.bakeTangent(acid_nan, r, THICK, H, dAcid=dh, dQuencher=dq, dStep=dstep, steps=STEPS, returnPrimal=True)
+                    for what, v in zip(("dacid", "dquencher", "dacid_dose", "acid", "quencher", "acid_dose"), outs):
+                        keep(f"{tag}/peb_bake_jvp/{name}/P{P}/primal/{what}", v)
+                    outs = tan.bakeTangent(acid, r, THICK, H, dQuencher=dq, dStep=dstep, steps=STEPS)
+                    for what, v in zip(("dacid", "dquencher", "dacid_dose"), outs):
+                        keep(f"{tag}/peb_bake_jvp/{name}/P{P}/no dacid_in/{what}", v)
+                dpar7 = rng.uniform(-1.0, 1.0, (P, 7))
+                for q, m_th in LAWS:
+                    r, law = mack(q, m_th), f"q{q}-mth{m_th}"
+                    dphi = tan.rateParameterTangent(dpar7, r, THICK, D)
+                    keep(f"{tag}/develop_rate_param_tangent/{law}/P{P}", dphi)
+                    keep(f"{tag}/develop_rate_jvp/{law}/P{P}", tan.developmentRateTangent(V, r, THICK, DOSES, dX=dI, dPhi=dphi))
+                    keep(f"{tag}/develop_rate_jvp/{law}/P{P}/no dX", tan.developmentRateTangent(V, r, THICK, DOSES, dPhi=dphi))
+                    out, phi = shifted((P,) + gained), dphi.contiguous().to(dev)
+                    nat.check(lib.litho_develop_rate_jvp(nat.ptr(shifted(V)), B, D, n, g3, nd, r.C, r.rMax, r.rMin, r.q, r.mTh, r.surfaceRate,
+                                                         r.surfaceDepth, THICK, P, nat.ptr(shifted(dI)), nat.ptr(phi), nat.ptr(out), st),
+                              "litho_develop_rate_jvp")
+                    keep(f"{tag}/develop_rate_jvp/{law}/P{P}/shifted", out)
+                ds = uniform(P, *vol)
+                ds[:, ~(torch.isfinite(s) & (s > 0))] = float("nan")                     # ignored on the walls
+                dT, launches = tan.developmentTimeTangent(s, T, ds, THICK, H, returnLaunches=True)
+                keep(f"{tag}/develop_time_jvp/P{P}/dT", dT)
+                keep(f"{tag}/develop_time_jvp/P{P}/launches", [launches])
+                nbytes = int(lib.litho_develop_jvp_work_bytes(B, D, n, P, 1024))
+                work, out, count = torch.empty(nbytes, dtype=torch.uint8, device=dev), shifted((P,) + vol), ctypes.c_int(-1)
+                nat.check(lib.litho_develop_time_jvp(nat.ptr(shifted(s)), nat.ptr(shifted(T)), nat.ptr(shifted(ds)), B, D, n, P, THICK, H, 1024,
+                                                     nat.ptr(out), nat.ptr(work), nbytes, ctypes.byref(count), st), "litho_develop_time_jvp")
+                keep(f"{tag}/develop_time_jvp/P{P}/shifted/dT", out)
+                keep(f"{tag}/develop_time_jvp/P{P}/shifted/launches", [count.value])
     torch.cuda.synchronize()
     np.savez(path, **res)
 
