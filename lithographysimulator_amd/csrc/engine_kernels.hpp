@@ -820,22 +820,40 @@ struct SizeOps {
 };
 const SizeOps* size_ops(int log2n);      // nullptr outside 4..14
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) is needed once per kernel and device, not once per launch
-// (a config-3 image is ~23,000 launches).  One LdsOnce lives in each launcher; bit d = done on device d.
-struct LdsOnce {
-    unsigned done = 0;
-};
-template <typename K>
-static hipError_t set_lds(LdsOnce& once, K kern, size_t bytes)
+// The dynamic-LDS opt-in is needed once per kernel and device, not once per launch (a config-3 image is ~23,000 launches):
+// lds_done<Kern>() is the kernel's own word for lds_opt_in (bit d = done on device d).  Keyed on the kernel alone: two call
+// sites of one kernel share the word, two kernels never do.
+template <auto Kern>
+inline unsigned& lds_done()
 {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static unsigned done = 0;
+    return done;
+}
+// What a launch leaves for litho_abbe_last_kernels: the arguments of note_kernel (pass 0 = x, 1 = y; the format spelt as
+// rocprofv3 prints the kernel).  LaunchNote{} = a launch outside the Abbe loop, not recorded.
+struct LaunchNote {
+    int pass = -1;
+    const char* fmt = nullptr;
+    int a0 = 0, a1 = 0, a2 = 0, a3 = 0;
+};
+// THE kernel launch of the engine (engine_kernels.hpp and wave_kernels.hpp): opt-in, launch, note, hipGetLastError().
+template <auto Kern, typename... Args>
+inline hipError_t launch_kernel(dim3 grid, dim3 block, size_t lds, hipStream_t st, const LaunchNote& n, const Args&... args)
+{
+    hipError_t e = lds_opt_in(lds_done<Kern>(), (const void*)Kern, lds);
     if (e != hipSuccess) return e;
-    const unsigned bit = 1u << (dev & 31);
-    if (__atomic_load_n(&once.done, __ATOMIC_ACQUIRE) & bit) return hipSuccess;
-    e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess) __atomic_fetch_or(&once.done, bit, __ATOMIC_RELEASE);
-    return e;
+    hipLaunchKernelGGL(Kern, grid, block, lds, st, args...);
+    if (n.fmt) note_kernel(n.pass, n.fmt, n.a0, n.a1, n.a2, n.a3);
+    return hipGetLastError();
+}
+// A launch with a weighted twin: KW is K's instantiation with the trailing `const float*` pack, it takes the weights behind
+// K's arguments and runs when there are weights; grid, block and LDS are the same by construction.
+template <auto K, auto KW, typename... Args>
+inline hipError_t launch_twin(const float* wts, dim3 grid, dim3 block, size_t lds, hipStream_t st, const LaunchNote& n,
+                              const LaunchNote& nw, const Args&... args)
+{
+    return wts ? launch_kernel<KW>(grid, block, lds, st, nw, args..., wts)
+               : launch_kernel<K>(grid, block, lds, st, n, args...);
 }
 
 // defined (and explicitly instantiated for 8 <= LOG2N <= 13) in instw_*.hip
@@ -855,30 +873,25 @@ struct SizeImpl {
     static hipError_t xa(const float2* P, const float2* M, const int* shifts, const float* wts, float2* T, const float2* tw,
                          const PassGeom& g, int nb, int chunk, hipStream_t st)
     {
+        // L == 1: grid.x padded to a multiple of 32 for the XCD-aware row mapping in the kernel
+        const int wrows = (g.rows + RP - 1) / RP;              // rows (RP = 2: row pairs) to hand out
+        const dim3 grid(LC::L == 1 ? (wrows + 31) / 32 * 32 : (wrows + LC::L - 1) / LC::L, (nb + chunk - 1) / chunk);
         if (wts) {
             if constexpr (RP == 1) {
-                static LdsOnce once_wt;
-                auto kern = k_xpass_abbe<LOG2N, RL, PRUNED, NP, 1, const float*>;
-                hipError_t e = set_lds(once_wt, kern, LC::LDS_BYTES);
-                if (e != hipSuccess) return e;
-                dim3 grid(LC::L == 1 ? (g.rows + 31) / 32 * 32 : (g.rows + LC::L - 1) / LC::L, (nb + chunk - 1) / chunk);
-                hipLaunchKernelGGL(kern, grid, dim3(LC::THREADS), LC::LDS_BYTES, st, P, M, shifts, T, tw, g, nb, chunk, wts);
-                note_kernel(0, PRUNED ? "k_xpass_abbe<%d, %d, true, %d, 1, float const*>" : "k_xpass_abbe<%d, %d, false, %d, 1, float const*>", LOG2N, RL, NP);
-                return hipGetLastError();
+                return launch_kernel<k_xpass_abbe<LOG2N, RL, PRUNED, NP, 1, const float*>>(
+                    grid, dim3(LC::THREADS), LC::LDS_BYTES, st,
+                    LaunchNote{0, PRUNED ? "k_xpass_abbe<%d, %d, true, %d, 1, float const*>"
+                                         : "k_xpass_abbe<%d, %d, false, %d, 1, float const*>", LOG2N, RL, NP},
+                    P, M, shifts, T, tw, g, nb, chunk, wts);
             } else {
                 return hipErrorInvalidValue;                   // (a weighted call never plans row pairs)
             }
         }
-        static LdsOnce once;
-        auto kern = k_xpass_abbe<LOG2N, RL, PRUNED, NP, RP>;
-        hipError_t e = set_lds(once, kern, LC::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        // L == 1: grid.x padded to a multiple of 32 for the XCD-aware row mapping in the kernel
-        const int wrows = (g.rows + RP - 1) / RP;              // rows (RP = 2: row pairs) to hand out
-        dim3 grid(LC::L == 1 ? (wrows + 31) / 32 * 32 : (wrows + LC::L - 1) / LC::L, (nb + chunk - 1) / chunk);
-        hipLaunchKernelGGL(kern, grid, dim3(LC::THREADS), LC::LDS_BYTES, st, P, M, shifts, T, tw, g, nb, chunk);
-        note_kernel(0, PRUNED ? "k_xpass_abbe<%d, %d, true, %d, %d>" : "k_xpass_abbe<%d, %d, false, %d, %d>", LOG2N, RL, NP, RP);   // as rocprofv3 prints it
-        return hipGetLastError();
+        return launch_kernel<k_xpass_abbe<LOG2N, RL, PRUNED, NP, RP>>(
+            grid, dim3(LC::THREADS), LC::LDS_BYTES, st,
+            LaunchNote{0, PRUNED ? "k_xpass_abbe<%d, %d, true, %d, %d>"      // as rocprofv3 prints it
+                                 : "k_xpass_abbe<%d, %d, false, %d, %d>", LOG2N, RL, NP, RP},
+            P, M, shifts, T, tw, g, nb, chunk);
     }
     template <int RL>
     static hipError_t xa_np(int np, const float2* P, const float2* M, const int* shifts, const float* wts, float2* T, const float2* tw,
@@ -906,52 +919,32 @@ struct SizeImpl {
                 return xa<-1, false, 1>(P, M, shifts, wts, T, tw, g, nb, chunk, st);
         }
     }
+    // k_xpass<LOG2N, SIGN, Loader>: `batch` transforms of g.rows rows each; what a row is made of is the loader's business
+    template <int SIGN, typename Loader>
+    static hipError_t xl(const Loader& ld, float2* T, const float2* tw, const PassGeom& g, int batch, hipStream_t st,
+                         const LaunchNote& n = {})
+    {
+        return launch_kernel<k_xpass<LOG2N, SIGN, Loader>>(
+            dim3((g.rows + LC::L - 1) / LC::L, batch), dim3(LC::THREADS), LC::LDS_BYTES, st, n, ld, T, tw, g);
+    }
     static hipError_t xpass_general(const AbbeLoader& ld, const float* wts, float2* T, const float2* tw, const PassGeom& g, int nb,
                                     hipStream_t st)
     {
         if (wts) {
-            static LdsOnce once_wt;
-            auto kern = k_xpass<LOG2N, +1, AbbeLoaderW>;
-            hipError_t e = set_lds(once_wt, kern, LC::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            AbbeLoaderW lw{ld, wts, 1.f, 0.f};
-            hipLaunchKernelGGL(kern, dim3((g.rows + LC::L - 1) / LC::L, nb), dim3(LC::THREADS), LC::LDS_BYTES, st, lw, T,
-                               tw, g);
-            note_kernel(0, "k_xpass<%d, 1, litho::AbbeLoaderW>", LOG2N);
-            return hipGetLastError();
+            return xl<+1>(AbbeLoaderW{ld, wts, 1.f, 0.f}, T, tw, g, nb, st,
+                          LaunchNote{0, "k_xpass<%d, 1, litho::AbbeLoaderW>", LOG2N});
         }
-        static LdsOnce once;
-        auto kern = k_xpass<LOG2N, +1, AbbeLoader>;
-        hipError_t e = set_lds(once, kern, LC::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3((g.rows + LC::L - 1) / LC::L, nb), dim3(LC::THREADS), LC::LDS_BYTES, st, ld, T,
-                           tw, g);
-        note_kernel(0, "k_xpass<%d, 1, litho::AbbeLoader>", LOG2N);
-        return hipGetLastError();
+        return xl<+1>(ld, T, tw, g, nb, st, LaunchNote{0, "k_xpass<%d, 1, litho::AbbeLoader>", LOG2N});
     }
     static hipError_t xpass_split(const float2* P, const float2* M, const int* shifts, const float* wts, float2* T, const float2* tw,
                                   const PassGeom& g, int nb, int chunk, hipStream_t st)
     {
         if constexpr (LOG2N == 13) {
             using LH = Launch<LOG2N - 1>;
-            if (wts) {
-                static LdsOnce once_wt;
-                auto kern = k_xpass_split<LOG2N, const float*>;
-                hipError_t e = set_lds(once_wt, kern, LH::LDS_BYTES);
-                if (e != hipSuccess) return e;
-                dim3 grid((g.rows + 31) / 32 * 32, (nb + chunk - 1) / chunk);
-                hipLaunchKernelGGL(kern, grid, dim3(LH::THREADS), LH::LDS_BYTES, st, P, M, shifts, T, tw, g, nb, chunk, wts);
-                note_kernel(0, "k_xpass_split<%d, float const*>", LOG2N);
-                return hipGetLastError();
-            }
-            static LdsOnce once;
-            auto kern = k_xpass_split<LOG2N>;
-            hipError_t e = set_lds(once, kern, LH::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            dim3 grid((g.rows + 31) / 32 * 32, (nb + chunk - 1) / chunk);
-            hipLaunchKernelGGL(kern, grid, dim3(LH::THREADS), LH::LDS_BYTES, st, P, M, shifts, T, tw, g, nb, chunk);
-            note_kernel(0, "k_xpass_split<%d>", LOG2N);
-            return hipGetLastError();
+            return launch_twin<k_xpass_split<LOG2N>, k_xpass_split<LOG2N, const float*>>(
+                wts, dim3((g.rows + 31) / 32 * 32, (nb + chunk - 1) / chunk), dim3(LH::THREADS), LH::LDS_BYTES, st,
+                LaunchNote{0, "k_xpass_split<%d>", LOG2N}, LaunchNote{0, "k_xpass_split<%d, float const*>", LOG2N},
+                P, M, shifts, T, tw, g, nb, chunk);
         } else {
             return hipErrorNotSupported;
         }
@@ -965,37 +958,21 @@ struct SizeImpl {
     static hipError_t xpass_real_fwd(const RealImageLoader& ld, float2* T, const float2* tw, const PassGeom& g,
                                      hipStream_t st)
     {
-        static LdsOnce once;
-        auto kern = k_xpass<LOG2N, -1, RealImageLoader>;
-        hipError_t e = set_lds(once, kern, LC::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3((g.rows + LC::L - 1) / LC::L, 1), dim3(LC::THREADS), LC::LDS_BYTES, st, ld, T, tw,
-                           g);
-        return hipGetLastError();
+        return xl<-1>(ld, T, tw, g, 1, st);
     }
     static hipError_t xpass_cplx_fwd(const ComplexImageLoader& ld, float2* T, const float2* tw, const PassGeom& g,
                                      hipStream_t st)
     {
-        static LdsOnce once;
-        auto kern = k_xpass<LOG2N, -1, ComplexImageLoader>;
-        hipError_t e = set_lds(once, kern, LC::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3((g.rows + LC::L - 1) / LC::L, 1), dim3(LC::THREADS), LC::LDS_BYTES, st, ld, T, tw,
-                           g);
-        return hipGetLastError();
+        return xl<-1>(ld, T, tw, g, 1, st);
     }
     template <int RL, bool PRUNED>
     static hipError_t ya(const float2* T, float* slab, const float2* tw, const PassGeom& g, int nb, int planes, int G,
                          int gstride, hipStream_t st)
     {
-        static LdsOnce once;
-        auto kern = k_ypass_acc<LOG2N, RL, PRUNED>;
-        hipError_t e = set_lds(once, kern, LC::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3((g.nt + LC::L - 1) / LC::L, planes * G), dim3(LC::THREADS), LC::LDS_BYTES, st, T,
-                           slab, tw, g, nb, G, gstride);
-        note_kernel(1, PRUNED ? "k_ypass_acc<%d, %d, true>" : "k_ypass_acc<%d, %d, false>", LOG2N, RL);
-        return hipGetLastError();
+        return launch_kernel<k_ypass_acc<LOG2N, RL, PRUNED>>(
+            dim3((g.nt + LC::L - 1) / LC::L, planes * G), dim3(LC::THREADS), LC::LDS_BYTES, st,
+            LaunchNote{1, PRUNED ? "k_ypass_acc<%d, %d, true>" : "k_ypass_acc<%d, %d, false>", LOG2N, RL},
+            T, slab, tw, g, nb, G, gstride);
     }
     static hipError_t ypass_acc(int variant, const float2* T, float* slab, const float2* tw, const PassGeom& g, int nb,
                                 int planes, int G, int gstride, hipStream_t st)
@@ -1009,39 +986,26 @@ struct SizeImpl {
     }
     static hipError_t xpass_field_inv(const FieldLoader& ld, float2* T, const float2* tw, const PassGeom& g, hipStream_t st)
     {
-        static LdsOnce once;
-        auto kern = k_xpass<LOG2N, +1, FieldLoader>;
-        hipError_t e = set_lds(once, kern, LC::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3((g.rows + LC::L - 1) / LC::L, 1), dim3(LC::THREADS), LC::LDS_BYTES, st, ld, T, tw, g);
-        return hipGetLastError();
+        return xl<+1>(ld, T, tw, g, 1, st);
     }
     static hipError_t ypass_addreal(const float2* T, float* img, float scale, const float2* tw, const PassGeom& g,
                                     hipStream_t st)
     {
-        static LdsOnce once;
-        auto kern = k_ypass_addreal<LOG2N>;
-        hipError_t e = set_lds(once, kern, LC::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3((g.nt + LC::L - 1) / LC::L), dim3(LC::THREADS), LC::LDS_BYTES, st, T, img, scale, tw, g);
-        return hipGetLastError();
+        return launch_kernel<k_ypass_addreal<LOG2N>>(
+            dim3((g.nt + LC::L - 1) / LC::L), dim3(LC::THREADS), LC::LDS_BYTES, st, LaunchNote{}, T, img, scale, tw, g);
     }
     static hipError_t xpass_w64(const float2* P, const float2* M, const int* shifts, float2* T, const float2* tw,
                                 const PassGeom& g, int nb, hipStream_t st)
     {
         if constexpr (LOG2N == 12) {
-            static LdsOnce once;
             constexpr size_t lds = 4 * Wave4096::LDS_FLOATS * sizeof(float);
-            auto kern = k_xpass_w64<LOG2N>;
-            hipError_t e = set_lds(once, kern, lds);
-            if (e != hipSuccess) return e;
             const int items = ((g.rows + 3) / 4) * nb;
             const int res = 2 * device_cus();                        // 2 resident workgroups per CU
             const int wgs = items < res ? items : res;
             const int per = (items + wgs - 1) / wgs;
-            hipLaunchKernelGGL(kern, dim3((items + per - 1) / per), dim3(256), lds, st, P, M, shifts, T, tw, g, nb, per);
-            note_kernel(0, "k_xpass_w64<%d>", LOG2N);
-            return hipGetLastError();
+            return launch_kernel<k_xpass_w64<LOG2N>>(
+                dim3((items + per - 1) / per), dim3(256), lds, st, LaunchNote{0, "k_xpass_w64<%d>", LOG2N},
+                P, M, shifts, T, tw, g, nb, per);
         } else {
             return hipErrorNotSupported;
         }
@@ -1054,24 +1018,16 @@ struct SizeImpl {
         if constexpr (LOG2N >= 8 && LOG2N <= 13) return launch_ypass_wave<LOG2N>(T, slab, tw, g, nb, planes, G, gstride, st);
         else return hipErrorNotSupported;
     }
+    template <int SIGN>
+    static hipError_t yf(const float2* T, float2* field, const float2* tw, const PassGeom& g, hipStream_t st)
+    {
+        return launch_kernel<k_ypass_field<LOG2N, SIGN>>(
+            dim3((g.nt + LC::L - 1) / LC::L), dim3(LC::THREADS), LC::LDS_BYTES, st, LaunchNote{}, T, field, tw, g);
+    }
     static hipError_t ypass_field(int sign, const float2* T, float2* field, const float2* tw, const PassGeom& g,
                                   hipStream_t st)
     {
-        dim3 grid((g.nt + LC::L - 1) / LC::L);
-        if (sign > 0) {
-            static LdsOnce once;
-            auto kern = k_ypass_field<LOG2N, +1>;
-            hipError_t e = set_lds(once, kern, LC::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, grid, dim3(LC::THREADS), LC::LDS_BYTES, st, T, field, tw, g);
-        } else {
-            static LdsOnce once;
-            auto kern = k_ypass_field<LOG2N, -1>;
-            hipError_t e = set_lds(once, kern, LC::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, grid, dim3(LC::THREADS), LC::LDS_BYTES, st, T, field, tw, g);
-        }
-        return hipGetLastError();
+        return sign > 0 ? yf<+1>(T, field, tw, g, st) : yf<-1>(T, field, tw, g, st);
     }
 };
 

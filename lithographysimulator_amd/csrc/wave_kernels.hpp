@@ -808,152 +808,82 @@ __global__ __launch_bounds__(256, 2) void k_xpass_rect(
     }
 }
 
+// FULL: the coarse-grid transforms (N = pn), every bin kept
+template <int LOG2N, bool FULL>
+static hipError_t launch_xpass_rect_as(const float2* P, const float2* M, const int* shifts, const float* wts, float2* T,
+                                       const float2* tw, const PassGeom& g, int nb, int chunk, hipStream_t st)
+{
+    constexpr size_t lds = 4 * WaveSq<6>::LDS_FLOATS * sizeof(float);
+    constexpr int NL = 4096 >> LOG2N;
+    const int groups = (g.rows + NL - 1) / NL;
+    return launch_twin<k_xpass_rect<LOG2N, FULL>, k_xpass_rect<LOG2N, FULL, const float*>>(
+        wts, dim3((groups + 3) / 4, (nb + chunk - 1) / chunk), dim3(256), lds, st,
+        LaunchNote{0, FULL ? "k_xpass_rect<%d, true>" : "k_xpass_rect<%d, false>", LOG2N},
+        LaunchNote{0, FULL ? "k_xpass_rect<%d, true, float const*>" : "k_xpass_rect<%d, false, float const*>", LOG2N},
+        P, M, shifts, T, tw, g, nb, chunk);
+}
+
 template <int LOG2N>
 hipError_t launch_xpass_rect(const float2* P, const float2* M, const int* shifts, const float* wts, float2* T, const float2* tw,
                              const PassGeom& g, int nb, int chunk, hipStream_t st)
 {
     if constexpr (LOG2N >= 9 && LOG2N <= 11) {
         if (g.tcl != 3) return hipErrorNotSupported;
-        static LdsOnce once;
-        constexpr size_t lds = 4 * WaveSq<6>::LDS_FLOATS * sizeof(float);
-        constexpr int NL = 4096 >> LOG2N;
-        const int groups = (g.rows + NL - 1) / NL;
-        const dim3 grid((groups + 3) / 4, (nb + chunk - 1) / chunk);
-        if (wts) {
-            if (g.N == g.pn) {
-                static LdsOnce once_full_wt;
-                auto kern = k_xpass_rect<LOG2N, true, const float*>;
-                hipError_t e = set_lds(once_full_wt, kern, lds);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, P, M, shifts, T, tw, g, nb, chunk, wts);
-                note_kernel(0, "k_xpass_rect<%d, true, float const*>", LOG2N);
-                return hipGetLastError();
-            }
-            static LdsOnce once_wt;
-            auto kern = k_xpass_rect<LOG2N, false, const float*>;
-            hipError_t e = set_lds(once_wt, kern, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, P, M, shifts, T, tw, g, nb, chunk, wts);
-            note_kernel(0, "k_xpass_rect<%d, false, float const*>", LOG2N);
-            return hipGetLastError();
-        }
-        if (g.N == g.pn) {
-            static LdsOnce once_full;
-            auto kern = k_xpass_rect<LOG2N, true>;
-            hipError_t e = set_lds(once_full, kern, lds);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, P, M, shifts, T, tw, g, nb, chunk);
-            note_kernel(0, "k_xpass_rect<%d, true>", LOG2N);
-            return hipGetLastError();
-        }
-        auto kern = k_xpass_rect<LOG2N>;
-        hipError_t e = set_lds(once, kern, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, P, M, shifts, T, tw, g, nb, chunk);
-        note_kernel(0, "k_xpass_rect<%d, false>", LOG2N);
-        return hipGetLastError();
+        return g.N == g.pn ? launch_xpass_rect_as<LOG2N, true>(P, M, shifts, wts, T, tw, g, nb, chunk, st)
+                           : launch_xpass_rect_as<LOG2N, false>(P, M, shifts, wts, T, tw, g, nb, chunk, st);
     } else {
         return hipErrorNotSupported;
     }
 }
 
-template <int LOG2N, int TC>
-static hipError_t launch_ypass_wave_tc(const float2* T, float* slab, const float2* tw, const PassGeom& g, int nb, int planes, int G,
-                     int gstride, hipStream_t st)
+// k_ypass_rect with GW groups of a column block in one 256 GW-thread workgroup
+template <int LOG2N, int TC, bool FULL, int GW>
+static hipError_t launch_ypass_rect(const float2* T, float* slab, const float2* tw, const PassGeom& g, int nb, int planes,
+                                    int G, int gstride, hipStream_t st)
 {
     constexpr size_t lds4 = 4 * WaveSq<6>::LDS_FLOATS * sizeof(float);       // four waves, one 64 x 65 matrix each
-    if (g.N == g.pn) {                                  // coarse-grid transforms (N = pn): every bin kept
-        if constexpr (LOG2N == 12) {
-            static LdsOnce once;
-            constexpr size_t ldsf = lds4 + (size_t)WaveSq<6>::TW_LDS_FLOAT2 * sizeof(float2);     // + the lane-twiddle table
-            auto kern = k_ypass_wave<LOG2N, TC, true>;
-            hipError_t e = set_lds(once, kern, ldsf);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, dim3(wave_grid_x<TC, 4>(g.pn), planes * G), dim3(256), ldsf, st, T, slab, tw, g, nb, G,
-                               gstride);
-            note_kernel(1, "k_ypass_wave<%d, %d, true>", LOG2N, TC);
-            return hipGetLastError();
-        } else if constexpr (LOG2N >= 8 && LOG2N <= 11) {
-            constexpr int NL = 4096 >> LOG2N;
-            if constexpr (NL <= TC || NL == 2 * TC) {
-                if (g.gcombine && G % 2 == 0) {             // both groups of a column block in one 512-thread workgroup
-                    static LdsOnce once2;
-                    auto kern2 = k_ypass_rect<LOG2N, TC, true, 2>;
-                    hipError_t e2 = set_lds(once2, kern2, 2 * lds4);
-                    if (e2 != hipSuccess) return e2;
-                    hipLaunchKernelGGL(kern2, dim3(wave_grid_x<TC, 4 * NL>(g.pn), planes * (G / 2)), dim3(512), 2 * lds4, st,
-                                       T, slab, tw, g, nb, G, gstride);
-                    note_kernel(1, "k_ypass_rect<%d, %d, true, 2>", LOG2N, TC);
-                    return hipGetLastError();
-                }
-                static LdsOnce once;
-                auto kern = k_ypass_rect<LOG2N, TC, true>;
-                hipError_t e = set_lds(once, kern, lds4);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(kern, dim3(wave_grid_x<TC, 4 * NL>(g.pn), planes * G), dim3(256), lds4, st, T, slab, tw,
-                                   g, nb, G, gstride);
-                note_kernel(1, "k_ypass_rect<%d, %d, true, 1>", LOG2N, TC);
-                return hipGetLastError();
-            }
+    constexpr int NL = 4096 >> LOG2N;                                        // columns per wave
+    return launch_kernel<k_ypass_rect<LOG2N, TC, FULL, GW>>(
+        dim3(wave_grid_x<TC, 4 * NL>(g.pn), planes * (G / GW)), dim3(256 * GW), GW * lds4, st,
+        LaunchNote{1, FULL ? "k_ypass_rect<%d, %d, true, %d>" : "k_ypass_rect<%d, %d, false, %d>", LOG2N, TC, GW},
+        T, slab, tw, g, nb, G, gstride);
+}
+
+// FULL: coarse-grid transforms (N = pn), every bin kept
+template <int LOG2N, int TC, bool FULL>
+static hipError_t launch_ypass_wave_tc(const float2* T, float* slab, const float2* tw, const PassGeom& g, int nb, int planes,
+                                       int G, int gstride, hipStream_t st)
+{
+    // which family: from LOG2N, TC and FULL here, g.rect_off and g.gcombine below
+    constexpr int NL = 4096 >> LOG2N;                           // columns per wave of k_ypass_rect
+    constexpr bool RECT = FULL ? (LOG2N >= 8 && LOG2N <= 11 && (NL <= TC || NL == 2 * TC))
+                               : (LOG2N >= 9 && LOG2N <= 11 && NL <= TC);
+    constexpr bool WAVE = FULL ? LOG2N == 12 : (LOG2N >= 10 && LOG2N <= 12);
+    constexpr bool PAIR = !FULL && LOG2N == 13;
+    if constexpr (RECT) {
+        // FULL always returns from here.  Only !FULL with g.rect_off falls through to what follows: LOG2N 10 - 11 to
+        // k_ypass_wave, LOG2N 9 to hipErrorNotSupported
+        if (FULL || !g.rect_off) {
+            return g.gcombine && G % 2 == 0               // both groups of a column block in one 512-thread workgroup
+                       ? launch_ypass_rect<LOG2N, TC, FULL, 2>(T, slab, tw, g, nb, planes, G, gstride, st)
+                       : launch_ypass_rect<LOG2N, TC, FULL, 1>(T, slab, tw, g, nb, planes, G, gstride, st);
         }
-        return hipErrorNotSupported;
     }
-    if constexpr (LOG2N == 13) {
-        static LdsOnce once;
-        auto kern = k_ypass_pair<LOG2N, TC>;
-        hipError_t e = set_lds(once, kern, lds4);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(wave_grid_x<TC, 2>(g.pn), planes * G), dim3(256), lds4, st, T, slab, tw, g, nb, G,
-                           gstride);
-        note_kernel(1, "k_ypass_pair<%d, %d>", LOG2N, TC);
-            return hipGetLastError();
-    } else if constexpr (LOG2N >= 9 && LOG2N <= 11) {
-        constexpr int NL = 4096 >> LOG2N;                       // columns per wave of k_ypass_rect
-        if constexpr (NL <= TC) {
-            if (!g.rect_off) {
-                if (g.gcombine && G % 2 == 0) {
-                    static LdsOnce once2;
-                    auto kern2 = k_ypass_rect<LOG2N, TC, false, 2>;
-                    hipError_t e2 = set_lds(once2, kern2, 2 * lds4);
-                    if (e2 != hipSuccess) return e2;
-                    hipLaunchKernelGGL(kern2, dim3(wave_grid_x<TC, 4 * NL>(g.pn), planes * (G / 2)), dim3(512), 2 * lds4, st,
-                                       T, slab, tw, g, nb, G, gstride);
-                    note_kernel(1, "k_ypass_rect<%d, %d, false, 2>", LOG2N, TC);
-                    return hipGetLastError();
-                }
-                static LdsOnce once;
-                auto kern = k_ypass_rect<LOG2N, TC>;
-                hipError_t e = set_lds(once, kern, lds4);
-                if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(kern, dim3(wave_grid_x<TC, 4 * NL>(g.pn), planes * G), dim3(256), lds4, st, T, slab, tw,
-                                   g, nb, G, gstride);
-                note_kernel(1, "k_ypass_rect<%d, %d, false, 1>", LOG2N, TC);
-                return hipGetLastError();
-            }
-        }
-        if constexpr (LOG2N >= 10) {
-            static LdsOnce once;
-            using WS = WaveShape<LOG2N>;
-            auto kern = k_ypass_wave<LOG2N, TC>;
-            hipError_t e = set_lds(once, kern, WS::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, dim3(wave_grid_x<TC, WS::COLS>(g.pn), planes * G), dim3(WS::THREADS),
-                               WS::LDS_BYTES, st, T, slab, tw, g, nb, G, gstride);
-            note_kernel(1, "k_ypass_wave<%d, %d, false>", LOG2N, TC);
-            return hipGetLastError();
-        } else {
-            return hipErrorNotSupported;
-        }
-    } else if constexpr (LOG2N == 12) {
-        static LdsOnce once;
+    if constexpr (WAVE) {
         using WS = WaveShape<LOG2N>;
-        auto kern = k_ypass_wave<LOG2N, TC>;
-        hipError_t e = set_lds(once, kern, WS::LDS_BYTES);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(wave_grid_x<TC, WS::COLS>(g.pn), planes * G), dim3(WS::THREADS), WS::LDS_BYTES,
-                           st, T, slab, tw, g, nb, G, gstride);
-        note_kernel(1, "k_ypass_wave<%d, %d, false>", LOG2N, TC);
-        return hipGetLastError();
+        // FULL: four columns per workgroup, and the lane-twiddle table behind the four 64 x 65 matrices
+        constexpr int cols = FULL ? 4 : WS::COLS, threads = FULL ? 256 : WS::THREADS;
+        constexpr size_t ldsf = 4 * WaveSq<6>::LDS_FLOATS * sizeof(float) + (size_t)WaveSq<6>::TW_LDS_FLOAT2 * sizeof(float2);
+        constexpr size_t lds = FULL ? ldsf : WS::LDS_BYTES;
+        return launch_kernel<k_ypass_wave<LOG2N, TC, FULL>>(
+            dim3(wave_grid_x<TC, cols>(g.pn), planes * G), dim3(threads), lds, st,
+            LaunchNote{1, FULL ? "k_ypass_wave<%d, %d, true>" : "k_ypass_wave<%d, %d, false>", LOG2N, TC},
+            T, slab, tw, g, nb, G, gstride);
+    } else if constexpr (PAIR) {
+        constexpr size_t lds4 = 4 * WaveSq<6>::LDS_FLOATS * sizeof(float);
+        return launch_kernel<k_ypass_pair<LOG2N, TC>>(
+            dim3(wave_grid_x<TC, 2>(g.pn), planes * G), dim3(256), lds4, st, LaunchNote{1, "k_ypass_pair<%d, %d>", LOG2N, TC},
+            T, slab, tw, g, nb, G, gstride);
     } else {
         return hipErrorNotSupported;
     }
@@ -963,36 +893,29 @@ template <int LOG2N>
 hipError_t launch_ypass_wave(const float2* T, float* slab, const float2* tw, const PassGeom& g, int nb, int planes,
                              int G, int gstride, hipStream_t st)
 {
-    if (g.tcl == 2) return launch_ypass_wave_tc<LOG2N, 4>(T, slab, tw, g, nb, planes, G, gstride, st);
-    if (g.tcl == 3) return launch_ypass_wave_tc<LOG2N, 8>(T, slab, tw, g, nb, planes, G, gstride, st);
+    const bool full = g.N == g.pn;
+    if (g.tcl == 2) return full ? launch_ypass_wave_tc<LOG2N, 4, true>(T, slab, tw, g, nb, planes, G, gstride, st)
+                                : launch_ypass_wave_tc<LOG2N, 4, false>(T, slab, tw, g, nb, planes, G, gstride, st);
+    if (g.tcl == 3) return full ? launch_ypass_wave_tc<LOG2N, 8, true>(T, slab, tw, g, nb, planes, G, gstride, st)
+                                : launch_ypass_wave_tc<LOG2N, 8, false>(T, slab, tw, g, nb, planes, G, gstride, st);
     if constexpr (LOG2N == 12) {
-        if (g.tcl == 4 && g.N == g.pn) {                       // 16-column tiles: the cooperative-loading kernel
+        if (g.tcl == 4 && full) {                              // 16-column tiles: the cooperative-loading kernel
 #ifndef LITHO_COOP_WAVES
 #define LITHO_COOP_WAVES 4
 #endif
             constexpr int NW = LITHO_COOP_WAVES;
-            if (g.coop_dma) {
 #ifndef LITHO_COOP_DMA_WAVES                     // build-time experiment: 8 = eight waves own 64 bytes of the row (one 144 KB workgroup per CU)
 #define LITHO_COOP_DMA_WAVES 4
 #endif
-                constexpr int ND = LITHO_COOP_DMA_WAVES;
-                static LdsOnce once_dma;
-                auto kd = k_ypass_coop_dma<LOG2N, ND>;
-                hipError_t ed = set_lds(once_dma, kd, CoopDmaShape<ND>::LDS_BYTES);
-                if (ed != hipSuccess) return ed;
-                hipLaunchKernelGGL(kd, dim3(CoopDmaShape<ND>::grid_x(g.pn), planes * G), dim3(64 * ND), CoopDmaShape<ND>::LDS_BYTES, st, T,
-                                   slab, tw, g, nb, G, gstride);
-                note_kernel(1, "k_ypass_coop_dma<%d, %d>", LOG2N, ND);
-                return hipGetLastError();
+            constexpr int ND = LITHO_COOP_DMA_WAVES;
+            if (g.coop_dma) {
+                return launch_kernel<k_ypass_coop_dma<LOG2N, ND>>(
+                    dim3(CoopDmaShape<ND>::grid_x(g.pn), planes * G), dim3(64 * ND), CoopDmaShape<ND>::LDS_BYTES, st,
+                    LaunchNote{1, "k_ypass_coop_dma<%d, %d>", LOG2N, ND}, T, slab, tw, g, nb, G, gstride);
             }
-            static LdsOnce once;
-            auto kern = k_ypass_coop<LOG2N, NW>;
-            hipError_t e = set_lds(once, kern, CoopShape<NW>::LDS_BYTES);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(kern, dim3(CoopShape<NW>::grid_x(g.pn), planes * G), dim3(64 * NW), CoopShape<NW>::LDS_BYTES, st, T,
-                               slab, tw, g, nb, G, gstride);
-            note_kernel(1, "k_ypass_coop<%d, %d>", LOG2N, NW);
-            return hipGetLastError();
+            return launch_kernel<k_ypass_coop<LOG2N, NW>>(
+                dim3(CoopShape<NW>::grid_x(g.pn), planes * G), dim3(64 * NW), CoopShape<NW>::LDS_BYTES, st,
+                LaunchNote{1, "k_ypass_coop<%d, %d>", LOG2N, NW}, T, slab, tw, g, nb, G, gstride);
         }
     }
     return hipErrorNotSupported;

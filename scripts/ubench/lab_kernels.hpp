@@ -381,13 +381,9 @@ hipError_t launch_ypass_line(const float2* T, float* slab, const float2* tw, con
     if constexpr (LOG2N == 11) {
         if (g.tcl != 1 || g.N != g.pn || g.N != (1 << LOG2N)) return hipErrorNotSupported;
         using W = WaveLine2048;
-        static LdsOnce once;
         constexpr size_t lds = 4 * W::LDS_FLOATS * sizeof(float) + (WPS >= 4 ? (size_t)W::TW_LDS_FLOAT2 * sizeof(float2) : 0);
-        auto kern = k_ypass_line<LOG2N, WPS>;
-        hipError_t e = set_lds(once, kern, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3((g.pn + 3) / 4, planes * G), dim3(256), lds, st, T, slab, tw, g, nb, G, gstride);
-        return hipGetLastError();
+        return launch_kernel<k_ypass_line<LOG2N, WPS>>(dim3((g.pn + 3) / 4, planes * G), dim3(256), lds, st, LaunchNote{}, T, slab,
+                                                       tw, g, nb, G, gstride);
     } else {
         return hipErrorNotSupported;
     }

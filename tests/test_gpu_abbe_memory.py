@@ -28,7 +28,9 @@ Per call (`run` below), with options.poison left at 0 -- the arena's 0xFF is the
      still 0xFF.  Asserted for every case, planes_in_flight > 1 included;
   7  the same call again into the used arena, `out` re-filled, nothing re-poisoned: the same bits;
   8  maskFT, pupil and out at 8 mod 16, shifts and weights at 4 mod 16: the aligned call's bits;
-  9  one case of every group also runs on a side stream.
+  9  one case of every group also runs on a side stream;
+ 10  litho_abbe_last_kernels names the case's `xk` / `yk` for the part that ran last, character for character (the spelling
+     bench.py matches against rocprofv3's): the table recorded on an MI355X, which the launch layer may not change.
 
 The case list is fixed (CASES); test_every_case_plans_as_stated (no GPU) holds every entry to its comment through the dry run.
 Pupils are disks with defocus computed here in float64 (support k^2 <= (pn/4)^2, as the reference's r <= 1; one sample on each
@@ -81,58 +83,73 @@ class Case:
 SMALL = {"coarse": 2, "batch": 1, "groups": 1}
 CASES = [
     # run size below 256: radix-16 kernels, T tile 4
-    Case("16-16", 16, 16, S=3, variant=0, tile=4, wave_y=0), Case("16-32", 16, 32, S=3, variant=1, tile=4, wave_y=0),
-    Case("16-64", 16, 64, S=3, variant=2, tile=4, wave_y=0, side=True), Case("30-64 generic", 30, 64, S=4, variant=-1, tile=4, wave_y=0),
-    Case("64-128", 64, 128, S=7, variant=1, tile=4, wave_y=0),
+    Case("16-16", 16, 16, S=3, variant=0, tile=4, wave_y=0, xk="k_xpass_abbe<4, 0, true, 1, 1>", yk="k_ypass_acc<4, 0, true>"),
+    Case("16-32", 16, 32, S=3, variant=1, tile=4, wave_y=0, xk="k_xpass_abbe<5, 1, true, 1, 1>", yk="k_ypass_acc<5, 1, true>"),
+    Case("16-64", 16, 64, S=3, variant=2, tile=4, wave_y=0, side=True, xk="k_xpass_abbe<6, 2, true, 1, 1>", yk="k_ypass_acc<6, 2, true>"),
+    Case("30-64 generic", 30, 64, S=4, variant=-1, tile=4, wave_y=0, xk="k_xpass_abbe<6, -1, false, 1, 1>", yk="k_ypass_acc<6, -1, false>"),
+    Case("64-128", 64, 128, S=7, variant=1, tile=4, wave_y=0, xk="k_xpass_abbe<7, 1, true, 1, 1>", yk="k_ypass_acc<7, 1, true>"),
     # run size 256, N 512
-    Case("256 default", 256, 512, variant=1, coarse=0, wave_y=1, tile=8, xkind=1),                 # 5 points: below the coarse threshold
-    Case("256 coarse 2", 256, 512, {"coarse": 2}, coarse=1, wave_y=1, xkind=1, side=True),
-    Case("256 coarse 2 gcombine 0", 256, 512, {"coarse": 2, "gcombine": 0}, coarse=1, wave_y=1),
-    Case("256 w64 0", 256, 512, {"coarse": 0, "w64": 0}, coarse=0, wave_y=0, variant=1, tile=4),
-    Case("256 tile 4", 256, 512, {"coarse": 0, "tile": 4}, coarse=0, wave_y=0, tile=4),
-    Case("256 rowpairs", 256, 512, {"coarse": 0, "rowpairs": 1}, coarse=0, wave_y=1, tile=8),
-    Case("256 w64x", 256, 512, {"coarse": 0, "w64x": 1}, coarse=0, tile=4),
-    Case("256 force_generic", 256, 512, {"coarse": 0, "force_generic": 1}, coarse=0, variant=-1, wave_y=0, xkind=0),
-    Case("256 force_general", 256, 512, {"force_general": 1}, general=1, variant=-1, coarse=0, xkind=0),
-    Case("256 wrapping list", 256, 512, src="wrap", general=1, variant=-1, split=0),              # general mode by itself
-    Case("256 wide pupil", 256, 512, pupil="wide", src="tiny", general=0, natural_box=0, variant=-1, wave_y=0, coarse=0),   # shifts of at most 5
-    Case("256 square corners", 256, 512, {"coarse": 2}, pupil="square", coarse=0, natural_box=1, wave_y=1),
+    Case("256 default", 256, 512, variant=1, coarse=0, wave_y=1, tile=8, xkind=1, xk="k_xpass_abbe<9, 1, true, 1, 1>", yk="k_ypass_rect<9, 8, false, 1>"),   # 5 points: below the coarse threshold
+    Case("256 coarse 2", 256, 512, {"coarse": 2}, coarse=1, wave_y=1, xkind=1, side=True, xk="k_xpass_abbe<8, 0, true, 1, 1>", yk="k_ypass_rect<8, 8, true, 1>"),
+    Case("256 coarse 2 gcombine 0", 256, 512, {"coarse": 2, "gcombine": 0}, coarse=1, wave_y=1, xk="k_xpass_abbe<8, 0, true, 1, 1>", yk="k_ypass_rect<8, 8, true, 1>"),
+    Case("256 w64 0", 256, 512, {"coarse": 0, "w64": 0}, coarse=0, wave_y=0, variant=1, tile=4, xk="k_xpass_abbe<9, 1, true, 1, 1>", yk="k_ypass_acc<9, 1, true>"),
+    Case("256 tile 4", 256, 512, {"coarse": 0, "tile": 4}, coarse=0, wave_y=0, tile=4, xk="k_xpass_abbe<9, 1, true, 1, 1>", yk="k_ypass_acc<9, 1, true>"),
+    Case("256 rowpairs", 256, 512, {"coarse": 0, "rowpairs": 1}, coarse=0, wave_y=1, tile=8, xk="k_xpass_abbe<9, 1, true, 1, 1>", yk="k_ypass_rect<9, 8, false, 1>"),
+    Case("256 w64x", 256, 512, {"coarse": 0, "w64x": 1}, coarse=0, tile=4, xk="k_xpass_abbe<9, 1, true, 1, 1>", yk="k_ypass_acc<9, 1, true>"),
+    Case("256 force_generic", 256, 512, {"coarse": 0, "force_generic": 1}, coarse=0, variant=-1, wave_y=0, xkind=0, xk="k_xpass_abbe<9, -1, false, 1, 1>", yk="k_ypass_acc<9, -1, false>"),
+    Case("256 force_general", 256, 512, {"force_general": 1}, general=1, variant=-1, coarse=0, xkind=0, xk="k_xpass<9, 1, litho::AbbeLoader>", yk="k_ypass_acc<9, -1, false>"),
+    Case("256 wrapping list", 256, 512, src="wrap", general=1, variant=-1, split=0, xk="k_xpass<9, 1, litho::AbbeLoader>", yk="k_ypass_acc<9, -1, false>"),   # general mode by itself
+    Case("256 wide pupil", 256, 512, pupil="wide", src="tiny", general=0, natural_box=0, variant=-1, wave_y=0, coarse=0, xk="k_xpass_abbe<9, -1, false, 1, 1>", yk="k_ypass_acc<9, -1, false>"),   # shifts of at most 5
+    Case("256 square corners", 256, 512, {"coarse": 2}, pupil="square", coarse=0, natural_box=1, wave_y=1, xk="k_xpass_abbe<9, 1, true, 1, 1>", yk="k_ypass_rect<9, 8, false, 1>"),
     # small geometry at 256: what makes assertion 5 sharp (5.5 MiB declared of 293.5)
-    Case("256 small fold", 256, 512, SMALL, S=70, coarse=1, batch=1, groups=1),                     # the slabs fold after 64 batches
+    Case("256 small fold", 256, 512, SMALL, S=70, coarse=1, batch=1, groups=1, xk="k_xpass_abbe<8, 0, true, 1, 1>", yk="k_ypass_rect<8, 8, true, 1>"),   # the slabs fold after 64 batches
     Case("256 small ragged planes", 256, 512, {"coarse": 2, "batch": 2, "groups": 2, "plane_chunk": 2}, S=7, planes=3, coarse=1, batch=2,
-         planes_in_flight=2, side=True),
-    Case("256 small ragged xchunk", 256, 512, {"coarse": 0, "batch": 3, "xchunk": 2}, S=7, coarse=0, batch=3, xchunk=2),
+         planes_in_flight=2, side=True, xk="k_xpass_abbe<8, 0, true, 1, 1>", yk="k_ypass_rect<8, 8, true, 1>"),
+    Case("256 small ragged xchunk", 256, 512, {"coarse": 0, "batch": 3, "xchunk": 2}, S=7, coarse=0, batch=3, xchunk=2, xk="k_xpass_abbe<9, 1, true, 1, 1>", yk="k_ypass_rect<9, 8, false, 1>"),
     # other run sizes and the remaining kernel families
-    Case("256-256", 256, 256, variant=0, wave_y=1), Case("512-512", 512, 512, S=3, variant=0, wave_y=1),
-    Case("512 rect", 512, 1024, {"coarse": 0}, S=3, coarse=0, xkind=3, wave_y=1),
-    Case("512 xrect 0", 512, 1024, {"coarse": 0, "xrect": 0}, S=3, coarse=0, xkind=1, wave_y=1),
-    Case("512 rect 0", 512, 1024, {"coarse": 0, "rect": 0}, S=3, coarse=0, wave_y=1),
-    Case("1024 coarse 2", 1024, 2048, {"coarse": 2}, S=12, coarse=1, xchunk=12),
-    Case("2048 coarse 2", 2048, 4096, {"coarse": 2}, S=2, coarse=1, wave_y=1),
-    Case("2048 coarse 0", 2048, 4096, {"coarse": 0}, S=2, coarse=0, wave_y=1, xkind=1, side=True),
+    Case("256-256", 256, 256, variant=0, wave_y=1, xk="k_xpass_abbe<8, 0, true, 1, 1>", yk="k_ypass_rect<8, 8, true, 1>"),
+    Case("512-512", 512, 512, S=3, variant=0, wave_y=1, xk="k_xpass_abbe<9, 0, true, 1, 1>", yk="k_ypass_rect<9, 8, true, 1>"),
+    Case("512 rect", 512, 1024, {"coarse": 0}, S=3, coarse=0, xkind=3, wave_y=1, xk="k_xpass_rect<10, false>", yk="k_ypass_rect<10, 8, false, 1>"),
+    Case("512 xrect 0", 512, 1024, {"coarse": 0, "xrect": 0}, S=3, coarse=0, xkind=1, wave_y=1, xk="k_xpass_abbe<10, 1, true, 1, 1>", yk="k_ypass_rect<10, 8, false, 1>"),
+    Case("512 rect 0", 512, 1024, {"coarse": 0, "rect": 0}, S=3, coarse=0, wave_y=1, xk="k_xpass_rect<10, false>", yk="k_ypass_wave<10, 8, false>"),
+    Case("1024 coarse 2", 1024, 2048, {"coarse": 2}, S=12, coarse=1, xchunk=12, xk="k_xpass_abbe<10, 0, true, 1, 1>", yk="k_ypass_rect<10, 8, true, 2>"),
+    Case("2048 coarse 2", 2048, 4096, {"coarse": 2}, S=2, coarse=1, wave_y=1, xk="k_xpass_abbe<11, 0, true, 1, 1>", yk="k_ypass_rect<11, 8, true, 2>"),
+    Case("2048 coarse 0", 2048, 4096, {"coarse": 0}, S=2, coarse=0, wave_y=1, xkind=1, side=True, xk="k_xpass_abbe<12, 1, true, 1, 1>", yk="k_ypass_wave<12, 8, false>"),
+    # launches no other case names: k_xpass_rect with every bin kept, k_ypass_rect's combined groups on the direct path, k_xpass_w64
+    Case("512-512 xrect 2", 512, 512, {"xrect": 2}, S=3, variant=0, xkind=3, wave_y=1, xk="k_xpass_rect<9, true>", yk="k_ypass_rect<9, 8, true, 1>"),
+    Case("512 rect groups 2", 512, 1024, {"coarse": 0, "groups": 2}, S=4, coarse=0, xkind=3, wave_y=1, groups=2, xk="k_xpass_rect<10, false>", yk="k_ypass_rect<10, 8, false, 2>"),
+    Case("2048 coarse 0 w64x", 2048, 4096, {"coarse": 0, "w64x": 1}, S=2, coarse=0, xkind=0, wave_y=1, tile=4, xk="k_xpass_w64<12>", yk="k_ypass_wave<12, 4, false>"),
     # embedded sizes
-    Case("200 embedded", 200, 512, SMALL, run_size=256, coarse=1, embedded=1),
-    Case("300 embedded", 300, 1024, {"coarse": 2}, S=3, run_size=512, coarse=1, embedded=1),
-    Case("200 wrapping list", 200, 512, src="wrap", run_size=256, part_size=200, general=1, embedded=0),   # refuses the embedding
-    Case("200 embed 0", 200, 512, {"embed": 0}, run_size=200, variant=-1, embedded=0),
-    Case("200 own-size workspace", 200, 512, ws="own", run_size=200, variant=-1, embedded=0),
+    Case("200 embedded", 200, 512, SMALL, run_size=256, coarse=1, embedded=1, xk="k_xpass_abbe<8, 0, true, 1, 1>", yk="k_ypass_rect<8, 8, true, 1>"),
+    Case("300 embedded", 300, 1024, {"coarse": 2}, S=3, run_size=512, coarse=1, embedded=1, xk="k_xpass_abbe<9, 0, true, 1, 1>", yk="k_ypass_rect<9, 8, true, 1>"),
+    Case("200 wrapping list", 200, 512, src="wrap", run_size=256, part_size=200, general=1, embedded=0, xk="k_xpass<9, 1, litho::AbbeLoader>", yk="k_ypass_acc<9, -1, false>"),   # refuses the embedding
+    Case("200 embed 0", 200, 512, {"embed": 0}, run_size=200, variant=-1, embedded=0, xk="k_xpass_abbe<9, -1, false, 1, 1>", yk="k_ypass_acc<9, -1, false>"),
+    Case("200 own-size workspace", 200, 512, ws="own", run_size=200, variant=-1, embedded=0, xk="k_xpass_abbe<9, -1, false, 1, 1>", yk="k_ypass_acc<9, -1, false>"),
     # split lists: part 0 keeps the fast path, part 1 runs general mode
-    Case("256 split", 256, 512, {"split": 2, "coarse": 2, "batch": 4, "groups": 2}, S=20, src="partial", split=1, parts=2, general=1, side=True),
+    Case("256 split", 256, 512, {"split": 2, "coarse": 2, "batch": 4, "groups": 2}, S=20, src="partial", split=1, parts=2, general=1, side=True, xk="k_xpass<9, 1, litho::AbbeLoader>", yk="k_ypass_acc<9, -1, false>"),
     Case("200 split embedded", 200, 512, {"split": 2, "coarse": 2, "batch": 4, "groups": 2}, S=20, src="partial", split=1, parts=2, general=1,
-         run_size=256, part_size=200, part0_size=256),
+         run_size=256, part_size=200, part0_size=256, xk="k_xpass<9, 1, litho::AbbeLoader>", yk="k_ypass_acc<9, -1, false>"),
     # the other entries, three representative plans each
-    Case("weighted 256 coarse", 256, 512, SMALL, S=6, entry="weighted", coarse=1),
-    Case("weighted 64", 64, 128, S=6, entry="weighted", variant=1), Case("weighted 200 embedded", 200, 512, SMALL, S=6, entry="weighted", run_size=256),
-    Case("counted 256 coarse", 256, 512, SMALL, S=6, entry="counted", coarse=1), Case("counted 30", 30, 64, S=4, entry="counted", variant=-1),
-    Case("counted 200 embedded", 200, 512, SMALL, S=6, entry="counted", run_size=256),
-    Case("planned 256 coarse", 256, 512, SMALL, S=6, entry="planned", coarse=1), Case("planned 64", 64, 128, S=6, entry="planned", variant=1),
+    Case("weighted 256 coarse", 256, 512, SMALL, S=6, entry="weighted", coarse=1, xk="k_xpass_abbe<8, 0, true, 1, 1, float const*>", yk="k_ypass_rect<8, 8, true, 1>"),
+    Case("weighted 64", 64, 128, S=6, entry="weighted", variant=1, xk="k_xpass_abbe<7, 1, true, 1, 1, float const*>", yk="k_ypass_acc<7, 1, true>"),
+    Case("weighted 200 embedded", 200, 512, SMALL, S=6, entry="weighted", run_size=256, xk="k_xpass_abbe<8, 0, true, 1, 1, float const*>", yk="k_ypass_rect<8, 8, true, 1>"),
+    Case("counted 256 coarse", 256, 512, SMALL, S=6, entry="counted", coarse=1, xk="k_xpass_abbe<8, 0, true, 1, 1>", yk="k_ypass_rect<8, 8, true, 1>"),
+    Case("counted 30", 30, 64, S=4, entry="counted", variant=-1, xk="k_xpass_abbe<6, -1, false, 1, 1>", yk="k_ypass_acc<6, -1, false>"),
+    Case("counted 200 embedded", 200, 512, SMALL, S=6, entry="counted", run_size=256, xk="k_xpass_abbe<8, 0, true, 1, 1>", yk="k_ypass_rect<8, 8, true, 1>"),
+    Case("planned 256 coarse", 256, 512, SMALL, S=6, entry="planned", coarse=1, xk="k_xpass_abbe<8, 0, true, 1, 1>", yk="k_ypass_rect<8, 8, true, 1>"),
+    Case("planned 64", 64, 128, S=6, entry="planned", variant=1, xk="k_xpass_abbe<7, 1, true, 1, 1>", yk="k_ypass_acc<7, 1, true>"),
     Case("planned 256 split", 256, 512, {"split": 2, "coarse": 2, "batch": 4, "groups": 2}, S=20, src="partial", entry="planned", split=1,
-         parts=2),
+         parts=2, xk="k_xpass<9, 1, litho::AbbeLoader>", yk="k_ypass_acc<9, -1, false>"),
+    # the weighted x-pass siblings no other name-asserting test reaches: k_xpass_rect (both FULL values) and the general x-pass
+    Case("weighted 512 rect", 512, 1024, {"coarse": 0}, S=3, entry="weighted", coarse=0, xkind=3, wave_y=1, xk="k_xpass_rect<10, false, float const*>", yk="k_ypass_rect<10, 8, false, 1>"),
+    Case("weighted 512-512 xrect 2", 512, 512, {"xrect": 2}, S=3, entry="weighted", variant=0, xkind=3, wave_y=1, xk="k_xpass_rect<9, true, float const*>", yk="k_ypass_rect<9, 8, true, 1>"),
+    Case("weighted 64 wrapping list", 64, 128, S=6, src="wrap", entry="weighted", general=1, variant=-1, split=0, xk="k_xpass<7, 1, litho::AbbeLoaderW>", yk="k_ypass_acc<7, -1, false>"),
 ]
-# 4096^2: two points and a 5 GiB workspace; the three calls run in turn in ONE arena (and one more with the other alignment)
-BIG = [Case("4096 coarse 2 coopdma 1", 4096, 8192, {"coarse": 2, "coopdma": 1}, S=2, coarse=1, tile=16, wave_y=1),
-       Case("4096 coarse 2 coopdma 0", 4096, 8192, {"coarse": 2, "coopdma": 0}, S=2, coarse=1, tile=16, wave_y=1),
-       Case("4096 coarse 0", 4096, 8192, {"coarse": 0}, S=2, coarse=0, xkind=2, wave_y=1)]
+# 4096^2: two points and a 5 GiB workspace; the four calls run in turn in ONE arena (and one more with the other alignment)
+BIG = [Case("4096 coarse 2 coopdma 1", 4096, 8192, {"coarse": 2, "coopdma": 1}, S=2, coarse=1, tile=16, wave_y=1, xk="k_xpass_abbe<12, 0, true, 1, 1>", yk="k_ypass_coop_dma<12, 4>"),
+       Case("4096 coarse 2 coopdma 0", 4096, 8192, {"coarse": 2, "coopdma": 0}, S=2, coarse=1, tile=16, wave_y=1, xk="k_xpass_abbe<12, 0, true, 1, 1>", yk="k_ypass_coop<12, 4>"),
+       Case("4096 coarse 0", 4096, 8192, {"coarse": 0}, S=2, coarse=0, xkind=2, wave_y=1, xk="k_xpass_split<13>", yk="k_ypass_pair<13, 8>"),
+       Case("4096 coarse 0 weighted", 4096, 8192, {"coarse": 0}, S=2, entry="weighted", coarse=0, xkind=2, wave_y=1, xk="k_xpass_split<13, float const*>", yk="k_ypass_pair<13, 8>")]
 BY_NAME = {c.name: c for c in CASES + BIG}
 assert len(BY_NAME) == len(CASES) + len(BIG)
 
@@ -263,6 +280,7 @@ def test_every_case_plans_as_stated(nat):
         assert pl.dry.run_size == exp.pop("run_size", case.pn), (case.name, pl.dry.run_size)
         assert last.run_size == exp.pop("part_size", pl.dry.run_size), (case.name, last.run_size)
         assert pl.parts[0].run_size == exp.pop("part0_size", pl.parts[0].run_size), case.name
+        exp.pop("xk", None), exp.pop("yk", None)                               # the kernels of the last part: held on the device (check_call)
         embedded = exp.pop("embedded", None)
         if embedded is not None:
             assert (pl.parts[0].embed_M.bytes > 0) == bool(embedded), case.name
@@ -329,12 +347,13 @@ def prefill(planes, pn):
     return (0.5 + (i % 97) / 97.0 + (i % 13) / 64.0).to(torch.float32).reshape(planes, pn, pn)
 
 
-def make_arena(case, pl, dev, odd=False, capacity=None, ws_bytes=None):
+def make_arena(case, pl, dev, odd=False, capacity=None, ws_bytes=None, weights=False):
+    """`weights`: a weights buffer for a case that takes none itself (an arena that a weighted case will run in later)."""
     pn, cap = case.pn, capacity or case.S
     m8, m4 = (8, 4) if odd else (0, 0)
     bufs = [Buf("maskFT", "in", torch.complex64, (pn, pn), m8), Buf("pupil", "in", torch.complex64, (case.planes, pn, pn), m8),
             Buf("shifts", "in", torch.int32, (cap, 2), m4)]
-    if case.entry == "weighted":
+    if case.entry == "weighted" or weights:
         bufs.append(Buf("weights", "in", torch.float32, (cap,), m4))
     if case.entry in ("counted", "planned"):
         bufs.append(Buf("count_dev", "in", torch.int32, (1,), m4))
@@ -345,7 +364,7 @@ def make_arena(case, pl, dev, odd=False, capacity=None, ws_bytes=None):
     a.fill("maskFT", mft.to(dev))
     a.fill("pupil", pupil.to(dev))
     a["shifts"][:case.S].copy_(shifts.to(dev))                                 # (capacity > S: the tail stays poison)
-    if case.entry == "weighted":
+    if "weights" in a.bufs:
         a["weights"][:case.S].copy_(weights.to(dev))
     if "count_dev" in a.bufs:
         a["count_dev"].fill_(case.S)
@@ -442,6 +461,7 @@ def check_call(nat, a, case, pl, dev, planning=True, last_plan_kind=None, want_b
     touched = a.touched_outside("workspace", tight.values())
     assert touched == [], f"{case.name}: {len(touched)} bytes of T behind the last item written, first {touched[:4]}"
     KERNELS[case.name] = nat.last_kernels()
+    assert KERNELS[case.name] == (case.expect["xk"], case.expect["yk"]), (case.name, KERNELS[case.name])                # 10
     return out
 
 
@@ -458,7 +478,7 @@ def run(nat, case, dev, cus, side=None, arenas=None):
             a.bytes[b.start:b.end].fill_(POISON)
             a.fill("out", a.sealed("out"))
         else:
-            a = make_arena(case, pl, dev, odd, capacity)
+            a = make_arena(case, pl, dev, odd, capacity, weights=arenas is not None)
             if arenas is not None:
                 arenas[odd] = a
         rc, cnt = call_in(nat, a, case, dev, capacity=capacity)
@@ -487,8 +507,9 @@ def test_abbe_call_stays_inside_what_the_dry_run_declares(nat, dev, cus, side, n
 
 @gpu
 def test_the_4096_group_in_one_arena(nat, dev, cus, side):
-    """k_ypass_coop_dma, k_ypass_coop (tile 16) and k_xpass_split<13> + k_ypass_pair<13>: the three calls in turn in ONE 5 GiB
-    arena per alignment, the workspace re-poisoned and `out` re-filled between them."""
+    """k_ypass_coop_dma, k_ypass_coop (tile 16), k_xpass_split<13> + k_ypass_pair<13> and the weighted k_xpass_split<13, float
+    const*>: the four calls in turn in ONE 5 GiB arena per alignment (with a weights buffer from the start, for the last of
+    them), the workspace re-poisoned and `out` re-filled between them."""
     arenas = {}
     for case in BIG:
         run(nat, case, dev, cus, side, arenas)
@@ -505,7 +526,7 @@ def test_weighted_entry(nat, dev, cus, side, name):
     a["weights"].fill_(1.0)
     a.seal()
     rc, _ = call_in(nat, a, case, dev)
-    plain = Case(case.name, case.pn, case.N, case.opts, S=case.S, planes=case.planes)
+    plain = Case(case.name, case.pn, case.N, case.opts, S=case.S, planes=case.planes, pupil=case.pupil, src=case.src)
     b = make_arena(plain, pl, dev)
     rc2, _ = call_in(nat, b, plain, dev)
     assert rc == 0 and rc2 == 0 and a.report({}).clean and b.report({}).clean and differing(a["out"], b["out"]) == [], name
