@@ -34,13 +34,13 @@ build/instw_%.o: $(CSRC)/instw_%.hip $(HDRS)
 build/abbe_engine.o: $(CSRC)/abbe_engine.hip $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-build/optics.o: $(CSRC)/optics.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
+build/optics.o: $(CSRC)/optics.hip $(CSRC)/cd_search.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 build/layout.o: $(CSRC)/layout.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
-build/metrology.o: $(CSRC)/metrology.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
+build/metrology.o: $(CSRC)/metrology.hip $(CSRC)/cd_search.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 build/contour.o: $(CSRC)/contour.hip $(CSRC)/engine_common.hpp include/litho_abbe.h

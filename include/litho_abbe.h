@@ -315,6 +315,29 @@ int litho_measure_cd(const float *image, int planes, int n, const int32_t *gauge
 int litho_measure_epe(const float *image, int planes, int n, const float *sites, int64_t n_sites, const float *gains_host,
                       int n_gains, float threshold, int exposed, float range_px, float pixel_size, float *out, void *stream);
 
+/* ---- Forward-mode metrology (csrc/metrology.hip; no reference counterpart, checked against tests/socs_tangent_oracle.py): the exact
+ * derivatives of the two piecewise formulas above along P <= LITHO_SOCS_JVP_MAX_DIRECTIONS image directions, not a finite
+ * difference.  dImage fp32 [P][planes][n][n] on the device; every other argument as in the primal.  Both kernels run the primal's
+ * own search on `image` (one device function serves both), so they differentiate the interval or the run the primal chose.
+ *
+ * litho_measure_epe_jvp: out fp32 [P][n_gains][planes][n_sites] = d(epe_nm).  With du = gain * (the bilinear sample of dImage at the
+ * same two points as u_k and u_{k+1}), h = 0.5 and w = u_{k+1} - u_k,
+ *   d epe = (pixel_size * h) * ((-du_k * w - (T - u_k) * (du_{k+1} - du_k)) / (w * w)),
+ * fp32 in this order; NaN wherever the primal is NaN.  LITHO_E_ARG as litho_measure_epe, and for P outside 1..16 or a null dImage.
+ *
+ * litho_measure_cd_jvp: out fp32 [P][n_gains][planes][n_gauges][3] = (dcd_nm, dx_lo, dx_hi).  A crossing x = i + (T - a) / (b - a)
+ * between samples i and i + 1 moves by dx = (-da * w - (T - a) * (db - da)) / (w * w), w = b - a, da and db the gained samples of
+ * dImage there; a border edge (x_lo = -0.5, x_hi = n - 0.5) has derivative 0; dcd_nm = (dx_hi - dx_lo) * pixel_size.  Where the
+ * gauge's sample is not inside: (0, NaN, NaN); a gauge outside the grid: three NaN -- the primal's pattern.  LITHO_E_ARG as
+ * litho_measure_cd, and for P outside 1..16 or a null dImage.  Both: asynchronous, one kernel, no allocation, no host wait. */
+#define LITHO_SOCS_JVP_MAX_DIRECTIONS 16
+int litho_measure_epe_jvp(const float *image, const float *dImage, int P, int planes, int n, const float *sites, int64_t n_sites,
+                          const float *gains_host, int n_gains, float threshold, int exposed, float range_px, float pixel_size,
+                          float *out, void *stream);
+int litho_measure_cd_jvp(const float *image, const float *dImage, int P, int planes, int n, const int32_t *gauges, int n_gauges,
+                         const float *gains_host, int n_gains, double threshold, int exposed, double pixel_size, float *out,
+                         void *stream);
+
 /* ---- Printed contours as polygons: a marching-squares tracer (no reference counterpart; checked against
  * tests/contour_oracle.py).  image fp32 [planes,n,n] on the device, sample (row r, column c) at (x = c, y = r) as in
  * litho_measure_epe; gains_host: n_gains <= 64 host floats.  One IMAGE is a (gain, plane) pair, numbered gain * planes + plane;
@@ -886,6 +909,19 @@ int litho_socs_fields(const void *kernels, const void *maskFT, int batch, int pn
  * device bytes (the field stack; 0 for a bad argument), less is LITHO_E_WORKSPACE. */
 size_t litho_socs_vjp_work_bytes(int groups, int K, int pn);
 int litho_socs_vjp(const void *kernels, const void *maskFT, const float *gradI, int groups, int K, int pn, int N, void *grad,
+                   int accumulate, void *work, size_t work_bytes, void *stream);
+/* litho_socs_jvp: forward mode through the same fields.  The image is quadratic in the mask spectrum, so along a direction dM
+ *   dI[p][g] (+)= 2 sum_{k < K} Re( conj(E_gk) . L(kernels[g K + k] . dMaskFT[p]) ),   E_gk = L(kernels[g K + k] . maskFT),
+ * k ascending, one running fp32 sum per output element and no atomics; accumulate != 0 continues from dI, so calls on consecutive
+ * chunks of the kernels give the chunk-ordered sum.  kernels complex64 [groups K,pn,pn] as for litho_socs_vjp, maskFT complex64
+ * [pn,pn], dMaskFT complex64 [P,pn,pn], dI fp32 [P,groups,pn,pn]; 1 <= P <= LITHO_SOCS_JVP_MAX_DIRECTIONS, groups <= 65535.  The
+ * directions run one after another through the same launches: direction p's bits depend neither on P nor on the other
+ * directions, and two calls give the same bits.  A tangent field is folded against its primal field as it leaves the second row
+ * pass and is never stored.  work: litho_socs_jvp_work_bytes(groups, K, P, pn) device bytes -- the chunk's field stack, one
+ * direction's stack between its two passes and one direction's real planes; nothing grows with P (0 for a bad argument), less is
+ * LITHO_E_WORKSPACE.  Domain and codes as litho_socs_vjp, and LITHO_E_ARG for P outside 1..16; every check precedes any launch. */
+size_t litho_socs_jvp_work_bytes(int groups, int K, int P, int pn);
+int litho_socs_jvp(const void *kernels, const void *maskFT, const void *dMaskFT, int P, int groups, int K, int pn, int N, float *dI,
                    int accumulate, void *work, size_t work_bytes, void *stream);
 
 /* ---- Source gradients of Abbe imaging (csrc/socs_grad.hip; no reference counterpart, checked against tests/source_grad_oracle.py).

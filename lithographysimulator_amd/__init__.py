@@ -33,6 +33,8 @@ from .calibrate import (bakeParameterChain, bakeParameterGradient, bakeStepGradi
 from .tangent import (amplifiedRateTangent, bakeParameterTangent, bakeTangent,         # noqa: F401
                       calibrationJacobian, developmentRateTangent, developmentTimeTangent,
                       exposeAcidTangent, rateParameterTangent, resistProfileTangent)
+from .sensitivity import (edgeCoverageTangent, epeJacobian, hopkinsTangent,            # noqa: F401
+                          maskErrorFactor, measureCDTangent, measureEPETangent, postProcessTangent)
 from .mask import Mask, alternatingPSM, attenuatedPSM                                   # noqa: F401
 from .pupil import (OSAindexToMN, Pupil, generatePhi, generateWavefrontError,           # noqa: F401
                     generateZ, throughFocusPupils)
@@ -56,4 +58,6 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "bakeStepGradient", "bakeParameterChain", "bakeParameterGradient", "rateParameterChain", "rateParameterGradient",
            "exposureParameterGradient", "resistParameterGradient", "calibrateResist", "resistArrivalTimes", "resistWith", "resistParameter",
            "exposeAcidTangent", "bakeTangent", "bakeParameterTangent", "developmentRateTangent", "amplifiedRateTangent",
-           "rateParameterTangent", "developmentTimeTangent", "resistProfileTangent", "calibrationJacobian"]
+           "rateParameterTangent", "developmentTimeTangent", "resistProfileTangent", "calibrationJacobian",
+           "hopkinsTangent", "postProcessTangent", "edgeCoverageTangent", "measureEPETangent", "measureCDTangent", "epeJacobian",
+           "maskErrorFactor"]

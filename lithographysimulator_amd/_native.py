@@ -53,6 +53,10 @@ _SIGNATURES = {
                                  c_void_p, c_void_p]),
     "litho_measure_epe": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_float, c_int, c_float, c_float,
                                   c_void_p, c_void_p]),
+    "litho_measure_epe_jvp": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int64, c_void_p, c_int, c_float, c_int,
+                                      c_float, c_float, c_void_p, c_void_p]),
+    "litho_measure_cd_jvp": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_double, c_int,
+                                     c_double, c_void_p, c_void_p]),
     "litho_contour_work_bytes": (c_size_t, [c_int, c_int, c_int]),
     "litho_contour_count": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
     "litho_contour_emit": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_float, c_int, c_void_p, c_size_t, c_void_p, c_void_p,
@@ -125,6 +129,9 @@ _SIGNATURES = {
     "litho_socs_fields": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "litho_socs_vjp_work_bytes": (c_size_t, [c_int, c_int, c_int]),
     "litho_socs_vjp": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t,
+                               c_void_p]),
+    "litho_socs_jvp_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "litho_socs_jvp": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_size_t,
                                c_void_p]),
     "litho_source_sensitivity_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "litho_source_sensitivity": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p,

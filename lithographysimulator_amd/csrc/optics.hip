@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/litho_abbe.h"
+#include "cd_search.hpp"
 #include "engine_common.hpp"
 
 namespace litho {
@@ -473,17 +474,8 @@ __global__ __launch_bounds__(64) void k_measure_cd(const float* __restrict__ ima
         auto u = [&](int i) { return line[(size_t)i * stride] * gain; };
         float cd = nan, x_lo = nan, x_hi = nan, ils_lo = nan, ils_hi = nan;
         if (ok && ((u(c) >= T) == ex)) {
-            int lo = 0, hi = n - 1;
-            for (int s = c + 1;; s += 64) {                                       // first sample to the right that is not inside
-                const int i = s + lane;
-                const unsigned long long m = __ballot(i >= n || ((u(i) >= T) != ex));
-                if (m) { hi = s + __ffsll((long long)m) - 2; break; }
-            }
-            for (int s = c - 1;; s -= 64) {                                       // ... and to the left
-                const int i = s - lane;
-                const unsigned long long m = __ballot(i < 0 || ((u(i) >= T) != ex));
-                if (m) { lo = s - __ffsll((long long)m) + 2; break; }
-            }
+            int lo, hi;
+            cd_run(u, c, n, lane, T, ex, lo, hi);                                 // cd_search.hpp, shared with the tangent
             x_lo = -0.5f;
             if (lo > 0) {
                 const float a = u(lo - 1), b = u(lo);

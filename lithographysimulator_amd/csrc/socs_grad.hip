@@ -28,6 +28,11 @@
 // adjoint transform of the mask-gradient path with the G of the item's plane, and a reducing pass that undoes each point's roll
 // and sums the points in list order (k_pupil_reduce); litho_pupil_project pairs the result with a basis of wavefront maps in a
 // two-stage reduction of fixed order.  Checked against tests/pupil_grad_oracle.py.
+//
+// The tangent of the image (litho_socs_jvp) is forward mode through the same fields: dI = 2 sum_k Re(conj(E_k) . L(phi_k . dM)).
+// A direction's first row pass is the fields' own (the kernel times a plane on the load -- the plane is dM instead of M); its second
+// row pass folds each output against the stored field as it comes out (STORE_FOLD), so a tangent field is never stored.
+// Checked against tests/socs_tangent_oracle.py.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -41,8 +46,9 @@ namespace litho {
 
 // What the row pass multiplies into the line as it loads it.
 enum : int { LOAD_PLAIN = 0, LOAD_TIMES_MASK = 1, LOAD_TIMES_GRAD = 2, LOAD_ROLLED = 3 };
-// What it does with the outputs: writes them, or reduces mul_r . |y|^2 over the line to one number.
-enum : int { STORE_FIELD = 0, STORE_REDUCE = 1 };
+// What it does with the outputs: writes them, reduces mul_r . |y|^2 over the line to one number, or folds them against a stored
+// field into a running real sum over the K items of a group (the tangent of the image, litho_socs_jvp).
+enum : int { STORE_FIELD = 0, STORE_REDUCE = 1, STORE_FOLD = 2 };
 
 // `lines` lines of pn = 2^LOG2P samples, line l = row (l mod pn) of item (l / pn); each becomes its centred pruned transform
 //   dst[q] = sum_i src[i] exp(SIGN 2 pi i (i - c)(q - c) / N),  q in [0, pn),  N = pn << log2m.
@@ -56,6 +62,13 @@ enum : int { STORE_FIELD = 0, STORE_REDUCE = 1 };
 // STORE_REDUCE: nothing is written to dst; partial[line] = sum_q mul_r[(item mod per_point) / per_group][row][q] |dst[q]|^2, each
 // thread over the outputs it owns (r ascending, then e), then the line's threads in a fixed order: the xor butterfly of a wave's
 // shuffles, every lane ending with the same bits, and for a line of several waves their sums through LDS, added in wave order.
+// STORE_FOLD: `lines` counts the lines of the GROUPS, line l = row (l mod pn) of group (l / pn), and the workgroup walks the
+//   per_group = K items of its group in ascending order: item g K + k's line is transformed and
+//   partial[l][q] += 2 Re(conj(mul_c[g K + k][row][q]) . dst[q])
+// (mul_c: the stored fields, one plane per item; nothing is written to dst).  The running sums of a line live in LDS, fp32, one
+// per output q, touched by the one thread that owns q and by nobody else between the two barriers around the loop; they start
+// from partial[l] when per_point != 0 (the accumulate flag of this mode) and from zero otherwise.  One sum per element in item
+// order, no atomics.
 template <int LOG2P, int SIGN, int LOAD, int STORE = STORE_FIELD>
 __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(const float2* src, float2* dst,
                                                                             const float2* __restrict__ mul_c,
@@ -75,78 +88,99 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
     F::load_twiddles(tw, g_twiddles, lt, smem + LS::LDS_EXCH, threadIdx.x, LS::THREADS, FFT_MAX_N / PN);
     const long long line = (long long)blockIdx.x * LS::L + lg;
     const bool active = line < lines;                       // every thread runs the transforms: they hold workgroup barriers
-    const long long l = active ? line : 0;
-    const int row = (int)(l & (PN - 1));
-    const float2* in = src + (size_t)l * PN;
-    float2* out = dst + (size_t)l * PN;
-    unsigned dx = 0;
-    if (LOAD == LOAD_ROLLED) {
-        const long long item = l >> LOG2P, point = item / per_point;
-        const unsigned dy = (unsigned)shifts[2 * point];    // unsigned: the modular index of any integer, no overflow
-        dx = (unsigned)shifts[2 * point + 1];
-        in = src + ((size_t)(item - point * per_point) * PN + (((unsigned)row - dy) & (PN - 1))) * PN;
+    float* sums_all = reinterpret_cast<float*>(smem + LS::LDS_EXCH + F::LDS_TW);   // STORE_FOLD: L lines of PN running sums
+    float* sums = sums_all + (size_t)lg * PN;
+    const long long fold_base = (long long)blockIdx.x * LS::L * PN, fold_end = lines * PN;
+    if (STORE == STORE_FOLD) {
+        for (int i = threadIdx.x; i < LS::L * PN; i += LS::THREADS)
+            sums_all[i] = (per_point != 0 && fold_base + i < fold_end) ? partial[fold_base + i] : 0.f;
+        __syncthreads();
     }
-    // transform index n = lt + T e stands for the sample at signed offset s = n (n < c) or n - pn from the centre: i = s + c
-    float2 x0[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-        const int n = lt + F::T * e;
-        const int i = (n + C) & (PN - 1);
-        float2 v = make_float2(0.f, 0.f);
-        if (active) {
-            v = LOAD == LOAD_ROLLED ? in[((unsigned)i - dx) & (PN - 1)] : in[i];
-            if (LOAD == LOAD_TIMES_MASK || LOAD == LOAD_ROLLED) v = cmul(v, mul_c[(size_t)row * PN + i]);
-            if (LOAD == LOAD_TIMES_GRAD) {
-                const float g = mul_r[((size_t)((l >> LOG2P) % per_point / per_group) * PN + row) * PN + i];
-                v = make_float2(v.x * g, v.y * g);
-            }
+    const int items = STORE == STORE_FOLD ? per_group : 1;
+    for (int item_k = 0; item_k < items; ++item_k) {
+        long long l = active ? line : 0;
+        const int row = (int)(l & (PN - 1));
+        if (STORE == STORE_FOLD) l = ((((l >> LOG2P) * per_group) + item_k) << LOG2P) + row;
+        const float2* in = src + (size_t)l * PN;
+        float2* out = dst + (size_t)l * PN;
+        const float2* fold = mul_c + (size_t)l * PN;             // STORE_FOLD only
+        unsigned dx = 0;
+        if (LOAD == LOAD_ROLLED) {
+            const long long item = l >> LOG2P, point = item / per_point;
+            const unsigned dy = (unsigned)shifts[2 * point];    // unsigned: the modular index of any integer, no overflow
+            dx = (unsigned)shifts[2 * point + 1];
+            in = src + ((size_t)(item - point * per_point) * PN + (((unsigned)row - dy) & (PN - 1))) * PN;
         }
-        x0[e] = v;
-    }
-    const int m = 1 << log2m;
-    const int nmask = (PN << log2m) - 1;                   // N - 1
-    const int tshift = 12 - LOG2P - log2m;                 // table stride 4096 / N
-    int flip = 0;
-    float acc = 0.f;
-    const float* gt = mul_r;
-    if (STORE == STORE_REDUCE) gt = mul_r + ((size_t)((l >> LOG2P) % per_point / per_group) * PN + row) * PN;
-    for (int r = 0; r < m; ++r) {
-        if (m > PN && r >= C && r < m - C) continue;       // no q in [0, pn) is congruent to c + r (uniform over the workgroup)
-        float2 x[16];
+        // transform index n = lt + T e stands for the sample at signed offset s = n (n < c) or n - pn from the centre: i = s + c
+        float2 x0[16];
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int n = lt + F::T * e;
-            const int s = n < C ? n : n - PN;
-            float2 w = g_twiddles[((s * r) & nmask) << tshift];
-            if (SIGN < 0) w.y = -w.y;
-            x[e] = r == 0 ? x0[e] : cmul(x0[e], w);
+            const int i = (n + C) & (PN - 1);
+            float2 v = make_float2(0.f, 0.f);
+            if (active) {
+                v = LOAD == LOAD_ROLLED ? in[((unsigned)i - dx) & (PN - 1)] : in[i];
+                if (LOAD == LOAD_TIMES_MASK || LOAD == LOAD_ROLLED) v = cmul(v, mul_c[(size_t)row * PN + i]);
+                if (LOAD == LOAD_TIMES_GRAD) {
+                    const float g = mul_r[((size_t)((l >> LOG2P) % per_point / per_group) * PN + row) * PN + i];
+                    v = make_float2(v.x * g, v.y * g);
+                }
+            }
+            x0[e] = v;
         }
-        F::template run<1>(x, tw, lds, lt, flip);
-        if (!active) continue;
+        const int m = 1 << log2m;
+        const int nmask = (PN << log2m) - 1;                   // N - 1
+        const int tshift = 12 - LOG2P - log2m;                 // table stride 4096 / N
+        int flip = 0;
+        float acc = 0.f;
+        const float* gt = mul_r;
+        if (STORE == STORE_REDUCE) gt = mul_r + ((size_t)((l >> LOG2P) % per_point / per_group) * PN + row) * PN;
+        for (int r = 0; r < m; ++r) {
+            if (m > PN && r >= C && r < m - C) continue;       // no q in [0, pn) is congruent to c + r (uniform over the workgroup)
+            float2 x[16];
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-            const int u = lt + F::T * e;
-            const int t = u < C ? u : u - PN;
-            const int q = C + (t << log2m) + r;
-            if (q >= 0 && q < PN) {
-                if (STORE == STORE_REDUCE) acc = fmaf(gt[q], fmaf(x[e].x, x[e].x, x[e].y * x[e].y), acc);
-                else out[q] = x[e];
+            for (int e = 0; e < 16; ++e) {
+                const int n = lt + F::T * e;
+                const int s = n < C ? n : n - PN;
+                float2 w = g_twiddles[((s * r) & nmask) << tshift];
+                if (SIGN < 0) w.y = -w.y;
+                x[e] = r == 0 ? x0[e] : cmul(x0[e], w);
+            }
+            F::template run<1>(x, tw, lds, lt, flip);
+            if (!active) continue;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int u = lt + F::T * e;
+                const int t = u < C ? u : u - PN;
+                const int q = C + (t << log2m) + r;
+                if (q >= 0 && q < PN) {
+                    if (STORE == STORE_REDUCE) acc = fmaf(gt[q], fmaf(x[e].x, x[e].x, x[e].y * x[e].y), acc);
+                    else if (STORE == STORE_FOLD) {
+                        const float2 ev = fold[q];
+                        sums[q] += 2.0f * fmaf(ev.x, x[e].x, ev.y * x[e].y);
+                    } else out[q] = x[e];
+                }
             }
         }
-    }
-    if (STORE == STORE_REDUCE) {
-        constexpr int W = F::T < 64 ? F::T : 64;           // the line's lanes within one wave: an aligned group of W
+        if (STORE == STORE_REDUCE) {
+            constexpr int W = F::T < 64 ? F::T : 64;           // the line's lanes within one wave: an aligned group of W
 #pragma unroll
-        for (int o = W / 2; o >= 1; o /= 2) acc += __shfl_xor(acc, o);
-        if (F::T > 64) {                                   // one line per workgroup, T / 64 waves
-            float* red = reinterpret_cast<float*>(smem);   // the exchange buffer, free once every thread has left the transforms
-            __syncthreads();
-            if ((lt & 63) == 0) red[lt >> 6] = acc;
-            __syncthreads();
-            acc = red[0];
-            for (int w = 1; w < F::T / 64; ++w) acc += red[w];
+            for (int o = W / 2; o >= 1; o /= 2) acc += __shfl_xor(acc, o);
+            if (F::T > 64) {                                   // one line per workgroup, T / 64 waves
+                float* red = reinterpret_cast<float*>(smem);   // the exchange buffer, free once every thread has left the transforms
+                __syncthreads();
+                if ((lt & 63) == 0) red[lt >> 6] = acc;
+                __syncthreads();
+                acc = red[0];
+                for (int w = 1; w < F::T / 64; ++w) acc += red[w];
+            }
+            if (active && lt == 0) partial[l] = acc;
         }
-        if (active && lt == 0) partial[l] = acc;
+    }
+    if (STORE == STORE_FOLD) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < LS::L * PN; i += LS::THREADS)
+            if (fold_base + i < fold_end) partial[fold_base + i] = sums_all[i];
     }
 }
 
@@ -310,11 +344,14 @@ static hipError_t centred_rows(const RowArgs& a, int pn, int sign, hipStream_t s
     return for_log2(log2_exact(pn), [&](auto l2) {
         constexpr int LOG2P = decltype(l2)::value;
         using LS = LineShape<LOG2P>;
+        // STORE_FOLD keeps the running sums of its L lines behind the exchange buffers and the twiddle tables
+        constexpr size_t LDS = LS::LDS_BYTES + (STORE == STORE_FOLD ? sizeof(float) * LS::L * (size_t(1) << LOG2P) : 0);
+        static_assert(LDS <= 64 * 1024, "the row pass stays inside the default LDS allowance");
         if (sign > 0)
-            hipLaunchKernelGGL((k_centred_rows<LOG2P, +1, LOAD, STORE>), LS::grid(a.lines), dim3(LS::THREADS), LS::LDS_BYTES, st, a.src,
+            hipLaunchKernelGGL((k_centred_rows<LOG2P, +1, LOAD, STORE>), LS::grid(a.lines), dim3(LS::THREADS), LDS, st, a.src,
                                a.dst, a.mul_c, a.mul_r, a.per_group, a.lines, a.log2m, a.shifts, a.per_point, a.partial);
         else
-            hipLaunchKernelGGL((k_centred_rows<LOG2P, -1, LOAD, STORE>), LS::grid(a.lines), dim3(LS::THREADS), LS::LDS_BYTES, st, a.src,
+            hipLaunchKernelGGL((k_centred_rows<LOG2P, -1, LOAD, STORE>), LS::grid(a.lines), dim3(LS::THREADS), LDS, st, a.src,
                                a.dst, a.mul_c, a.mul_r, a.per_group, a.lines, a.log2m, a.shifts, a.per_point, a.partial);
         return hipGetLastError();
     });
@@ -421,6 +458,63 @@ int litho_socs_vjp(const void* kernels, const void* maskFT, const float* gradI, 
     hipLaunchKernelGGL(k_vjp_reduce, dim3((unsigned)blocks), dim3(256), 0, st, (const float2*)kernels, (const float2*)w, (int)batch,
                        cells, (float2*)grad, accumulate ? 1 : 0);
     HIP_TRY(hipGetLastError());
+    return LITHO_OK;
+}
+
+// The tangent of the image: dI[p][g] (+)= 2 sum_k Re(conj(E_gk) . L(kernels[gK+k] . dMaskFT[p])).  Workspace: the chunk's fields
+// E^T (their final transpose left out: the fold meets them line for line in the transposed layout), one direction's stack between
+// its two passes, and the real planes of one direction in the transposed layout -- nothing grows with P.
+size_t litho_socs_jvp_work_bytes(int groups, int K, int P, int pn)
+{
+    using namespace litho;
+    if (groups < 1 || groups > 65535 || K < 1 || P < 1 || P > LITHO_SOCS_JVP_MAX_DIRECTIONS || !fft_size_ok(pn) ||
+        (long long)groups * K * pn > INT_MAX)
+        return 0;
+    const size_t cells = (size_t)pn * pn;
+    return 2 * (size_t)groups * K * cells * sizeof(float2) + (size_t)groups * cells * sizeof(float);
+}
+
+int litho_socs_jvp(const void* kernels, const void* maskFT, const void* dMaskFT, int P, int groups, int K, int pn, int N, float* dI,
+                   int accumulate, void* work, size_t work_bytes, void* stream)
+{
+    using namespace litho;
+    if (!kernels || !maskFT || !dMaskFT || !dI || !work || groups < 1 || groups > 65535 || K < 1 || P < 1 ||
+        P > LITHO_SOCS_JVP_MAX_DIRECTIONS)
+        return LITHO_E_ARG;
+    const long long batch = (long long)groups * K;
+    const int rc = check_sizes(batch, pn, N);
+    if (rc != LITHO_OK) return rc;
+    if (work_bytes < litho_socs_jvp_work_bytes(groups, K, P, pn)) return LITHO_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t cells = (size_t)pn * pn;
+    float2* fields = (float2*)work;                                // E^T, item by item
+    float2* tang = fields + (size_t)batch * cells;                 // one direction between its passes
+    float* sums = (float*)(tang + (size_t)batch * cells);          // dI[p]^T, plane by plane
+    const int log2m = log2_exact(N) - log2_exact(pn);
+    const long long lines = batch * pn;
+    const unsigned tiles = (unsigned)((pn + TR_TILE - 1) / TR_TILE);
+    const dim3 tgrid(tiles, tiles, (unsigned)groups);
+    HIP_TRY(fill_twiddles(st));
+    // the fields of the chunk once per call: rows of phi . M, transpose, rows -- and no transpose back
+    HIP_TRY(centred_rows<LOAD_TIMES_MASK>(RowArgs{(const float2*)kernels, fields, (const float2*)maskFT, nullptr, 1, lines, log2m}, pn,
+                                          +1, st));
+    HIP_TRY(transpose(fields, (int)batch, pn, st));
+    HIP_TRY(centred_rows<LOAD_PLAIN>(RowArgs{fields, fields, nullptr, nullptr, 1, lines, log2m}, pn, +1, st));
+    // direction by direction, each by the same launches: its bits do not depend on P or on its neighbours
+    for (int p = 0; p < P; ++p) {
+        float* out = dI + (size_t)p * groups * cells;
+        HIP_TRY(centred_rows<LOAD_TIMES_MASK>(RowArgs{(const float2*)kernels, tang, (const float2*)dMaskFT + (size_t)p * cells, nullptr, 1,
+                                                      lines, log2m}, pn, +1, st));
+        HIP_TRY(transpose(tang, (int)batch, pn, st));
+        if (accumulate) {
+            hipLaunchKernelGGL(k_transpose_real, tgrid, dim3(256), 0, st, (const float*)out, sums, pn);
+            HIP_TRY(hipGetLastError());
+        }
+        HIP_TRY((centred_rows<LOAD_PLAIN, STORE_FOLD>(RowArgs{tang, tang, fields, nullptr, K, (long long)groups * pn, log2m, nullptr,
+                                                              accumulate ? 1 : 0, sums}, pn, +1, st)));
+        hipLaunchKernelGGL(k_transpose_real, tgrid, dim3(256), 0, st, (const float*)sums, out, pn);
+        HIP_TRY(hipGetLastError());
+    }
     return LITHO_OK;
 }
 

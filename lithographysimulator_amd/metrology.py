@@ -252,12 +252,13 @@ class OPCResult:
     best_iteration: int = 0
     epe_nm: Optional[np.ndarray] = None
     epe_history: List[np.ndarray] = field(default_factory=list)
+    jacobian: Optional[np.ndarray] = None   # step="meef": the frozen MEEF matrix J[i, j] = dEPE_i / dbias_j of the first iterate
 
 
 def correctLayout(polygons, pixelNumber, pixelSize, origin, wavelength, pupil, source, threshold, *, spacing, iterations=6,
                   gain=0.6, maxBias, antialias=16, exposed=True, diffusionLength=0.0, searchRange=8.0,
                   imager: Optional[Callable] = None, epe: Optional[Callable] = None, device=None, model="abbe",
-                  kernels=64, socs=None) -> OPCResult:
+                  kernels=64, socs=None, step="damped", sensitivity: Optional[Callable] = None) -> OPCResult:
     """Model-based optical proximity correction of a Manhattan layout (nanometres; the polygons are the mask's openings):
     edge fragments of at most `spacing` are moved along their normals until the printed contour lies on the target's edges.
     Every iteration: biasLayout -> rasterizeLayout(antialias=) -> Mask(transmission=) -> fraunhofer -> abbeIntensity through
@@ -275,7 +276,28 @@ def correctLayout(polygons, pixelNumber, pixelSize, origin, wavelength, pupil, s
     and `source`; with model="socs" only, one plane, and its pn must be the window's (ValueError otherwise).
 
     `imager(polygons) -> image` replaces the raster-to-image steps and `epe(image) -> EPE in nm per site` (NaN where nothing
-    is found) the measurement, so the loop itself runs without a GPU on any model; give both or neither."""
+    is found) the measurement, so the loop itself runs without a GPU on any model; give both or neither.
+
+    `step="damped"` (the default) is the update above, whose model of the process is the identity: every fragment moves its own
+    edge one for one and nobody else's.  `step="meef"` replaces that model by the MEEF matrix J[i, j] = dEPE_i / dbias_j, computed
+    once at the first iterate and kept (a frozen Jacobian: one Jacobian, then one image per iteration).  It needs model="socs"
+    (ValueError otherwise): mask tangents go through the SOCS kernels (sensitivity.epeJacobian, forward mode, one pass per
+    fragment).  On the sites that found an edge the step solves (J^T J + mu diag J^T J) delta = -J^T e in float64 on the host,
+    with the accept / reject rule of calibrate._levenberg_marquardt -- an iterate that is not better (fewer lost sites, then lower
+    RMS) than the best so far is not accepted, the next step starts from the best again and mu grows tenfold, an accepted one
+    divides mu by ten -- then the +-maxBias clip.  mu starts at that rule's floor, 1e-12 (on a frozen Jacobian of a nearly linear
+    map the undamped step is the right first try), and a rejection raises it to at least 1e-3, the rule's own start.  Sites that
+    found no edge keep the +maxBias / 6 rule.  `sensitivity(polygons, bias) -> J [S,S]` replaces epeJacobian when imager= and epe=
+    are given; the loop then runs on the CPU on any model.  `gain` is not used by this step; OPCResult.jacobian holds J."""
+    if step not in ("damped", "meef"):
+        raise ValueError(f"correctLayout: step must be 'damped' or 'meef'; got {step!r}")
+    if step == "meef" and imager is None and model != "socs":
+        raise ValueError("correctLayout: step='meef' needs model='socs' (mask tangents go through the SOCS kernels), or imager=, "
+                         "epe= and sensitivity= of the caller's own model")
+    if step == "meef" and imager is not None and sensitivity is None:
+        raise ValueError("correctLayout: step='meef' with imager= and epe= needs sensitivity(polygons, bias) -> J as well")
+    if sensitivity is not None and (step != "meef" or imager is None):
+        raise ValueError("correctLayout: sensitivity= goes with step='meef' and the imager= / epe= pair")
     if (imager is None) != (epe is None):
         raise ValueError("correctLayout: imager and epe replace the image and its measurement together; give both or neither")
     if model not in ("abbe", "socs"):
@@ -304,8 +326,19 @@ def correctLayout(polygons, pixelNumber, pixelSize, origin, wavelength, pupil, s
         raise ValueError("correctLayout: the layout has no edges")
     biasLayout(target, sites, np.zeros(len(sites)))            # raises for a non-Manhattan layout before any image is made
     if imager is None:
+        state = {}
         imager, epe = _gpu_model(pn, ps, origin, wavelength, pupil, source, threshold, antialias, exposed, diffusionLength,
-                                 searchRange, sites, device, model, kernels, socs)
+                                 searchRange, sites, device, model, kernels, socs, state)
+        if step == "meef":
+            if float(diffusionLength) > 0.0:
+                raise ValueError("correctLayout: step='meef' differentiates the aerial image; diffusionLength > 0 is not built")
+
+            def sensitivity(polys, b):
+                from .sensitivity import epeJacobian
+                return epeJacobian(target, sites, b, state["socs"], pn, ps, origin, wavelength, threshold, antialias=antialias,
+                                   searchRange=searchRange)[1]
+    if step == "meef":
+        return _meef_loop(target, sites, imager, epe, sensitivity, iterations, maxBias)
     bias = np.zeros(len(sites))
     history, measured, best = [], [], None
     for it in range(iterations):
@@ -325,9 +358,49 @@ def correctLayout(polygons, pixelNumber, pixelSize, origin, wavelength, pupil, s
     return OPCResult(best[1], best[2], history, sites, best[0], best[3], measured)
 
 
+def _meef_loop(target, sites, imager, epe, sensitivity, iterations, maxBias):
+    """correctLayout(step="meef"): Levenberg-Marquardt steps on a Jacobian frozen at the first iterate."""
+    S = len(sites)
+    bias = np.zeros(S)
+    history, measured, best, J, mu = [], [], None, None, 1e-12
+    for it in range(iterations):
+        polys = biasLayout(target, sites, bias)
+        e = np.asarray(epe(imager(polys)), dtype=np.float64).reshape(-1)
+        if e.shape[0] != S:
+            raise ValueError(f"correctLayout: epe returned {e.shape[0]} values for {S} sites")
+        measured.append(e.copy())
+        lost = np.isnan(e)
+        found = e[~lost]
+        rms = float(np.sqrt(np.mean(found * found))) if found.size else float("inf")
+        worst = float(np.abs(found).max()) if found.size else float("inf")
+        history.append((rms, worst, int(lost.sum())))
+        if J is None:
+            J = np.asarray(sensitivity(polys, bias.copy()), dtype=np.float64)
+            if J.shape != (S, S):
+                raise ValueError(f"correctLayout: sensitivity returned {J.shape} for {S} sites")
+        accepted = best is None or (int(lost.sum()), rms) < (history[best[0]][2], history[best[0]][0])
+        if accepted:
+            best = (it, polys, bias.copy(), e.copy())
+            if it:
+                mu = max(mu / 10.0, 1e-12)
+        else:
+            mu = max(mu * 10.0, 1e-3)
+        b0, e0 = best[2], best[3]                                   # every step starts from the best iterate
+        gone = np.isnan(e0)
+        Jf = np.where(np.isfinite(J[~gone]), J[~gone], 0.0)         # a row of a site that lost its edge in the Jacobian's image
+        A, g = Jf.T @ Jf, Jf.T @ e0[~gone]
+        diag = np.diag(A)
+        move = (diag > 0.0) & ~gone                                 # a fragment without a column, or without an edge, does not move
+        delta = np.zeros(S)
+        if move.any():
+            delta[move] = np.linalg.solve((A + mu * np.diag(diag))[np.ix_(move, move)], -g[move])
+        bias = np.clip(np.where(gone, b0 + maxBias / 6.0, b0 + delta), -maxBias, maxBias)
+    return OPCResult(best[1], best[2], history, sites, best[0], best[3], measured, J)
+
+
 def _gpu_model(pn, ps, origin, wavelength, pupil, source, threshold, antialias, exposed, diffusionLength, searchRange, sites,
-               device, model="abbe", kernels=64, socs=None):
-    """(imager, epe) of correctLayout on the HIP path."""
+               device, model="abbe", kernels=64, socs=None, state=None):
+    """(imager, epe) of correctLayout on the HIP path; `state` (a dict) receives the SOCS kernels under "socs"."""
     import torch
 
     from .imageformation import PlanCache, ShapeError, abbeIntensity, postProcess, resistContour
@@ -343,7 +416,7 @@ def _gpu_model(pn, ps, origin, wavelength, pupil, source, threshold, antialias, 
     eps, N = nat.epsilon_n(4.0 / pn, ps, float(wavelength))
     pupil = pupil.to(device=dev, dtype=torch.complex64).contiguous()
     cache = PlanCache()
-    state = {}
+    state = {} if state is None else state
     site_rows = torch.from_numpy(sites.sites_px).to(dev)
     if model == "socs" and socs is not None:
         from .socs import hopkinsIntensity
