@@ -73,6 +73,10 @@ build/develop_grad.o: $(CSRC)/develop_grad.hip $(CSRC)/resist_volume.hpp $(CSRC)
 build/peb.o: $(CSRC)/peb.hip $(CSRC)/resist_volume.hpp $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
+# tiled imaging: the stitch copy and the seam measure, plain fp32 copies and differences
+build/tiling.o: $(CSRC)/tiling.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -ffp-contract=off -c $< -o $@
 build/common.o: $(CSRC)/common.hip $(CSRC)/engine_common.hpp include/litho_abbe.h
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -84,7 +88,7 @@ build/plan_dry_run.o: $(CSRC)/plan_dry_run.cpp $(CSRC)/abbe_plan.hpp include/lit
 build/contour_link.o: $(CSRC)/contour_link.cpp include/litho_abbe.h
 	@mkdir -p build
 	g++ -O2 -std=c++17 -fPIC -Wall -Wextra -c $< -o $@
-$(OUT): build/abbe_engine.o build/optics.o build/layout.o build/metrology.o build/contour.o build/socs.o build/socs_grad.o build/film.o build/develop.o build/develop_grad.o build/peb.o build/common.o build/plan_dry_run.o build/contour_link.o $(INST) $(INSTW)
+$(OUT): build/abbe_engine.o build/optics.o build/layout.o build/metrology.o build/contour.o build/socs.o build/socs_grad.o build/film.o build/develop.o build/develop_grad.o build/peb.o build/tiling.o build/common.o build/plan_dry_run.o build/contour_link.o $(INST) $(INSTW)
 	@mkdir -p lithographysimulator_amd/lib
 	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -o $@ $^
 

@@ -923,6 +923,45 @@ int litho_socs_vjp(const void *kernels, const void *maskFT, const float *gradI, 
 size_t litho_socs_jvp_work_bytes(int groups, int K, int P, int pn);
 int litho_socs_jvp(const void *kernels, const void *maskFT, const void *dMaskFT, int P, int groups, int K, int pn, int N, float *dI,
                    int accumulate, void *work, size_t work_bytes, void *stream);
+/* litho_socs_image_batch: the Hopkins image of MANY mask spectra through one kernel set in one call,
+ *   out[b][g] (+)= sum_{k < K} | L(kernels[g K + k] . maskFTs[b]) |^2,   b < tiles, g < groups,
+ * k ascending, each term added as fmaf(re, re, im im) to one running fp32 sum per output element that lives in LDS through the
+ * second row pass: no K-plane stack is written and nothing is atomic.  accumulate != 0 starts the sums from out, so calls on
+ * consecutive chunks of the kernels continue the same sequence of additions (bit for bit what one call on all of them gives);
+ * accumulate == 0 starts from zero.  The bits of out[b] depend on maskFTs[b] and the kernels alone: not on tiles, on b, or on how
+ * the caller cuts the spectra into calls.  kernels complex64 [groups K,pn,pn] as for litho_socs_vjp (groups = the planes of a
+ * through-focus set), maskFTs complex64 [tiles,pn,pn], out fp32 [tiles,groups,pn,pn].  work: litho_socs_image_batch_work_bytes(tiles,
+ * groups, K, pn) device bytes = tiles groups K pn^2 complex (the fields between the two row passes) + tiles groups pn^2 floats (the
+ * image in the transposed layout); 0 for a bad argument, less is LITHO_E_WORKSPACE.  Domain and codes as litho_socs_vjp, and
+ * LITHO_E_ARG for tiles < 1, groups > 65535 or tiles groups K pn > INT_MAX lines; every check precedes any launch. */
+size_t litho_socs_image_batch_work_bytes(int tiles, int groups, int K, int pn);
+int litho_socs_image_batch(const void *kernels, const void *maskFTs, int tiles, int groups, int K, int pn, int N, float *out,
+                           int accumulate, void *work, size_t work_bytes, void *stream);
+
+/* ---- Tiled imaging of large layouts (csrc/tiling.hip; no reference counterpart, checked against numpy slicing in
+ * tests/tiling_oracle.py).  A layout larger than one window is imaged as `count` windows of nt x nt pixels on one pixel lattice;
+ * each window's image is trusted on its core, the `core` x `core` pixels that start at (j0, j0), and the cores are disjoint.
+ *
+ * litho_tiles_stitch: image[p][place[t][0] + i][place[t][1] + j] = tiles[t][p][j0 + i][j0 + j],  0 <= i, j < core, t < count,
+ * p < planes; a pixel outside [0, n) is skipped (an edge tile is clipped) and nothing else of image is written -- the caller
+ * zeroes it.  tiles fp32 [count,planes,nt,nt], place device int32 [count][2] = (row, col), any integers, image fp32 [planes,n,n].
+ * A pure copy, one wave per core row.  LITHO_E_ARG: a null pointer, count, planes, nt, core or n < 1, j0 < 0, j0 + core > nt,
+ * or count planes core > INT_MAX rows.
+ *
+ * litho_tiles_seam: how much two neighbouring windows disagree where their cores meet.  neighbours device int32 [count][2] =
+ * (right, lower) tile of tile t, the tiles whose windows lie `core` columns / rows further; a value outside [0, count) means none.
+ * With a = tiles[t][p] and b = tiles[right][p], b[r][c] shows what a[r][c + core] shows, and
+ *   out[t][p][0] = max over i < core, d in {0, 1} of | a[j0 + i][j0 + core - 1 + d] - b[j0 + i][j0 - 1 + d] |
+ * -- the two pixel columns either side of the common core boundary, on the core's rows; out[t][p][1] likewise for the lower
+ * neighbour on the two rows either side, over the core's columns.  NaN (0x7fc00000) where there is no neighbour; a NaN difference
+ * is ignored by the maximum (fmaxf).  One wave per (tile, plane, side), lanes stride the line, the maximum through the xor
+ * butterfly: no atomics, one fixed order.  out fp32 [count,planes,2], every element written.  LITHO_E_ARG: as above, and
+ * j0 < 1 or j0 + core >= nt (both windows must hold both lines: a halo of at least one pixel).
+ * Both calls are asynchronous, allocate nothing and wait for nothing. */
+int litho_tiles_stitch(const float *tiles, int count, int planes, int nt, const int32_t *place, int j0, int core, float *image, int n,
+                       void *stream);
+int litho_tiles_seam(const float *tiles, int count, int planes, int nt, const int32_t *neighbours, int j0, int core, float *out,
+                     void *stream);
 
 /* ---- Source gradients of Abbe imaging (csrc/socs_grad.hip; no reference counterpart, checked against tests/source_grad_oracle.py).
  * The weighted Abbe sum I = sum_s w_s |E_s|^2 is linear in the weights, and source point s is the coherent kernel roll(P, d_s) of

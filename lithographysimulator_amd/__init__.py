@@ -11,7 +11,10 @@ from .metrology import (LayoutSites, OPCResult, biasLayout, correctLayout,      
                         imageRegistration, layoutSites, measureEPE)
 from .contours import (Contours, contourVertices, contoursToGDSII, contoursToLayout,   # noqa: F401
                        doseFocusEnvelope, processVariationBand, simplifyContour, traceContours)
-from .socs import SOCSKernels, hopkinsImage, hopkinsIntensity, socsKernels          # noqa: F401
+from .socs import (SOCSKernels, hopkinsImage, hopkinsIntensity, hopkinsIntensityBatch,  # noqa: F401
+                   socsKernels)
+from .tiling import (TiledImage, TilePlan, hopkinsImageTiled, planTiles,              # noqa: F401
+                     tileValidRegion)
 from .ilt import (ILTResult, bakedResistModel, developedResistModel, hopkinsFields,     # noqa: F401
                   hopkinsGradient, hopkinsIntensityAD, maskSpectrumAdjoint, optimizeMask, postProcessAdjoint)
 from .smo import (SourceResult, optimizeSource, optimizeSourceMask, projectedStep,      # noqa: F401
@@ -60,4 +63,5 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "exposeAcidTangent", "bakeTangent", "bakeParameterTangent", "developmentRateTangent", "amplifiedRateTangent",
            "rateParameterTangent", "developmentTimeTangent", "resistProfileTangent", "calibrationJacobian",
            "hopkinsTangent", "postProcessTangent", "edgeCoverageTangent", "measureEPETangent", "measureCDTangent", "epeJacobian",
-           "maskErrorFactor"]
+           "maskErrorFactor",
+           "hopkinsIntensityBatch", "tileValidRegion", "planTiles", "hopkinsImageTiled", "TilePlan", "TiledImage"]

@@ -33,6 +33,11 @@
 // A direction's first row pass is the fields' own (the kernel times a plane on the load -- the plane is dM instead of M); its second
 // row pass folds each output against the stored field as it comes out (STORE_FOLD), so a tangent field is never stored.
 // Checked against tests/socs_tangent_oracle.py.
+//
+// The image of a batch of mask spectra (litho_socs_image_batch) is the same two row passes with two other ends: the first reads
+// kernel plane and mask plane per item (LOAD_BATCH), the second adds |E|^2 over a group's K items into the running sums that
+// STORE_FOLD keeps (STORE_SQUARE), so the K fields of a tile meet in LDS and no K-plane stack of intensities is written.
+// Checked against tests/socs_oracle.py (kernel_image).
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -45,10 +50,11 @@
 namespace litho {
 
 // What the row pass multiplies into the line as it loads it.
-enum : int { LOAD_PLAIN = 0, LOAD_TIMES_MASK = 1, LOAD_TIMES_GRAD = 2, LOAD_ROLLED = 3 };
-// What it does with the outputs: writes them, reduces mul_r . |y|^2 over the line to one number, or folds them against a stored
-// field into a running real sum over the K items of a group (the tangent of the image, litho_socs_jvp).
-enum : int { STORE_FIELD = 0, STORE_REDUCE = 1, STORE_FOLD = 2 };
+enum : int { LOAD_PLAIN = 0, LOAD_TIMES_MASK = 1, LOAD_TIMES_GRAD = 2, LOAD_ROLLED = 3, LOAD_BATCH = 4 };
+// What it does with the outputs: writes them, reduces mul_r . |y|^2 over the line to one number, folds them against a stored
+// field into a running real sum over the K items of a group (the tangent of the image, litho_socs_jvp), or sums their squared
+// moduli over the K items of a group (the image itself, litho_socs_image_batch).
+enum : int { STORE_FIELD = 0, STORE_REDUCE = 1, STORE_FOLD = 2, STORE_SQUARE = 3 };
 
 // `lines` lines of pn = 2^LOG2P samples, line l = row (l mod pn) of item (l / pn); each becomes its centred pruned transform
 //   dst[q] = sum_i src[i] exp(SIGN 2 pi i (i - c)(q - c) / N),  q in [0, pn),  N = pn << log2m.
@@ -69,6 +75,12 @@ enum : int { STORE_FIELD = 0, STORE_REDUCE = 1, STORE_FOLD = 2 };
 // per output q, touched by the one thread that owns q and by nobody else between the two barriers around the loop; they start
 // from partial[l] when per_point != 0 (the accumulate flag of this mode) and from zero otherwise.  One sum per element in item
 // order, no atomics.
+// LOAD_BATCH: many mask spectra through one kernel set.  Item b is kernel plane (b mod per_point) under mask plane (b / per_point):
+//   src[i] = src_planes[b mod per_point][row][i] . mul_c[b / per_point][row][i]
+// (src holds the per_point = groups K kernel planes once, mul_c one plane per tile; dst is the item's own plane, never src).
+// STORE_SQUARE: STORE_FOLD's walk and LDS layout with another term: item g K + k's line adds
+//   partial[l][q] += fmaf(dst[q].re, dst[q].re, dst[q].im dst[q].im)
+// -- the image of group l / pn, nothing read besides the line.  per_point != 0 is again the accumulate flag.
 template <int LOG2P, int SIGN, int LOAD, int STORE = STORE_FIELD>
 __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(const float2* src, float2* dst,
                                                                             const float2* __restrict__ mul_c,
@@ -96,14 +108,26 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
             sums_all[i] = (per_point != 0 && fold_base + i < fold_end) ? partial[fold_base + i] : 0.f;
         __syncthreads();
     }
-    const int items = STORE == STORE_FOLD ? per_group : 1;
+    if (STORE == STORE_SQUARE) {
+        for (int i = threadIdx.x; i < LS::L * PN; i += LS::THREADS)
+            sums_all[i] = (per_point != 0 && fold_base + i < fold_end) ? partial[fold_base + i] : 0.f;
+        __syncthreads();
+    }
+    const int items = (STORE == STORE_FOLD || STORE == STORE_SQUARE) ? per_group : 1;
     for (int item_k = 0; item_k < items; ++item_k) {
         long long l = active ? line : 0;
         const int row = (int)(l & (PN - 1));
         if (STORE == STORE_FOLD) l = ((((l >> LOG2P) * per_group) + item_k) << LOG2P) + row;
+        if (STORE == STORE_SQUARE) l = ((((l >> LOG2P) * per_group) + item_k) << LOG2P) + row;
         const float2* in = src + (size_t)l * PN;
         float2* out = dst + (size_t)l * PN;
         const float2* fold = mul_c + (size_t)l * PN;             // STORE_FOLD only
+        const float2* tile_m = mul_c;                            // LOAD_BATCH only: the item's mask plane
+        if (LOAD == LOAD_BATCH) {
+            const long long item = l >> LOG2P, tile = item / per_point;
+            in = src + ((size_t)(item - tile * per_point) * PN + row) * PN;
+            tile_m = mul_c + (size_t)tile * PN * PN;
+        }
         unsigned dx = 0;
         if (LOAD == LOAD_ROLLED) {
             const long long item = l >> LOG2P, point = item / per_point;
@@ -121,6 +145,7 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
             if (active) {
                 v = LOAD == LOAD_ROLLED ? in[((unsigned)i - dx) & (PN - 1)] : in[i];
                 if (LOAD == LOAD_TIMES_MASK || LOAD == LOAD_ROLLED) v = cmul(v, mul_c[(size_t)row * PN + i]);
+                if (LOAD == LOAD_BATCH) v = cmul(v, tile_m[(size_t)row * PN + i]);
                 if (LOAD == LOAD_TIMES_GRAD) {
                     const float g = mul_r[((size_t)((l >> LOG2P) % per_point / per_group) * PN + row) * PN + i];
                     v = make_float2(v.x * g, v.y * g);
@@ -158,7 +183,8 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
                     else if (STORE == STORE_FOLD) {
                         const float2 ev = fold[q];
                         sums[q] += 2.0f * fmaf(ev.x, x[e].x, ev.y * x[e].y);
-                    } else out[q] = x[e];
+                    } else if (STORE == STORE_SQUARE) sums[q] += fmaf(x[e].x, x[e].x, x[e].y * x[e].y);
+                    else out[q] = x[e];
                 }
             }
         }
@@ -178,6 +204,11 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
         }
     }
     if (STORE == STORE_FOLD) {
+        __syncthreads();
+        for (int i = threadIdx.x; i < LS::L * PN; i += LS::THREADS)
+            if (fold_base + i < fold_end) partial[fold_base + i] = sums_all[i];
+    }
+    if (STORE == STORE_SQUARE) {
         __syncthreads();
         for (int i = threadIdx.x; i < LS::L * PN; i += LS::THREADS)
             if (fold_base + i < fold_end) partial[fold_base + i] = sums_all[i];
@@ -344,8 +375,9 @@ static hipError_t centred_rows(const RowArgs& a, int pn, int sign, hipStream_t s
     return for_log2(log2_exact(pn), [&](auto l2) {
         constexpr int LOG2P = decltype(l2)::value;
         using LS = LineShape<LOG2P>;
-        // STORE_FOLD keeps the running sums of its L lines behind the exchange buffers and the twiddle tables
-        constexpr size_t LDS = LS::LDS_BYTES + (STORE == STORE_FOLD ? sizeof(float) * LS::L * (size_t(1) << LOG2P) : 0);
+        // STORE_FOLD and STORE_SQUARE keep the running sums of their L lines behind the exchange buffers and the twiddle tables
+        constexpr size_t LDS =
+            LS::LDS_BYTES + ((STORE == STORE_FOLD || STORE == STORE_SQUARE) ? sizeof(float) * LS::L * (size_t(1) << LOG2P) : 0);
         static_assert(LDS <= 64 * 1024, "the row pass stays inside the default LDS allowance");
         if (sign > 0)
             hipLaunchKernelGGL((k_centred_rows<LOG2P, +1, LOAD, STORE>), LS::grid(a.lines), dim3(LS::THREADS), LDS, st, a.src,
@@ -515,6 +547,55 @@ int litho_socs_jvp(const void* kernels, const void* maskFT, const void* dMaskFT,
         hipLaunchKernelGGL(k_transpose_real, tgrid, dim3(256), 0, st, (const float*)sums, out, pn);
         HIP_TRY(hipGetLastError());
     }
+    return LITHO_OK;
+}
+
+// The image of many mask spectra: out[b][g] (+)= sum_k |L(kernels[gK+k] . maskFTs[b])|^2.  Workspace: the fields of every (tile,
+// plane, kernel) between their two row passes, and the images in the transposed layout, where the second pass sums them.
+size_t litho_socs_image_batch_work_bytes(int tiles, int groups, int K, int pn)
+{
+    using namespace litho;
+    if (tiles < 1 || groups < 1 || groups > 65535 || K < 1 || !fft_size_ok(pn)) return 0;
+    const long long planes = (long long)tiles * groups;
+    if (planes > INT_MAX || planes * K > INT_MAX || planes * K * pn > INT_MAX) return 0;
+    const size_t cells = (size_t)pn * pn;
+    return (size_t)planes * K * cells * sizeof(float2) + (size_t)planes * cells * sizeof(float);
+}
+
+int litho_socs_image_batch(const void* kernels, const void* maskFTs, int tiles, int groups, int K, int pn, int N, float* out,
+                           int accumulate, void* work, size_t work_bytes, void* stream)
+{
+    using namespace litho;
+    if (!kernels || !maskFTs || !out || !work || tiles < 1 || groups < 1 || groups > 65535 || K < 1) return LITHO_E_ARG;
+    const long long planes = (long long)tiles * groups;
+    if (planes > INT_MAX || planes * K > INT_MAX) return LITHO_E_ARG;
+    const long long batch = planes * K;
+    const int rc = check_sizes(batch, pn, N);
+    if (rc != LITHO_OK) return rc;
+    if (work_bytes < litho_socs_image_batch_work_bytes(tiles, groups, K, pn)) return LITHO_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t cells = (size_t)pn * pn;
+    float2* fields = (float2*)work;                                // item (b groups + g) K + k between its passes
+    float* sums = (float*)(fields + (size_t)batch * cells);        // out[b][g]^T, plane by plane
+    const int log2m = log2_exact(N) - log2_exact(pn);
+    const unsigned tr = (unsigned)((pn + TR_TILE - 1) / TR_TILE);
+    // the real transpose of `planes` planes, at most 65535 per launch (grid.z)
+    auto transpose_real = [&](const float* from, float* to) {
+        for (long long p0 = 0; p0 < planes; p0 += 65535) {
+            const unsigned nb = (unsigned)(planes - p0 < 65535 ? planes - p0 : 65535);
+            hipLaunchKernelGGL(k_transpose_real, dim3(tr, tr, nb), dim3(256), 0, st, from + (size_t)p0 * cells, to + (size_t)p0 * cells, pn);
+        }
+        return hipGetLastError();
+    };
+    HIP_TRY(fill_twiddles(st));
+    // rows of phi . M for every (tile, plane, kernel), transpose, then the columns, squared and summed over k as they come out
+    HIP_TRY(centred_rows<LOAD_BATCH>(RowArgs{(const float2*)kernels, fields, (const float2*)maskFTs, nullptr, 1, batch * pn, log2m, nullptr,
+                                             groups * K}, pn, +1, st));
+    HIP_TRY(transpose(fields, (int)batch, pn, st));
+    if (accumulate) HIP_TRY(transpose_real(out, sums));
+    HIP_TRY((centred_rows<LOAD_PLAIN, STORE_SQUARE>(RowArgs{fields, fields, nullptr, nullptr, K, planes * pn, log2m, nullptr,
+                                                            accumulate ? 1 : 0, sums}, pn, +1, st)));
+    HIP_TRY(transpose_real(sums, out));
     return LITHO_OK;
 }
 

@@ -111,18 +111,24 @@ def _window_origin(polygons, pn, pixelSize):
 
 
 def layoutSites(polygons: Sequence[np.ndarray], spacing: float, pixelSize: float, origin, pixelNumber: int,
-                wavelength: float) -> LayoutSites:
+                wavelength: float, registration=None) -> LayoutSites:
     """Measurement sites on every edge of every polygon (nanometres, any angle; made counter-clockwise as polygonEdges does):
     an edge of length L is cut into ceil(L / spacing) equal fragments, each with one site at its midpoint and the unit
     outward normal (dy, -dx) / L.  `sites_px` places them on the image grid: `origin` exactly as rasterizeLayout takes it
-    (None: the window centred on the bounding box), then the registration of imageRegistration."""
+    (None: the window centred on the bounding box), then the registration of imageRegistration.
+    `registration` = (n_out, scale, offset) replaces the single window's own map J = scale * i + offset from raster pixel i to
+    image pixel J: what a stitched image of several windows carries (tiling.py); None is the window's, as before."""
     spacing, ps, pn = float(spacing), float(pixelSize), int(pixelNumber)
     if not (spacing > 0.0 and math.isfinite(spacing)) or not (ps > 0.0 and math.isfinite(ps)):
         raise ValueError(f"layoutSites: spacing and pixelSize must be finite and > 0; got {spacing} and {ps}")
     polys = _counter_clockwise(polygons)
     if origin is None:
         origin = _window_origin(polys, pn, ps)
-    _, scale, offset = _registration(pn, ps, wavelength)
+    if registration is None:
+        _, scale, offset = _registration(pn, ps, wavelength)
+    else:
+        _, scale, offset = registration
+        scale, offset = float(scale), float(offset)
     xy, nrm, pidx, eidx, ends = [], [], [], [], []
     for pi, q in enumerate(polys):
         if len(q) < 3:

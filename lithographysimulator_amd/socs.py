@@ -316,6 +316,57 @@ def hopkinsIntensity(maskFT, socs, N, out=None, options=None, kernelChunk=None):
     return out
 
 
+def hopkinsIntensityBatch(maskFTs, socs, N, out=None, tileChunk=None):
+    """hopkinsIntensity's image for MANY mask spectra in one call per chunk: fp32 [B,pn,pn] (or [B,planes,pn,pn] for the kernels
+    of a pupil stack) from `maskFTs` complex [B,pn,pn] -- the windows of a tiled layout (tiling.py), the masks of a correction
+    loop.  litho_socs_image_batch (csrc/socs_grad.hip): B x K fields in two row passes, the sum over the kernels kept in LDS in
+    the second, so no K-plane stack is written; one running fp32 sum per pixel in kernel order, no atomics.  This is NOT
+    hopkinsIntensity's route (the Abbe engine and litho_socs_fold), so the two agree to rounding and not bit for bit.
+
+    `tileChunk` spectra go into one native call; it bounds the workspace, chunk * planes * (K * 8 + 4) * pn^2 bytes (default:
+    what keeps it under STACK_BYTES, at least 1; where a single spectrum's workspace is larger than that, the kernels are walked
+    in chunks as well, each continuing the running sums of the one before).  A spectrum's bits depend on that spectrum and the
+    kernels alone: not on B, on its place in the batch or on `tileChunk`.  `out`: accumulated into when given."""
+    from .imageformation import ShapeError
+    if not isinstance(socs, SOCSKernels):
+        raise TypeError("hopkinsIntensityBatch: socs must be the SOCSKernels socsKernels returned")
+    pn, planes, K = socs.pn, socs.planes, socs.K
+    if (not isinstance(maskFTs, torch.Tensor) or not maskFTs.is_complex() or maskFTs.dim() != 3 or maskFTs.shape[0] < 1
+            or tuple(maskFTs.shape[-2:]) != (pn, pn)):
+        raise ShapeError(f"maskFTs must be a complex tensor [B,{pn},{pn}] to match the kernels; got "
+                         f"{getattr(maskFTs, 'dtype', type(maskFTs).__name__)} {tuple(getattr(maskFTs, 'shape', ()))}")
+    dev = nat.require_gpu(maskFTs.device)
+    if socs.kernels.device != dev:
+        raise ShapeError(f"the kernels live on {socs.kernels.device}, the mask spectra on {dev}")
+    B = int(maskFTs.shape[0])
+    cells = pn * pn
+    if tileChunk is None:
+        tileChunk = max(1, STACK_BYTES // (planes * (K * 8 + 4) * cells))
+    tileChunk = int(tileChunk)
+    if tileChunk < 1:
+        raise ValueError(f"hopkinsIntensityBatch: tileChunk must be >= 1; got {tileChunk}")
+    tileChunk = min(tileChunk, B)
+    size = K if planes * (K * 8 + 4) * cells <= STACK_BYTES else max(1, (STACK_BYTES // (planes * cells) - 4) // 8)
+    m = maskFTs.detach().to(torch.complex64).contiguous()
+    out, given = _accumulate_into(out, (B, planes, pn, pn) if socs.stacked else (B, pn, pn), torch.float32, dev)
+    lib = nat.lib()
+    work = None
+    for b0 in range(0, B, tileChunk):
+        nb = min(tileChunk, B - b0)
+        for i, (stack, _, k) in enumerate(socs.chunks(min(size, K))):
+            nbytes = int(lib.litho_socs_image_batch_work_bytes(nb, planes, k, pn))
+            if nbytes == 0:
+                raise ValueError(f"hopkinsIntensityBatch: {nb} spectra x {planes} planes x {k} kernels at pn {pn} are more lines than "
+                                 "one call takes; pass a smaller tileChunk")
+            if work is None or work.numel() < nbytes:
+                work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            with torch.cuda.device(dev):
+                nat.check(lib.litho_socs_image_batch(nat.ptr(stack), nat.ptr(m[b0]), nb, planes, k, pn, int(N), nat.ptr(out[b0]),
+                                                     1 if (given or i > 0) else 0, nat.ptr(work), work.numel(), nat.stream_ptr(dev)),
+                          "litho_socs_image_batch")
+    return out
+
+
 def hopkinsImage(mask, maskFT, socs, pixelSize, deltaK, wavelength, normalize=False, options=None, kernelChunk=None):
     """abbeImage's post-processing (|.|, bilinear resample by 1 / epsilon, zero pad) on top of hopkinsIntensity: the same return
     shape as abbeImage with the pupil (stack) and source the kernels were made from.  `normalize` divides by the sum of the
