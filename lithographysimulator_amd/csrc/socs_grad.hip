@@ -1,8 +1,8 @@
-// socs_grad.hip -- mask gradients of Hopkins imaging: the K coherent fields of one mask spectrum and the adjoint (vector-Jacobian
-// product) of I = sum_k |E_k|^2 with respect to the mask spectrum.
+// socs_grad.hip -- the coherent fields of Hopkins imaging and what is differentiated through them: mask, source and pupil
+// gradients, the image tangent, the image of a batch of mask spectra.
 //
-//   E_k = L(phi_k . M),   L(X) = F X F^T,   F[q][i] = exp(+2 pi i (i - c)(q - c) / N),  c = pn / 2,  q, i in [0, pn)
-//   g   = 2 sum_p sum_k conj(phi_pk) . L^H(G_p . E_pk),   L^H(Y) = conj(F) Y conj(F)^T          (include/litho_abbe.h)
+//   E = L(X),   L(X) = F X F^T,   F[q][i] = exp(+2 pi i (i - c)(q - c) / N),  c = pn / 2,  q, i in [0, pn)
+//   L^H(Y) = conj(F) Y conj(F)^T                                                       (include/litho_abbe.h)
 //
 // L is the engine's chain at shift (0, 0) (imageformation.py:32-45: pad to N, centred inverse transform, centre pn x pn); the
 // engine keeps |E|^2 only, so the fields are formed here, by a route that never holds an N^2 array and runs no line longer than
@@ -13,35 +13,34 @@
 //
 // Layout as socs.hip: rows, tiled transpose, rows, tiled transpose -- every global access of a row pass is a contiguous line
 // (thread t of a line owns samples t + T e, fft_core.hpp); the twiddle table, the line geometry, the transpose and the dispatch on
-// the line size are plane_fft.hpp's, shared with socs.hip.  The elementwise products of both directions ride on the first row
-// pass's load (phi . M on the way in, G . E on the way back), the reduction over the batch is one running fp32 sum per element
-// in ascending item order: no atomics, so the result is deterministic and a chunked call gives the chunk-ordered sum.
-// No reference counterpart; checked against tests/socs_grad_oracle.py.
+// the line size are plane_fft.hpp's, shared with socs.hip.  There is one row kernel, k_centred_rows<size, sign, Load, Store>: what
+// a pass multiplies into its lines on the way in and what it does with the outputs are its two ends, small structs that carry
+// their own arguments (below).  Every entry is two_passes -- a first row pass with the entry's load into a stack of planes, the
+// transpose, a second row pass with the entry's store -- plus, where it has one, a reduction kernel:
 //
-// Source sensitivities (litho_source_sensitivity) are the same field code with two other ends: a source point is the coherent
-// kernel roll(P, d_s), so the first row pass reads the one pupil plane rolled (LOAD_ROLLED) instead of a stored kernel, and the
-// second row pass reduces G^T . |E|^2 over its line (STORE_REDUCE) instead of writing the field; a small kernel sums a point's
-// line partials.  Every sum has one fixed order and nothing is atomic, so a point's number depends on that point alone.
-// Checked against tests/source_grad_oracle.py.
+//   entry                      first pass: load, sign                   second pass: store      after it
+//   litho_socs_fields          TimesPlane(kernels . maskFT)        +1   Field                   transposed back
+//   litho_socs_vjp             TimesPlane(kernels . maskFT)        +1   Field                   transposed back
+//                              TimesGroupReal(fields . gradI)      -1   Field                   transposed back, k_vjp_reduce
+//   litho_socs_jvp             TimesPlane(kernels . maskFT)        +1   Field                   left transposed: E^T is kept
+//     per direction p          TimesPlane(kernels . dMaskFT[p])    +1   GroupSums<FoldTerm>     the real planes transposed
+//   litho_socs_image_batch     KernelTimesTile(kernels . maskFTs)  +1   GroupSums<SquareTerm>   the real planes transposed
+//   litho_source_sensitivity   Rolled(roll(pupils, d) . maskFT)    +1   LineReduce              k_sum_partials
+//   litho_pupil_vjp            Rolled(roll(pupils, d) . maskFT)    +1   Field                   transposed back
+//                              TimesGroupReal(fields . gradI)      -1   Field                   transposed back, k_pupil_reduce
+//   litho_pupil_project        no row pass: k_project_partial, k_project_final
 //
-// Pupil gradients (litho_pupil_vjp) join the two: the rolled load with the stored field (the field in natural layout), the
-// adjoint transform of the mask-gradient path with the G of the item's plane, and a reducing pass that undoes each point's roll
-// and sums the points in list order (k_pupil_reduce); litho_pupil_project pairs the result with a basis of wavefront maps in a
-// two-stage reduction of fixed order.  Checked against tests/pupil_grad_oracle.py.
-//
-// The tangent of the image (litho_socs_jvp) is forward mode through the same fields: dI = 2 sum_k Re(conj(E_k) . L(phi_k . dM)).
-// A direction's first row pass is the fields' own (the kernel times a plane on the load -- the plane is dM instead of M); its second
-// row pass folds each output against the stored field as it comes out (STORE_FOLD), so a tangent field is never stored.
-// Checked against tests/socs_tangent_oracle.py.
-//
-// The image of a batch of mask spectra (litho_socs_image_batch) is the same two row passes with two other ends: the first reads
-// kernel plane and mask plane per item (LOAD_BATCH), the second adds |E|^2 over a group's K items into the running sums that
-// STORE_FOLD keeps (STORE_SQUARE), so the K fields of a tile meet in LDS and no K-plane stack of intensities is written.
-// Checked against tests/socs_oracle.py (kernel_image).
+// The first pass always stores its field lines (StoreField) and the second always loads them plain (LoadPlain).  The running
+// sums of GroupSums and the G of LineReduce are real planes in the transposed layout, where the second pass meets them line for
+// line (transpose_real).  Every reduction is one running fp32 sum per element in one fixed order: no atomics, so every result
+// is deterministic, a chunked call gives the chunk-ordered sum, and a source point's numbers depend on that point alone.
+// No reference counterpart; checked against tests/socs_grad_oracle.py, source_grad_oracle.py, pupil_grad_oracle.py,
+// socs_tangent_oracle.py and socs_oracle.py (kernel_image).
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cstdint>
+#include <initializer_list>
 
 #include "../../include/litho_abbe.h"
 #include "engine_common.hpp"
@@ -49,45 +48,183 @@
 
 namespace litho {
 
-// What the row pass multiplies into the line as it loads it.
-enum : int { LOAD_PLAIN = 0, LOAD_TIMES_MASK = 1, LOAD_TIMES_GRAD = 2, LOAD_ROLLED = 3, LOAD_BATCH = 4 };
-// What it does with the outputs: writes them, reduces mul_r . |y|^2 over the line to one number, folds them against a stored
-// field into a running real sum over the K items of a group (the tangent of the image, litho_socs_jvp), or sums their squared
-// moduli over the K items of a group (the image itself, litho_socs_image_batch).
-enum : int { STORE_FIELD = 0, STORE_REDUCE = 1, STORE_FOLD = 2, STORE_SQUARE = 3 };
+// ---- The ways in.  open(l, row, log2p) takes line l = row `row` of item l >> log2p and returns at(i), its sample i in [0, pn). ----
 
-// `lines` lines of pn = 2^LOG2P samples, line l = row (l mod pn) of item (l / pn); each becomes its centred pruned transform
-//   dst[q] = sum_i src[i] exp(SIGN 2 pi i (i - c)(q - c) / N),  q in [0, pn),  N = pn << log2m.
-// LOAD_TIMES_MASK: src[i] is first multiplied by mul_c[row][i] (complex [pn][pn], the same for every item);
-// LOAD_TIMES_GRAD: by mul_r[(item mod per_point) / per_group][row][i] (real; per_point = the batch for litho_socs_vjp, whose items
-// are the planes themselves, groups K for the point-major chunks of litho_pupil_vjp).  dst may BE src: a line is in registers
-// before any of its outputs is written (every write follows a barrier that the line's threads reach with their loads consumed; a 16-point line has one
-// thread), and no workgroup touches another's lines.
-// LOAD_ROLLED: item b is plane (b mod per_point) of source point (b / per_point); src holds the per_point planes once and
-//   src[i] = plane[(row - dy) mod pn][(i - dx) mod pn] . mul_c[row][i],  (dy, dx) = shifts[point], read once per line.
-// STORE_REDUCE: nothing is written to dst; partial[line] = sum_q mul_r[(item mod per_point) / per_group][row][q] |dst[q]|^2, each
-// thread over the outputs it owns (r ascending, then e), then the line's threads in a fixed order: the xor butterfly of a wave's
-// shuffles, every lane ending with the same bits, and for a line of several waves their sums through LDS, added in wave order.
-// STORE_FOLD: `lines` counts the lines of the GROUPS, line l = row (l mod pn) of group (l / pn), and the workgroup walks the
-//   per_group = K items of its group in ascending order: item g K + k's line is transformed and
-//   partial[l][q] += 2 Re(conj(mul_c[g K + k][row][q]) . dst[q])
-// (mul_c: the stored fields, one plane per item; nothing is written to dst).  The running sums of a line live in LDS, fp32, one
-// per output q, touched by the one thread that owns q and by nobody else between the two barriers around the loop; they start
-// from partial[l] when per_point != 0 (the accumulate flag of this mode) and from zero otherwise.  One sum per element in item
-// order, no atomics.
-// LOAD_BATCH: many mask spectra through one kernel set.  Item b is kernel plane (b mod per_point) under mask plane (b / per_point):
-//   src[i] = src_planes[b mod per_point][row][i] . mul_c[b / per_point][row][i]
-// (src holds the per_point = groups K kernel planes once, mul_c one plane per tile; dst is the item's own plane, never src).
-// STORE_SQUARE: STORE_FOLD's walk and LDS layout with another term: item g K + k's line adds
-//   partial[l][q] += fmaf(dst[q].re, dst[q].re, dst[q].im dst[q].im)
-// -- the image of group l / pn, nothing read besides the line.  per_point != 0 is again the accumulate flag.
-template <int LOG2P, int SIGN, int LOAD, int STORE = STORE_FIELD>
-__global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(const float2* src, float2* dst,
-                                                                            const float2* __restrict__ mul_c,
-                                                                            const float* __restrict__ mul_r, int per_group,
-                                                                            long long lines, int log2m,
-                                                                            const int32_t* __restrict__ shifts, int per_point,
-                                                                            float* __restrict__ partial)
+// The item's own line.
+struct LoadPlain {
+    const float2* src;                                      // [items][pn][pn]
+    __device__ auto open(long long l, int, int log2p) const { return [in = src + ((size_t)l << log2p)](int i) { return in[i]; }; }
+};
+
+// src . plane: one complex plane, the same for every item (the kernels times a mask spectrum or a direction of it).
+struct LoadTimesPlane {
+    const float2* src;                                      // [items][pn][pn]
+    const float2* plane;                                    // [pn][pn]
+    __device__ auto open(long long l, int row, int log2p) const
+    {
+        const float2 *in = src + ((size_t)l << log2p), *mul = plane + ((size_t)row << log2p);
+        return [=](int i) { return cmul(in[i], mul[i]); };
+    }
+};
+
+// src . G[group]: the items are `planes` planes per source point, point-major, and plane j of a point belongs to group j / K
+// (a plain stack of planes is one point).  G is real.
+struct LoadTimesGroupReal {
+    const float2* src;                                      // [points][planes][pn][pn]
+    const float* G;                                         // [planes / K][pn][pn]
+    int planes, K;
+    __device__ auto open(long long l, int row, int log2p) const
+    {
+        const float2* in = src + ((size_t)l << log2p);
+        const float* g = G + ((((size_t)((l >> log2p) % planes / K) << log2p) + row) << log2p);
+        return [=](int i) { return make_float2(in[i].x * g[i], in[i].y * g[i]); };
+    }
+};
+
+// roll(pupil plane, d) . mask: item b is plane (b mod planes) of source point (b / planes), and
+//   at(i) = pupils[plane][(row - dy) mod pn][(i - dx) mod pn] . mask[row][i],  (dy, dx) = shifts[point], read once per line.
+// The indices are unsigned: the modular index of any integer shift, no overflow.
+struct LoadRolled {
+    const float2* pupils;                                   // [planes][pn][pn], held once
+    const float2* mask;                                     // [pn][pn]
+    const int32_t* shifts;                                  // [points][2]
+    int planes;
+    __device__ auto open(long long l, int row, int log2p) const
+    {
+        const long long item = l >> log2p, point = item / planes;
+        const unsigned dy = (unsigned)shifts[2 * point], dx = (unsigned)shifts[2 * point + 1], wrap = (1u << log2p) - 1;
+        const float2* in = pupils + ((((size_t)(item - point * planes) << log2p) + (((unsigned)row - dy) & wrap)) << log2p);
+        const float2* mul = mask + ((size_t)row << log2p);
+        return [=](int i) { return cmul(in[((unsigned)i - dx) & wrap], mul[i]); };
+    }
+};
+
+// Many mask spectra through one kernel set: item b is kernel plane (b mod kernels) under the mask plane of tile (b / kernels).
+// The kernel planes are read by every tile's items, so the pass writes the item's own plane, never kernel_planes.
+struct LoadKernelTimesTile {
+    const float2* kernel_planes;                            // [kernels][pn][pn], held once
+    const float2* tile_masks;                               // [tiles][pn][pn]
+    int kernels;
+    __device__ auto open(long long l, int row, int log2p) const
+    {
+        const long long item = l >> log2p, tile = item / kernels;
+        const float2* in = kernel_planes + ((((size_t)(item - tile * kernels) << log2p) + row) << log2p);
+        const float2* mul = tile_masks + ((((size_t)tile << log2p) + row) << log2p);
+        return [=](int i) { return cmul(in[i], mul[i]); };
+    }
+};
+
+// ---- The ways out.  The grid covers `lines` line slots, slot s = row (s mod pn) of unit s / pn, and a unit is walk(store)
+// consecutive items, transformed one after another by the slot's threads.  store.open(l, row, log2p, lds_line) takes an item line
+// and returns put(q, y), which is handed every output of the line; finish sees the line off (every thread of the workgroup calls
+// it).  A store may keep lds_floats of LDS per workgroup behind the transform's own (lds_line: the slot's pn of them); begin and
+// end run once per workgroup, on every thread, around the walk.  What a store answers unless it says otherwise: one item per
+// slot, no LDS of its own, nothing to do when a line ends. ----
+constexpr size_t lds_floats(const void*, int, int) { return 0; }
+template <class S> __host__ __device__ int walk(const S&) { return 1; }
+template <class S> __device__ void begin(const S&, float*, long long, int, int, int) {}
+template <class S> __device__ void end(const S&, float*, long long, int, int, int) {}
+template <int T, class S, class Put> __device__ void finish(const S&, Put&, float2*, int, bool) {}
+
+// dst[l][q] = y.  dst may BE the pass's src: a line is in registers before any of its outputs is written (every write follows a
+// barrier that the line's threads reach with their loads consumed; a 16-point line has one thread), and no workgroup touches
+// another's lines.
+struct StoreField {
+    float2* dst;                                            // [items][pn][pn]
+    __device__ auto open(long long l, int, int log2p, float*) const { return [out = dst + ((size_t)l << log2p)](int q, float2 y) { out[q] = y; }; }
+};
+
+// partial[l] = sum_q Gt[group][row][q] |y[q]|^2 and nothing else is written (items and groups as LoadTimesGroupReal's).  Each
+// thread sums the outputs it owns (r ascending, then e), then the line's threads meet in a fixed order: the xor butterfly of a
+// wave's shuffles, every lane ending with the same bits, and for a line of several waves their sums through LDS, added in wave
+// order.
+struct StoreLineReduce {
+    const float* Gt;                                        // [planes / K][pn][pn], transposed planes
+    int planes, K;
+    float* partial;                                         // [lines]
+    struct Put {
+        const float* gt;
+        float* to;                                          // partial + l
+        float acc;
+        __device__ void operator()(int q, float2 y) { acc = fmaf(gt[q], fmaf(y.x, y.x, y.y * y.y), acc); }
+    };
+    __device__ Put open(long long l, int row, int log2p, float*) const
+    {
+        return {Gt + ((((size_t)((l >> log2p) % planes / K) << log2p) + row) << log2p), partial + l, 0.f};
+    }
+};
+// T threads per line, this one thread lt of it; inactive lines come with acc = 0
+template <int T>
+__device__ void finish(const StoreLineReduce&, StoreLineReduce::Put& put, float2* smem, int lt, bool active)
+{
+    float& acc = put.acc;
+    constexpr int W = T < 64 ? T : 64;                      // the line's lanes within one wave: an aligned group of W
+#pragma unroll
+    for (int o = W / 2; o >= 1; o /= 2) acc += __shfl_xor(acc, o);
+    if (T > 64) {                                           // one line per workgroup, T / 64 waves
+        float* red = reinterpret_cast<float*>(smem);        // the exchange buffer, free once every thread has left the transforms
+        __syncthreads();
+        if ((lt & 63) == 0) red[lt >> 6] = acc;
+        __syncthreads();
+        acc = red[0];
+        for (int w = 1; w < T / 64; ++w) acc += red[w];
+    }
+    if (active && lt == 0) *put.to = acc;
+}
+
+// What one output adds to a group's running sum: its squared modulus (the image), or twice the real part of its product with
+// the conjugate of a stored field (the image tangent; E holds one plane per item, in the layout of the outputs).
+struct SquareTerm {
+    __device__ auto open(long long, int) const { return [](int, float2 y) { return fmaf(y.x, y.x, y.y * y.y); }; }
+};
+struct FoldTerm {
+    const float2* E;                                        // [groups K][pn][pn]
+    __device__ auto open(long long l, int log2p) const
+    {
+        return [e = E + ((size_t)l << log2p)](int q, float2 y) { return 2.0f * fmaf(e[q].x, y.x, e[q].y * y.y); };
+    }
+};
+
+// sums[s][q] (+)= sum_k term(y of item g K + k), g = s / pn: the slots are the lines of the GROUPS, and the workgroup walks the
+// K items of its group in ascending order; nothing is written besides.  The running sums of the workgroup's lines live in LDS,
+// fp32, one per output q, touched by the one thread that owns q and by nobody else between the barrier that ends begin and the
+// one that opens end; they start from `sums` when accumulate != 0 and from zero otherwise.  One sum per element in item order,
+// no atomics.
+template <class Term>
+struct StoreGroupSums {
+    Term term;
+    float* sums;                                            // [groups][pn][pn]
+    int K, accumulate;
+    __device__ auto open(long long l, int, int log2p, float* lds_line) const
+    {
+        return [add = term.open(l, log2p), lds_line](int q, float2 y) { lds_line[q] += add(q, y); };
+    }
+};
+template <class Term> constexpr size_t lds_floats(const StoreGroupSums<Term>*, int L, int pn) { return (size_t)L * pn; }
+template <class Term> __host__ __device__ int walk(const StoreGroupSums<Term>& s) { return s.K; }
+// `cells` sums from the workgroup's first slot on, `threads` threads; the last workgroup's may run past the `slots` there are
+template <class Term>
+__device__ void begin(const StoreGroupSums<Term>& s, float* lds, long long slots, int cells, int threads, int log2p)
+{
+    const long long base = (long long)blockIdx.x * cells, limit = slots << log2p;
+    for (int i = threadIdx.x; i < cells; i += threads) lds[i] = (s.accumulate != 0 && base + i < limit) ? s.sums[base + i] : 0.f;
+    __syncthreads();
+}
+template <class Term>
+__device__ void end(const StoreGroupSums<Term>& s, float* lds, long long slots, int cells, int threads, int log2p)
+{
+    const long long base = (long long)blockIdx.x * cells, limit = slots << log2p;
+    __syncthreads();
+    for (int i = threadIdx.x; i < cells; i += threads)
+        if (base + i < limit) s.sums[base + i] = lds[i];
+}
+
+// `lines` line slots of pn = 2^LOG2P samples; each item line x of a slot's unit becomes its centred pruned transform
+//   y[q] = sum_i x[i] exp(SIGN 2 pi i (i - c)(q - c) / N),  q in [0, pn),  N = pn << log2m,
+// x from `load`, y to `store`.
+template <int LOG2P, int SIGN, class Load, class Store>
+__global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(const Load load, const Store store, long long lines,
+                                                                            int log2m)
 {
     using F = LineFFT<LOG2P, SIGN>;
     using LS = LineShape<LOG2P>;
@@ -98,68 +235,28 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
     float2* lds = smem + (size_t)lg * F::LDS_LINE;
     typename F::Twiddles tw;
     F::load_twiddles(tw, g_twiddles, lt, smem + LS::LDS_EXCH, threadIdx.x, LS::THREADS, FFT_MAX_N / PN);
-    const long long line = (long long)blockIdx.x * LS::L + lg;
-    const bool active = line < lines;                       // every thread runs the transforms: they hold workgroup barriers
-    float* sums_all = reinterpret_cast<float*>(smem + LS::LDS_EXCH + F::LDS_TW);   // STORE_FOLD: L lines of PN running sums
-    float* sums = sums_all + (size_t)lg * PN;
-    const long long fold_base = (long long)blockIdx.x * LS::L * PN, fold_end = lines * PN;
-    if (STORE == STORE_FOLD) {
-        for (int i = threadIdx.x; i < LS::L * PN; i += LS::THREADS)
-            sums_all[i] = (per_point != 0 && fold_base + i < fold_end) ? partial[fold_base + i] : 0.f;
-        __syncthreads();
-    }
-    if (STORE == STORE_SQUARE) {
-        for (int i = threadIdx.x; i < LS::L * PN; i += LS::THREADS)
-            sums_all[i] = (per_point != 0 && fold_base + i < fold_end) ? partial[fold_base + i] : 0.f;
-        __syncthreads();
-    }
-    const int items = (STORE == STORE_FOLD || STORE == STORE_SQUARE) ? per_group : 1;
-    for (int item_k = 0; item_k < items; ++item_k) {
-        long long l = active ? line : 0;
-        const int row = (int)(l & (PN - 1));
-        if (STORE == STORE_FOLD) l = ((((l >> LOG2P) * per_group) + item_k) << LOG2P) + row;
-        if (STORE == STORE_SQUARE) l = ((((l >> LOG2P) * per_group) + item_k) << LOG2P) + row;
-        const float2* in = src + (size_t)l * PN;
-        float2* out = dst + (size_t)l * PN;
-        const float2* fold = mul_c + (size_t)l * PN;             // STORE_FOLD only
-        const float2* tile_m = mul_c;                            // LOAD_BATCH only: the item's mask plane
-        if (LOAD == LOAD_BATCH) {
-            const long long item = l >> LOG2P, tile = item / per_point;
-            in = src + ((size_t)(item - tile * per_point) * PN + row) * PN;
-            tile_m = mul_c + (size_t)tile * PN * PN;
-        }
-        unsigned dx = 0;
-        if (LOAD == LOAD_ROLLED) {
-            const long long item = l >> LOG2P, point = item / per_point;
-            const unsigned dy = (unsigned)shifts[2 * point];    // unsigned: the modular index of any integer, no overflow
-            dx = (unsigned)shifts[2 * point + 1];
-            in = src + ((size_t)(item - point * per_point) * PN + (((unsigned)row - dy) & (PN - 1))) * PN;
-        }
+    const long long slot = (long long)blockIdx.x * LS::L + lg;
+    const bool active = slot < lines;                       // every thread runs the transforms: they hold workgroup barriers
+    float* store_lds = reinterpret_cast<float*>(smem + LS::LDS_EXCH + F::LDS_TW);   // behind the exchange buffers and the tables
+    begin(store, store_lds, lines, LS::L * PN, LS::THREADS, LOG2P);
+    const int items = walk(store);
+    for (int k = 0; k < items; ++k) {
+        const long long mine = active ? slot : 0;
+        const int row = (int)(mine & (PN - 1));
+        const long long l = ((((mine >> LOG2P) * items) + k) << LOG2P) + row;
+        const auto at = load.open(l, row, LOG2P);
+        auto put = store.open(l, row, LOG2P, store_lds + (size_t)lg * PN);
         // transform index n = lt + T e stands for the sample at signed offset s = n (n < c) or n - pn from the centre: i = s + c
         float2 x0[16];
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
             const int n = lt + F::T * e;
-            const int i = (n + C) & (PN - 1);
-            float2 v = make_float2(0.f, 0.f);
-            if (active) {
-                v = LOAD == LOAD_ROLLED ? in[((unsigned)i - dx) & (PN - 1)] : in[i];
-                if (LOAD == LOAD_TIMES_MASK || LOAD == LOAD_ROLLED) v = cmul(v, mul_c[(size_t)row * PN + i]);
-                if (LOAD == LOAD_BATCH) v = cmul(v, tile_m[(size_t)row * PN + i]);
-                if (LOAD == LOAD_TIMES_GRAD) {
-                    const float g = mul_r[((size_t)((l >> LOG2P) % per_point / per_group) * PN + row) * PN + i];
-                    v = make_float2(v.x * g, v.y * g);
-                }
-            }
-            x0[e] = v;
+            x0[e] = active ? at((n + C) & (PN - 1)) : make_float2(0.f, 0.f);
         }
         const int m = 1 << log2m;
         const int nmask = (PN << log2m) - 1;                   // N - 1
         const int tshift = 12 - LOG2P - log2m;                 // table stride 4096 / N
         int flip = 0;
-        float acc = 0.f;
-        const float* gt = mul_r;
-        if (STORE == STORE_REDUCE) gt = mul_r + ((size_t)((l >> LOG2P) % per_point / per_group) * PN + row) * PN;
         for (int r = 0; r < m; ++r) {
             if (m > PN && r >= C && r < m - C) continue;       // no q in [0, pn) is congruent to c + r (uniform over the workgroup)
             float2 x[16];
@@ -178,41 +275,12 @@ __global__ __launch_bounds__(LineShape<LOG2P>::THREADS) void k_centred_rows(cons
                 const int u = lt + F::T * e;
                 const int t = u < C ? u : u - PN;
                 const int q = C + (t << log2m) + r;
-                if (q >= 0 && q < PN) {
-                    if (STORE == STORE_REDUCE) acc = fmaf(gt[q], fmaf(x[e].x, x[e].x, x[e].y * x[e].y), acc);
-                    else if (STORE == STORE_FOLD) {
-                        const float2 ev = fold[q];
-                        sums[q] += 2.0f * fmaf(ev.x, x[e].x, ev.y * x[e].y);
-                    } else if (STORE == STORE_SQUARE) sums[q] += fmaf(x[e].x, x[e].x, x[e].y * x[e].y);
-                    else out[q] = x[e];
-                }
+                if (q >= 0 && q < PN) put(q, x[e]);
             }
         }
-        if (STORE == STORE_REDUCE) {
-            constexpr int W = F::T < 64 ? F::T : 64;           // the line's lanes within one wave: an aligned group of W
-#pragma unroll
-            for (int o = W / 2; o >= 1; o /= 2) acc += __shfl_xor(acc, o);
-            if (F::T > 64) {                                   // one line per workgroup, T / 64 waves
-                float* red = reinterpret_cast<float*>(smem);   // the exchange buffer, free once every thread has left the transforms
-                __syncthreads();
-                if ((lt & 63) == 0) red[lt >> 6] = acc;
-                __syncthreads();
-                acc = red[0];
-                for (int w = 1; w < F::T / 64; ++w) acc += red[w];
-            }
-            if (active && lt == 0) partial[l] = acc;
-        }
+        finish<F::T>(store, put, smem, lt, active);
     }
-    if (STORE == STORE_FOLD) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < LS::L * PN; i += LS::THREADS)
-            if (fold_base + i < fold_end) partial[fold_base + i] = sums_all[i];
-    }
-    if (STORE == STORE_SQUARE) {
-        __syncthreads();
-        for (int i = threadIdx.x; i < LS::L * PN; i += LS::THREADS)
-            if (fold_base + i < fold_end) partial[fold_base + i] = sums_all[i];
-    }
+    end(store, store_lds, lines, LS::L * PN, LS::THREADS, LOG2P);
 }
 
 // out[g][c][r] = in[g][r][c] for `gridDim.z` real n x n planes, through a 32 x 32 LDS tile: the copy of gradI whose lines the
@@ -356,81 +424,124 @@ __global__ __launch_bounds__(64) void k_project_final(const float* __restrict__ 
     if (threadIdx.x == 0) out[blockIdx.x] = acc;
 }
 
-struct RowArgs {
-    const float2* src;
-    float2* dst;
-    const float2* mul_c;
-    const float* mul_r;
-    int per_group;
-    long long lines;
-    int log2m;
-    const int32_t* shifts = nullptr;                       // LOAD_ROLLED / STORE_REDUCE only
-    int per_point = 1;
-    float* partial = nullptr;
-};
-
-template <int LOAD, int STORE = STORE_FIELD>
-static hipError_t centred_rows(const RowArgs& a, int pn, int sign, hipStream_t st)
+// One row pass over `lines` line slots of pn samples.  The sign is the call site's, so only the passes some entry runs exist.
+template <int SIGN, class Load, class Store>
+static hipError_t centred_rows(const Load& load, const Store& store, long long lines, int pn, int log2m, hipStream_t st)
 {
     return for_log2(log2_exact(pn), [&](auto l2) {
         constexpr int LOG2P = decltype(l2)::value;
         using LS = LineShape<LOG2P>;
-        // STORE_FOLD and STORE_SQUARE keep the running sums of their L lines behind the exchange buffers and the twiddle tables
-        constexpr size_t LDS =
-            LS::LDS_BYTES + ((STORE == STORE_FOLD || STORE == STORE_SQUARE) ? sizeof(float) * LS::L * (size_t(1) << LOG2P) : 0);
+        constexpr size_t LDS = LS::LDS_BYTES + sizeof(float) * lds_floats((const Store*)nullptr, LS::L, 1 << LOG2P);
         static_assert(LDS <= 64 * 1024, "the row pass stays inside the default LDS allowance");
-        if (sign > 0)
-            hipLaunchKernelGGL((k_centred_rows<LOG2P, +1, LOAD, STORE>), LS::grid(a.lines), dim3(LS::THREADS), LDS, st, a.src,
-                               a.dst, a.mul_c, a.mul_r, a.per_group, a.lines, a.log2m, a.shifts, a.per_point, a.partial);
-        else
-            hipLaunchKernelGGL((k_centred_rows<LOG2P, -1, LOAD, STORE>), LS::grid(a.lines), dim3(LS::THREADS), LDS, st, a.src,
-                               a.dst, a.mul_c, a.mul_r, a.per_group, a.lines, a.log2m, a.shifts, a.per_point, a.partial);
+        hipLaunchKernelGGL((k_centred_rows<LOG2P, SIGN, Load, Store>), LS::grid(lines), dim3(LS::THREADS), LDS, st, load, store, lines,
+                           log2m);
         return hipGetLastError();
     });
 }
 
-// data <- L(first-pass product) for sign +1, L^H for sign -1: rows (with the product on the load), transpose, rows, transpose.
-// The `batch` items are `per_point` planes per source point, point-major (LOAD_ROLLED reads shifts[point]; LOAD_TIMES_GRAD takes
-// the plane's G); a plain batch of planes is one point of `batch` planes.
-template <int LOAD>
-static hipError_t centred2d(const float2* src, float2* data, const float2* mul_c, const float* mul_r, int per_group, int batch, int pn,
-                            int log2m, int sign, hipStream_t st, int per_point, const int32_t* shifts = nullptr)
+// The real-plane transpose to[g] = from[g]^T of `planes` pn x pn planes, at most 65535 per launch (grid.z).
+static hipError_t transpose_real(const float* from, float* to, long long planes, int pn, hipStream_t st)
 {
-    const long long lines = (long long)batch * pn;
-    hipError_t e = centred_rows<LOAD>(RowArgs{src, data, mul_c, mul_r, per_group, lines, log2m, shifts, per_point}, pn, sign, st);
-    if (e != hipSuccess) return e;
-    e = transpose(data, batch, pn, st);
-    if (e != hipSuccess) return e;
-    e = centred_rows<LOAD_PLAIN>(RowArgs{data, data, nullptr, nullptr, 1, lines, log2m}, pn, sign, st);
-    if (e != hipSuccess) return e;
-    return transpose(data, batch, pn, st);
+    const unsigned tiles = (unsigned)((pn + TR_TILE - 1) / TR_TILE);
+    const size_t cells = (size_t)pn * pn;
+    for (long long p0 = 0; p0 < planes; p0 += 65535) {
+        const unsigned nb = (unsigned)(planes - p0 < 65535 ? planes - p0 : 65535);
+        hipLaunchKernelGGL(k_transpose_real, dim3(tiles, tiles, nb), dim3(256), 0, st, from + p0 * cells, to + p0 * cells, pn);
+    }
+    return hipGetLastError();
 }
 
-// LITHO_OK, or the code of the first size rule broken (litho_fft2_c2c's domain for pn and for N, then N >= pn).
-static int check_sizes(long long batch, int pn, int N)
+// What every entry is made of: rows of the `items` planes of `data` with `load` on the way in, transpose, rows again with
+// `store` on the way out -- the planes are left transposed.  Running sums that start from real planes `start` get them in their
+// own layout, `start_t`, ahead of the second pass (one plane per unit of the store).
+template <int SIGN, class Load, class Store>
+static hipError_t two_passes(const Load& load, float2* data, long long items, const Store& store, int pn, int log2m, hipStream_t st,
+                             const float* start = nullptr, float* start_t = nullptr)
 {
-    if (batch < 1 || !fft_size_ok(pn) || !fft_size_ok(N)) return LITHO_E_ARG;
-    if (N < pn) return LITHO_E_NSMALL;
-    if (batch * pn > INT_MAX) return LITHO_E_ARG;                   // one workgroup per line at the large sizes
-    return LITHO_OK;
+    const long long units = items / walk(store);
+    hipError_t e = centred_rows<SIGN>(load, StoreField{data}, items * pn, pn, log2m, st);
+    if (e == hipSuccess) e = transpose(data, (int)items, pn, st);
+    if (e == hipSuccess && start) e = transpose_real(start, start_t, units, pn, st);
+    return e != hipSuccess ? e : centred_rows<SIGN>(LoadPlain{data}, store, units * pn, pn, log2m, st);
 }
 
-// The three parts of litho_source_sensitivity's workspace, in float2 / float / float elements.
-struct SensWork {
-    size_t fields, gt, partial;
-    size_t bytes() const { return fields * sizeof(float2) + (gt + partial) * sizeof(float); }
+// data <- L(the load's product) for sign +1, L^H for sign -1, in natural layout.
+template <int SIGN, class Load>
+static hipError_t centred2d(const Load& load, float2* data, long long items, int pn, int log2m, hipStream_t st)
+{
+    const hipError_t e = two_passes<SIGN>(load, data, items, StoreField{data}, pn, log2m, st);
+    return e != hipSuccess ? e : transpose(data, (int)items, pn, st);
+}
+
+// ---- The size rules, once.  A stack of planes: whether its counts are in range (`counts`) and whether the row pass can number
+// its lines (`fits`: pn a transform size and at most INT_MAX lines -- one workgroup per line at the large sizes).  Every entry's
+// workspace layout is one, its *_work_bytes is the layout's bytes(), and admit turns it into the entry's return code. ----
+struct Stack {
+    bool counts, fits = false;
+    int pn;
+    long long items = 0;                                    // the product of the counts; 0 unless the stack fits
+    Stack(std::initializer_list<int> n, int pn, bool counts_ok = true) : counts(counts_ok), pn(pn)
+    {
+        for (int c : n) counts = counts && c >= 1;
+        if (!counts || !fft_size_ok(pn)) return;
+        long long lines = pn;                               // counts in [1, INT_MAX]: no partial product leaves a long long
+        for (int c : n)
+            if ((lines *= c) > INT_MAX) return;
+        fits = true;
+        items = lines / pn;
+    }
+    size_t cells(long long planes) const { return fits ? (size_t)planes * pn * pn : 0; }
 };
 
-static bool sens_work(int groups, int K, int batch, int pn, SensWork& w)
+// The order in which every entry refuses: bad pointers and counts, sizes outside litho_fft2_c2c's domain (pn, then N), N < pn,
+// too many lines, a workspace too small.
+static int admit(bool pointers, const Stack& s, int pn, int N, size_t work_need = 0, size_t work_bytes = 0)
 {
-    if (groups < 1 || K < 1 || batch < 1 || !fft_size_ok(pn)) return false;
-    const long long items = (long long)groups * K;
-    if (items > INT_MAX || items * batch > INT_MAX || items * batch * pn > INT_MAX) return false;
-    w.partial = (size_t)(items * batch * pn);
-    w.fields = w.partial * pn;
-    w.gt = (size_t)groups * pn * pn;
-    return true;
+    if (!pointers || !s.counts || !fft_size_ok(pn) || !fft_size_ok(N)) return LITHO_E_ARG;
+    if (N < pn) return LITHO_E_NSMALL;
+    if (!s.fits) return LITHO_E_ARG;
+    return work_bytes < work_need ? LITHO_E_WORKSPACE : LITHO_OK;
 }
+
+// litho_socs_vjp: the fields of the batch, turned into their adjoints in place.
+struct VjpWork : Stack {
+    VjpWork(int groups, int K, int pn) : Stack({groups, K}, pn) {}
+    size_t bytes() const { return cells(items) * sizeof(float2); }
+};
+
+// litho_socs_jvp: the chunk's fields E^T (their final transpose left out: the fold meets them line for line in the transposed
+// layout), one direction's stack between its two passes, and the real planes of one direction in the transposed layout --
+// nothing grows with P.
+struct JvpWork : Stack {
+    int groups;
+    JvpWork(int groups, int K, int P, int pn)
+        : Stack({groups, K}, pn, groups <= 65535 && P >= 1 && P <= LITHO_SOCS_JVP_MAX_DIRECTIONS), groups(groups) {}
+    size_t tangent() const { return cells(items); }         // float2 elements behind the fields
+    size_t sums() const { return 2 * cells(items); }        // float2 elements ahead of the real planes
+    size_t bytes() const { return sums() * sizeof(float2) + cells(groups) * sizeof(float); }
+};
+
+// litho_socs_image_batch: the fields of every (tile, plane, kernel) between their two row passes, and the images in the
+// transposed layout, where the second pass sums them.  tiles groups K <= INT_MAX is a rule for the counts (refused ahead of N).
+struct BatchWork : Stack {
+    long long planes;                                       // tiles groups
+    BatchWork(int tiles, int groups, int K, int pn)
+        : Stack({tiles, groups, K}, pn, groups <= 65535 && (long long)tiles * groups <= INT_MAX / (K > 0 ? K : 1)),
+          planes((long long)tiles * groups) {}
+    size_t sums() const { return cells(items); }            // float2 elements ahead of the real planes
+    size_t bytes() const { return sums() * sizeof(float2) + cells(planes) * sizeof(float); }
+};
+
+// litho_source_sensitivity: a chunk's fields, G^T, and one partial per line of the chunk.  litho_pupil_vjp: the fields alone.
+struct SensWork : Stack {
+    int groups;
+    SensWork(int groups, int K, int batch, int pn) : Stack({groups, K, batch}, pn), groups(groups) {}
+    size_t fields() const { return cells(items); }          // float2
+    size_t gt() const { return cells(groups); }             // float
+    size_t partial() const { return (size_t)items * pn; }   // float
+    size_t field_bytes() const { return fields() * sizeof(float2); }
+    size_t bytes() const { return field_bytes() + (gt() + partial()) * sizeof(float); }
+};
 
 // Workgroups of litho_pupil_project's first stage: a function of the sizes alone, so the order of every sum is too.  0 for a
 // bad argument.
@@ -450,215 +561,134 @@ extern "C" {
 int litho_socs_fields(const void* kernels, const void* maskFT, int batch, int pn, int N, void* fields, void* stream)
 {
     using namespace litho;
-    if (!kernels || !maskFT || !fields) return LITHO_E_ARG;
-    const int rc = check_sizes(batch, pn, N);
+    const int rc = admit(kernels && maskFT && fields, Stack({batch}, pn), pn, N);
     if (rc != LITHO_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     HIP_TRY(fill_twiddles(st));
-    HIP_TRY(centred2d<LOAD_TIMES_MASK>((const float2*)kernels, (float2*)fields, (const float2*)maskFT, nullptr, 1, batch, pn,
-                                       log2_exact(N) - log2_exact(pn), +1, st, batch));
+    HIP_TRY(centred2d<+1>(LoadTimesPlane{(const float2*)kernels, (const float2*)maskFT}, (float2*)fields, batch, pn,
+                          log2_exact(N) - log2_exact(pn), st));
     return LITHO_OK;
 }
 
-size_t litho_socs_vjp_work_bytes(int groups, int K, int pn)
-{
-    using namespace litho;
-    if (groups < 1 || K < 1 || !fft_size_ok(pn) || (long long)groups * K * pn > INT_MAX) return 0;
-    return (size_t)groups * K * pn * pn * sizeof(float2);
-}
+size_t litho_socs_vjp_work_bytes(int groups, int K, int pn) { return litho::VjpWork(groups, K, pn).bytes(); }
 
 int litho_socs_vjp(const void* kernels, const void* maskFT, const float* gradI, int groups, int K, int pn, int N, void* grad,
                    int accumulate, void* work, size_t work_bytes, void* stream)
 {
     using namespace litho;
-    if (!kernels || !maskFT || !gradI || !grad || !work || groups < 1 || K < 1) return LITHO_E_ARG;
-    const long long batch = (long long)groups * K;
-    const int rc = check_sizes(batch, pn, N);
+    const VjpWork w(groups, K, pn);
+    const int rc = admit(kernels && maskFT && gradI && grad && work, w, pn, N, w.bytes(), work_bytes);
     if (rc != LITHO_OK) return rc;
-    if (work_bytes < litho_socs_vjp_work_bytes(groups, K, pn)) return LITHO_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    float2* w = (float2*)work;
-    const int log2m = log2_exact(N) - log2_exact(pn);
+    float2* fields = (float2*)work;
+    const int batch = (int)w.items, log2m = log2_exact(N) - log2_exact(pn);
     HIP_TRY(fill_twiddles(st));
     // the fields of the batch, then L^H of G . E in place
-    HIP_TRY(centred2d<LOAD_TIMES_MASK>((const float2*)kernels, w, (const float2*)maskFT, nullptr, 1, (int)batch, pn, log2m, +1, st,
-                                       (int)batch));
-    HIP_TRY(centred2d<LOAD_TIMES_GRAD>(w, w, nullptr, gradI, K, (int)batch, pn, log2m, -1, st, (int)batch));
+    HIP_TRY(centred2d<+1>(LoadTimesPlane{(const float2*)kernels, (const float2*)maskFT}, fields, batch, pn, log2m, st));
+    HIP_TRY(centred2d<-1>(LoadTimesGroupReal{fields, gradI, batch, K}, fields, batch, pn, log2m, st));
     const long long cells = (long long)pn * pn, pairs = cells / 2;
     long long blocks = (pairs + 255) / 256;
     if (blocks > 65536) blocks = 65536;                            // grid-stride beyond that
-    hipLaunchKernelGGL(k_vjp_reduce, dim3((unsigned)blocks), dim3(256), 0, st, (const float2*)kernels, (const float2*)w, (int)batch,
+    hipLaunchKernelGGL(k_vjp_reduce, dim3((unsigned)blocks), dim3(256), 0, st, (const float2*)kernels, (const float2*)fields, batch,
                        cells, (float2*)grad, accumulate ? 1 : 0);
     HIP_TRY(hipGetLastError());
     return LITHO_OK;
 }
 
-// The tangent of the image: dI[p][g] (+)= 2 sum_k Re(conj(E_gk) . L(kernels[gK+k] . dMaskFT[p])).  Workspace: the chunk's fields
-// E^T (their final transpose left out: the fold meets them line for line in the transposed layout), one direction's stack between
-// its two passes, and the real planes of one direction in the transposed layout -- nothing grows with P.
-size_t litho_socs_jvp_work_bytes(int groups, int K, int P, int pn)
-{
-    using namespace litho;
-    if (groups < 1 || groups > 65535 || K < 1 || P < 1 || P > LITHO_SOCS_JVP_MAX_DIRECTIONS || !fft_size_ok(pn) ||
-        (long long)groups * K * pn > INT_MAX)
-        return 0;
-    const size_t cells = (size_t)pn * pn;
-    return 2 * (size_t)groups * K * cells * sizeof(float2) + (size_t)groups * cells * sizeof(float);
-}
+// The tangent of the image: dI[p][g] (+)= 2 sum_k Re(conj(E_gk) . L(kernels[gK+k] . dMaskFT[p])).
+size_t litho_socs_jvp_work_bytes(int groups, int K, int P, int pn) { return litho::JvpWork(groups, K, P, pn).bytes(); }
 
 int litho_socs_jvp(const void* kernels, const void* maskFT, const void* dMaskFT, int P, int groups, int K, int pn, int N, float* dI,
                    int accumulate, void* work, size_t work_bytes, void* stream)
 {
     using namespace litho;
-    if (!kernels || !maskFT || !dMaskFT || !dI || !work || groups < 1 || groups > 65535 || K < 1 || P < 1 ||
-        P > LITHO_SOCS_JVP_MAX_DIRECTIONS)
-        return LITHO_E_ARG;
-    const long long batch = (long long)groups * K;
-    const int rc = check_sizes(batch, pn, N);
+    const JvpWork w(groups, K, P, pn);
+    const int rc = admit(kernels && maskFT && dMaskFT && dI && work, w, pn, N, w.bytes(), work_bytes);
     if (rc != LITHO_OK) return rc;
-    if (work_bytes < litho_socs_jvp_work_bytes(groups, K, P, pn)) return LITHO_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const size_t cells = (size_t)pn * pn;
     float2* fields = (float2*)work;                                // E^T, item by item
-    float2* tang = fields + (size_t)batch * cells;                 // one direction between its passes
-    float* sums = (float*)(tang + (size_t)batch * cells);          // dI[p]^T, plane by plane
+    float2* tang = fields + w.tangent();                           // one direction between its passes
+    float* sums = (float*)(fields + w.sums());                     // dI[p]^T, plane by plane
     const int log2m = log2_exact(N) - log2_exact(pn);
-    const long long lines = batch * pn;
-    const unsigned tiles = (unsigned)((pn + TR_TILE - 1) / TR_TILE);
-    const dim3 tgrid(tiles, tiles, (unsigned)groups);
     HIP_TRY(fill_twiddles(st));
-    // the fields of the chunk once per call: rows of phi . M, transpose, rows -- and no transpose back
-    HIP_TRY(centred_rows<LOAD_TIMES_MASK>(RowArgs{(const float2*)kernels, fields, (const float2*)maskFT, nullptr, 1, lines, log2m}, pn,
-                                          +1, st));
-    HIP_TRY(transpose(fields, (int)batch, pn, st));
-    HIP_TRY(centred_rows<LOAD_PLAIN>(RowArgs{fields, fields, nullptr, nullptr, 1, lines, log2m}, pn, +1, st));
-    // direction by direction, each by the same launches: its bits do not depend on P or on its neighbours
+    // the fields of the chunk once per call, left transposed
+    HIP_TRY(two_passes<+1>(LoadTimesPlane{(const float2*)kernels, (const float2*)maskFT}, fields, w.items, StoreField{fields}, pn,
+                           log2m, st));
+    // direction by direction, each by the same launches: its bits do not depend on P or on its neighbours.  Each output is
+    // folded against the stored field as it comes out, so a tangent field is never stored.
     for (int p = 0; p < P; ++p) {
         float* out = dI + (size_t)p * groups * cells;
-        HIP_TRY(centred_rows<LOAD_TIMES_MASK>(RowArgs{(const float2*)kernels, tang, (const float2*)dMaskFT + (size_t)p * cells, nullptr, 1,
-                                                      lines, log2m}, pn, +1, st));
-        HIP_TRY(transpose(tang, (int)batch, pn, st));
-        if (accumulate) {
-            hipLaunchKernelGGL(k_transpose_real, tgrid, dim3(256), 0, st, (const float*)out, sums, pn);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY((centred_rows<LOAD_PLAIN, STORE_FOLD>(RowArgs{tang, tang, fields, nullptr, K, (long long)groups * pn, log2m, nullptr,
-                                                              accumulate ? 1 : 0, sums}, pn, +1, st)));
-        hipLaunchKernelGGL(k_transpose_real, tgrid, dim3(256), 0, st, (const float*)sums, out, pn);
-        HIP_TRY(hipGetLastError());
+        HIP_TRY(two_passes<+1>(LoadTimesPlane{(const float2*)kernels, (const float2*)dMaskFT + (size_t)p * cells}, tang, w.items,
+                               StoreGroupSums<FoldTerm>{{fields}, sums, K, accumulate ? 1 : 0}, pn, log2m, st, accumulate ? out : nullptr, sums));
+        HIP_TRY(transpose_real(sums, out, groups, pn, st));
     }
     return LITHO_OK;
 }
 
-// The image of many mask spectra: out[b][g] (+)= sum_k |L(kernels[gK+k] . maskFTs[b])|^2.  Workspace: the fields of every (tile,
-// plane, kernel) between their two row passes, and the images in the transposed layout, where the second pass sums them.
-size_t litho_socs_image_batch_work_bytes(int tiles, int groups, int K, int pn)
-{
-    using namespace litho;
-    if (tiles < 1 || groups < 1 || groups > 65535 || K < 1 || !fft_size_ok(pn)) return 0;
-    const long long planes = (long long)tiles * groups;
-    if (planes > INT_MAX || planes * K > INT_MAX || planes * K * pn > INT_MAX) return 0;
-    const size_t cells = (size_t)pn * pn;
-    return (size_t)planes * K * cells * sizeof(float2) + (size_t)planes * cells * sizeof(float);
-}
+// The image of many mask spectra: out[b][g] (+)= sum_k |L(kernels[gK+k] . maskFTs[b])|^2.
+size_t litho_socs_image_batch_work_bytes(int tiles, int groups, int K, int pn) { return litho::BatchWork(tiles, groups, K, pn).bytes(); }
 
 int litho_socs_image_batch(const void* kernels, const void* maskFTs, int tiles, int groups, int K, int pn, int N, float* out,
                            int accumulate, void* work, size_t work_bytes, void* stream)
 {
     using namespace litho;
-    if (!kernels || !maskFTs || !out || !work || tiles < 1 || groups < 1 || groups > 65535 || K < 1) return LITHO_E_ARG;
-    const long long planes = (long long)tiles * groups;
-    if (planes > INT_MAX || planes * K > INT_MAX) return LITHO_E_ARG;
-    const long long batch = planes * K;
-    const int rc = check_sizes(batch, pn, N);
+    const BatchWork w(tiles, groups, K, pn);
+    const int rc = admit(kernels && maskFTs && out && work, w, pn, N, w.bytes(), work_bytes);
     if (rc != LITHO_OK) return rc;
-    if (work_bytes < litho_socs_image_batch_work_bytes(tiles, groups, K, pn)) return LITHO_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const size_t cells = (size_t)pn * pn;
     float2* fields = (float2*)work;                                // item (b groups + g) K + k between its passes
-    float* sums = (float*)(fields + (size_t)batch * cells);        // out[b][g]^T, plane by plane
-    const int log2m = log2_exact(N) - log2_exact(pn);
-    const unsigned tr = (unsigned)((pn + TR_TILE - 1) / TR_TILE);
-    // the real transpose of `planes` planes, at most 65535 per launch (grid.z)
-    auto transpose_real = [&](const float* from, float* to) {
-        for (long long p0 = 0; p0 < planes; p0 += 65535) {
-            const unsigned nb = (unsigned)(planes - p0 < 65535 ? planes - p0 : 65535);
-            hipLaunchKernelGGL(k_transpose_real, dim3(tr, tr, nb), dim3(256), 0, st, from + (size_t)p0 * cells, to + (size_t)p0 * cells, pn);
-        }
-        return hipGetLastError();
-    };
+    float* sums = (float*)(fields + w.sums());                     // out[b][g]^T, plane by plane
     HIP_TRY(fill_twiddles(st));
-    // rows of phi . M for every (tile, plane, kernel), transpose, then the columns, squared and summed over k as they come out
-    HIP_TRY(centred_rows<LOAD_BATCH>(RowArgs{(const float2*)kernels, fields, (const float2*)maskFTs, nullptr, 1, batch * pn, log2m, nullptr,
-                                             groups * K}, pn, +1, st));
-    HIP_TRY(transpose(fields, (int)batch, pn, st));
-    if (accumulate) HIP_TRY(transpose_real(out, sums));
-    HIP_TRY((centred_rows<LOAD_PLAIN, STORE_SQUARE>(RowArgs{fields, fields, nullptr, nullptr, K, planes * pn, log2m, nullptr,
-                                                            accumulate ? 1 : 0, sums}, pn, +1, st)));
-    HIP_TRY(transpose_real(sums, out));
+    // rows of phi . M for every (tile, plane, kernel), transpose, then the columns, squared and summed over k as they come out:
+    // the K fields of a tile meet in LDS and no K-plane stack of intensities is written
+    HIP_TRY(two_passes<+1>(LoadKernelTimesTile{(const float2*)kernels, (const float2*)maskFTs, groups * K}, fields, w.items,
+                           StoreGroupSums<SquareTerm>{{}, sums, K, accumulate ? 1 : 0}, pn, log2_exact(N) - log2_exact(pn), st,
+                           accumulate ? out : nullptr, sums));
+    HIP_TRY(transpose_real(sums, out, w.planes, pn, st));
     return LITHO_OK;
 }
 
-size_t litho_source_sensitivity_work_bytes(int groups, int K, int batch, int pn)
-{
-    litho::SensWork w;
-    return litho::sens_work(groups, K, batch, pn, w) ? w.bytes() : 0;
-}
+size_t litho_source_sensitivity_work_bytes(int groups, int K, int batch, int pn) { return litho::SensWork(groups, K, batch, pn).bytes(); }
 
 int litho_source_sensitivity(const void* pupils, const void* maskFT, const float* gradI, int groups, int K, const int32_t* shifts,
                              int64_t count, int pn, int N, float* sens, int batch, void* work, size_t work_bytes, void* stream)
 {
     using namespace litho;
-    if (!pupils || !maskFT || !gradI || !shifts || !sens || !work || groups < 1 || K < 1 || batch < 1 || count < 0) return LITHO_E_ARG;
-    if (!fft_size_ok(pn) || !fft_size_ok(N)) return LITHO_E_ARG;
-    if (N < pn) return LITHO_E_NSMALL;
-    SensWork w;
-    if (!sens_work(groups, K, batch, pn, w)) return LITHO_E_ARG;   // more than INT_MAX lines in a chunk
-    if (work_bytes < w.bytes()) return LITHO_E_WORKSPACE;
+    const SensWork w(groups, K, batch, pn);
+    const int rc = admit(pupils && maskFT && gradI && shifts && sens && work && count >= 0, w, pn, N, w.bytes(), work_bytes);
+    if (rc != LITHO_OK) return rc;
     if (count == 0) return LITHO_OK;
     hipStream_t st = (hipStream_t)stream;
     float2* fields = (float2*)work;
-    float* gt = (float*)(fields + w.fields);
-    float* partial = gt + w.gt;
+    float* gt = (float*)(fields + w.fields());
+    float* partial = gt + w.gt();
     const int log2m = log2_exact(N) - log2_exact(pn), per_point = groups * K;
     HIP_TRY(fill_twiddles(st));
-    const unsigned tiles = (unsigned)((pn + TR_TILE - 1) / TR_TILE);
-    hipLaunchKernelGGL(k_transpose_real, dim3(tiles, tiles, (unsigned)groups), dim3(256), 0, st, gradI, gt, pn);
-    HIP_TRY(hipGetLastError());
+    HIP_TRY(transpose_real(gradI, gt, groups, pn, st));
     for (int64_t p0 = 0; p0 < count; p0 += batch) {
         const int nb = count - p0 < batch ? (int)(count - p0) : batch;
-        const int items = nb * per_point;
-        const long long lines = (long long)items * pn;
-        // rows of roll(P, d) . M, transpose, then the columns, each reduced against its line of G^T as it comes out
-        HIP_TRY(centred_rows<LOAD_ROLLED>(RowArgs{(const float2*)pupils, fields, (const float2*)maskFT, nullptr, 1, lines, log2m,
-                                                  shifts + 2 * p0, per_point, nullptr}, pn, +1, st));
-        HIP_TRY(transpose(fields, items, pn, st));
-        HIP_TRY((centred_rows<LOAD_PLAIN, STORE_REDUCE>(RowArgs{fields, fields, nullptr, gt, K, lines, log2m, nullptr, per_point,
-                                                                partial}, pn, +1, st)));
+        // a source point is the coherent kernel roll(P, d): rows of roll(P, d) . M, transpose, then the columns, each reduced
+        // against its line of G^T as it comes out; a point's line partials are summed last
+        HIP_TRY(two_passes<+1>(LoadRolled{(const float2*)pupils, (const float2*)maskFT, shifts + 2 * p0, per_point}, fields,
+                               (long long)nb * per_point, StoreLineReduce{gt, per_point, K, partial}, pn, log2m, st));
         hipLaunchKernelGGL(k_sum_partials, dim3((unsigned)nb), dim3(64), 0, st, (const float*)partial, per_point * pn, sens + p0);
         HIP_TRY(hipGetLastError());
     }
     return LITHO_OK;
 }
 
-size_t litho_pupil_vjp_work_bytes(int groups, int K, int batch, int pn)
-{
-    litho::SensWork w;
-    return litho::sens_work(groups, K, batch, pn, w) ? w.fields * sizeof(float2) : 0;
-}
+size_t litho_pupil_vjp_work_bytes(int groups, int K, int batch, int pn) { return litho::SensWork(groups, K, batch, pn).field_bytes(); }
 
 int litho_pupil_vjp(const void* pupils, const void* maskFT, const float* gradI, int groups, int K, const int32_t* shifts,
                     const float* weights, int64_t count, int pn, int N, void* grad, int accumulate, int batch, void* work,
                     size_t work_bytes, void* stream)
 {
     using namespace litho;
-    if (!pupils || !maskFT || !gradI || !grad || !work || groups < 1 || K < 1 || batch < 1 || count < 0) return LITHO_E_ARG;
-    if (!shifts && count > 0) return LITHO_E_ARG;                  // an empty list has no address
-    if (!fft_size_ok(pn) || !fft_size_ok(N)) return LITHO_E_ARG;
-    if (N < pn) return LITHO_E_NSMALL;
-    SensWork w;
-    if (!sens_work(groups, K, batch, pn, w)) return LITHO_E_ARG;   // more than INT_MAX lines in a chunk
-    if (work_bytes < w.fields * sizeof(float2)) return LITHO_E_WORKSPACE;
+    const SensWork w(groups, K, batch, pn);
+    const bool pointers = pupils && maskFT && gradI && grad && work && (shifts || count == 0);   // an empty list has no address
+    const int rc = admit(pointers && count >= 0, w, pn, N, w.field_bytes(), work_bytes);
+    if (rc != LITHO_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const int log2pn = log2_exact(pn), log2m = log2_exact(N) - log2pn, per_point = groups * K;
     const size_t cells = (size_t)pn * pn;
@@ -672,10 +702,10 @@ int litho_pupil_vjp(const void* pupils, const void* maskFT, const float* gradI, 
     for (int64_t p0 = 0; p0 < count; p0 += batch) {
         const int nb = count - p0 < batch ? (int)(count - p0) : batch;
         const int items = nb * per_point;
-        // the fields of the chunk in natural layout, L^H of G . E in place, then the roll undone and the points summed
-        HIP_TRY(centred2d<LOAD_ROLLED>((const float2*)pupils, fields, (const float2*)maskFT, nullptr, 1, items, pn, log2m, +1, st,
-                                       per_point, shifts + 2 * p0));
-        HIP_TRY(centred2d<LOAD_TIMES_GRAD>(fields, fields, nullptr, gradI, K, items, pn, log2m, -1, st, per_point));
+        // the fields of the chunk in natural layout, L^H of G . E in place, then the roll undone and the points summed in list order
+        HIP_TRY(centred2d<+1>(LoadRolled{(const float2*)pupils, (const float2*)maskFT, shifts + 2 * p0, per_point}, fields, items, pn,
+                              log2m, st));
+        HIP_TRY(centred2d<-1>(LoadTimesGroupReal{fields, gradI, per_point, K}, fields, items, pn, log2m, st));
         hipLaunchKernelGGL(k_pupil_reduce, rgrid, dim3(256), 0, st, (const float2*)fields, (const float2*)maskFT, shifts + 2 * p0,
                            weights ? weights + p0 : nullptr, nb, per_point, log2pn, (float2*)grad, (accumulate || p0 > 0) ? 1 : 0);
         HIP_TRY(hipGetLastError());
@@ -683,6 +713,7 @@ int litho_pupil_vjp(const void* pupils, const void* maskFT, const float* gradI, 
     return LITHO_OK;
 }
 
+// The pupil gradient paired with a basis of wavefront maps, in a two-stage reduction of fixed order.
 size_t litho_pupil_project_work_bytes(int planes, int J, int pn)
 {
     return (size_t)litho::project_blocks(planes, J, pn) * (size_t)(J > 0 ? J : 0) * sizeof(float);

@@ -10,7 +10,10 @@ differing bit is a bug to explain.  Stops at the first child that fails; exit st
 
 Workload (seconds in all): litho_fft2_c2c both ways, batch 3, n = 16 / 32 / 512 / 1024; litho_tcc_apply and
 litho_tcc_apply_vector, batch 3, n = 16 / 64; litho_socs_fields and litho_socs_vjp (accumulate 0 and 1) at (pn, N) = (16, 16),
-(16, 32), (16, 1024), (64, 256), (1024, 1024); socsKernels (bitmap, grey map, two-plane stack) and vectorSocsKernels (TE, the
+(16, 32), (16, 1024), (64, 256), (1024, 1024); litho_socs_jvp (2 directions), litho_socs_image_batch (3 tiles),
+litho_source_sensitivity and litho_pupil_vjp (8 source points in chunks of 3, with and without weights), accumulate 0 and 1, at
+(16, 16), (16, 32), (16, 512), (64, 256), (1024, 1024) with 3 x 2 kernels (1 x 2 at 1024), the sensitivities at 2048 as well;
+litho_pupil_project (pn 64, 2 planes, 17 terms); socsKernels (bitmap, grey map, two-plane stack) and vectorSocsKernels (TE, the
 same three, and applyBytes = 1) at pn 64 with 8 kernels; hopkinsIntensity (kernelChunk None / 3, with and without out),
 vectorAbbeIntensity("unpolarized") and hopkinsGradient (kernelChunk 3)."""
 import argparse
@@ -77,6 +80,60 @@ def child(root, path):
                 nat.check(lib.litho_socs_vjp(nat.ptr(k), nat.ptr(m), nat.ptr(G), groups, K, pn, N, nat.ptr(g), acc, nat.ptr(work), nbytes,
                                              st), "litho_socs_vjp")
                 keep(f"vjp/{pn}/{N}/accumulate{acc}", g)
+
+        def work_for(sizer, *args):
+            nbytes = int(sizer(*args))
+            assert nbytes > 0, (sizer.__name__, args)
+            return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+
+        def ints(*shape, span):
+            return torch.randint(-span, span, shape, generator=gen, dtype=torch.int32).to(dev).contiguous()
+
+        # c': the other ends of the row pass.  (16, 16) with 3 groups is 48 group lines under 64-line workgroups.
+        for pn, N in ((16, 16), (16, 32), (16, 512), (64, 256), (1024, 1024), (2048, 2048)):
+            groups, K = (3, 2) if pn <= 64 else (1, 2)
+            points, batch = (8, 3) if pn < 2048 else (2, 1)                          # chunks of 3 + 3 + 2
+            planes = groups * K
+            k, m, G = cplx(planes, pn, pn), cplx(pn, pn), real(groups, pn, pn)
+            shifts, weights = ints(points, 2, span=pn), real(points)
+            work, nbytes = work_for(lib.litho_source_sensitivity_work_bytes, groups, K, batch, pn)
+            sens = torch.empty(points, dtype=torch.float32, device=dev)
+            nat.check(lib.litho_source_sensitivity(nat.ptr(k), nat.ptr(m), nat.ptr(G), groups, K, nat.ptr(shifts), points, pn, N,
+                                                   nat.ptr(sens), batch, nat.ptr(work), nbytes, st), "litho_source_sensitivity")
+            keep(f"sensitivity/{pn}/{N}", sens)
+            if pn == 2048:                                                           # the reducing store alone goes there
+                continue
+            work, nbytes = work_for(lib.litho_pupil_vjp_work_bytes, groups, K, batch, pn)
+            start = cplx(planes, pn, pn)
+            for acc in (0, 1):
+                for name, w in (("plain", None), ("weighted", nat.ptr(weights))):
+                    g = start.clone()
+                    nat.check(lib.litho_pupil_vjp(nat.ptr(k), nat.ptr(m), nat.ptr(G), groups, K, nat.ptr(shifts), w, points, pn, N,
+                                                  nat.ptr(g), acc, batch, nat.ptr(work), nbytes, st), "litho_pupil_vjp")
+                    keep(f"pupil_vjp/{pn}/{N}/{name}/accumulate{acc}", g)
+            P, tiles = 2, 3
+            dM, masks = cplx(P, pn, pn), cplx(tiles, pn, pn)
+            work, nbytes = work_for(lib.litho_socs_jvp_work_bytes, groups, K, P, pn)
+            start = real(P, groups, pn, pn)
+            for acc in (0, 1):
+                dI = start.clone()
+                nat.check(lib.litho_socs_jvp(nat.ptr(k), nat.ptr(m), nat.ptr(dM), P, groups, K, pn, N, nat.ptr(dI), acc, nat.ptr(work),
+                                             nbytes, st), "litho_socs_jvp")
+                keep(f"jvp/{pn}/{N}/accumulate{acc}", dI)
+            work, nbytes = work_for(lib.litho_socs_image_batch_work_bytes, tiles, groups, K, pn)
+            start = real(tiles, groups, pn, pn)
+            for acc in (0, 1):
+                out = start.clone()
+                nat.check(lib.litho_socs_image_batch(nat.ptr(k), nat.ptr(masks), tiles, groups, K, pn, N, nat.ptr(out), acc, nat.ptr(work),
+                                                     nbytes, st), "litho_socs_image_batch")
+                keep(f"image_batch/{pn}/{N}/accumulate{acc}", out)
+        pn, planes, J = 64, 2, 17                                                    # one term more than a tile of 16
+        g, pups, basis = cplx(planes, pn, pn), cplx(planes, pn, pn), real(J, pn, pn)
+        work, nbytes = work_for(lib.litho_pupil_project_work_bytes, planes, J, pn)
+        coeff = torch.empty(J, dtype=torch.float32, device=dev)
+        nat.check(lib.litho_pupil_project(nat.ptr(g), nat.ptr(pups), planes, nat.ptr(basis), J, pn, nat.ptr(coeff), nat.ptr(work), nbytes,
+                                          st), "litho_pupil_project")
+        keep("pupil_project", coeff)
 
     pn, WL, NA, PS = 64, 193.0, 0.7, 25                                              # d, e: the factorisations
     mask = L.Mask(bernoulli_mask(pn), PS, dev)
