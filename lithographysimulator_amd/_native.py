@@ -296,6 +296,13 @@ def epsilon_n(deltaK, pixelSize, wavelength):
     return eps.value, N.value
 
 
+def postprocess_size(pn, epsilon):
+    """litho_postprocess_size: the side n_out of the post-processed grid of a pn x pn raw image at `epsilon`."""
+    n_out = c_int(0)
+    check(lib().litho_postprocess_size(int(pn), float(epsilon), ctypes.byref(n_out)), "litho_postprocess_size")
+    return n_out.value
+
+
 class PlanRecord(ctypes.Structure):
     """litho_abbe_plan (include/litho_abbe.h)."""
     _fields_ = [("words", ctypes.c_int32 * 16), ("valid", ctypes.c_int32), ("pn", ctypes.c_int32),

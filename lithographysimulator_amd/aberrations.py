@@ -16,19 +16,17 @@ This is the fp32 wavefront model: W is summed in fp32 and goes through generateP
 (Pupil(...), litho_pupil) rounds W to fp16 after every term and is not differentiable at that granularity; it keeps its parity
 path untouched.  K > 1 returns the gradient with respect to each given pupil and stops there: the chain from effective vector or
 film pupils back to Zernikes is not built."""
-import ctypes
 import math
+from functools import partial
 
 import torch
 
+from . import _descent
 from . import _native as nat
 from . import smo as _smo
-from . import socs as _socs
 
 
-def _pow2_size(who, what, n):
-    if n < _socs.MIN_PN or n > _socs.MAX_PN or n & (n - 1):
-        raise ValueError(f"{who}: {what} must be a power of two, {_socs.MIN_PN} ... {_socs.MAX_PN} (litho_pupil_vjp); got {n}")
+_pow2_size = partial(_descent.pow2_size, entry="litho_pupil_vjp")
 
 
 def pupilGradient(maskFT, pupilF, shifts, N, gradIntensity, weights=None, pupilsPerPlane=1, batch=None, out=None):
@@ -164,14 +162,11 @@ class AberrationResult:
 
 def _device_aberration_model(transmission, shifts, weights, basis, baseWavefront, pn, pixelSize, deltaK, wavelength, normalize, dev):
     """(imager, gradient) of fitAberrations on the HIP path."""
-    from .ilt import postProcessAdjoint
-    from .imageformation import PlanCache, abbeIntensity, postProcess
-    from .mask import Mask
+    from .ilt import _Optics
+    from .imageformation import abbeIntensity
     from .pupil import generatePhi
-    epsilon, N = nat.epsilon_n(deltaK, pixelSize, wavelength)
-    M = Mask(transmission=transmission, pixelSize=pixelSize, device=dev)._ffFraunhofer(epsilon, N)
-    cache = PlanCache()
-    gain = 1.0 / float(weights.double().sum()) if normalize else 1.0
+    o = _Optics(pn, pixelSize, deltaK, wavelength, dev, 1.0 / float(weights.double().sum()) if normalize else 1.0)
+    M = o.spectrum(transmission)
 
     def pupils(c):
         W = torch.tensordot(c.to(torch.float32), basis, dims=1)             # the fp32 wavefront, in waves
@@ -180,17 +175,11 @@ def _device_aberration_model(transmission, shifts, weights, basis, baseWavefront
         return torch.stack([generatePhi(W0 + W, pn, dev) for W0 in baseWavefront])
 
     def imager(c):
-        raw, _ = abbeIntensity(M, pupils(c), shifts, N, plan=cache, weights=weights)
-        if gain != 1.0:
-            raw *= gain
-        return postProcess(raw, epsilon)
+        return o.image(abbeIntensity(M, pupils(c), shifts, o.N, plan=o.cache, weights=weights)[0])
 
     def gradient(c, gradImage):
-        graw = postProcessAdjoint(gradImage, pn, epsilon)
-        if gain != 1.0:
-            graw *= gain
         P = pupils(c)
-        return aberrationGradient(pupilGradient(M, P, shifts, N, graw, weights=weights), P, basis)
+        return aberrationGradient(pupilGradient(M, P, shifts, o.N, o.raw_gradient(gradImage), weights=weights), P, basis)
 
     return imager, gradient
 
@@ -247,11 +236,7 @@ def fitAberrations(measured, transmission, source, basis, pixelSize, deltaK, wav
         dev = nat.require_gpu(measured.device)
         epsilon, N = nat.epsilon_n(deltaK, pixelSize, wavelength)
         _pow2_size(who, "N", int(N))
-        n_out = ctypes.c_int(0)
-        nat.check(nat.lib().litho_postprocess_size(pn, float(epsilon), ctypes.byref(n_out)), "litho_postprocess_size")
-        if measured.shape[-1] != n_out.value:
-            raise ValueError(f"{who}: measured must be [{n_out.value},{n_out.value}] per plane, the post-processed grid of pn {pn} at "
-                             f"epsilon {epsilon:.6g}; got {tuple(measured.shape)}")
+        _descent.check_image_grid(who, "measured", measured, pn, epsilon, per_plane=True)
         lit = lit.to(dev)
         if not bool(lit.any()):
             raise ValueError(f"{who}: source has no lit point")
@@ -288,7 +273,7 @@ def fitAberrations(measured, transmission, source, basis, pixelSize, deltaK, wav
             break
         if improved:
             grad = gradient(c, (2.0 / diff.numel()) * diff).to(c.dtype)
-            direction = grad / torch.clamp(grad.abs().max(), min=torch.finfo(grad.dtype).tiny)
+            direction = grad / _descent.peak(grad)
         else:
             step *= 0.5                                                        # back to the best iterate with half the step
         c, taken = best_c - step * direction, step

@@ -12,14 +12,16 @@ the adjoints of the two linear bookends (mask transmission -> spectrum, raw inte
 pixel mask through all of it; `bakedResistModel` replaces its constant-threshold resist by the post-exposure bake of a chemically
 amplified resist and its adjoint (peb.py), through optimizeMask's imager= / adjoint= pair.  Mask gradients only: the source and the pupil are constants here (source gradients: smo.py;
 DESIGN.md section 10)."""
-import ctypes
 import math
 
 import numpy as np
 import torch
 
+from . import _descent
 from . import _native as nat
 from . import socs as _socs
+from .imageformation import PlanCache, postProcess
+from .mask import Mask
 from .socs import SOCSKernels
 
 MAX_N = _socs.MAX_PN              # litho_fft2_c2c's and litho_socs_fields' largest transform: one limit, stated in socs.py
@@ -204,26 +206,43 @@ class ILTResult:
         self.losses, self.best = losses, best
 
 
+class _Optics:
+    """What the device models of optimizeMask, optimizeSource and fitAberrations build around their intensity call: `epsilon` and
+    `N` of the grid, the spectrum `M` of the transmission last given to `spectrum`, a PlanCache (`cache`) for Abbe calls on a
+    fixed source list, and the two linear bookends with the normalisation `gain` folded in: raw intensity -> image, and the
+    gradient on the image -> the gradient on the raw intensity.  The gain multiplies in place and is skipped at 1.0; the bits of
+    the loops depend on both."""
+
+    def __init__(self, pn, pixelSize, deltaK, wavelength, dev, gain=1.0):
+        self.pn, self.pixelSize, self.dev, self.gain = pn, pixelSize, dev, gain
+        self.epsilon, self.N = nat.epsilon_n(deltaK, pixelSize, wavelength)
+        self.M, self.cache = None, PlanCache()
+
+    def spectrum(self, transmission):
+        self.M = Mask(transmission=transmission, pixelSize=self.pixelSize, device=self.dev)._ffFraunhofer(self.epsilon, self.N)
+        return self.M
+
+    def image(self, raw):
+        if self.gain != 1.0:
+            raw *= self.gain
+        return postProcess(raw, self.epsilon)
+
+    def raw_gradient(self, gradImage):
+        graw = postProcessAdjoint(gradImage, self.pn, self.epsilon)
+        if self.gain != 1.0:
+            graw *= self.gain
+        return graw
+
+
 def _device_model(socs, pn, pixelSize, deltaK, wavelength, normalize, dev):
     """(imager, adjoint) of optimizeMask on the HIP path."""
-    from .imageformation import postProcess
-    from .mask import Mask
-    epsilon, N = nat.epsilon_n(deltaK, pixelSize, wavelength)
-    gain = 1.0 / float(socs.weight_sum) if normalize and socs.weight_sum > 0 else 1.0
-    state = {}
+    o = _Optics(pn, pixelSize, deltaK, wavelength, dev, 1.0 / float(socs.weight_sum) if normalize and socs.weight_sum > 0 else 1.0)
 
     def imager(transmission):
-        state["M"] = Mask(transmission=transmission, pixelSize=pixelSize, device=dev)._ffFraunhofer(epsilon, N)
-        raw = _socs.hopkinsIntensity(state["M"], socs, N)
-        if gain != 1.0:
-            raw *= gain
-        return postProcess(raw, epsilon)
+        return o.image(_socs.hopkinsIntensity(o.spectrum(transmission), socs, o.N))
 
     def adjoint(gradImage):
-        graw = postProcessAdjoint(gradImage, pn, epsilon)
-        if gain != 1.0:
-            graw *= gain
-        return maskSpectrumAdjoint(hopkinsGradient(state["M"], socs, N, graw), pn, epsilon, N)
+        return maskSpectrumAdjoint(hopkinsGradient(o.M, socs, o.N, o.raw_gradient(gradImage)), pn, o.epsilon, o.N)
 
     return imager, adjoint
 
@@ -344,9 +363,7 @@ def optimizeMask(target, socs, pixelSize, deltaK, wavelength, threshold, dose=1.
         raise ValueError("optimizeMask: imager and adjoint replace the model and its backward pass together; give both or neither")
     iterations = int(iterations)
     if resistSteepness is None:
-        # the image is in the engine's raw units (a clear field is ~1e7 at pn 64), so a fixed slope would saturate the sigmoid:
-        # the default puts 25 per threshold, i.e. the resist goes from 8 % to 92 % between 0.9 and 1.1 thresholds
-        resistSteepness = 25.0 / abs(float(threshold)) if float(threshold) != 0 else 25.0
+        resistSteepness = _descent.default_resist_steepness(threshold)
     if iterations < 1 or not float(step) > 0 or not float(maskSteepness) > 0 or not float(resistSteepness) > 0:
         raise ValueError(f"optimizeMask: iterations >= 1 and step, maskSteepness, resistSteepness > 0; got {iterations}, {step}, "
                          f"{maskSteepness}, {resistSteepness}")
@@ -359,12 +376,7 @@ def optimizeMask(target, socs, pixelSize, deltaK, wavelength, threshold, dose=1.
         if not isinstance(socs, SOCSKernels):
             raise TypeError("optimizeMask: socs must be the SOCSKernels socsKernels returned")
         dev = nat.require_gpu(socs.kernels.device)
-        epsilon, _ = nat.epsilon_n(deltaK, pixelSize, wavelength)
-        n_out = ctypes.c_int(0)
-        nat.check(nat.lib().litho_postprocess_size(pn, float(epsilon), ctypes.byref(n_out)), "litho_postprocess_size")
-        if target.shape[0] != n_out.value:
-            raise ValueError(f"optimizeMask: target must be [{n_out.value},{n_out.value}], the post-processed grid of pn {pn} at "
-                             f"epsilon {epsilon:.6g}; got {tuple(target.shape)}")
+        _descent.check_image_grid("optimizeMask", "target", target, pn, nat.epsilon_n(deltaK, pixelSize, wavelength)[0])
         imager, adjoint = _device_model(socs, pn, pixelSize, deltaK, wavelength, normalize, dev)
     else:
         dev = target.device
@@ -387,16 +399,13 @@ def optimizeMask(target, socs, pixelSize, deltaK, wavelength, threshold, dose=1.
     for it in range(iterations + 1):
         s = torch.sigmoid(a_m * theta)
         image = imager((bg + span * s).to(torch.complex64))
-        resist = torch.sigmoid(a_r * (dose * image - threshold))
-        diff = resist - target
-        losses.append(float((diff * diff).mean()))                                # the one host read of this iterate
+        loss, grad_image = _descent.resist_loss(image, target, a_r, dose, threshold, gradient=it < iterations)
+        losses.append(float(loss))                                                 # the one host read of this iterate
         if losses[-1] < losses[best]:
             best, best_theta = it, theta.clone()
         if it == iterations or not math.isfinite(losses[-1]):
             break
-        grad_image = (2.0 * a_r * dose / diff.numel()) * diff * resist * (1.0 - resist)
         grad_t = adjoint(grad_image)                                               # dl/dRe t + i dl/dIm t
         grad_theta = a_m * s * (1.0 - s) * (grad_t * span.conjugate()).real       # dl = Re(conj(grad_t) dt), dt = span s' dtheta
-        peak = grad_theta.abs().max()
-        theta = theta - float(step) * grad_theta / torch.clamp(peak, min=torch.finfo(torch.float32).tiny)
+        theta = theta - float(step) * grad_theta / _descent.peak(grad_theta, torch.float32)   # the floor of theta's precision
     return ILTResult(best_theta, transmission_of(best_theta), losses, best)

@@ -131,7 +131,8 @@ def abbeIntensity(maskFT, pupilF, shifts, N, out=None, count=None, plan=None, op
     `weights`: optional float32 [S] tensor on the mask's device, one INTENSITY weight per row of `shifts` (a weighted,
     grey-level source: sum_s w_s |E_s|^2; sourceWeights).  Combines with count, plan and options.  w = 0 adds nothing;
     a negative, NaN or infinite weight raises ValueError from the call that plans (a call planned from a PlanCache record
-    does not look again).  Without weights the call goes to the same C entries as ever."""
+    does not look again).  Every combination is one call of litho_abbe_accumulate_weighted with NULL for what is not given,
+    which is what the narrower C entries forward: without weights the library runs the statements it always ran."""
     pn = _square(maskFT, "maskFT")
     if pupilF.dim() not in (2, 3) or tuple(pupilF.shape[-2:]) != (pn, pn) or (pupilF.dim() == 3 and pupilF.shape[0] < 1):
         # e.g. a default Pupil() (pixelNumber 64) with a 256^2 mask: the reference fails at pf * maskFFFT
@@ -156,6 +157,7 @@ def abbeIntensity(maskFT, pupilF, shifts, N, out=None, count=None, plan=None, op
     nat.check(rc, "abbeImage")
     if count is not None and (count.dtype != torch.int32 or count.numel() != 1 or count.device != m.device):
         raise ShapeError("count must be a 1-element int32 tensor on the mask's device")
+    wt = None
     if weights is not None:
         if (not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32 or weights.dim() != 1
                 or weights.shape[0] != shifts.shape[0] or weights.device != m.device):
@@ -165,47 +167,21 @@ def abbeIntensity(maskFT, pupilF, shifts, N, out=None, count=None, plan=None, op
         wt = weights.contiguous()
     ws = _plan_workspace(plan, dev, pn, int(N), pupilF, shifts, weights)
     opts = nat.current_options(options)
+    # One call site: litho_abbe_accumulate_weighted is the superset of the five entries (each forwards to the same function with
+    # NULL for what it does not take).  An error still names the narrowest entry that takes the arguments given.
+    what = ("litho_abbe_accumulate_weighted (sizes, or a negative / NaN / infinite weight)" if wt is not None
+            else "litho_abbe_accumulate_opts" if opts is not None else "litho_abbe_accumulate_planned" if plan is not None
+            else "litho_abbe_accumulate_counted" if count is not None else "litho_abbe_accumulate")
+    S = ctypes.c_int64(0)
     with torch.cuda.device(dev):
-        if weights is not None:
-            S = ctypes.c_int64(0)
-            nat.check(nat.lib().litho_abbe_accumulate_weighted(nat.ptr(m), nat.ptr(p), planes, nat.ptr(sh),
-                                                               nat.ptr(count) if count is not None else None, sh.shape[0],
-                                                               pn, int(N), nat.ptr(out), nat.ptr(ws), ws.numel(),
-                                                               nat.stream_ptr(dev),
-                                                               ctypes.byref(plan.record) if plan is not None else None,
-                                                               ctypes.byref(opts) if opts is not None else None,
-                                                               ctypes.byref(S), nat.ptr(wt)),
-                      "litho_abbe_accumulate_weighted (sizes, or a negative / NaN / infinite weight)")
-            return (out, S.value) if (plan is not None or count is not None) else out
-        if opts is not None:
-            S = ctypes.c_int64(0)
-            nat.check(nat.lib().litho_abbe_accumulate_opts(nat.ptr(m), nat.ptr(p), planes, nat.ptr(sh),
+        nat.check(nat.lib().litho_abbe_accumulate_weighted(nat.ptr(m), nat.ptr(p), planes, nat.ptr(sh),
                                                            nat.ptr(count) if count is not None else None, sh.shape[0],
                                                            pn, int(N), nat.ptr(out), nat.ptr(ws), ws.numel(),
                                                            nat.stream_ptr(dev),
                                                            ctypes.byref(plan.record) if plan is not None else None,
-                                                           ctypes.byref(opts), ctypes.byref(S)),
-                      "litho_abbe_accumulate_opts")
-            return (out, S.value) if (plan is not None or count is not None) else out
-        if plan is not None:
-            S = ctypes.c_int64(0)
-            nat.check(nat.lib().litho_abbe_accumulate_planned(nat.ptr(m), nat.ptr(p), planes, nat.ptr(sh),
-                                                              nat.ptr(count) if count is not None else None, sh.shape[0],
-                                                              pn, int(N), nat.ptr(out), nat.ptr(ws), ws.numel(),
-                                                              nat.stream_ptr(dev), ctypes.byref(plan.record), ctypes.byref(S)),
-                      "litho_abbe_accumulate_planned")
-            return out, S.value
-        if count is not None:
-            S = ctypes.c_int64(0)
-            nat.check(nat.lib().litho_abbe_accumulate_counted(nat.ptr(m), nat.ptr(p), planes, nat.ptr(sh), nat.ptr(count),
-                                                              sh.shape[0], pn, int(N), nat.ptr(out), nat.ptr(ws),
-                                                              ws.numel(), nat.stream_ptr(dev), ctypes.byref(S)),
-                      "litho_abbe_accumulate_counted")
-            return out, S.value
-        nat.check(nat.lib().litho_abbe_accumulate(nat.ptr(m), nat.ptr(p), planes, nat.ptr(sh), sh.shape[0], pn,
-                                                  int(N), nat.ptr(out), nat.ptr(ws), ws.numel(),
-                                                  nat.stream_ptr(dev)), "litho_abbe_accumulate")
-    return out
+                                                           ctypes.byref(opts) if opts is not None else None,
+                                                           ctypes.byref(S), nat.ptr(wt) if wt is not None else None), what)
+    return (out, S.value) if (plan is not None or count is not None) else out
 
 
 def postProcess(raw, epsilon):
@@ -214,11 +190,9 @@ def postProcess(raw, epsilon):
     stacked = raw.dim() == 3
     planes = raw.shape[0] if stacked else 1
     pn = raw.shape[-1]
-    n_out = ctypes.c_int(0)
-    nat.check(nat.lib().litho_postprocess_size(pn, float(epsilon), ctypes.byref(n_out)), "litho_postprocess_size")
+    n_out = nat.postprocess_size(pn, epsilon)
     r = raw.to(torch.float32).contiguous()
-    out = torch.empty((planes, n_out.value, n_out.value) if stacked else (n_out.value, n_out.value),
-                      dtype=torch.float32, device=dev)
+    out = torch.empty((planes, n_out, n_out) if stacked else (n_out, n_out), dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         nat.check(nat.lib().litho_postprocess(nat.ptr(r), planes, pn, float(epsilon), nat.ptr(out),
                                               nat.stream_ptr(dev)), "litho_postprocess")
@@ -256,10 +230,9 @@ def resistContour(raw, epsilon, threshold, dose=1.0, return_image=False, diffusi
     stacked = raw.dim() == 3
     planes = raw.shape[0] if stacked else 1
     pn = raw.shape[-1]
-    n_out = ctypes.c_int(0)
-    nat.check(nat.lib().litho_postprocess_size(pn, float(epsilon), ctypes.byref(n_out)), "litho_postprocess_size")
+    n_out = nat.postprocess_size(pn, epsilon)
     r = raw.to(torch.float32).contiguous()
-    shape = (planes, n_out.value, n_out.value) if stacked else (n_out.value, n_out.value)
+    shape = (planes, n_out, n_out) if stacked else (n_out, n_out)
     resist = torch.empty(shape, dtype=torch.uint8, device=dev)
     image = torch.empty(shape, dtype=torch.float32, device=dev) if return_image else None
     with torch.cuda.device(dev):
@@ -401,9 +374,6 @@ def abbeImage(mask, maskFT: torch.Tensor, pupilF: torch.Tensor, lightsource: tor
     before.  True -- `lightsource` is a real map [pn,pn] whose values are per-point intensity weights (a measured pupil fill,
     a freeform or apodised source): the image is sum_s w_s |E_s|^2 over the pixels with w > 0, and `normalize` divides by
     sum_s w_s (the global sum when sharded) instead of S, on the device.  The reference cannot express this."""
-    if weighted:
-        return _abbe_image_weighted(mask, maskFT, pupilF, lightsource, pixelSize, deltaK, wavelength, fft, device, group,
-                                    normalize, plan_cache, options)
     if not fft:
         raise NotImplementedError("only the FFT formulation (fft=True) is built; the direct integral "
                                   "(imageformation.py:3-30) is outside the hot path")
@@ -412,8 +382,11 @@ def abbeImage(mask, maskFT: torch.Tensor, pupilF: torch.Tensor, lightsource: tor
     if pupilF.dim() not in (2, 3) or tuple(pupilF.shape[-2:]) != (pixelNumber, pixelNumber):
         raise ShapeError(f"pupilF must be [{pixelNumber},{pixelNumber}] or [planes,{pixelNumber},{pixelNumber}] to "
                          f"match maskFT; got {tuple(pupilF.shape)} (build the Pupil with mask.pixelNumber)")
-    if tuple(lightsource.shape) != (pixelNumber, pixelNumber):
+    if tuple(lightsource.shape) != (pixelNumber, pixelNumber) or (weighted and lightsource.is_complex()):
         # the reference silently mis-shifts when the source grid differs from the mask's
+        if weighted:
+            raise ShapeError(f"a weighted source must be a real map [{pixelNumber},{pixelNumber}] (the mask's pixelNumber); "
+                             f"got {lightsource.dtype} {tuple(lightsource.shape)}")
         raise ShapeError(f"the source bitmap must be [{pixelNumber},{pixelNumber}] (the mask's pixelNumber); got "
                          f"{tuple(lightsource.shape)}")
     dev = nat.require_gpu(device)
@@ -423,89 +396,52 @@ def abbeImage(mask, maskFT: torch.Tensor, pupilF: torch.Tensor, lightsource: tor
     if group is not None and plan_cache is not None:
         raise ValueError("plan_cache is for single-GPU image sequences; a sharded call (group=...) plans per rank and per "
                          "call -- pass one or the other")
+    # `weighted` selects three things and nothing else.  The compaction: a bitmap goes through sourceShifts(Async) -- int64, every
+    # non-zero pixel lit, a negative one too -- and a map through sourceWeights(Async) -- float32, w > 0 lit; a bitmap is never
+    # sent through the weighted one "with ones".  Whether weights travel: an unweighted call reaches sourceShifts, abbeIntensity
+    # and postProcess with exactly the arguments it always did (no weights= at all).  The divisor: the host's count S for a bitmap,
+    # the device-side sum of the weights for a map.
+    def intensity(shifts, weights, **kw):
+        if weighted:
+            kw["weights"] = weights
+        return abbeIntensity(maskFT, pupilF.to(dev), shifts, N, options=options, **kw)          # imageformation.py:62-67
+
+    def compact_async():                                                            # imageformation.py:59, count left on the device
+        if weighted:
+            return sourceWeightsAsync(lightsource.to(dev), pixelNumber)
+        shifts, count = sourceShiftsAsync(lightsource.to(dev), pixelNumber)
+        return shifts, None, count
+
     if plan_cache is not None:
         planes = pupilF.shape[0] if pupilF.dim() == 3 else 1
-        r = plan_cache.record
-        ident = _identity(pupilF, lightsource)
-        if (plan_cache.shifts is None or not plan_cache.valid or (r.pn, r.N, r.planes) != (pixelNumber, int(N), planes)
-                or plan_cache.image_identity != ident):
-            plan_cache.invalidate()
-            plan_cache.image_identity = ident
-            plan_cache.shifts, plan_cache.count = sourceShiftsAsync(lightsource.to(dev), pixelNumber)
-            image, total = abbeIntensity(maskFT, pupilF.to(dev), plan_cache.shifts, N, count=plan_cache.count, plan=plan_cache,
-                                         options=options)
-            plan_cache.S, plan_cache.count = total, None           # the count is on the host now (and in the record)
+        r, c = plan_cache.record, plan_cache
+        ident = _identity(pupilF, lightsource) + (("weighted",) if weighted else ())    # one cache, both kinds: plans afresh
+        if (c.shifts is None or (weighted and c.weights is None) or not c.valid
+                or (r.pn, r.N, r.planes) != (pixelNumber, int(N), planes) or c.image_identity != ident):
+            c.invalidate()
+            c.image_identity = ident
+            c.shifts, c.weights, c.count = compact_async()
+            image, total = intensity(c.shifts, c.weights, count=c.count, plan=c)
+            c.S, c.count = total, None                             # the count is on the host now (and in the record)
+            if weighted:
+                c.weight_sum = c.weights[:total].sum()             # device side, no host wait
         else:
-            image, total = abbeIntensity(maskFT, pupilF.to(dev), plan_cache.shifts[:plan_cache.S], N, plan=plan_cache,
-                                         options=options)
+            image, total = intensity(c.shifts[:c.S], c.weights[:c.S] if weighted else None, plan=c)
+        wsum = c.weight_sum
     elif group is None:
         # single GPU: the source count never visits the host on its own -- one stream wait per image
-        shifts, count = sourceShiftsAsync(lightsource.to(dev), pixelNumber)          # imageformation.py:59
-        image, total = abbeIntensity(maskFT, pupilF.to(dev), shifts, N, count=count, options=options)  # imageformation.py:62-67
+        shifts, weights, count = compact_async()
+        image, total = intensity(shifts, weights, count=count)
+        wsum = weights[:total].sum() if weighted else None
     else:
         import torch.distributed as dist
-        shifts = sourceShifts(lightsource.to(dev), pixelNumber)            # imageformation.py:59
+        source = lightsource.to(dev)
+        shifts, weights = sourceWeights(source, pixelNumber) if weighted else (sourceShifts(source, pixelNumber), None)
         total = shifts.shape[0]
         lo, hi = shard_bounds(total, dist.get_rank(group), dist.get_world_size(group))
-        image = abbeIntensity(maskFT, pupilF.to(dev), shifts[lo:hi], N, options=options)    # imageformation.py:62-67
+        image = intensity(shifts[lo:hi], weights[lo:hi] if weighted else None)
         _all_reduce_sum(image, group)
+        wsum = weights.sum() if weighted else None             # every rank compacts the whole map: the GLOBAL sum
     if normalize and total > 0:
-        image /= float(total)
+        image /= wsum.to(image.dtype) if weighted else float(total)
     return postProcess(image, epsilon)                                      # imageformation.py:69-77
-
-
-def _abbe_image_weighted(mask, maskFT, pupilF, lightsource, pixelSize, deltaK, wavelength, fft, device, group, normalize,
-                         plan_cache, options):
-    """abbeImage(..., weighted=True): the same three branches (plan cache / single GPU / sharded) with the weights travelling
-    next to the shifts.  Kept apart so that an unweighted call reaches sourceShifts, abbeIntensity and postProcess with exactly
-    the arguments it always did."""
-    if not fft:
-        raise NotImplementedError("only the FFT formulation (fft=True) is built; the direct integral "
-                                  "(imageformation.py:3-30) is outside the hot path")
-    epsilon, N = Mask.calculateEpsilonN(self=mask, deltaK=deltaK, pixelSize=pixelSize, wavelength=wavelength)
-    pixelNumber = _square(maskFT, "maskFT")
-    if pupilF.dim() not in (2, 3) or tuple(pupilF.shape[-2:]) != (pixelNumber, pixelNumber):
-        raise ShapeError(f"pupilF must be [{pixelNumber},{pixelNumber}] or [planes,{pixelNumber},{pixelNumber}] to "
-                         f"match maskFT; got {tuple(pupilF.shape)} (build the Pupil with mask.pixelNumber)")
-    if tuple(lightsource.shape) != (pixelNumber, pixelNumber) or lightsource.is_complex():
-        raise ShapeError(f"a weighted source must be a real map [{pixelNumber},{pixelNumber}] (the mask's pixelNumber); got "
-                         f"{lightsource.dtype} {tuple(lightsource.shape)}")
-    dev = nat.require_gpu(device)
-    maskFT = maskFT.to(dev)
-    from .distributed import resolve_group, shard_bounds
-    group = resolve_group(group)
-    if group is not None and plan_cache is not None:
-        raise ValueError("plan_cache is for single-GPU image sequences; a sharded call (group=...) plans per rank and per "
-                         "call -- pass one or the other")
-    if plan_cache is not None:
-        planes = pupilF.shape[0] if pupilF.dim() == 3 else 1
-        r = plan_cache.record
-        ident = _identity(pupilF, lightsource) + ("weighted",)
-        if (plan_cache.shifts is None or plan_cache.weights is None or not plan_cache.valid
-                or (r.pn, r.N, r.planes) != (pixelNumber, int(N), planes) or plan_cache.image_identity != ident):
-            plan_cache.invalidate()
-            plan_cache.image_identity = ident
-            plan_cache.shifts, plan_cache.weights, plan_cache.count = sourceWeightsAsync(lightsource.to(dev), pixelNumber)
-            image, total = abbeIntensity(maskFT, pupilF.to(dev), plan_cache.shifts, N, count=plan_cache.count, plan=plan_cache,
-                                         options=options, weights=plan_cache.weights)
-            plan_cache.S, plan_cache.count = total, None
-            plan_cache.weight_sum = plan_cache.weights[:total].sum()          # device side, no host wait
-        else:
-            image, total = abbeIntensity(maskFT, pupilF.to(dev), plan_cache.shifts[:plan_cache.S], N, plan=plan_cache,
-                                         options=options, weights=plan_cache.weights[:plan_cache.S])
-        wsum = plan_cache.weight_sum
-    elif group is None:
-        shifts, weights, count = sourceWeightsAsync(lightsource.to(dev), pixelNumber)
-        image, total = abbeIntensity(maskFT, pupilF.to(dev), shifts, N, count=count, options=options, weights=weights)
-        wsum = weights[:total].sum()
-    else:
-        import torch.distributed as dist
-        shifts, weights = sourceWeights(lightsource.to(dev), pixelNumber)
-        total = shifts.shape[0]
-        lo, hi = shard_bounds(total, dist.get_rank(group), dist.get_world_size(group))
-        image = abbeIntensity(maskFT, pupilF.to(dev), shifts[lo:hi], N, options=options, weights=weights[lo:hi])
-        _all_reduce_sum(image, group)
-        wsum = weights.sum()                                    # every rank compacts the whole map: the GLOBAL sum
-    if normalize and total > 0:
-        image /= wsum.to(image.dtype)
-    return postProcess(image, epsilon)

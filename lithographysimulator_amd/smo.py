@@ -12,20 +12,19 @@ source point is a coherent kernel of the SOCS field code, read rolled and reduce
 scatters it onto the source grid, `optimizeSource` descends the weights of a fixed candidate list with optimizeMask's loss, and
 `optimizeSourceMask` alternates it with socsKernels and optimizeMask.  Source gradients only: the pupil is a constant here, and the
 weights stay real and non-negative."""
-import ctypes
 import math
+from functools import partial
 
 import torch
 
+from . import _descent
 from . import _native as nat
 from . import socs as _socs
 
 WORK_BYTES = 256 << 20            # default ceiling of sourceSensitivities' workspace (the coverage rasteriser's default as well)
 
 
-def _pow2_size(who, what, n):
-    if n < _socs.MIN_PN or n > _socs.MAX_PN or n & (n - 1):
-        raise ValueError(f"{who}: {what} must be a power of two, {_socs.MIN_PN} ... {_socs.MAX_PN} (litho_source_sensitivity); got {n}")
+_pow2_size = partial(_descent.pow2_size, entry="litho_source_sensitivity")
 
 
 def sourceSensitivities(maskFT, pupilF, shifts, N, gradIntensity, pupilsPerPlane=1, batch=None):
@@ -132,12 +131,9 @@ def sourceLossGradient(weights, target, imager, sensitivity, threshold, dose, re
     wsum = weights.sum()
     if normalize:
         image = image / wsum.to(image.dtype)
-    resist = torch.sigmoid(float(resistSteepness) * (float(dose) * image - float(threshold)))
-    diff = resist - target.to(image.dtype)
-    loss = (diff * diff).mean()
+    loss, G = _descent.resist_loss(image, target, resistSteepness, dose, threshold, gradient)
     if not gradient:
         return loss, None
-    G = (2.0 * float(resistSteepness) * float(dose) / diff.numel()) * diff * resist * (1.0 - resist)
     g = sensitivity(G)
     if normalize:
         g = (g - (G * image).sum().to(g.dtype)) / wsum.to(g.dtype)
@@ -147,26 +143,22 @@ def sourceLossGradient(weights, target, imager, sensitivity, threshold, dose, re
 def projectedStep(weights, grad, step):
     """w <- max(w - step max(w) grad / max|grad|, 0): optimizeMask's scale-free step in units of the largest weight, projected onto
     w >= 0."""
-    peak = torch.clamp(grad.abs().max(), min=torch.finfo(grad.dtype).tiny)
-    return torch.clamp(weights - float(step) * weights.max() * grad / peak, min=0)
+    return torch.clamp(weights - float(step) * weights.max() * grad / _descent.peak(grad), min=0)
 
 
 def _device_source_model(transmission, pupilF, shifts, pn, pixelSize, deltaK, wavelength, dev):
     """(imager, sensitivity) of optimizeSource on the HIP path: the weighted Abbe sum of the fixed list through one PlanCache and
     postProcess; postProcessAdjoint and sourceSensitivities."""
-    from .ilt import postProcessAdjoint
-    from .imageformation import PlanCache, abbeIntensity, postProcess
-    from .mask import Mask
-    epsilon, N = nat.epsilon_n(deltaK, pixelSize, wavelength)
-    M = Mask(transmission=transmission, pixelSize=pixelSize, device=dev)._ffFraunhofer(epsilon, N)
-    cache = PlanCache()
+    from .ilt import _Optics
+    from .imageformation import abbeIntensity
+    o = _Optics(pn, pixelSize, deltaK, wavelength, dev)
+    M = o.spectrum(transmission)
 
     def imager(w):
-        raw, _ = abbeIntensity(M, pupilF, shifts, N, plan=cache, weights=w.contiguous())
-        return postProcess(raw, epsilon)
+        return o.image(abbeIntensity(M, pupilF, shifts, o.N, plan=o.cache, weights=w.contiguous())[0])
 
     def sensitivity(gradImage):
-        return sourceSensitivities(M, pupilF, shifts, N, postProcessAdjoint(gradImage, pn, epsilon))
+        return sourceSensitivities(M, pupilF, shifts, o.N, o.raw_gradient(gradImage))
 
     return imager, sensitivity
 
@@ -193,7 +185,7 @@ def optimizeSource(target, transmission, pupilF, candidates, pixelSize, deltaK, 
         raise ValueError(f"{who}: imager and sensitivity replace the model and its backward pass together; give both or neither")
     iterations = int(iterations)
     if resistSteepness is None:
-        resistSteepness = 25.0 / abs(float(threshold)) if float(threshold) != 0 else 25.0
+        resistSteepness = _descent.default_resist_steepness(threshold)
     if iterations < 1 or not float(step) > 0 or not float(resistSteepness) > 0:
         raise ValueError(f"{who}: iterations >= 1 and step, resistSteepness > 0; got {iterations}, {step}, {resistSteepness}")
     if not isinstance(target, torch.Tensor) or target.dim() != 2 or target.shape[0] != target.shape[1] or target.is_complex():
@@ -213,11 +205,7 @@ def optimizeSource(target, transmission, pupilF, candidates, pixelSize, deltaK, 
         dev = nat.require_gpu(pupilF.device)
         epsilon, N = nat.epsilon_n(deltaK, pixelSize, wavelength)
         _pow2_size(who, "N", int(N))
-        n_out = ctypes.c_int(0)
-        nat.check(nat.lib().litho_postprocess_size(pn, float(epsilon), ctypes.byref(n_out)), "litho_postprocess_size")
-        if target.shape[0] != n_out.value:
-            raise ValueError(f"{who}: target must be [{n_out.value},{n_out.value}], the post-processed grid of pn {pn} at epsilon "
-                             f"{epsilon:.6g}; got {tuple(target.shape)}")
+        _descent.check_image_grid(who, "target", target, pn, epsilon)
         lit = lit.to(dev)
         shifts = sourceShifts(lit, pn)
         imager, sensitivity = _device_source_model(transmission.to(dev), pupilF, shifts, pn, pixelSize, deltaK, wavelength, dev)
