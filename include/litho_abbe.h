@@ -937,6 +937,22 @@ int litho_socs_jvp(const void *kernels, const void *maskFT, const void *dMaskFT,
 size_t litho_socs_image_batch_work_bytes(int tiles, int groups, int K, int pn);
 int litho_socs_image_batch(const void *kernels, const void *maskFTs, int tiles, int groups, int K, int pn, int N, float *out,
                            int accumulate, void *work, size_t work_bytes, void *stream);
+/* litho_socs_vjp_batch: the mask gradients of MANY windows through one kernel set in one call,
+ *   grads[b] (+)= 2 sum_{j < groups K} conj(kernels[j]) . L^H( gradIs[b][j / K] . L(kernels[j] . maskFTs[b]) ),   b < tiles,
+ * j ascending, each term added as litho_socs_vjp adds it to one running fp32 sum per component: no atomics.  accumulate != 0 starts
+ * the sums from grads, so calls on consecutive chunks of the kernels continue the same sequence of additions (bit for bit what one
+ * call on all of them gives); accumulate == 0 starts from zero.  The bits of grads[b] depend on maskFTs[b], gradIs[b] and the kernels
+ * alone: not on tiles, on b, or on how the caller cuts the windows into calls.  kernels complex64 [groups K,pn,pn] as for
+ * litho_socs_vjp, maskFTs complex64 [tiles,pn,pn], gradIs fp32 [tiles,groups,pn,pn] (the layout of litho_socs_image_batch's out),
+ * grads complex64 [tiles,pn,pn].  Two routes by pn: up to 2048 the sum over j is held in LDS through the adjoint's last row pass
+ * and the adjoint stack is never stored after it; at 4096, where those sums do not fit, the adjoints are stored and summed tile by
+ * tile by litho_socs_vjp's reduction.  Their sums are the same sequence; their bits may differ from litho_socs_vjp's, whose
+ * transforms run in the other order.  work: litho_socs_vjp_batch_work_bytes(tiles, groups, K, pn) device bytes = tiles groups K
+ * pn^2 complex (the field stack, turned into the adjoints in place) + tiles groups pn^2 floats (gradIs in the transposed layout); 0
+ * for a bad argument, less is LITHO_E_WORKSPACE.  Domain and codes as litho_socs_image_batch; every check precedes any launch. */
+size_t litho_socs_vjp_batch_work_bytes(int tiles, int groups, int K, int pn);
+int litho_socs_vjp_batch(const void *kernels, const void *maskFTs, const float *gradIs, int tiles, int groups, int K, int pn, int N,
+                         void *grads, int accumulate, void *work, size_t work_bytes, void *stream);
 
 /* ---- Tiled imaging of large layouts (csrc/tiling.hip; no reference counterpart, checked against numpy slicing in
  * tests/tiling_oracle.py).  A layout larger than one window is imaged as `count` windows of nt x nt pixels on one pixel lattice;
@@ -962,6 +978,26 @@ int litho_tiles_stitch(const float *tiles, int count, int planes, int nt, const 
                        void *stream);
 int litho_tiles_seam(const float *tiles, int count, int planes, int nt, const int32_t *neighbours, int j0, int core, float *out,
                      void *stream);
+/* The tiled inverse-lithography loop keeps ONE complex transmission `plane` [rows,cols] on the raster lattice (the cores of the
+ * plan: rows = ny core, cols = nx core, core = pn - 2 halo) and place[t] = (row, col) of core t's first pixel in it.
+ *
+ * litho_tiles_cut: windows[t][r][c] = plane[place[t][0] - halo + r][place[t][1] - halo + c], and (fill_re, fill_im) where that lies
+ * outside the plane; plane complex64 [rows,cols], windows complex64 [count,pn,pn], every element written.
+ * litho_tiles_overlap_add: the cut's adjoint as a gather, plane[R][C] = sum over the tiles t whose window holds (R, C), t ascending,
+ * of windows[t][R - place[t][0] + halo][C - place[t][1] + halo]: one thread per plane pixel, one running fp32 sum per component
+ * from zero, what falls outside the plane dropped, no atomics; the result does not depend on the launch geometry.  Every
+ * element of plane is written.
+ * litho_tiles_unstitch: the stitch's adjoint, tiles[t][p][j0 + i][j0 + j] = image[p][place[t][0] + i][place[t][1] + j] for
+ * 0 <= i, j < core where the image has that pixel, and zero everywhere else; image fp32 [planes,n,n], tiles fp32
+ * [count,planes,nt,nt], every element written.
+ * LITHO_E_ARG, before any launch: a null pointer, count < 1, a size < 1, halo < 0 or 2 halo >= pn, a core larger than the plane
+ * (cut, overlap-add) or than the image (unstitch), j0 < 0 or j0 + core > nt, more than INT_MAX rows.  Asynchronous. */
+int litho_tiles_cut(const void *plane, int rows, int cols, const int32_t *place, int count, int pn, int halo, float fill_re,
+                    float fill_im, void *windows, void *stream);
+int litho_tiles_overlap_add(const void *windows, int count, int pn, int halo, const int32_t *place, void *plane, int rows, int cols,
+                            void *stream);
+int litho_tiles_unstitch(const float *image, int n, const int32_t *place, int count, int planes, int nt, int j0, int core, float *tiles,
+                         void *stream);
 
 /* ---- Source gradients of Abbe imaging (csrc/socs_grad.hip; no reference counterpart, checked against tests/source_grad_oracle.py).
  * The weighted Abbe sum I = sum_s w_s |E_s|^2 is linear in the weights, and source point s is the coherent kernel roll(P, d_s) of

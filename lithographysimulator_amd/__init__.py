@@ -13,10 +13,10 @@ from .contours import (Contours, contourVertices, contoursToGDSII, contoursToLay
                        doseFocusEnvelope, processVariationBand, simplifyContour, traceContours)
 from .socs import (SOCSKernels, hopkinsImage, hopkinsIntensity, hopkinsIntensityBatch,  # noqa: F401
                    socsKernels)
-from .tiling import (TiledImage, TilePlan, hopkinsImageTiled, planTiles,              # noqa: F401
-                     tileValidRegion)
+from .tiling import (TiledImage, TilePlan, cutTiles, hopkinsImageTiled, maskImageTiled, maskPolygons,   # noqa: F401
+                     optimizeMaskTiled, overlapAddTiles, planTiles, stitchTiles, tileValidRegion, unstitchTiles)
 from .ilt import (ILTResult, bakedResistModel, developedResistModel, hopkinsFields,     # noqa: F401
-                  hopkinsGradient, hopkinsIntensityAD, maskSpectrumAdjoint, optimizeMask, postProcessAdjoint)
+                  hopkinsGradient, hopkinsGradientBatch, hopkinsIntensityAD, maskSpectrumAdjoint, optimizeMask, postProcessAdjoint)
 from .smo import (SourceResult, optimizeSource, optimizeSourceMask, projectedStep,      # noqa: F401
                   sourceGradient, sourceLossGradient, sourceSensitivities)
 from .aberrations import (AberrationResult, aberrationGradient, fitAberrations,         # noqa: F401
@@ -64,4 +64,5 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "rateParameterTangent", "developmentTimeTangent", "resistProfileTangent", "calibrationJacobian",
            "hopkinsTangent", "postProcessTangent", "edgeCoverageTangent", "measureEPETangent", "measureCDTangent", "epeJacobian",
            "maskErrorFactor",
-           "hopkinsIntensityBatch", "tileValidRegion", "planTiles", "hopkinsImageTiled", "TilePlan", "TiledImage"]
+           "hopkinsIntensityBatch", "tileValidRegion", "planTiles", "hopkinsImageTiled", "TilePlan", "TiledImage",
+           "hopkinsGradientBatch", "cutTiles", "overlapAddTiles", "stitchTiles", "unstitchTiles", "optimizeMaskTiled", "maskPolygons", "maskImageTiled"]

@@ -138,6 +138,12 @@ _SIGNATURES = {
                                        c_void_p]),
     "litho_tiles_stitch": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
     "litho_tiles_seam": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "litho_socs_vjp_batch_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "litho_socs_vjp_batch": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                                     c_size_t, c_void_p]),
+    "litho_tiles_cut": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p]),
+    "litho_tiles_overlap_add": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p]),
+    "litho_tiles_unstitch": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "litho_source_sensitivity_work_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "litho_source_sensitivity": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_int, c_int, c_void_p,
                                          c_int, c_void_p, c_size_t, c_void_p]),

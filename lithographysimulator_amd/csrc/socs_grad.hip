@@ -25,6 +25,9 @@
 //   litho_socs_jvp             TimesPlane(kernels . maskFT)        +1   Field                   left transposed: E^T is kept
 //     per direction p          TimesPlane(kernels . dMaskFT[p])    +1   GroupSums<FoldTerm>     the real planes transposed
 //   litho_socs_image_batch     KernelTimesTile(kernels . maskFTs)  +1   GroupSums<SquareTerm>   the real planes transposed
+//   litho_socs_vjp_batch       KernelTimesTile(kernels . maskFTs)  +1   Field                   left transposed: E^T is kept
+//                              TimesGroupReal(fields^T . gradIs^T) -1   TileSums                nothing: the sums are the gradients
+//     at pn 4096               as above                            -1   Field                   k_vjp_reduce per tile
 //   litho_source_sensitivity   Rolled(roll(pupils, d) . maskFT)    +1   LineReduce              k_sum_partials
 //   litho_pupil_vjp            Rolled(roll(pupils, d) . maskFT)    +1   Field                   transposed back
 //                              TimesGroupReal(fields . gradI)      -1   Field                   transposed back, k_pupil_reduce
@@ -119,8 +122,9 @@ struct LoadKernelTimesTile {
 // and returns put(q, y), which is handed every output of the line; finish sees the line off (every thread of the workgroup calls
 // it).  A store may keep lds_floats of LDS per workgroup behind the transform's own (lds_line: the slot's pn of them); begin and
 // end run once per workgroup, on every thread, around the walk.  What a store answers unless it says otherwise: one item per
-// slot, no LDS of its own, nothing to do when a line ends. ----
+// slot, no LDS of its own, every line size, nothing to do when a line ends. ----
 constexpr size_t lds_floats(const void*, int, int) { return 0; }
+constexpr int max_log2(const void*) { return 12; }           // the largest line, 2^max_log2, a store's LDS leaves room for
 template <class S> __host__ __device__ int walk(const S&) { return 1; }
 template <class S> __device__ void begin(const S&, float*, long long, int, int, int) {}
 template <class S> __device__ void end(const S&, float*, long long, int, int, int) {}
@@ -217,6 +221,47 @@ __device__ void end(const StoreGroupSums<Term>& s, float* lds, long long slots, 
     __syncthreads();
     for (int i = threadIdx.x; i < cells; i += threads)
         if (base + i < limit) s.sums[base + i] = lds[i];
+}
+
+// The complex sibling of StoreGroupSums: grads[s][q] (+)= sum_j 2 conj(kernels[j][row][q]) . y of item t J + j, t = s / pn the TILE
+// of slot s and row = s mod pn; the workgroup walks the J = groups K items of its tile in ascending order and the adjoint stack
+// is not written.  Two running fp32 sums per output, the real parts of the workgroup's `cells` outputs in LDS ahead of the
+// imaginary parts (two float planes: a wave's accesses are to consecutive words at m = 1 and m words apart otherwise, as
+// StoreGroupSums'), touched by the one thread that owns q between the barrier that ends begin and the one that opens end.  The
+// products are k_vjp_reduce's, so a sum that starts from grads (`accumulate`) continues one sequence of additions.  cells is
+// LineShape's L pn, what begin and end are handed; the LDS (8 L pn bytes) fits beside the transform's up to pn 2048.
+struct StoreTileSums {
+    const float2* kernels;                                  // [J][pn][pn], held once
+    float2* grads;                                          // [tiles][pn][pn]
+    int J, accumulate, cells;
+    __device__ auto open(long long l, int row, int log2p, float* lds_line) const
+    {
+        const float2* k = kernels + ((((size_t)((l >> log2p) % J) << log2p) + row) << log2p);
+        return [k, re = lds_line, im = lds_line + cells](int q, float2 y) {
+            re[q] += 2.0f * (k[q].x * y.x + k[q].y * y.y);
+            im[q] += 2.0f * (k[q].x * y.y - k[q].y * y.x);
+        };
+    }
+};
+constexpr size_t lds_floats(const StoreTileSums*, int L, int pn) { return 2 * (size_t)L * pn; }
+constexpr int max_log2(const StoreTileSums*) { return 11; }
+__host__ __device__ inline int walk(const StoreTileSums& s) { return s.J; }
+__device__ inline void begin(const StoreTileSums& s, float* lds, long long slots, int cells, int threads, int log2p)
+{
+    const long long base = (long long)blockIdx.x * cells, limit = slots << log2p;
+    for (int i = threadIdx.x; i < cells; i += threads) {
+        const float2 g = (s.accumulate != 0 && base + i < limit) ? s.grads[base + i] : make_float2(0.f, 0.f);
+        lds[i] = g.x;
+        lds[cells + i] = g.y;
+    }
+    __syncthreads();
+}
+__device__ inline void end(const StoreTileSums& s, float* lds, long long slots, int cells, int threads, int log2p)
+{
+    const long long base = (long long)blockIdx.x * cells, limit = slots << log2p;
+    __syncthreads();
+    for (int i = threadIdx.x; i < cells; i += threads)
+        if (base + i < limit) s.grads[base + i] = make_float2(lds[i], lds[cells + i]);
 }
 
 // `lines` line slots of pn = 2^LOG2P samples; each item line x of a slot's unit becomes its centred pruned transform
@@ -430,12 +475,16 @@ static hipError_t centred_rows(const Load& load, const Store& store, long long l
 {
     return for_log2(log2_exact(pn), [&](auto l2) {
         constexpr int LOG2P = decltype(l2)::value;
-        using LS = LineShape<LOG2P>;
-        constexpr size_t LDS = LS::LDS_BYTES + sizeof(float) * lds_floats((const Store*)nullptr, LS::L, 1 << LOG2P);
-        static_assert(LDS <= 64 * 1024, "the row pass stays inside the default LDS allowance");
-        hipLaunchKernelGGL((k_centred_rows<LOG2P, SIGN, Load, Store>), LS::grid(lines), dim3(LS::THREADS), LDS, st, load, store, lines,
-                           log2m);
-        return hipGetLastError();
+        if constexpr (LOG2P > max_log2((const Store*)nullptr)) {
+            return hipErrorInvalidValue;                        // no such kernel: the entry takes another route at this size
+        } else {
+            using LS = LineShape<LOG2P>;
+            constexpr size_t LDS = LS::LDS_BYTES + sizeof(float) * lds_floats((const Store*)nullptr, LS::L, 1 << LOG2P);
+            static_assert(LDS <= 64 * 1024, "the row pass stays inside the default LDS allowance");
+            hipLaunchKernelGGL((k_centred_rows<LOG2P, SIGN, Load, Store>), LS::grid(lines), dim3(LS::THREADS), LDS, st, load, store,
+                               lines, log2m);
+            return hipGetLastError();
+        }
     });
 }
 
@@ -530,6 +579,23 @@ struct BatchWork : Stack {
           planes((long long)tiles * groups) {}
     size_t sums() const { return cells(items); }            // float2 elements ahead of the real planes
     size_t bytes() const { return sums() * sizeof(float2) + cells(planes) * sizeof(float); }
+};
+
+// litho_socs_vjp_batch: BatchWork's layout and count rules with other contents -- the fields E^T of every (tile, plane, kernel),
+// turned into their adjoints in place, and behind them the planes of gradIs in the transposed layout.
+struct VjpBatchWork : BatchWork {
+    using BatchWork::BatchWork;
+    size_t stack() const { return sums(); }                 // float2 elements ahead of G^T
+    // L pn of the row pass at this size: the outputs one workgroup sums (StoreTileSums::cells)
+    int line_cells() const
+    {
+        int c = 0;
+        (void)for_log2(log2_exact(pn), [&](auto l2) {
+            c = LineShape<decltype(l2)::value>::L << decltype(l2)::value;
+            return hipSuccess;
+        });
+        return c;
+    }
 };
 
 // litho_source_sensitivity: a chunk's fields, G^T, and one partial per line of the chunk.  litho_pupil_vjp: the fields alone.
@@ -646,6 +712,51 @@ int litho_socs_image_batch(const void* kernels, const void* maskFTs, int tiles, 
                            StoreGroupSums<SquareTerm>{{}, sums, K, accumulate ? 1 : 0}, pn, log2_exact(N) - log2_exact(pn), st,
                            accumulate ? out : nullptr, sums));
     HIP_TRY(transpose_real(sums, out, w.planes, pn, st));
+    return LITHO_OK;
+}
+
+// The mask gradients of many windows: grads[b] (+)= 2 sum_j conj(kernels[j]) . L^H(gradIs[b][j / K] . L(kernels[j] . maskFTs[b])),
+// j < groups K ascending.  The fields are left transposed and the adjoint is taken of (G . E)^T, since L^H(Y)^T = L^H(Y^T): it
+// comes out of its own transpose in natural layout, where it meets the kernels line for line.  Two routes by pn alone:
+//   pn <= 2048  fused: the adjoint's second row pass ends in StoreTileSums, the sum over j held in LDS; the adjoint stack is not
+//               stored after that pass and no reduction kernel runs;
+//   pn == 4096  unfused (the sums would take 32 KiB of LDS beside 36 KiB of exchange buffer and the tables): the second pass
+//               stores the adjoints (natural layout, after the pass pair's own transpose) and k_vjp_reduce sums them tile by
+//               tile.
+// Either way a tile's sum is one sequence of additions in j, started from grads[b] when accumulate != 0.
+size_t litho_socs_vjp_batch_work_bytes(int tiles, int groups, int K, int pn) { return litho::VjpBatchWork(tiles, groups, K, pn).bytes(); }
+
+int litho_socs_vjp_batch(const void* kernels, const void* maskFTs, const float* gradIs, int tiles, int groups, int K, int pn, int N,
+                         void* grads, int accumulate, void* work, size_t work_bytes, void* stream)
+{
+    using namespace litho;
+    const VjpBatchWork w(tiles, groups, K, pn);
+    const int rc = admit(kernels && maskFTs && gradIs && grads && work, w, pn, N, w.bytes(), work_bytes);
+    if (rc != LITHO_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    float2* fields = (float2*)work;                                // item (b groups + g) K + k: E^T, then its adjoint
+    float* gt = (float*)(fields + w.stack());                      // gradIs[b][g]^T, plane by plane
+    const int log2m = log2_exact(N) - log2_exact(pn), J = groups * K;
+    HIP_TRY(fill_twiddles(st));
+    HIP_TRY(two_passes<+1>(LoadKernelTimesTile{(const float2*)kernels, (const float2*)maskFTs, J}, fields, w.items, StoreField{fields},
+                           pn, log2m, st));
+    HIP_TRY(transpose_real(gradIs, gt, w.planes, pn, st));
+    const LoadTimesGroupReal load{fields, gt, (int)w.items, K};    // item i meets plane i / K
+    if (pn <= 1 << max_log2((const StoreTileSums*)nullptr)) {
+        const StoreTileSums sums{(const float2*)kernels, (float2*)grads, J, accumulate ? 1 : 0, w.line_cells()};
+        HIP_TRY(two_passes<-1>(load, fields, w.items, sums, pn, log2m, st));
+        return LITHO_OK;
+    }
+    HIP_TRY(two_passes<-1>(load, fields, w.items, StoreField{fields}, pn, log2m, st));    // natural layout: no transpose back
+    const long long cells = (long long)pn * pn, pairs = cells / 2;
+    long long blocks = (pairs + 255) / 256;
+    if (blocks > 65536) blocks = 65536;                            // grid-stride beyond that
+    for (int b = 0; b < tiles; ++b) {
+        hipLaunchKernelGGL(k_vjp_reduce, dim3((unsigned)blocks), dim3(256), 0, st, (const float2*)kernels,
+                           (const float2*)fields + (size_t)b * J * cells, J, cells, (float2*)grads + (size_t)b * cells,
+                           accumulate ? 1 : 0);
+    }
+    HIP_TRY(hipGetLastError());
     return LITHO_OK;
 }
 

@@ -76,6 +76,61 @@ def hopkinsGradient(maskFT, socs, N, gradIntensity, out=None, kernelChunk=None):
     return out
 
 
+def hopkinsGradientBatch(maskFTs, socs, N, gradIntensities, out=None, tileChunk=None):
+    """hopkinsGradient for MANY mask spectra: complex64 [B,pn,pn] from `maskFTs` complex [B,pn,pn] and `gradIntensities` real
+    [B,pn,pn] (or [B,planes,pn,pn] for the kernels of a pupil stack), the layout of hopkinsIntensityBatch's image -- the windows
+    of a tiled inverse-lithography loop (tiling.optimizeMaskTiled).  Each chunk of `tileChunk` spectra is ONE litho_socs_vjp_batch
+    call on the whole kernel set (csrc/socs_grad.hip): the fields of every (spectrum, kernel) are left transposed, the adjoint
+    transform runs on (G . E)^T, and the sum over the kernels is folded into its last row pass (pn <= 2048; at 4096 the adjoints
+    are stored and reduced spectrum by spectrum).  `tileChunk` bounds the workspace, chunk * planes * (K * 8 + 4) * pn^2 bytes
+    (default: what keeps it under socs.STACK_BYTES, at least 1).  A spectrum's bits depend on that spectrum, its gradient and the
+    kernels alone: not on B, on its place in the batch or on `tileChunk`.  The sum runs in another order of transforms than
+    hopkinsGradient's, so the two agree to rounding and not bit for bit.  `out`: accumulated into when given."""
+    from .imageformation import ShapeError
+    if not isinstance(socs, SOCSKernels):
+        raise TypeError("hopkinsGradientBatch: socs must be the SOCSKernels socsKernels returned")
+    pn, planes, K = socs.pn, socs.planes, socs.K
+    if (not isinstance(maskFTs, torch.Tensor) or not maskFTs.is_complex() or maskFTs.dim() != 3 or maskFTs.shape[0] < 1
+            or tuple(maskFTs.shape[-2:]) != (pn, pn)):
+        raise ShapeError(f"maskFTs must be a complex tensor [B,{pn},{pn}] to match the kernels; got "
+                         f"{getattr(maskFTs, 'dtype', type(maskFTs).__name__)} {tuple(getattr(maskFTs, 'shape', ()))}")
+    if socs.kernels.device != maskFTs.device:
+        raise ShapeError(f"the kernels live on {socs.kernels.device}, the mask spectra on {maskFTs.device}")
+    dev = nat.require_gpu(maskFTs.device)
+    B = int(maskFTs.shape[0])
+    want = (B, planes, pn, pn) if socs.stacked else (B, pn, pn)
+    if (not isinstance(gradIntensities, torch.Tensor) or tuple(gradIntensities.shape) != want or gradIntensities.is_complex()
+            or gradIntensities.device != dev):
+        raise ShapeError(f"gradIntensities must be a real tensor of shape {want} on {dev} (hopkinsIntensityBatch's image); got "
+                         f"{getattr(gradIntensities, 'dtype', type(gradIntensities).__name__)} "
+                         f"{tuple(getattr(gradIntensities, 'shape', ()))} on {getattr(gradIntensities, 'device', None)}")
+    if tileChunk is None:
+        tileChunk = max(1, _socs.STACK_BYTES // (planes * (K * 8 + 4) * pn * pn))
+    tileChunk = int(tileChunk)
+    if tileChunk < 1:
+        raise ValueError(f"hopkinsGradientBatch: tileChunk must be >= 1; got {tileChunk}")
+    tileChunk = min(tileChunk, B)
+    out, given = _socs._accumulate_into(out, (B, pn, pn), torch.complex64, dev)
+    m = maskFTs.detach().to(torch.complex64).contiguous()
+    G = gradIntensities.detach().to(torch.float32).contiguous().reshape(B, planes, pn, pn)
+    kernels = socs.kernels.contiguous()
+    lib = nat.lib()
+    work = None
+    for b0 in range(0, B, tileChunk):
+        nb = min(tileChunk, B - b0)
+        nbytes = int(lib.litho_socs_vjp_batch_work_bytes(nb, planes, K, pn))
+        if nbytes == 0:
+            raise ValueError(f"hopkinsGradientBatch: {nb} spectra x {planes} planes x {K} kernels at pn {pn} are more lines than one "
+                             "call takes; pass a smaller tileChunk")
+        if work is None or work.numel() < nbytes:
+            work = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            nat.check(lib.litho_socs_vjp_batch(nat.ptr(kernels), nat.ptr(m[b0]), nat.ptr(G[b0]), nb, planes, K, pn, int(N),
+                                               nat.ptr(out[b0]), 1 if given else 0, nat.ptr(work), work.numel(), nat.stream_ptr(dev)),
+                      "litho_socs_vjp_batch")
+    return out
+
+
 class _HopkinsIntensityAD(torch.autograd.Function):
     @staticmethod
     def forward(ctx, maskFT, socs, N):

@@ -289,3 +289,262 @@ def hopkinsImageTiled(polygons, socs, pixelNumber: int, pixelSize: float, wavele
         if finite.numel() and top > 0:
             seam_error = float(finite.max()) / top
     return TiledImage(image if socs.stacked else image[0], plan, seam, seam_error)
+
+
+# ---- tiled inverse lithography -----------------------------------------------------------------------------------------------------
+def _tile_args(who, place, dev):
+    import torch
+    from .imageformation import ShapeError
+    if not isinstance(place, torch.Tensor) or place.dtype != torch.int32 or place.dim() != 2 or place.shape[1] != 2 or place.shape[0] < 1:
+        raise ShapeError(f"{who}: place must be an int32 tensor [count,2]; got {getattr(place, 'dtype', type(place).__name__)} "
+                         f"{tuple(getattr(place, 'shape', ()))}")
+    if place.device != dev:
+        raise ShapeError(f"{who}: place lives on {place.device}, the data on {dev}")
+    return place.contiguous()
+
+
+def cutTiles(plane, place, pixelNumber, halo, fill=0.0):
+    """litho_tiles_cut: complex64 [count,pn,pn], window t = plane[place[t] - halo ... + pn) on both axes, `fill` (complex) where
+    that leaves `plane` complex64 [rows,cols]; `place` int32 [count,2] = (row, col) of each core's first pixel (device)."""
+    import torch
+    from .imageformation import ShapeError
+    if not isinstance(plane, torch.Tensor) or plane.dtype != torch.complex64 or plane.dim() != 2:
+        raise ShapeError(f"cutTiles: plane must be a complex64 tensor [rows,cols]; got {getattr(plane, 'dtype', type(plane).__name__)} "
+                         f"{tuple(getattr(plane, 'shape', ()))}")
+    dev = nat.require_gpu(plane.device)
+    place = _tile_args("cutTiles", place, dev)
+    pn, halo, fill = int(pixelNumber), int(halo), complex(fill)
+    rows, cols, count = int(plane.shape[0]), int(plane.shape[1]), int(place.shape[0])
+    if pn < 1 or halo < 0 or 2 * halo >= pn or pn - 2 * halo > min(rows, cols):
+        raise ShapeError(f"cutTiles: halo {halo} at pixelNumber {pn} leaves no core inside a plane of {rows} x {cols}")
+    plane = plane.contiguous()
+    windows = torch.empty((count, pn, pn), dtype=torch.complex64, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_tiles_cut(nat.ptr(plane), rows, cols, nat.ptr(place), count, pn, halo, fill.real, fill.imag,
+                                            nat.ptr(windows), nat.stream_ptr(dev)), "litho_tiles_cut")
+    return windows
+
+
+def overlapAddTiles(windows, place, halo, rows, cols):
+    """litho_tiles_overlap_add, the adjoint of cutTiles: complex64 [rows,cols], every pixel the sum of the `windows` complex64
+    [count,pn,pn] samples that show it, in ascending tile order in fp32 from zero (no atomics); what a window holds outside the
+    plane is dropped."""
+    import torch
+    from .imageformation import ShapeError
+    if (not isinstance(windows, torch.Tensor) or windows.dtype != torch.complex64 or windows.dim() != 3
+            or windows.shape[1] != windows.shape[2]):
+        raise ShapeError(f"overlapAddTiles: windows must be a complex64 tensor [count,pn,pn]; got "
+                         f"{getattr(windows, 'dtype', type(windows).__name__)} {tuple(getattr(windows, 'shape', ()))}")
+    dev = nat.require_gpu(windows.device)
+    place = _tile_args("overlapAddTiles", place, dev)
+    count, pn, halo, rows, cols = int(windows.shape[0]), int(windows.shape[-1]), int(halo), int(rows), int(cols)
+    if int(place.shape[0]) != count:
+        raise ShapeError(f"overlapAddTiles: {count} windows and {int(place.shape[0])} places")
+    if rows < 1 or cols < 1 or halo < 0 or 2 * halo >= pn or pn - 2 * halo > min(rows, cols):
+        raise ShapeError(f"overlapAddTiles: halo {halo} at pixelNumber {pn} leaves no core inside a plane of {rows} x {cols}")
+    windows = windows.contiguous()
+    plane = torch.empty((rows, cols), dtype=torch.complex64, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_tiles_overlap_add(nat.ptr(windows), count, pn, halo, nat.ptr(place), nat.ptr(plane), rows, cols,
+                                                    nat.stream_ptr(dev)), "litho_tiles_overlap_add")
+    return plane
+
+
+def unstitchTiles(image, place, nt, j0, core):
+    """litho_tiles_unstitch, the adjoint of stitchTiles: fp32 [count,planes,nt,nt], the cores read back from `image` fp32
+    [planes,n,n] at `place` int32 [count,2] (device) and zero around them."""
+    import torch
+    from .imageformation import ShapeError
+    if (not isinstance(image, torch.Tensor) or image.dtype != torch.float32 or image.dim() != 3 or image.shape[1] != image.shape[2]):
+        raise ShapeError(f"unstitchTiles: image must be an fp32 tensor [planes,n,n]; got {getattr(image, 'dtype', type(image).__name__)} "
+                         f"{tuple(getattr(image, 'shape', ()))}")
+    dev = nat.require_gpu(image.device)
+    place = _tile_args("unstitchTiles", place, dev)
+    planes, n, count, nt, j0, core = int(image.shape[0]), int(image.shape[-1]), int(place.shape[0]), int(nt), int(j0), int(core)
+    if nt < 1 or core < 1 or j0 < 0 or j0 + core > nt or core > n:
+        raise ShapeError(f"unstitchTiles: the core [{j0}, {j0 + core}) leaves a window image of {nt} or a stitched image of {n}")
+    image = image.contiguous()
+    tiles = torch.empty((count, planes, nt, nt), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_tiles_unstitch(nat.ptr(image), n, nat.ptr(place), count, planes, nt, j0, core, nat.ptr(tiles),
+                                                 nat.stream_ptr(dev)), "litho_tiles_unstitch")
+    return tiles
+
+
+def maskPolygons(plan: TilePlan, mask, level: float = 0.5) -> List[np.ndarray]:
+    """The cells of a mask on the plan's raster lattice as polygons in layout nanometres: `mask` an ILTResult of optimizeMaskTiled
+    or a bool / real [ny core, nx core] tensor (cell (r, c) covers origin + (c, r) ... (c + 1, r + 1) pixels).  The outlines are
+    traceContours' at `level`, a cell's centre sitting at (c + 0.5, r + 0.5) pixels: what contoursToGDSII takes."""
+    import torch
+
+    from .contours import traceContours
+    m = getattr(mask, "mask", mask)
+    m = torch.as_tensor(m).to(torch.float32)
+    traced = traceContours(m, float(level))[0][0]
+    o = np.array([plan.origin[0], plan.origin[1]])
+    return [(np.asarray(q, dtype=np.float64).reshape(-1, 2) + 0.5) * plan.pixelSize + o for q in getattr(traced, "polygons", traced)]
+
+
+def _window_spectra(windows, plan, eps, N):
+    """complex64 [count,pn,pn]: the spectra of `windows` (transmissions) by the mask-spectrum entry, window by window."""
+    import torch
+    from .mask import Mask
+    specs = torch.empty_like(windows)
+    for b in range(int(windows.shape[0])):
+        specs[b] = Mask(transmission=windows[b], pixelSize=plan.pixelSize, device=windows.device)._ffFraunhofer(eps, N)
+    return specs
+
+
+def _image_windows(windows, socs, plan, place, gain, chunks, keep=False):
+    """(image fp32 [planes,n,n], {t0: spectra of the chunk that starts at t0} when `keep`): per chunk (t0, t1) of `windows` the
+    spectra, ONE hopkinsIntensityBatch, the gain, ONE postProcess with the windows as planes, ONE stitch."""
+    import torch
+
+    from . import socs as _socs
+    from .imageformation import postProcess
+    pn, planes, nt = plan.pixelNumber, socs.planes, plan.n_tile
+    eps, N = nat.epsilon_n(4.0 / pn, plan.pixelSize, plan.wavelength)
+    image = torch.zeros((planes, plan.n, plan.n), dtype=torch.float32, device=windows.device)
+    kept = {}
+    for t0, t1 in chunks:
+        specs = _window_spectra(windows[t0:t1], plan, eps, N)
+        if keep:
+            kept[t0] = specs
+        raw = _socs.hopkinsIntensityBatch(specs, socs, N, tileChunk=t1 - t0)
+        if gain != 1.0:
+            raw *= gain
+        tiles = postProcess(raw.reshape(-1, pn, pn), eps).reshape(t1 - t0, planes, nt, nt)
+        stitchTiles(tiles, place[t0:t1], plan.j0, plan.core, image)
+    return image, kept
+
+
+def _tile_chunks(who, tileChunk, socs, plan):
+    from . import socs as _socs
+    if tileChunk is None:
+        tileChunk = max(1, _socs.STACK_BYTES // (socs.planes * (socs.K * 8 + 4) * plan.pixelNumber ** 2))
+    tileChunk = int(tileChunk)
+    if tileChunk < 1:
+        raise ValueError(f"{who}: tileChunk must be >= 1; got {tileChunk}")
+    return [(t0, min(plan.count, t0 + tileChunk)) for t0 in range(0, plan.count, tileChunk)]
+
+
+def maskImageTiled(transmission, socs, plan: TilePlan, background=0, normalize=False, tileChunk=None):
+    """The stitched Hopkins image of a PIXEL mask on the plan's raster lattice: `transmission` complex or real [ny core, nx core],
+    cut into the plan's windows (`background` outside the plane) and imaged as optimizeMaskTiled's forward sweep images them.
+    fp32 [n,n] (or [planes,n,n] for the kernels of a pupil stack), the grid of hopkinsImageTiled(...).image."""
+    import torch
+
+    from . import socs as _socs
+    from .imageformation import ShapeError
+    if not isinstance(socs, _socs.SOCSKernels):
+        raise TypeError("maskImageTiled: socs must be the SOCSKernels socsKernels returned")
+    if not isinstance(plan, TilePlan):
+        raise TypeError("maskImageTiled: plan must be the TilePlan planTiles returned")
+    rows, cols = plan.ny * plan.core, plan.nx * plan.core
+    if not isinstance(transmission, torch.Tensor) or tuple(transmission.shape) != (rows, cols) or plan.pixelNumber != socs.pn:
+        raise ShapeError(f"maskImageTiled: transmission must be [{rows},{cols}] and the kernels {plan.pixelNumber} x {plan.pixelNumber}; "
+                         f"got {tuple(getattr(transmission, 'shape', ()))} and {socs.pn}")
+    dev = nat.require_gpu(socs.kernels.device)
+    place = torch.from_numpy(plan.place).to(dev)
+    windows = cutTiles(transmission.detach().to(device=dev, dtype=torch.complex64), place, plan.pixelNumber, plan.halo, background)
+    gain = 1.0 / float(socs.weight_sum) if normalize and socs.weight_sum > 0 else 1.0
+    image, _ = _image_windows(windows, socs, plan, place, gain, _tile_chunks("maskImageTiled", tileChunk, socs, plan))
+    return image if socs.stacked else image[0]
+
+
+def optimizeMaskTiled(target, socs, plan: TilePlan, threshold, dose=1.0, iterations=20, step=0.25, maskSteepness=4.0,
+                      resistSteepness=None, background=0, feature=1, initial=None, normalize=True, tileChunk=None):
+    """ilt.optimizeMask for a layout block larger than one window: ONE theta, fp32 [ny core, nx core] on the plan's raster lattice
+    (exactly the cores), one loss on the stitched image, and the exact gradient of the tiled forward model.
+
+    Per iterate: t = background + (feature - background) sigmoid(maskSteepness theta); the windows are cut from t with their halos
+    (cutTiles, `background` outside the plane); per chunk of `tileChunk` windows (None: what keeps the batched workspaces under
+    socs.STACK_BYTES) their spectra, ONE hopkinsIntensityBatch, the normalisation, ONE postProcess with the windows as planes, ONE
+    stitch.  The loss is _descent.resist_loss on image[:, :ny core, :nx core] -- the covered region: the empty part of the square
+    image of a non-square plan carries no loss.  `target`: real [n,n] or [planes,n,n] on the stitched grid, the grid of
+    hopkinsImageTiled(...).image.  Backwards: unstitchTiles, postProcessAdjoint, the normalisation, ONE hopkinsGradientBatch per
+    chunk, maskSpectrumAdjoint per window, overlapAddTiles -- a window's halo pixels carry gradient into the neighbouring cores --
+    then the theta chain and the peak-normalised step of optimizeMask.  The loss is read on the host once per iterate.  The
+    spectra are kept from the forward sweep when all of them fit under socs.STACK_BYTES and recomputed chunk by chunk otherwise;
+    neither that nor `tileChunk` changes a bit.  theta starts at +-1 from the target where the two grids share samples, or from
+    `initial` (real [ny core, nx core]).  Returns an ILTResult (theta, transmission, mask on the global lattice) with `.plan`.
+    See the module's caveat on pixel sizes with epsilon != 1."""
+    import torch
+
+    from . import _descent
+    from . import socs as _socs
+    from .ilt import ILTResult, hopkinsGradientBatch, maskSpectrumAdjoint, postProcessAdjoint
+    from .imageformation import ShapeError
+    who = "optimizeMaskTiled"
+    if not isinstance(socs, _socs.SOCSKernels):
+        raise TypeError(f"{who}: socs must be the SOCSKernels socsKernels returned")
+    if not isinstance(plan, TilePlan):
+        raise TypeError(f"{who}: plan must be the TilePlan planTiles returned")
+    iterations = int(iterations)
+    if resistSteepness is None:
+        resistSteepness = _descent.default_resist_steepness(threshold)
+    if iterations < 1 or not float(step) > 0 or not float(maskSteepness) > 0 or not float(resistSteepness) > 0:
+        raise ValueError(f"{who}: iterations >= 1 and step, maskSteepness, resistSteepness > 0; got {iterations}, {step}, "
+                         f"{maskSteepness}, {resistSteepness}")
+    if complex(feature) == complex(background):
+        raise ValueError(f"{who}: feature and background transmissions are equal; nothing to optimise")
+    pn, planes = int(socs.pn), socs.planes
+    if plan.pixelNumber != pn:
+        raise ShapeError(f"{who}: the kernels are {pn} x {pn}, the plan's windows {plan.pixelNumber}")
+    dev = nat.require_gpu(socs.kernels.device)
+    n, nt, core, halo, T = plan.n, plan.n_tile, plan.core, plan.halo, plan.count
+    rows, cols = plan.ny * core, plan.nx * core
+    want = ((planes, n, n), (n, n)) if socs.stacked else ((n, n),)
+    if not isinstance(target, torch.Tensor) or target.is_complex() or tuple(target.shape) not in want:
+        raise ShapeError(f"{who}: target must be a real tensor of shape {' or '.join(map(str, want))}, the stitched image's grid; got "
+                         f"{tuple(getattr(target, 'shape', ()))}")
+    target = target.detach().to(device=dev, dtype=torch.float32)
+    covered = target[..., :rows, :cols]
+    if initial is not None:
+        if not isinstance(initial, torch.Tensor) or tuple(initial.shape) != (rows, cols) or initial.is_complex():
+            raise ShapeError(f"{who}: initial must be a real [{rows},{cols}] tensor; got {tuple(getattr(initial, 'shape', ()))}")
+        theta = initial.detach().to(device=dev, dtype=torch.float32).clone()
+    else:
+        first = covered if covered.dim() == 2 else covered[0]                      # the two grids share their first sample
+        theta = torch.where(first > 0.5, 1.0, -1.0).to(torch.float32)
+    chunks = _tile_chunks(who, tileChunk, socs, plan)
+    eps, N = nat.epsilon_n(4.0 / pn, plan.pixelSize, plan.wavelength)
+    gain = 1.0 / float(socs.weight_sum) if normalize and socs.weight_sum > 0 else 1.0
+    keep = T * pn * pn * 8 <= _socs.STACK_BYTES
+    place = torch.from_numpy(plan.place).to(dev)
+    bg, span = complex(background), complex(feature) - complex(background)
+    a_m, a_r, dose, threshold = float(maskSteepness), float(resistSteepness), float(dose), float(threshold)
+
+    def transmission_of(th):
+        return (bg + span * torch.sigmoid(a_m * th)).to(torch.complex64)
+
+    losses, best, best_theta = [], 0, theta.clone()
+    for it in range(iterations + 1):
+        s = torch.sigmoid(a_m * theta)
+        windows = cutTiles((bg + span * s).to(torch.complex64), place, pn, halo, bg)
+        image, kept = _image_windows(windows, socs, plan, place, gain, chunks, keep)
+        loss, grad_cov = _descent.resist_loss(image[:, :rows, :cols], covered, a_r, dose, threshold, gradient=it < iterations)
+        losses.append(float(loss))                                                 # the one host read of this iterate
+        if losses[-1] < losses[best]:
+            best, best_theta = it, theta.clone()
+        if it == iterations or not math.isfinite(losses[-1]):
+            break
+        grad_image = torch.zeros((planes, n, n), dtype=torch.float32, device=dev)
+        grad_image[:, :rows, :cols] = grad_cov
+        grad_windows = torch.empty((T, pn, pn), dtype=torch.complex64, device=dev)
+        for t0, t1 in chunks:
+            specs = kept[t0] if keep else _window_spectra(windows[t0:t1], plan, eps, N)
+            gtiles = unstitchTiles(grad_image, place[t0:t1], nt, plan.j0, core)
+            # window by window: the same launches whatever the chunk, so the chunking changes no bit
+            graw = torch.stack([postProcessAdjoint(gtiles[b], pn, eps) for b in range(t1 - t0)])
+            if gain != 1.0:
+                graw *= gain
+            g = hopkinsGradientBatch(specs, socs, N, graw if socs.stacked else graw[:, 0], tileChunk=t1 - t0)
+            for b in range(t1 - t0):
+                grad_windows[t0 + b] = maskSpectrumAdjoint(g[b], pn, eps, N)
+        grad_t = overlapAddTiles(grad_windows, place, halo, rows, cols)           # dl/dRe t + i dl/dIm t on the global lattice
+        grad_theta = a_m * s * (1.0 - s) * (grad_t * span.conjugate()).real
+        theta = theta - float(step) * grad_theta / _descent.peak(grad_theta, torch.float32)
+    result = ILTResult(best_theta, transmission_of(best_theta), losses, best)
+    result.plan = plan
+    return result
