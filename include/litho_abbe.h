@@ -1092,6 +1092,29 @@ size_t litho_rasterize_coverage_work_bytes(int pn, int s, int band_rows);
 int litho_rasterize_coverage(const double *edges, int64_t n_edges, int pn, double x0, double y0, double pixel, int s, void *work,
                              size_t work_bytes, float *coverage, void *stream);
 
+/* ---- The same coverage for all windows of a tiled layout in one call (tiling.py: rasterizeLayoutTiles).  coverage[t], t < tiles,
+ * equals bit for bit what litho_rasterize_coverage writes for the edge list edges[tile_edges[i]], tile_offsets[t] <= i <
+ * tile_offsets[t + 1], at origin (windows[t][0], windows[t][1]) with the same pixel and s: one inside rule, one q = pixel /
+ * (double)s, one text for the sub-centre positions, the candidate-row test and the crossing abscissa.
+ * A tile's list must hold WHOLE closed polygons: an edge to the right of the window adds winding to every sub-column of its
+ * rows, and only the polygon's other edges cancel it.  So the caller culls per POLYGON (a polygon whose bounding box misses the
+ * window may be left out), never per edge.
+ * All arrays live on the device and are not inspected by the host; the kernel guards itself: an edge number outside
+ * [0, n_edges) is skipped, offsets are clamped to [0, n_index] (a descending pair is an empty list), non-finite and horizontal
+ * edges are skipped, a tile with a non-finite origin is written as zeros; nothing in them can make it read or write out of range.
+ * s outside {1, 2, 4, 8, 16}, pn < 1, pn * s > 32768, tiles < 1, n_edges or n_index < 0, n_edges >= 2^31, pixel <= 0 or not
+ * finite, or a null pointer (edges may be null when n_edges is 0, tile_edges when n_index is 0): LITHO_E_ARG, before any launch.
+ * No workspace: one workgroup per (tile, pixel row) keeps the winding deltas of one sub-row, pn * s int32, in LDS (at most
+ * 128 KiB of the 160 KiB a gfx950 workgroup may declare), adds the edges with LDS integer atomics -- the order cannot show --
+ * and scans; no global delta array, no clear pass, no global atomics.  Asynchronous, no allocation, no host wait; ONE launch
+ * whatever `tiles` is, up to 65535 tiles, and one more per further 65535. */
+int litho_rasterize_coverage_tiles(const double *edges, int64_t n_edges,          /* device fp64 [n_edges][4], layout units  */
+                                   const int64_t *tile_offsets,                   /* device [tiles + 1], ascending, into ... */
+                                   const int32_t *tile_edges, int64_t n_index,    /* device [n_index] edge numbers           */
+                                   const double *windows,                         /* device fp64 [tiles][2] = (x0, y0)       */
+                                   int tiles, int pn, double pixel, int s,
+                                   float *coverage /* [tiles][pn][pn] */, void *stream);
+
 /* ---- Mask spectrum pre-step: Mask._ffFraunhofer (mask.py:74-90).  geometry int16
  * [pn,pn]; spectrum complex64 [pn,pn].  Uses the same workspace as the Abbe calls. */
 int litho_mask_spectrum(const int16_t *geometry, int pn, double epsilon, int N, void *spectrum,

@@ -14,7 +14,8 @@ from .contours import (Contours, contourVertices, contoursToGDSII, contoursToLay
 from .socs import (SOCSKernels, hopkinsImage, hopkinsIntensity, hopkinsIntensityBatch,  # noqa: F401
                    socsKernels)
 from .tiling import (TiledImage, TilePlan, cutTiles, hopkinsImageTiled, maskImageTiled, maskPolygons,   # noqa: F401
-                     optimizeMaskTiled, overlapAddTiles, planTiles, stitchTiles, tileValidRegion, unstitchTiles)
+                     optimizeMaskTiled, overlapAddTiles, planTiles, stitchTiles, tileValidRegion, unstitchTiles,
+                     tileEdgeIndex, rasterizeLayoutTiles, correctLayoutTiled, epeJacobianTiled)
 from .ilt import (ILTResult, bakedResistModel, developedResistModel, hopkinsFields,     # noqa: F401
                   hopkinsGradient, hopkinsGradientBatch, hopkinsIntensityAD, maskSpectrumAdjoint, optimizeMask, postProcessAdjoint)
 from .smo import (SourceResult, optimizeSource, optimizeSourceMask, projectedStep,      # noqa: F401
@@ -65,4 +66,5 @@ __all__ = ["Mask", "attenuatedPSM", "alternatingPSM", "LightSource", "Pupil", "a
            "hopkinsTangent", "postProcessTangent", "edgeCoverageTangent", "measureEPETangent", "measureCDTangent", "epeJacobian",
            "maskErrorFactor",
            "hopkinsIntensityBatch", "tileValidRegion", "planTiles", "hopkinsImageTiled", "TilePlan", "TiledImage",
-           "hopkinsGradientBatch", "cutTiles", "overlapAddTiles", "stitchTiles", "unstitchTiles", "optimizeMaskTiled", "maskPolygons", "maskImageTiled"]
+           "hopkinsGradientBatch", "cutTiles", "overlapAddTiles", "stitchTiles", "unstitchTiles", "optimizeMaskTiled", "maskPolygons", "maskImageTiled",
+           "tileEdgeIndex", "rasterizeLayoutTiles", "correctLayoutTiled", "epeJacobianTiled"]

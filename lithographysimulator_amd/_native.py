@@ -159,6 +159,8 @@ _SIGNATURES = {
     "litho_rasterize_coverage_work_bytes": (c_size_t, [c_int, c_int, c_int]),
     "litho_rasterize_coverage": (c_int, [c_void_p, c_int64, c_int, c_double, c_double, c_double, c_int, c_void_p, c_size_t, c_void_p,
                                          c_void_p]),
+    "litho_rasterize_coverage_tiles": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_double, c_int,
+                                               c_void_p, c_void_p]),
     "litho_abbe_last_plan": (c_int, [POINTER(c_int64)]),
     "litho_abbe_last_kernels": (c_int, [c_void_p, c_void_p, c_size_t]),
     "litho_abbe_set_profiling": (c_int, [c_int]),

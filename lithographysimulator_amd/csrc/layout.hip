@@ -11,11 +11,13 @@
 //                    edge -1:  delta[row][0] += dir, delta[row][k] -= dir  (int32 atomics, [pn][pn + 1]).
 //   k_raster_fill    one workgroup per row: prefix sum of delta = winding number of every centre; geometry = (w != 0).
 // litho_rasterize_coverage (further down) applies the same rule to s x s sub-centres per pixel: k_cov_edges, k_cov_fill.
+// litho_rasterize_coverage_tiles does that for all windows of a tiled layout in one launch, the deltas of one sub-row in LDS: k_cov_tiles.
 #include "engine_common.hpp"
 #include "../../include/litho_abbe.h"
 
 #include <cmath>
 #include <cstdint>
+#include <type_traits>
 
 namespace litho {
 
@@ -87,8 +89,50 @@ __global__ __launch_bounds__(256) void k_raster_fill(const int* __restrict__ del
 // band's sub-rows -> fill and reduce.  Every sub-row is computed from its own deltas alone: the band height cannot show.
 constexpr int COV_CHUNK = 128;                                 // sub-rows one k_cov_edges thread walks at most
 
-// k_raster_edges' arithmetic at pitch q (W = pn s sub-columns), one thread per (edge, chunk of COV_CHUNK sub-rows of the band
-// [sub_lo, sub_hi)): at s = 16 a tall edge crosses 32768 sub-rows, which is not one thread's work.  delta holds the band only.
+// ---- The crossing arithmetic of the coverage rasterisers, ONE text for k_cov_edges and k_cov_tiles: k_raster_edges' at pitch q
+// (W = pn s sub-columns).  cov_edge_load: the edge and its candidate sub-rows [rlo, rhi] -- one spare on both sides, clipped to
+// [c_lo, c_hi]; the exact test in cov_edge_cross decides.  false: the edge cannot add to those sub-rows (a non-finite coordinate
+// -- NaN or +-inf: inf * 0 and inf - inf would be NaN and the cast to int undefined --, a horizontal edge, an empty clip).
+struct CovEdge {
+    double x0, y0, slope_num, slope_den, ymin, ymax, rlo, rhi;
+    int dir;
+};
+
+__device__ __forceinline__ bool cov_edge_load(const double* __restrict__ edge, double oy, double q, int c_lo, int c_hi, CovEdge& E)
+{
+    const double x0 = edge[0], y0 = edge[1], x1 = edge[2], y1 = edge[3];
+    if (!(isfinite(x0) && isfinite(y0) && isfinite(x1) && isfinite(y1)) || y0 == y1) return false;
+    E.dir = y1 > y0 ? 1 : -1;
+    E.ymin = y0 < y1 ? y0 : y1;
+    E.ymax = y0 < y1 ? y1 : y0;
+    double rlo = floor((E.ymin - oy) / q - 0.5) - 1.0, rhi = ceil((E.ymax - oy) / q - 0.5) + 1.0;
+    if (rlo < (double)c_lo) rlo = (double)c_lo;
+    if (rhi > (double)c_hi) rhi = (double)c_hi;
+    if (!(rlo <= rhi)) return false;
+    E.rlo = rlo;
+    E.rhi = rhi;
+    E.x0 = x0;
+    E.y0 = y0;
+    E.slope_num = x1 - x0;
+    E.slope_den = y1 - y0;
+    return true;
+}
+
+// k = the number of sub-columns C of sub-row r with ox + (C + 0.5) q left of the edge's crossing, clamped to [0, W]; 0 as well
+// where the sub-row's ordinate misses [ymin, ymax).  The caller adds dir at column 0 and -dir at column k when k > 0.
+__device__ __forceinline__ int cov_edge_cross(const CovEdge& E, int r, double ox, double oy, double q, int W)
+{
+    const double yc = oy + ((double)r + 0.5) * q;
+    if (!(E.ymin <= yc && yc < E.ymax)) return 0;
+    const double xc = E.x0 + ((yc - E.y0) * E.slope_num) / E.slope_den;
+    double t = ceil((xc - ox) / q - 0.5);                      // sub-columns C with ox + (C + 0.5) q < xc
+    if (t < 0.0) t = 0.0;
+    if (t > (double)W) t = (double)W;
+    return (int)t;
+}
+
+// One thread per (edge, chunk of COV_CHUNK sub-rows of the band [sub_lo, sub_hi)): at s = 16 a tall edge crosses 32768 sub-rows,
+// which is not one thread's work.  delta holds the band only.
 __global__ __launch_bounds__(256) void k_cov_edges(const double* __restrict__ edges, int ne, int W, double ox, double oy, double q,
                                                    int sub_lo, int sub_hi, int* __restrict__ delta)
 {
@@ -96,28 +140,14 @@ __global__ __launch_bounds__(256) void k_cov_edges(const double* __restrict__ ed
     if (e >= ne) return;
     const int c_lo = sub_lo + (int)blockIdx.y * COV_CHUNK;
     const int c_hi = min(sub_hi, c_lo + COV_CHUNK) - 1;       // inclusive; grid.y covers the band, so c_lo <= c_hi
-    const double x0 = edges[4 * e], y0 = edges[4 * e + 1], x1 = edges[4 * e + 2], y1 = edges[4 * e + 3];
-    if (!(isfinite(x0) && isfinite(y0) && isfinite(x1) && isfinite(y1)) || y0 == y1) return;
-    const int dir = y1 > y0 ? 1 : -1;
-    const double ymin = y0 < y1 ? y0 : y1, ymax = y0 < y1 ? y1 : y0;
-    // candidate sub-rows: one spare on both sides, clipped to this thread's chunk; the exact test below decides
-    double rlo = floor((ymin - oy) / q - 0.5) - 1.0, rhi = ceil((ymax - oy) / q - 0.5) + 1.0;
-    if (rlo < (double)c_lo) rlo = (double)c_lo;
-    if (rhi > (double)c_hi) rhi = (double)c_hi;
-    if (!(rlo <= rhi)) return;
-    const double slope_num = x1 - x0, slope_den = y1 - y0;
-    for (int r = (int)rlo; r <= (int)rhi; ++r) {
-        const double yc = oy + ((double)r + 0.5) * q;
-        if (!(ymin <= yc && yc < ymax)) continue;
-        const double xc = x0 + ((yc - y0) * slope_num) / slope_den;
-        double t = ceil((xc - ox) / q - 0.5);                  // sub-columns C with ox + (C + 0.5) q < xc
-        if (t < 0.0) t = 0.0;
-        if (t > (double)W) t = (double)W;
-        const int k = (int)t;
+    CovEdge E;
+    if (!cov_edge_load(edges + 4 * (size_t)e, oy, q, c_lo, c_hi, E)) return;
+    for (int r = (int)E.rlo; r <= (int)E.rhi; ++r) {
+        const int k = cov_edge_cross(E, r, ox, oy, q, W);
         if (k == 0) continue;
         int* row = delta + (size_t)(r - sub_lo) * ((size_t)W + 1);
-        atomicAdd(row, dir);
-        atomicAdd(row + k, -dir);
+        atomicAdd(row, E.dir);
+        atomicAdd(row + k, -E.dir);
     }
 }
 
@@ -204,6 +234,158 @@ static void launch_cov_fill(hipStream_t st, const int* delta, int pn, int rows, 
 
 static bool cov_supersampling(int s) { return s == 1 || s == 2 || s == 4 || s == 8 || s == 16; }
 
+// ---- All windows of a chunk in one launch (litho_rasterize_coverage_tiles): one workgroup per (tile, pixel row), the winding
+// deltas of ONE sub-row in LDS -- no global delta array, no clear pass, no global atomics.  Dynamic LDS, in this order:
+//   line  int32 [W + W / 32 + 1]   deltas of the current sub-row, one pad word per 32 (k_cov_fill's layout: the S-strided reads
+//                                  of the scan are conflict-free); the sink at sub-column W is never stored
+//   list  int32 [COV_LIST]         the numbers of the tile's edges whose candidate sub-rows meet this pixel row, compacted once
+//   misc  int32 [16]               [0] the list's length, [8 + 4 (parity) + wave] the waves' totals of a scan step
+//   cnt   CovCount<S> [pn]         inside sub-centres per pixel over the sub-rows done so far (S > 1; S = 1 writes at once)
+// Per sub-row: the threads walk the list (or, when it overflowed, the tile's whole index range) and add +-1 with LDS integer
+// atomics -- the order cannot show; barrier; steps of 256 pixels, one pixel per thread: the thread reads the S deltas of its
+// pixel and stores zeros in their place (the line is clear again for the next sub-row), a shuffle scan per wave and the waves'
+// totals through `misc` (one barrier per step, two parities) give the winding left of the pixel.  A pixel belongs to the same
+// thread in every sub-row, so `cnt` needs no barrier of its own.
+constexpr int COV_LIST = 1024;
+constexpr int COV_TILES_LDS_MAX = 160 * 1024;
+template <int S>
+using CovCount = typename std::conditional<(S * S < 256), uint8_t, uint16_t>::type;
+
+__host__ __device__ constexpr int cov_line_words(int W) { return W + (W >> 5) + 1; }
+
+template <int S>
+static size_t cov_tiles_lds(int pn)
+{
+    const size_t words = (size_t)cov_line_words(pn * S) + COV_LIST + 16;
+    return words * sizeof(int) + (S > 1 ? (((size_t)pn * sizeof(CovCount<S>) + 3) & ~(size_t)3) : 0);
+}
+
+template <int S>
+__global__ __launch_bounds__(256) void k_cov_tiles(const double* __restrict__ edges, long long n_edges,
+                                                   const long long* __restrict__ tile_offsets, const int* __restrict__ tile_edges,
+                                                   long long n_index, const double* __restrict__ windows, int tile0, int pn, double q,
+                                                   float* __restrict__ coverage)
+{
+    extern __shared__ __attribute__((aligned(16))) int cov_lds[];
+    const int W = pn * S;
+    int* line = cov_lds;
+    int* list = line + cov_line_words(W);
+    int* misc = list + COV_LIST;
+    CovCount<S>* cnt = (CovCount<S>*)(misc + 16);
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    const int tile = tile0 + (int)blockIdx.y, prow = (int)blockIdx.x;
+    float* out = coverage + ((size_t)tile * pn + prow) * pn;
+    const double ox = windows[2 * (size_t)tile], oy = windows[2 * (size_t)tile + 1];
+    if (!(isfinite(ox) && isfinite(oy))) {                     // workgroup-uniform
+        for (int p = t; p < pn; p += 256) out[p] = 0.0f;
+        return;
+    }
+    long long lo = tile_offsets[tile], hi = tile_offsets[tile + 1];
+    lo = lo < 0 ? 0 : (lo > n_index ? n_index : lo);
+    hi = hi < lo ? lo : (hi > n_index ? n_index : hi);
+    const long long span = hi - lo;
+    const int sub0 = prow * S;
+    for (int i = t; i < cov_line_words(W); i += 256) line[i] = 0;
+    if (S > 1)
+        for (int p = t; p < pn; p += 256) cnt[p] = 0;
+    if (t == 0) misc[0] = 0;
+    __syncthreads();
+    // the edges that can meet this pixel row, once; more than COV_LIST of them: every sub-row walks the whole range instead
+    for (long long i = t; i < span; i += 256) {
+        const long long e = tile_edges[lo + i];
+        CovEdge E;
+        if (e < 0 || e >= n_edges || !cov_edge_load(edges + 4 * (size_t)e, oy, q, sub0, sub0 + S - 1, E)) continue;
+        const int at = atomicAdd(&misc[0], 1);
+        if (at < COV_LIST) list[at] = (int)e;
+    }
+    __syncthreads();
+    const int found = misc[0];
+    const bool listed = found <= COV_LIST;
+    const long long walk = listed ? (long long)found : span;
+    int parity = 0;
+    for (int j = 0; j < S; ++j) {
+        const int r = sub0 + j;
+        int first = 0;                                         // this thread's share of column 0
+        for (long long i = t; i < walk; i += 256) {
+            const long long e = listed ? (long long)list[i] : (long long)tile_edges[lo + i];
+            CovEdge E;
+            if (e < 0 || e >= n_edges || !cov_edge_load(edges + 4 * (size_t)e, oy, q, r, r, E)) continue;
+            const int k = cov_edge_cross(E, r, ox, oy, q, W);
+            if (k == 0) continue;
+            first += E.dir;
+            if (k < W) atomicAdd(&line[k + (k >> 5)], -E.dir);
+        }
+        if (first != 0) atomicAdd(&line[0], first);
+        __syncthreads();
+        int carry = 0;                                         // winding left of the step's first sub-centre
+        for (int p0 = 0; p0 < pn; p0 += 256) {
+            const int p = p0 + t;
+            int x[S], tot = 0;
+#pragma unroll
+            for (int c = 0; c < S; ++c) {
+                const int i = p * S + c;
+                x[c] = p < pn ? line[i + (i >> 5)] : 0;
+                tot += x[c];
+            }
+            if (p < pn) {
+#pragma unroll
+                for (int c = 0; c < S; ++c) {
+                    const int i = p * S + c;
+                    line[i + (i >> 5)] = 0;
+                }
+            }
+            int incl = tot;
+#pragma unroll
+            for (int off = 1; off < 64; off <<= 1) {
+                const int u = __shfl_up(incl, off);
+                if (lane >= off) incl += u;
+            }
+            int* wt = misc + 8 + 4 * parity;
+            if (lane == 63) wt[wave] = incl;
+            __syncthreads();
+            int w = carry + incl - tot;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                const int u = wt[v];
+                if (v < wave) w += u;
+                carry += u;
+            }
+            parity ^= 1;
+            int inside = 0;
+#pragma unroll
+            for (int c = 0; c < S; ++c) {
+                w += x[c];
+                inside += w != 0 ? 1 : 0;
+            }
+            if (p < pn) {
+                if (S == 1) out[p] = (float)inside;
+                else if (j == S - 1) out[p] = (float)((int)cnt[p] + inside) * (1.0f / (float)(S * S));
+                else cnt[p] = (CovCount<S>)((int)cnt[p] + inside);
+            }
+        }
+    }
+}
+
+template <int S>
+static hipError_t launch_cov_tiles(hipStream_t st, const double* edges, int64_t n_edges, const int64_t* offsets, const int32_t* index,
+                                   int64_t n_index, const double* windows, int tiles, int pn, double q, float* cov)
+{
+    const size_t lds = cov_tiles_lds<S>(pn);
+    if (lds > 64 * 1024) {                                     // once per device: the most a workgroup may declare
+        static unsigned lds_done = 0;
+        const hipError_t e = lds_opt_in(lds_done, (const void*)k_cov_tiles<S>, COV_TILES_LDS_MAX);
+        if (e != hipSuccess) return e;
+    }
+    for (int t0 = 0; t0 < tiles; t0 += 65535) {                // grid.y
+        const int n = tiles - t0 < 65535 ? tiles - t0 : 65535;
+        hipLaunchKernelGGL(k_cov_tiles<S>, dim3((unsigned)pn, (unsigned)n), dim3(256), lds, st, edges, (long long)n_edges,
+                           (const long long*)offsets, index, (long long)n_index, windows, t0, pn, q, cov);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 }  // namespace litho
 
 extern "C" {
@@ -274,6 +456,27 @@ int litho_rasterize_coverage(const double* edges, int64_t n_edges, int pn, doubl
         default: launch_cov_fill<16>(st, (const int*)work, pn, rows, out); break;
         }
         HIP_TRY(hipGetLastError());
+    }
+    return LITHO_OK;
+}
+
+int litho_rasterize_coverage_tiles(const double* edges, int64_t n_edges, const int64_t* tile_offsets, const int32_t* tile_edges,
+                                   int64_t n_index, const double* windows, int tiles, int pn, double pixel, int s, float* coverage,
+                                   void* stream)
+{
+    using namespace litho;
+    if (!cov_supersampling(s) || pn < 1 || (int64_t)pn * s > 32768 || tiles < 1 || n_edges < 0 || n_edges > 0x7FFFFFFF || n_index < 0 ||
+        !(pixel > 0.0) || !(pixel <= 1.7976931348623157e308) || !coverage || !tile_offsets || !windows || (n_edges > 0 && !edges) ||
+        (n_index > 0 && !tile_edges))
+        return LITHO_E_ARG;
+    const double q = pixel / (double)s;
+    hipStream_t st = (hipStream_t)stream;
+    switch (s) {
+    case 1: HIP_TRY(launch_cov_tiles<1>(st, edges, n_edges, tile_offsets, tile_edges, n_index, windows, tiles, pn, q, coverage)); break;
+    case 2: HIP_TRY(launch_cov_tiles<2>(st, edges, n_edges, tile_offsets, tile_edges, n_index, windows, tiles, pn, q, coverage)); break;
+    case 4: HIP_TRY(launch_cov_tiles<4>(st, edges, n_edges, tile_offsets, tile_edges, n_index, windows, tiles, pn, q, coverage)); break;
+    case 8: HIP_TRY(launch_cov_tiles<8>(st, edges, n_edges, tile_offsets, tile_edges, n_index, windows, tiles, pn, q, coverage)); break;
+    default: HIP_TRY(launch_cov_tiles<16>(st, edges, n_edges, tile_offsets, tile_edges, n_index, windows, tiles, pn, q, coverage)); break;
     }
     return LITHO_OK;
 }

@@ -390,6 +390,18 @@ def polygonEdges(polygons: Sequence[np.ndarray], orient: bool = True) -> np.ndar
     return np.ascontiguousarray(np.concatenate(rows, axis=0)) if rows else np.zeros((0, 4))
 
 
+def polygonEdgeOwners(polygons: Sequence[np.ndarray]) -> np.ndarray:
+    """int64 [n_edges]: for every row of polygonEdges(polygons) the number of its polygon in `polygons` (polygons of fewer than
+    three vertices have no edge and keep their number)."""
+    groups: Dict[int, List[int]] = {}
+    for i, q in enumerate(polygons):
+        k = np.asarray(q).size // 2
+        if k >= 3:
+            groups.setdefault(k, []).append(i)
+    rows = [np.repeat(np.asarray(items, dtype=np.int64), k) for k, items in groups.items()]
+    return np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+
+
 ANTIALIAS_LEVELS = (1, 2, 4, 8, 16)
 COVERAGE_WORK_BYTES = 256 << 20            # default ceiling of the coverage rasteriser's workspace
 
@@ -443,6 +455,45 @@ def rasterizeLayout(polygons: Sequence[np.ndarray], pixelNumber: int, pixelSize:
                                                   float(pixelSize), nat.ptr(work), work.numel(), nat.ptr(geo),
                                                   nat.stream_ptr(dev)), "litho_rasterize_edges")
     return geo
+
+
+def rasterizeCoverageTiles(edges, offsets, index, windows, pixelNumber: int, pixelSize: float, antialias: int = 16):
+    """litho_rasterize_coverage_tiles: float32 [tiles,pn,pn], window t the area coverage (rasterizeLayout(antialias=s), bit for
+    bit; s = 1 gives 0.0 / 1.0) of the edges edges[index[offsets[t]:offsets[t + 1]]] at origin windows[t] -- all windows in one
+    launch.  `edges` float64 [E,4] (polygonEdges), `offsets` int64 [tiles + 1], `index` int32 [M], `windows` float64 [tiles,2], all
+    on one GPU.  A window's list must hold whole polygons (tiling.tileEdgeIndex culls per polygon).  The values of the device arrays
+    are not read here (the kernel skips what is out of range): tiling.rasterizeLayoutTiles checks them on the host first."""
+    import torch
+
+    from . import _native as nat
+    from .imageformation import ShapeError
+    s, pn = int(antialias), int(pixelNumber)
+    if s != antialias or s not in ANTIALIAS_LEVELS:
+        raise ValueError(f"rasterizeCoverageTiles: antialias must be one of {ANTIALIAS_LEVELS}; got {antialias!r}")
+    if pn < 1 or pn * s > 32768:
+        raise ValueError(f"rasterizeCoverageTiles: pixelNumber * antialias must lie in 1..32768; got {pn} * {s}")
+    if not (float(pixelSize) > 0.0 and math.isfinite(float(pixelSize))):
+        raise ValueError(f"rasterizeCoverageTiles: pixelSize must be finite and > 0; got {pixelSize}")
+    want = (("edges", edges, torch.float64, 2, 4), ("offsets", offsets, torch.int64, 1, None), ("index", index, torch.int32, 1, None),
+            ("windows", windows, torch.float64, 2, 2))
+    for name, a, dtype, dim, last in want:
+        if not isinstance(a, torch.Tensor) or a.dtype != dtype or a.dim() != dim or (last is not None and a.shape[-1] != last):
+            raise ShapeError(f"rasterizeCoverageTiles: {name} must be a {dtype} tensor of {dim} dimensions"
+                             f"{'' if last is None else f' with rows of {last}'}; got {getattr(a, 'dtype', type(a).__name__)} "
+                             f"{tuple(getattr(a, 'shape', ()))}")
+    dev = nat.require_gpu(windows.device)
+    tiles = int(windows.shape[0])
+    if tiles < 1 or int(offsets.shape[0]) != tiles + 1 or any(a.device != dev for a in (edges, offsets, index)):
+        raise ShapeError(f"rasterizeCoverageTiles: {tiles} windows need {tiles + 1} offsets (got {int(offsets.shape[0])}) and every "
+                         f"array on {dev}")
+    edges, offsets, index, windows = edges.contiguous(), offsets.contiguous(), index.contiguous(), windows.contiguous()
+    cov = torch.empty((tiles, pn, pn), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(nat.lib().litho_rasterize_coverage_tiles(nat.ptr(edges) if edges.numel() else None, int(edges.shape[0]),
+                                                           nat.ptr(offsets), nat.ptr(index) if index.numel() else None,
+                                                           int(index.shape[0]), nat.ptr(windows), tiles, pn, float(pixelSize), s,
+                                                           nat.ptr(cov), nat.stream_ptr(dev)), "litho_rasterize_coverage_tiles")
+    return cov
 
 
 def composeTransmission(coverages, values, background: complex = 0):

@@ -345,6 +345,11 @@ def correctLayout(polygons, pixelNumber, pixelSize, origin, wavelength, pupil, s
                                    searchRange=searchRange)[1]
     if step == "meef":
         return _meef_loop(target, sites, imager, epe, sensitivity, iterations, maxBias)
+    return _damped_loop(target, sites, imager, epe, iterations, gain, maxBias)
+
+
+def _damped_loop(target, sites, imager, epe, iterations, gain, maxBias):
+    """correctLayout(step="damped"): bias <- clip(bias - gain * EPE, +-maxBias), +maxBias / 6 where a site found no edge."""
     bias = np.zeros(len(sites))
     history, measured, best = [], [], None
     for it in range(iterations):

@@ -204,6 +204,123 @@ def seamTiles(tiles, neighbours, j0, core):
     return out
 
 
+def tileEdgeIndex(polygons, plan: TilePlan, orient: bool = True):
+    """(edges float64 [E,4], offsets int64 [T + 1], index int32 [M]) on the host: `edges` = polygonEdges(polygons, orient), and
+    tile t of `plan` rasterises the edges index[offsets[t]:offsets[t + 1]], ascending.  Culling is per POLYGON, never per edge: a
+    polygon belongs to a tile when its bounding box overlaps the window (strictly: touching a border is no overlap), and then
+    ALL its edges do -- an edge to the right of a window adds winding to every column of its rows, which only the polygon's other
+    edges cancel.  No Python loop over polygons times tiles."""
+    from .layout import polygonEdgeOwners, polygonEdges
+    if not isinstance(plan, TilePlan):
+        raise TypeError("tileEdgeIndex: plan must be the TilePlan planTiles returned")
+    polygons = list(polygons)
+    edges = polygonEdges(polygons, orient=orient)
+    owner = polygonEdgeOwners(polygons)
+    E, T, P = int(edges.shape[0]), plan.count, len(polygons)
+    if E >= 2 ** 31:
+        raise ValueError(f"tileEdgeIndex: {E} edges do not fit the int32 index")
+    if E == 0:
+        return edges, np.zeros(T + 1, dtype=np.int64), np.zeros(0, dtype=np.int32)
+    xs, ys = edges[:, 0], edges[:, 1]                       # every vertex starts one edge
+    boxes = np.empty((P, 4))
+    boxes[:, :2], boxes[:, 2:] = np.inf, -np.inf
+    np.minimum.at(boxes[:, 0], owner, xs)
+    np.minimum.at(boxes[:, 1], owner, ys)
+    np.maximum.at(boxes[:, 2], owner, xs)
+    np.maximum.at(boxes[:, 3], owner, ys)
+    span = plan.pixelNumber * plan.pixelSize
+    wx, wy = plan.windows_nm[:, 0:1], plan.windows_nm[:, 1:2]
+    hit = (boxes[None, :, 2] > wx) & (boxes[None, :, 0] < wx + span) & (boxes[None, :, 3] > wy) & (boxes[None, :, 1] < wy + span)
+    tt, pp = np.nonzero(hit)                                # by tile, then polygon
+    by_owner = np.argsort(owner, kind="stable")             # a polygon's edges, ascending
+    count = np.bincount(owner, minlength=P)
+    start = np.cumsum(count) - count
+    n = count[pp]
+    total = int(n.sum())
+    first = np.cumsum(n) - n
+    within = np.arange(total, dtype=np.int64) - np.repeat(first, n)
+    tile = np.repeat(tt, n)
+    picked = by_owner[np.repeat(start[pp], n) + within]
+    order = np.argsort(tile.astype(np.int64) * E + picked, kind="stable")
+    offsets = np.concatenate([[0], np.cumsum(np.bincount(tile, minlength=T))]).astype(np.int64)
+    return edges, offsets, picked[order].astype(np.int32)
+
+
+def _check_tile_index(who, edges, offsets, index, tiles):
+    """The host-side check the C entry cannot make: shapes, ascending offsets inside the index, edge numbers inside the edges."""
+    if (edges.ndim != 2 or edges.shape[1] != 4 or offsets.shape != (tiles + 1,) or index.ndim != 1 or offsets[0] < 0
+            or np.any(np.diff(offsets) < 0) or offsets[-1] > index.shape[0]
+            or (index.size and (int(index.min()) < 0 or int(index.max()) >= edges.shape[0]))):
+        raise ValueError(f"{who}: the tile index does not fit its edges ({edges.shape}, {offsets.shape}, {index.shape} for {tiles} tiles)")
+
+
+def _upload_tile_index(who, polygons, plan, orient, dev):
+    """tileEdgeIndex on the device: (edges, offsets, index, windows), ONE upload of each."""
+    import torch
+    edges, offsets, index = tileEdgeIndex(polygons, plan, orient)
+    _check_tile_index(who, edges, offsets, index, plan.count)
+    return (torch.from_numpy(edges).to(dev), torch.from_numpy(offsets).to(dev), torch.from_numpy(index).to(dev),
+            torch.from_numpy(np.ascontiguousarray(plan.windows_nm, dtype=np.float64)).to(dev))
+
+
+def _raster_tiles(arrays, plan, antialias, t0, t1):
+    from .layout import rasterizeCoverageTiles
+    edges, offsets, index, windows = arrays
+    return rasterizeCoverageTiles(edges, offsets[t0:t1 + 1], index, windows[t0:t1], plan.pixelNumber, plan.pixelSize, antialias)
+
+
+def rasterizeLayoutTiles(polygons, plan: TilePlan, antialias: int = 16, device=None, orient: bool = True, tiles=None):
+    """The area coverage of every window of `plan`: float32 [count,pn,pn], window t bit for bit
+    rasterizeLayout(the polygons whose boxes overlap it, pn, pixelSize, origin=plan.windows_nm[t], antialias=antialias) -- all of
+    them in ONE launch (litho_rasterize_coverage_tiles) after ONE upload of the edges and of the per-tile index (tileEdgeIndex).
+    antialias = 1 gives 0.0 / 1.0, the binary raster as a transmission.  `tiles` = (t0, t1) rasterises the windows t0 .. t1 - 1
+    only; a window's bits do not depend on the others.  `orient` as rasterizeLayout takes it."""
+    from .layout import ANTIALIAS_LEVELS
+    if not isinstance(plan, TilePlan):
+        raise TypeError("rasterizeLayoutTiles: plan must be the TilePlan planTiles returned")
+    s = int(antialias)
+    if s != antialias or s not in ANTIALIAS_LEVELS:
+        raise ValueError(f"rasterizeLayoutTiles: antialias must be one of {ANTIALIAS_LEVELS}; got {antialias!r}")
+    if plan.pixelNumber * s > 32768:
+        raise ValueError(f"rasterizeLayoutTiles: pixelNumber * antialias must lie in 1..32768; got {plan.pixelNumber} * {s}")
+    t0, t1 = (0, plan.count) if tiles is None else (int(tiles[0]), int(tiles[1]))
+    if not 0 <= t0 < t1 <= plan.count:
+        raise ValueError(f"rasterizeLayoutTiles: tiles must be (t0, t1) with 0 <= t0 < t1 <= {plan.count}; got {tiles!r}")
+    if not np.isfinite(plan.windows_nm).all():
+        raise ValueError("rasterizeLayoutTiles: a window origin of the plan is not finite")
+    dev = nat.require_gpu(nat.pick_device(device, "layout"))
+    return _raster_tiles(_upload_tile_index("rasterizeLayoutTiles", polygons, plan, orient, dev), plan, s, t0, t1)
+
+
+def _sweep_layout(polygons, socs, plan, antialias, divide, chunks, dev, orient=True, each=None, spectra=None):
+    """The stitched image fp32 [planes,n,n] of a layout, the sweep hopkinsImageTiled, correctLayoutTiled and epeJacobianTiled
+    share: ONE upload of the culled edges; per chunk (t0, t1) ONE raster launch, the window spectra, ONE hopkinsIntensityBatch,
+    the division by `divide` (None: none), ONE postProcess with the windows as planes, ONE stitch.  `each(t0, t1, tiles)` sees
+    every chunk's window images; `spectra` (a dict) receives the spectrum of every window under its tile number."""
+    import torch
+
+    from . import socs as _socs
+    from .imageformation import postProcess
+    pn, planes, nt = plan.pixelNumber, socs.planes, plan.n_tile
+    eps, N = nat.epsilon_n(4.0 / pn, plan.pixelSize, float(plan.wavelength))
+    arrays = _upload_tile_index("tiled imaging", polygons, plan, orient, dev)
+    image = torch.zeros((planes, plan.n, plan.n), dtype=torch.float32, device=dev)
+    place = torch.from_numpy(plan.place).to(dev)
+    for t0, t1 in chunks:
+        specs = _window_spectra(_raster_tiles(arrays, plan, antialias, t0, t1), plan, eps, N)
+        if spectra is not None:
+            for t in range(t0, t1):
+                spectra[t] = specs[t - t0]
+        raw = _socs.hopkinsIntensityBatch(specs, socs, N, tileChunk=t1 - t0)
+        if divide is not None:
+            raw /= divide
+        tiles = postProcess(raw.reshape(-1, pn, pn), eps).reshape(t1 - t0, planes, nt, nt)
+        stitchTiles(tiles, place[t0:t1], plan.j0, plan.core, image)
+        if each is not None:
+            each(t0, t1, tiles)
+    return image
+
+
 def hopkinsImageTiled(polygons, socs, pixelNumber: int, pixelSize: float, wavelength: float, bounds=None, halo: Optional[int] = None,
                       antialias: int = 1, normalize: bool = False, tileChunk: Optional[int] = None, origin=None) -> TiledImage:
     """The Hopkins aerial image of a layout larger than one window.  `polygons` in nanometres (as rasterizeLayout takes them),
@@ -211,10 +328,11 @@ def hopkinsImageTiled(polygons, socs, pixelNumber: int, pixelSize: float, wavele
     image (None: the polygons' bounding box), `halo` in pixels (None: pixelNumber / 4), `antialias` and `normalize` as
     rasterizeLayout and hopkinsImage take them, `origin` the pixel lattice's (planTiles).
 
-    Per chunk of `tileChunk` tiles (None: what keeps hopkinsIntensityBatch's workspace under socs.STACK_BYTES): the polygons
-    are culled against each window by bounding box on the host, every window is rasterised and transformed by the existing
-    entries (rasterizeLayout(origin=window), Mask.fraunhofer), then ONE hopkinsIntensityBatch, ONE postProcess with the chunk's
-    tiles as planes, ONE litho_tiles_stitch.  litho_tiles_seam runs per chunk on the chunk and the one row of tiles before it
+    The polygons are culled against every window by bounding box on the host (tileEdgeIndex) and uploaded once.  Per chunk of
+    `tileChunk` tiles (None: what keeps hopkinsIntensityBatch's workspace under socs.STACK_BYTES): the chunk's windows are
+    rasterised in ONE launch (rasterizeCoverageTiles: the bits of rasterizeLayout(origin=window) per window) and transformed by
+    the mask-spectrum entry, then ONE hopkinsIntensityBatch, ONE postProcess with the chunk's tiles as planes, ONE
+    litho_tiles_stitch.  litho_tiles_seam runs per chunk on the chunk and the one row of tiles before it
     (the only earlier tiles a later one can border), so no more than nx + tileChunk window images are alive at a time.  A window
     without a polygon is imaged like any other: a dark or clear field is not zero intensity for a phase mask or a bright
     background.  The image does not depend on tileChunk, bit for bit.
@@ -223,9 +341,7 @@ def hopkinsImageTiled(polygons, socs, pixelNumber: int, pixelSize: float, wavele
     import torch
 
     from . import socs as _socs
-    from .imageformation import ShapeError, postProcess
-    from .layout import rasterizeLayout
-    from .mask import Mask
+    from .imageformation import ShapeError
     if not isinstance(socs, _socs.SOCSKernels):
         raise TypeError("hopkinsImageTiled: socs must be the SOCSKernels socsKernels returned")
     pn, ps = int(pixelNumber), float(pixelSize)
@@ -244,44 +360,32 @@ def hopkinsImageTiled(polygons, socs, pixelNumber: int, pixelSize: float, wavele
     tileChunk = int(tileChunk)
     if tileChunk < 1:
         raise ValueError(f"hopkinsImageTiled: tileChunk must be >= 1; got {tileChunk}")
-    eps, N = nat.epsilon_n(4.0 / pn, ps, float(wavelength))
-    image = torch.zeros((planes, plan.n, plan.n), dtype=torch.float32, device=dev)
-    place = torch.from_numpy(plan.place).to(dev)
     can_seam = plan.j0 >= 1 and plan.j0 + plan.core < nt
     seam = torch.full((T, planes, 2), float("nan"), dtype=torch.float32, device=dev)
-    kept, kept_ids = None, np.zeros(0, dtype=np.int64)                # the last row of window images and their tile numbers
-    span = pn * ps
-    for t0 in range(0, T, tileChunk):
-        t1 = min(T, t0 + tileChunk)
-        specs = torch.empty((t1 - t0, pn, pn), dtype=torch.complex64, device=dev)
-        for t in range(t0, t1):
-            wx, wy = plan.windows_nm[t]
-            hit = (boxes[:, 2] > wx) & (boxes[:, 0] < wx + span) & (boxes[:, 3] > wy) & (boxes[:, 1] < wy + span)
-            raster = rasterizeLayout([polys[i] for i in np.nonzero(hit)[0]], pn, ps, origin=(wx, wy), device=dev, antialias=antialias)
-            mask = Mask(transmission=raster, pixelSize=ps, device=dev) if int(antialias) > 1 else Mask(raster, ps, dev)
-            specs[t - t0] = mask.fraunhofer(wavelength, True)
-        raw = _socs.hopkinsIntensityBatch(specs, socs, N, tileChunk=t1 - t0)
-        if normalize and socs.weight_sum > 0:
-            raw /= float(socs.weight_sum)
-        tiles = postProcess(raw.reshape(-1, pn, pn), eps).reshape(t1 - t0, planes, nt, nt)
-        stitchTiles(tiles, place[t0:t1], plan.j0, plan.core, image)
-        if can_seam and T > 1:
-            # the chunk behind the kept tiles; a pair is measured when its later tile arrives, so every pair is measured once
-            ids = np.concatenate([kept_ids, np.arange(t0, t1)])
-            both = tiles if kept is None else torch.cat([kept, tiles])
-            local = {int(g): i for i, g in enumerate(ids)}
-            nb = np.full((len(ids), 2), -1, dtype=np.int32)
-            for i, g in enumerate(ids):
-                for side in (0, 1):
-                    other = int(plan.neighbours[g, side])
-                    if t0 <= other < t1:
-                        nb[i, side] = local[other]
-            part = seamTiles(both, torch.from_numpy(nb).to(dev), plan.j0, plan.core)
-            at = torch.from_numpy(ids).to(dev)
-            seam[at] = torch.fmax(seam[at], part)
-            keep = ids >= t1 - plan.nx
-            kept_ids = ids[keep]
-            kept = both[torch.from_numpy(np.nonzero(keep)[0]).to(dev)]
+    state = {"kept": None, "ids": np.zeros(0, dtype=np.int64)}        # the last row of window images and their tile numbers
+
+    def measure_seams(t0, t1, tiles):
+        # the chunk behind the kept tiles; a pair is measured when its later tile arrives, so every pair is measured once
+        kept, kept_ids = state["kept"], state["ids"]
+        ids = np.concatenate([kept_ids, np.arange(t0, t1)])
+        both = tiles if kept is None else torch.cat([kept, tiles])
+        local = {int(g): i for i, g in enumerate(ids)}
+        nb = np.full((len(ids), 2), -1, dtype=np.int32)
+        for i, g in enumerate(ids):
+            for side in (0, 1):
+                other = int(plan.neighbours[g, side])
+                if t0 <= other < t1:
+                    nb[i, side] = local[other]
+        part = seamTiles(both, torch.from_numpy(nb).to(dev), plan.j0, plan.core)
+        at = torch.from_numpy(ids).to(dev)
+        seam[at] = torch.fmax(seam[at], part)
+        keep = ids >= t1 - plan.nx
+        state["ids"] = ids[keep]
+        state["kept"] = both[torch.from_numpy(np.nonzero(keep)[0]).to(dev)]
+
+    chunks = [(t0, min(T, t0 + tileChunk)) for t0 in range(0, T, tileChunk)]
+    image = _sweep_layout(polys, socs, plan, antialias, float(socs.weight_sum) if normalize and socs.weight_sum > 0 else None, chunks,
+                          dev, each=measure_seams if can_seam and T > 1 else None)
     seam_error = float("nan")
     if can_seam and T > 1:
         finite = seam[~torch.isnan(seam)]
@@ -386,10 +490,11 @@ def maskPolygons(plan: TilePlan, mask, level: float = 0.5) -> List[np.ndarray]:
 
 
 def _window_spectra(windows, plan, eps, N):
-    """complex64 [count,pn,pn]: the spectra of `windows` (transmissions) by the mask-spectrum entry, window by window."""
+    """complex64 [count,pn,pn]: the spectra of `windows` (transmissions, complex or real) by the mask-spectrum entry, window by
+    window."""
     import torch
     from .mask import Mask
-    specs = torch.empty_like(windows)
+    specs = torch.empty(windows.shape, dtype=torch.complex64, device=windows.device)
     for b in range(int(windows.shape[0])):
         specs[b] = Mask(transmission=windows[b], pixelSize=plan.pixelSize, device=windows.device)._ffFraunhofer(eps, N)
     return specs
@@ -548,3 +653,201 @@ def optimizeMaskTiled(target, socs, plan: TilePlan, threshold, dose=1.0, iterati
     result = ILTResult(best_theta, transmission_of(best_theta), losses, best)
     result.plan = plan
     return result
+
+
+# ---- tiled optical proximity correction ------------------------------------------------------------------------------------------
+MEEF_MATRIX_BYTES = 2 << 30               # ceiling of the dense S x S float64 MEEF matrix of correctLayoutTiled(step="meef")
+
+
+def _check_tiled_socs(who, socs, plan):
+    from . import socs as _socs
+    if not isinstance(socs, _socs.SOCSKernels):
+        raise TypeError(f"{who}: socs must be a SOCSKernels (socsKernels / vectorSocsKernels)")
+    if socs.pn != plan.pixelNumber or socs.stacked:
+        raise ValueError(f"{who}: the kernels are {'a stack of ' if socs.stacked else ''}{socs.pn} x {socs.pn}, the windows "
+                         f"{plan.pixelNumber} x {plan.pixelNumber}: one plane on the window's grid is needed")
+
+
+def _opc_bounds(polygons, maxBias, searchRange, pixelSize):
+    """The polygons' bounding box grown on every side by maxBias + (searchRange + 2) pixels: every biased polygon and every site's
+    search segment (searchRange pixels along the normal, bilinear samples one pixel further) then lies in covered image."""
+    polys, boxes = _bounding_boxes(polygons)
+    if not polys:
+        raise ValueError("correctLayoutTiled: the layout has no polygon")
+    m = float(maxBias) + (float(searchRange) + 2.0) * float(pixelSize)
+    return (boxes[:, 0].min() - m, boxes[:, 1].min() - m, boxes[:, 2].max() + m, boxes[:, 3].max() + m)
+
+
+def _tiled_model(who, socs, plan, sites, threshold, antialias, searchRange, normalize, tileChunk):
+    """(imager, epe) of correctLayoutTiled: imager(polygons) -> the stitched image fp32 [n,n] by hopkinsImageTiled's sweep,
+    epe(image) -> EPE in nm per site (plane 0, dose 1; NaN where nothing crosses) by ONE measureEPE."""
+    import torch
+
+    from .metrology import measureEPE
+    chunks = _tile_chunks(who, tileChunk, socs, plan)
+    dev = nat.require_gpu(socs.kernels.device)
+    divide = float(socs.weight_sum) if normalize and socs.weight_sum > 0 else None
+    site_rows = torch.from_numpy(sites.sites_px).to(dev)
+
+    def imager(polys):
+        return _sweep_layout(polys, socs, plan, antialias, divide, chunks, dev)[0]
+
+    def epe(image):
+        return measureEPE(image, threshold, site_rows, plan.pixelSize, searchRange=searchRange)[0, 0, :, 0].cpu().numpy()
+
+    return imager, epe
+
+
+def correctLayoutTiled(polygons, socs, pixelNumber, pixelSize, wavelength, threshold, *, spacing, maxBias, halo=None, bounds=None,
+                       origin=None, iterations=6, gain=0.6, antialias=16, searchRange=8.0, step="damped", normalize=False,
+                       tileChunk=None, exposed=True):
+    """metrology.correctLayout for a Manhattan layout block larger than one window: the fragments of ALL polygons move on one
+    stitched image.  `socs` the SOCSKernels at `pixelNumber` (one plane), `halo` in pixels (None: pixelNumber / 4), `bounds` =
+    (x0, y0, x1, y1) the rectangle to image -- None: the polygons' bounding box grown on every side by maxBias + (searchRange + 2)
+    * pixelSize, so that every biased polygon and every site's search segment lies in covered image --, `origin` the pixel
+    lattice's (planTiles).  The sites are layoutSites of the target on the stitched grid and stay fixed.
+
+    Per iterate: biasLayout, tileEdgeIndex and ONE upload; per chunk of `tileChunk` windows ONE raster launch
+    (rasterizeCoverageTiles), the window spectra, ONE hopkinsIntensityBatch, ONE postProcess with the windows as planes, ONE stitch
+    -- hopkinsImageTiled's own sweep, so the image of an iterate IS hopkinsImageTiled's of the biased layout on the same plan, bit
+    for bit --; then ONE measureEPE on the stitched image.  The two update rules are correctLayout's (`step` "damped" or "meef",
+    `gain`, `maxBias`); step="meef" takes its frozen matrix from epeJacobianTiled, the exact Jacobian of this tiled model, dense
+    [S,S] float64 on the host (ValueError where that would exceed 2 GiB: raise `spacing`).  The result depends on neither
+    `tileChunk` nor the chunking of the Jacobian's directions, bit for bit.  Returns an OPCResult with `.plan`.  ValueError before
+    any image is made: a non-Manhattan layout, a stacked or wrong-size `socs`, exposed=False, an unknown `step`."""
+    from .metrology import _counter_clockwise, _damped_loop, _meef_loop, biasLayout
+    who = "correctLayoutTiled"
+    if step not in ("damped", "meef"):
+        raise ValueError(f"{who}: step must be 'damped' or 'meef'; got {step!r}")
+    if not exposed:
+        raise ValueError(f"{who}: the loop is defined for exposed features (the polygons are the mask's openings and print bright)")
+    iterations, gain, maxBias = int(iterations), float(gain), float(maxBias)
+    if iterations < 1 or not maxBias >= 0.0 or not math.isfinite(maxBias) or not math.isfinite(gain):
+        raise ValueError(f"{who}: iterations >= 1, finite gain and maxBias >= 0; got {iterations}, {gain}, {maxBias}")
+    if not 0.0 < float(searchRange) <= 32.0:
+        raise ValueError(f"{who}: searchRange must lie in (0, 32] pixels; got {searchRange}")
+    pn, ps = int(pixelNumber), float(pixelSize)
+    target = _counter_clockwise(polygons)
+    if bounds is None:
+        bounds = _opc_bounds(target, maxBias, searchRange, ps)
+    plan = planTiles(bounds, pn, ps, wavelength, pn // 4 if halo is None else halo, origin)
+    _check_tiled_socs(who, socs, plan)
+    sites = layoutSites(target, spacing, ps, plan.origin, pn, wavelength, registration=plan.registration)
+    if len(sites) == 0:
+        raise ValueError(f"{who}: the layout has no edges")
+    biasLayout(target, sites, np.zeros(len(sites)))            # raises for a non-Manhattan layout before any image is made
+    if step == "meef" and len(sites) ** 2 * 8 > MEEF_MATRIX_BYTES:
+        raise ValueError(f"{who}: {len(sites)} sites make a dense MEEF matrix of {len(sites) ** 2 * 8 / 2 ** 30:.1f} GiB, more than "
+                         f"{MEEF_MATRIX_BYTES >> 30} GiB; raise spacing (now {spacing}) or use step='damped'")
+    imager, epe = _tiled_model(who, socs, plan, sites, threshold, antialias, searchRange, normalize, tileChunk)
+    if step == "meef":
+        def sensitivity(polys, b):
+            return epeJacobianTiled(target, sites, b, socs, plan, threshold, antialias=antialias, searchRange=searchRange,
+                                    normalize=normalize, tileChunk=tileChunk)[1]
+        result = _meef_loop(target, sites, imager, epe, sensitivity, iterations, maxBias)
+    else:
+        result = _damped_loop(target, sites, imager, epe, iterations, gain, maxBias)
+    result.plan = plan
+    return result
+
+
+def _global_fragment_cells(sites, bias, plan):
+    """sensitivity._fragment_cells once on the lattice of ALL windows, halo included: (rows, cols, fragment, weight) with (row, col)
+    counted from the first window's corner, so that window (ix, iy) holds the cells [iy core, iy core + pn) x [ix core, ix core + pn)
+    at (row - iy core, col - ix core)."""
+    from .sensitivity import _fragment_cells
+    side = plan.core * max(plan.nx, plan.ny) + 2 * plan.halo
+    corner = (plan.origin[0] - plan.halo * plan.pixelSize, plan.origin[1] - plan.halo * plan.pixelSize)
+    return _fragment_cells(sites, bias, side, plan.pixelSize, corner)
+
+
+def epeJacobianTiled(polygons, sites, bias_nm, socs, plan: TilePlan, threshold, *, antialias=16, searchRange=8.0, directions=None,
+                     normalize=False, tileChunk=None, directionChunk=None, cull=True):
+    """(epe_nm [S], J [S,P]) of the TILED forward model at biasLayout(polygons, sites, bias_nm), float64 on the host: the EPE at
+    `sites` (layoutSites on the stitched grid of `plan`; NaN where nothing crosses in range) on the stitched image of
+    correctLayoutTiled, and its exact derivative along `directions` [P,S] of the fragment biases (None: the identity, the MEEF
+    matrix).  For direction p: the coverage tangent of window w is edgeCoverageTangentHost's at the window's origin (the cells are
+    found once on the lattice of all windows, halo included, and sliced per window); the image tangent of w is
+    postProcessTangent(hopkinsTangent(M_w, socs, N, spectrum of that tangent)), divided as the image is when `normalize`; the
+    stitched tangent holds the cores of those and zero in every core whose window holds no cell of a moving fragment; J[:, p] =
+    measureEPETangent(stitched image, stitched tangent).  A fragment in one window's halo moves edges in the neighbouring core:
+    the matrix is NOT block diagonal by tile.  Windows a direction cannot reach are skipped -- their tangent is exactly zero --,
+    `cull=False` evaluates every window for every direction and gives the same bits.  Directions go in chunks of at most 16
+    (`directionChunk`), lowered until the stitched tangents stay under socs.STACK_BYTES, windows in tile order; neither that nor
+    `tileChunk` (the primal sweep's) changes a bit.  A row of J is NaN where the site's EPE is."""
+    import torch
+
+    from . import socs as _socs
+    from .mask import Mask
+    from .metrology import _counter_clockwise, biasLayout, measureEPE
+    from .sensitivity import MAX_DIRECTIONS, hopkinsTangent, measureEPETangent, postProcessTangent
+    who = "epeJacobianTiled"
+    if not isinstance(plan, TilePlan):
+        raise TypeError(f"{who}: plan must be the TilePlan planTiles returned")
+    _check_tiled_socs(who, socs, plan)
+    if not isinstance(sites, LayoutSites):
+        raise TypeError(f"{who}: sites must be a LayoutSites (layoutSites on the plan's stitched grid)")
+    S = len(sites)
+    bias = np.asarray(bias_nm, dtype=np.float64).reshape(-1)
+    d = np.eye(S) if directions is None else np.asarray(directions, dtype=np.float64)
+    if d.ndim != 2 or d.shape[1] != S or d.shape[0] < 1 or not np.isfinite(d).all():
+        raise ValueError(f"{who}: directions must be finite [P,{S}]; got {d.shape}")
+    if bias.shape[0] != S or not np.isfinite(bias).all():
+        raise ValueError(f"{who}: {S} finite biases are needed; got {bias.shape[0]}")
+    P = int(d.shape[0])
+    size = MAX_DIRECTIONS if directionChunk is None else int(directionChunk)
+    if not 1 <= size <= MAX_DIRECTIONS:
+        raise ValueError(f"{who}: directionChunk must lie in 1..{MAX_DIRECTIONS}; got {directionChunk}")
+    pn, ps, core, n, j0 = plan.pixelNumber, plan.pixelSize, plan.core, plan.n, plan.j0
+    while size > 1 and size * n * n * 4 > _socs.STACK_BYTES:
+        size -= 1
+    target = _counter_clockwise(polygons)
+    dev = nat.require_gpu(socs.kernels.device)
+    eps, N = nat.epsilon_n(4.0 / pn, ps, float(plan.wavelength))
+    divide = float(socs.weight_sum) if normalize and socs.weight_sum > 0 else None
+    chunks = _tile_chunks(who, tileChunk, socs, plan)
+    polys = biasLayout(target, sites, bias)
+    rows, cols, frag, wts = _global_fragment_cells(sites, bias, plan)
+    keep = plan.count * pn * pn * 8 <= _socs.STACK_BYTES
+    spectra = {} if keep else None
+    image = _sweep_layout(polys, socs, plan, antialias, divide, chunks, dev, spectra=spectra)[0]
+    arrays = None if keep else _upload_tile_index(who, polys, plan, True, dev)
+
+    def spectrum_of(w):
+        if keep:
+            return spectra[w]
+        return _window_spectra(_raster_tiles(arrays, plan, antialias, w, w + 1), plan, eps, N)[0]
+
+    site_rows = torch.from_numpy(sites.sites_px).to(dev)
+    epe = measureEPE(image, threshold, site_rows, ps, searchRange=searchRange)[0, 0, :, 0].double().cpu().numpy()
+    # the cells of every window: window (ix, iy) holds the global cells [iy core, iy core + pn) x [ix core, ix core + pn)
+    inside = []
+    for w in range(plan.count):
+        r0, c0 = int(plan.place[w, 0]), int(plan.place[w, 1])
+        inside.append(np.nonzero((rows >= r0) & (rows < r0 + pn) & (cols >= c0) & (cols < c0 + pn))[0])
+    J = np.empty((S, P))
+    for p0 in range(0, P, size):
+        dd = d[p0:p0 + size]
+        k = dd.shape[0]
+        stitched = torch.zeros((k, n, n), dtype=torch.float32, device=dev)
+        for w in range(plan.count):
+            cells = inside[w]
+            moving = dd[:, frag[cells]] != 0.0                                     # [k, cells of w]
+            reach = np.nonzero(moving.any(axis=1))[0] if cull else np.arange(k)
+            if reach.size == 0:
+                continue
+            r0, c0 = int(plan.place[w, 0]), int(plan.place[w, 1])
+            dt = np.zeros((reach.size, pn, pn), dtype=np.float64)
+            for a, p in enumerate(reach):
+                np.add.at(dt[a], (rows[cells] - r0, cols[cells] - c0), dd[p, frag[cells]] * wts[cells])
+            dts = torch.from_numpy(dt.astype(np.float32)).to(dev)
+            dM = torch.stack([Mask(pixelSize=ps, device=dev, transmission=t)._ffFraunhofer(eps, N) for t in dts])
+            draw = hopkinsTangent(spectrum_of(w), socs, N, dM)
+            if divide is not None:
+                draw /= divide
+            for a, p in enumerate(reach):                                          # one direction a call: the batch cannot show
+                tile = postProcessTangent(draw[a], pn, eps)
+                stitched[int(p), r0:r0 + core, c0:c0 + core] = tile[j0:j0 + core, j0:j0 + core]
+        dE = measureEPETangent(image, stitched, threshold, site_rows, ps, searchRange=searchRange)[:, 0, 0, :]
+        J[:, p0:p0 + k] = dE.double().cpu().numpy().T
+    return epe, J
